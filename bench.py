@@ -12,9 +12,13 @@ All inputs are resident in HBM before the timed region.  `value` counts 64-block
 variables on 8 GPUs: banded W_i, 95 first-stage variables, 31 two-link rows between neighbouring blocks: S = 8000); there the
 sparse head of the leaf factorisation is the dominant kernel group and the roofline object prices it against HBM.
 
-The line accounts for itself: `phase_ms` lists every phase of the step (HIP events on the streams the work runs on, one
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, ms_per_step, config, ...).
+--dump-outputs DIR also writes what the last timed step returned (the solutions x0 and x_leaf) as DIR/<name>.npy.
+
+With --full the line accounts for itself: `phase_ms` lists every phase of the step (HIP events on the streams the work runs on, one
 instrumented step after the timed region), `roofline` is the kernel group with the largest share of the step for the
 configuration that was run, `roofline_all` the others; with N > 1 `collective` carries the reductions' time, bytes and overlap.
+--full also adds `cpu_baseline` and `ipm_end_to_end` (N = 1) and `config.same_shape_on_one_gpu` (N > 1).
 """
 import argparse
 import json
@@ -33,6 +37,23 @@ PEAK_FP64_MFMA_TFLOPS = 78.6   # MI355X dense FP64 matrix peak (256
 PEAK_HBM_GBS = 8000.0          # MI355X HBM3E (MI355X_MICROARCH.md)
 TILE = 128
 R_SOLVES = 4
+DUMP_BYTES_MAX = 60 * 2**20     # --dump-outputs: all arrays together (below 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 20261016     # --dump-outputs: the fixed sample of an array that does not fit
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: arrays (name -> 1-D float64 numpy array, in order) as out_dir/<name>.npy.  An array that would take the total
+    past DUMP_BYTES_MAX is cut to a sample of the entries that fit: the same sorted, seeded positions for the same arguments, so
+    that two builds can be compared entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    room = DUMP_BYTES_MAX
+    for name, v in arrays:
+        v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+        if v.nbytes > room:
+            pick = np.random.default_rng(DUMP_SAMPLE_SEED).choice(v.size, size=room // v.itemsize, replace=False)
+            v = v[np.sort(pick)]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        room -= v.nbytes
 
 
 def update_kernel_algorithmic_flops(m, nb):
@@ -363,6 +384,14 @@ def main():
     ap.add_argument("--solve-check-every", type=int, default=None,
                     help="measure every k-th solveCompressed that goes by sweeps of the augmented factor against the leaf rows "
                          "(library default 1: every one; 0: only the first after a factorisation - rounds 4's behaviour)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the instrumented step (phase_ms, roofline, roofline_all, collective), the "
+                         "CPU baseline and the end-to-end IPM (N = 1; --no-cpu-baseline / --no-ipm drop them), the one-GPU line of the same "
+                         "shape (N > 1).  Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "x0.npy, the first-stage solution, and x_leaf.npy, the leaf solutions of rank 0's blocks (a fixed, seeded sample "
+                         "of them where they exceed the size limit)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -542,104 +571,110 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if share_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        # what the last timed step handed back: the 4th solveCompressed's solution, in place in b0 / b_leaf
+        dump_outputs(a.dump_outputs, [("x0", b0.cpu().numpy()), ("x_leaf", b_leaf.cpu().numpy())])
 
-    # ---- phase table + rooflines: ONE instrumented step (1 factorize + 4 solveCompressed) after the timed region, HIP events on
-    #      the streams the work runs on (pips_hip_batch_get_timing / pips_hip_kkt_get_timing)
-    bt.set_timing(True)
-    aug0 = bt.info().get("augmented_passes", 0)
-    barrier()
-    t_instr = time.perf_counter()
-    step()
-    torch.cuda.synchronize()
-    bt.sync()
-    t_instr = (time.perf_counter() - t_instr) * 1e3
-    aug_passes = bt.info().get("augmented_passes", 0) - aug0    # passes of this step that swept the augmented factor (border rows included)
-    tm = bt.get_timing()
-    tk = kkt.get_timing()
-    bt.set_timing(False)
     info = bt.info()
     nb_blocks = len(blocks)
-    upd_ms, upd_launches = tm["tail_update"]
     # per-block tail sizes are statistically equal; use the exact aggregate from the symbolic phase
     m_avg = info["m"] / nb_blocks
     # border rows that ride along = the NON-EMPTY border columns of a block (info["nb"]), not S: on configurations whose blocks
     # touch only part of the linking columns the difference is large (configs[4] share: S = 16000, ~3700 non-empty per block)
     nb_avg = info["nb"] / nb_blocks
-    n_solve_once = max(tm["solve_tail"][1], 1)
+    roofline = groups = phase_ms = collective = None
+    if a.full:
+        # ---- phase table + rooflines: ONE instrumented step (1 factorize + 4 solveCompressed) after the timed region, HIP events on
+        #      the streams the work runs on (pips_hip_batch_get_timing / pips_hip_kkt_get_timing)
+        bt.set_timing(True)
+        aug0 = bt.info().get("augmented_passes", 0)
+        barrier()
+        t_instr = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        bt.sync()
+        t_instr = (time.perf_counter() - t_instr) * 1e3
+        aug_passes = bt.info().get("augmented_passes", 0) - aug0    # passes of this step that swept the augmented factor (border rows included)
+        tm = bt.get_timing()
+        tk = kkt.get_timing()
+        bt.set_timing(False)
+        info = bt.info()
+        upd_ms, upd_launches = tm["tail_update"]
+        n_solve_once = max(tm["solve_tail"][1], 1)
 
-    def group(name, kernel, bound, ms_, launches, work, note=None):
-        """work: algorithmic flops (mfma) or bytes (hbm) of the group per step"""
-        peak, unit, scale = (PEAK_FP64_MFMA_TFLOPS, "TFLOP/s", 1e12) if bound == "mfma" else (PEAK_HBM_GBS, "GB/s", 1e9)
-        ach = work / (ms_ * 1e-3) / scale if ms_ > 0 else 0.0
-        g = {"group": name, "kernel": kernel, "bound": bound, "achieved": round(ach, 2), "peak": peak, "unit": unit,
-             "frac": round(ach / peak, 4), "ms_per_step": round(ms_, 3), "launches_per_step": int(launches),
-             "avg_launch_ms": round(ms_ / max(launches, 1), 4),
-             ("algorithmic_flops_per_step" if bound == "mfma" else "algorithmic_bytes_per_step"): work,
-             ("algorithmic_flops_per_launch" if bound == "mfma" else "algorithmic_bytes_per_launch"): work / max(launches, 1)}
-        if note:
-            g["note"] = note
-        return g
+        def group(name, kernel, bound, ms_, launches, work, note=None):
+            """work: algorithmic flops (mfma) or bytes (hbm) of the group per step"""
+            peak, unit, scale = (PEAK_FP64_MFMA_TFLOPS, "TFLOP/s", 1e12) if bound == "mfma" else (PEAK_HBM_GBS, "GB/s", 1e9)
+            ach = work / (ms_ * 1e-3) / scale if ms_ > 0 else 0.0
+            g = {"group": name, "kernel": kernel, "bound": bound, "achieved": round(ach, 2), "peak": peak, "unit": unit,
+                 "frac": round(ach / peak, 4), "ms_per_step": round(ms_, 3), "launches_per_step": int(launches),
+                 "avg_launch_ms": round(ms_ / max(launches, 1), 4),
+                 ("algorithmic_flops_per_step" if bound == "mfma" else "algorithmic_bytes_per_step"): work,
+                 ("algorithmic_flops_per_launch" if bound == "mfma" else "algorithmic_bytes_per_launch"): work / max(launches, 1)}
+            if note:
+                g["note"] = note
+            return g
 
-    upd_flops = nb_blocks * update_kernel_algorithmic_flops(int(round(m_avg)), int(round(nb_avg)))
-    groups = [
-        group("tail update", "k_tile_gemm_bal<0> (v_mfma_f64_4x4x4_4b_f64)", "mfma", upd_ms, upd_launches, upd_flops,
-              "sum_j 2 (128 j) [tc below + tc (tc + 1) / 2 + nb tc] per block (DESIGN.md 4)"),
-        group("Schur SYRK", "k_tile_gemm_bal<2>", "mfma", tm["schur"][0], tm["schur"][1], nb_blocks * nb_avg * (nb_avg + 1) * m_avg,
-              "nb (nb + 1) m per block"),
-        # SURVEY 8d: bytes_F = 8 (nnz K + nnz L) + 4 (nnz K + nnz_idx L), here for the part of L the sparse head produces
-        group("sparse head", "k_front<*> + k_head_factor_simple" if info.get("multifrontal_head") else "k_head_factor*", "hbm", tm["head"][0], tm["head"][1],
-              8.0 * (info["nnzK"] + info["nnzL_head"]) + 4.0 * (info["nnzK"] + info["head_row_indices"]),
-              "8 (nnz K + nnz L_head) + 4 (nnz K + row indices of the head supernodes): read K once, write L once"),
-    ] + ([group("dense root", "k_tile_gemm<3> + k_tile_diag + k_tile_gemm<1>", "mfma", tk["root_factor"][0], 1, S ** 3 / 3.0, "S^3 / 3")]
-         if not sparse_root else []) + [
-        # a solve with K_i reads the rows of K of the factor twice (16 bytes per entry and pass); a pass over the AUGMENTED factor also its
-        # border rows (head panels / border-row arena, the tails' border rows)
-        group("leaf solve sweeps", "k_leaf_fwd_gather / k_head_fwd_chain / k_tail_rows_fwd / k_tail_rows_bwd / k_head_bwd_chain / k_leaf_bwd", "hbm",
-              tm["solve_head_fwd"][0] + tm["solve_tail"][0] + tm["solve_head_bwd"][0], n_solve_once,
-              16.0 * (n_solve_once * (info["nnzL"] - info.get("nnzL_border", 0)) + aug_passes * (info.get("nnzL_border", 0) + info.get("tail_border_entries", 0))),
-              "16 bytes per entry of L and pass (forward + backward): the rows of K in every pass, the border rows in the passes over the augmented factor "
-              f"({aug_passes} of {n_solve_once})"),
-    ]
-    dominant = max(groups, key=lambda g: g["ms_per_step"])
-    roofline = dict(dominant)
-    if dominant["group"] == "tail update":
-        traffic = update_kernel_traffic(n_blocks_total, n_i, S, world)
-    elif dominant["group"] == "sparse head":
-        traffic = head_traffic(shape)
-    elif dominant["group"] == "leaf solve sweeps":
-        traffic = head_traffic(shape, "solve_hbm_bytes_per_step")
-    else:
-        traffic = None
-    # per launch, like `achieved` (the rocprofv3 average duration of the kernel is ms_per_step / launches_per_step)
-    roofline["traffic"] = (traffic / dominant["launches_per_step"] if traffic and dominant["launches_per_step"] else None)
-    roofline["traffic_per_step"] = traffic
-    # every phase of the step.  Top level: the partition of pips_hip_kkt_factorize / pips_hip_kkt_solve_compressed (4 solves);
-    # below it what the leaf engine reports for its own part.  The root factorisation runs on a stream of its own beside the first
-    # Lsolve's leaf solve; only what exceeds that solve is on the critical path.
-    top = {k: round(v[0], 3) for k, v in tk.items()}
-    # what the main stream waited for the root: the join before the first Dsolve where the root has a stream of its own (measured by
-    # events around the join, phase root_wait), the whole factorisation where it sits on the main stream
-    root_exposed = tk["root_wait"][0] + tk["root_factor_main_stream"][0]
-    accounted = sum(tk[k][0] for k in ("diag_zero", "leaf_factor", "reduce", "finalize", "root_factor_main_stream", "lsolve_leaf", "lsolve_border_reduce",
-                                       "root_wait", "dsolve", "ltsolve", "solve_check", "combine"))
-    phase_ms = {"step": top, "root_factor_exposed": round(root_exposed, 3), "accounted": round(accounted, 3),
-                "host_waits_per_step": round(host_waits_per_step, 2),   # how often a timed step made the host wait for the device inside the library
-                "instrumented_step_wall": round(t_instr, 3),   # the one step the phases were taken from, host clock around it (events and two extra waits inside)
-                "leaf_factor": {k: round(tm[k][0], 3) for k in ("scatter", "head", "tail_update", "tail_diag", "tail_trsm", "schur")},
-                "leaf_solves": {k: round(tm[k][0], 3) for k in ("solve_permute", "solve_head_fwd", "solve_tail", "solve_head_bwd", "solve_refine")},
-                "leaf_solve_passes": n_solve_once, "leaf_solve_passes_augmented": aug_passes}
-    collective = None
-    if use_dist:
-        # bytes of the Schur reduction: the packed triangle of the dense root, or the value array of the sparse root's pattern
-        payload = 8.0 * kkt.schur_sparse_nnz() if sparse_root else 8.0 * S * (S + 1) / 2
-        P = max(world, 1)
-        tot = tk["reduce_panels"][0] if tk["reduce_panels"][1] > 0 else tk["reduce"][0]
-        collective = {"ranks_seen": ranks_seen, "schur_reduce_exposed_ms": round(tk["reduce"][0], 3), "schur_reduce_total_ms": round(tot, 3),
-                      "schur_panels": tk["reduce_panels"][1] or 1,
-                      "overlapped_fraction": (round(1.0 - tk["reduce"][0] / tot, 3) if tk["reduce_panels"][1] > 0 and tot > 0 else 0.0),
-                      "b0_reduce_ms_in": "phase_ms.step.lsolve_border_reduce (border product + all-reduce of S doubles, x4)",
-                      "payload_bytes_per_step": payload + R_SOLVES * 8.0 * S,
-                      "wire_bytes_per_gpu_per_step": 2.0 * (P - 1) / P * (payload + R_SOLVES * 8.0 * S)}
+        upd_flops = nb_blocks * update_kernel_algorithmic_flops(int(round(m_avg)), int(round(nb_avg)))
+        groups = [
+            group("tail update", "k_tile_gemm_bal<0> (v_mfma_f64_4x4x4_4b_f64)", "mfma", upd_ms, upd_launches, upd_flops,
+                  "sum_j 2 (128 j) [tc below + tc (tc + 1) / 2 + nb tc] per block (DESIGN.md 4)"),
+            group("Schur SYRK", "k_tile_gemm_bal<2>", "mfma", tm["schur"][0], tm["schur"][1], nb_blocks * nb_avg * (nb_avg + 1) * m_avg,
+                  "nb (nb + 1) m per block"),
+            # SURVEY 8d: bytes_F = 8 (nnz K + nnz L) + 4 (nnz K + nnz_idx L), here for the part of L the sparse head produces
+            group("sparse head", "k_front<*> + k_head_factor_simple" if info.get("multifrontal_head") else "k_head_factor*", "hbm", tm["head"][0], tm["head"][1],
+                  8.0 * (info["nnzK"] + info["nnzL_head"]) + 4.0 * (info["nnzK"] + info["head_row_indices"]),
+                  "8 (nnz K + nnz L_head) + 4 (nnz K + row indices of the head supernodes): read K once, write L once"),
+        ] + ([group("dense root", "k_tile_gemm<3> + k_tile_diag + k_tile_gemm<1>", "mfma", tk["root_factor"][0], 1, S ** 3 / 3.0, "S^3 / 3")]
+             if not sparse_root else []) + [
+            # a solve with K_i reads the rows of K of the factor twice (16 bytes per entry and pass); a pass over the AUGMENTED factor also its
+            # border rows (head panels / border-row arena, the tails' border rows)
+            group("leaf solve sweeps", "k_leaf_fwd_gather / k_head_fwd_chain / k_tail_rows_fwd / k_tail_rows_bwd / k_head_bwd_chain / k_leaf_bwd", "hbm",
+                  tm["solve_head_fwd"][0] + tm["solve_tail"][0] + tm["solve_head_bwd"][0], n_solve_once,
+                  16.0 * (n_solve_once * (info["nnzL"] - info.get("nnzL_border", 0)) + aug_passes * (info.get("nnzL_border", 0) + info.get("tail_border_entries", 0))),
+                  "16 bytes per entry of L and pass (forward + backward): the rows of K in every pass, the border rows in the passes over the augmented factor "
+                  f"({aug_passes} of {n_solve_once})"),
+        ]
+        dominant = max(groups, key=lambda g: g["ms_per_step"])
+        roofline = dict(dominant)
+        if dominant["group"] == "tail update":
+            traffic = update_kernel_traffic(n_blocks_total, n_i, S, world)
+        elif dominant["group"] == "sparse head":
+            traffic = head_traffic(shape)
+        elif dominant["group"] == "leaf solve sweeps":
+            traffic = head_traffic(shape, "solve_hbm_bytes_per_step")
+        else:
+            traffic = None
+        # per launch, like `achieved` (the rocprofv3 average duration of the kernel is ms_per_step / launches_per_step)
+        roofline["traffic"] = (traffic / dominant["launches_per_step"] if traffic and dominant["launches_per_step"] else None)
+        roofline["traffic_per_step"] = traffic
+        # every phase of the step.  Top level: the partition of pips_hip_kkt_factorize / pips_hip_kkt_solve_compressed (4 solves);
+        # below it what the leaf engine reports for its own part.  The root factorisation runs on a stream of its own beside the first
+        # Lsolve's leaf solve; only what exceeds that solve is on the critical path.
+        top = {k: round(v[0], 3) for k, v in tk.items()}
+        # what the main stream waited for the root: the join before the first Dsolve where the root has a stream of its own (measured by
+        # events around the join, phase root_wait), the whole factorisation where it sits on the main stream
+        root_exposed = tk["root_wait"][0] + tk["root_factor_main_stream"][0]
+        accounted = sum(tk[k][0] for k in ("diag_zero", "leaf_factor", "reduce", "finalize", "root_factor_main_stream", "lsolve_leaf", "lsolve_border_reduce",
+                                           "root_wait", "dsolve", "ltsolve", "solve_check", "combine"))
+        phase_ms = {"step": top, "root_factor_exposed": round(root_exposed, 3), "accounted": round(accounted, 3),
+                    "host_waits_per_step": round(host_waits_per_step, 2),   # how often a timed step made the host wait for the device inside the library
+                    "instrumented_step_wall": round(t_instr, 3),   # the one step the phases were taken from, host clock around it (events and two extra waits inside)
+                    "leaf_factor": {k: round(tm[k][0], 3) for k in ("scatter", "head", "tail_update", "tail_diag", "tail_trsm", "schur")},
+                    "leaf_solves": {k: round(tm[k][0], 3) for k in ("solve_permute", "solve_head_fwd", "solve_tail", "solve_head_bwd", "solve_refine")},
+                    "leaf_solve_passes": n_solve_once, "leaf_solve_passes_augmented": aug_passes}
+        collective = None
+        if use_dist:
+            # bytes of the Schur reduction: the packed triangle of the dense root, or the value array of the sparse root's pattern
+            payload = 8.0 * kkt.schur_sparse_nnz() if sparse_root else 8.0 * S * (S + 1) / 2
+            P = max(world, 1)
+            tot = tk["reduce_panels"][0] if tk["reduce_panels"][1] > 0 else tk["reduce"][0]
+            collective = {"ranks_seen": ranks_seen, "schur_reduce_exposed_ms": round(tk["reduce"][0], 3), "schur_reduce_total_ms": round(tot, 3),
+                          "schur_panels": tk["reduce_panels"][1] or 1,
+                          "overlapped_fraction": (round(1.0 - tk["reduce"][0] / tot, 3) if tk["reduce_panels"][1] > 0 and tot > 0 else 0.0),
+                          "b0_reduce_ms_in": "phase_ms.step.lsolve_border_reduce (border product + all-reduce of S doubles, x4)",
+                          "payload_bytes_per_step": payload + R_SOLVES * 8.0 * S,
+                          "wire_bytes_per_gpu_per_step": 2.0 * (P - 1) / P * (payload + R_SOLVES * 8.0 * S)}
 
     if rank == 0:
         ms = dt / a.steps * 1e3
@@ -655,7 +690,7 @@ def main():
                                                     if sparse_root else "dense LDL^T"), "sparse_head": "multifrontal (k_front)" if info.get("multifrontal_head") else "scatter (FP64 atomics)",
                        # N > 1 runs the configs[2] shape, N = 1 configs[1]: per-GPU throughput of the two differs by the Schur dimension alone
                        # (the driver's efficiency against the N = 1 line mixes that in) - the same shape on ONE device, measured, for reference
-                       **({"same_shape_on_one_gpu": same_shape_on_one_gpu(shape)} if world > 1 else {}),
+                       **({"same_shape_on_one_gpu": same_shape_on_one_gpu(shape)} if world > 1 and a.full else {}),
                        "solves_per_unit": R_SOLVES, "collective": comm_kind, "leaf_refinement": "adaptive, <=2 steps, normwise backward error <= 1e-15 (steps taken in the last solve: %d)" % bt.last_refinement_steps(),
                        "solve_path": {0: "every solveCompressed: two leaf solves with adaptive refinement + the two sparse border products",
                                       1: "refined Lsolve; Ltsolve by one backward sweep of the augmented factor (no pivot perturbed, the refined Lsolve needed no step)",
@@ -668,10 +703,11 @@ def main():
                        "iter_per_s": round(a.steps / dt, 4),
                        "nnzL_per_gpu": info["nnzL"], "tail_dim_avg": round(m_avg, 1), "border_rows_avg": round(nb_avg, 1),
                        "factor_flops_per_gpu": info["flops_factor"] + info["flops_border"]},
-            "roofline": roofline,
-            "roofline_all": [{k: g[k] for k in ("group", "bound", "achieved", "peak", "unit", "frac", "ms_per_step", "launches_per_step")} for g in groups],
-            "phase_ms": phase_ms,
         }
+        if a.full:
+            out["roofline"] = roofline
+            out["roofline_all"] = [{k: g[k] for k in ("group", "bound", "achieved", "peak", "unit", "frac", "ms_per_step", "launches_per_step")} for g in groups]
+            out["phase_ms"] = phase_ms
         if collective:
             out["collective"] = collective
     # The loop's handles go down HERE, before the end-to-end IPM and the CPU baseline: with the HIP runtime alive and the streams idle (not from
@@ -687,7 +723,7 @@ def main():
         # them would drop the bench line of a large run whose optional sections are long)
         import faulthandler
         wd = float(os.environ.get("PIPS_BENCH_WATCHDOG", "3000"))
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             faulthandler.dump_traceback_later(wd, exit=True)
             try:
                 out["cpu_baseline"] = cpu_baseline(pa, a.seed, n_i, my_i, n0, myl, a.rho, n_blocks_total, bpg,
@@ -695,7 +731,7 @@ def main():
             except Exception as e:  # the baseline must never break the bench line
                 out["cpu_baseline"] = {"value": None, "unit": f"{bpg}-block work units/s", "cores": 0, "kind": "port",
                                        "sample": f"failed: {e}"}
-        if not a.no_ipm and world == 1:
+        if a.full and not a.no_ipm and world == 1:
             faulthandler.dump_traceback_later(wd, exit=True)
             # "report units/s, and separately end-to-end IPM iterations/s of a full solve with the host driver" - the
             # device-resident harness on the LP of the same generator and shape, outside the timed region of the metric

@@ -1,6 +1,6 @@
-"""bench.py's one-line contract on small workloads (the driver reads this line): required keys, the self-accounting objects, the root
-the time-coupled family takes, and the N > 1 control flow with two processes sharing the one GPU (gloo, host-staged reductions:
-validation, not a measurement)."""
+"""bench.py's one-line contract on small workloads (the driver reads this line): required keys, the self-accounting objects of --full, the
+root the time-coupled family takes, the plain run's line and --dump-outputs, and the N > 1 control flow with two processes sharing the
+one GPU (gloo, host-staged reductions: validation, not a measurement)."""
 import json
 import os
 import subprocess
@@ -53,7 +53,7 @@ def _check_line(d, n_gpus):
 
 
 def test_default_family_small():
-    d = _run(["--blocks-per-gpu", "4", "--n", "1000", "--schur-dim", "200", "--rho", "0.01", "--steps", "2", "--warmup", "1", "--no-ipm"])
+    d = _run(["--blocks-per-gpu", "4", "--n", "1000", "--schur-dim", "200", "--rho", "0.01", "--steps", "2", "--warmup", "1", "--no-ipm", "--full"])
     _check_line(d, 1)
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and (cb["value"] is None or cb["value"] > 0)
@@ -64,7 +64,7 @@ def test_default_family_small():
 @pytest.mark.parametrize("root", ["auto", "dense"])
 def test_time_coupled_family_small(root):
     d = _run(["--family", "time-coupled", "--blocks-per-gpu", "8", "--n", "2000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-              "--root", root])
+              "--root", root, "--full"])
     _check_line(d, 1)
     assert d["config"]["family"].startswith("time-coupled (surrogate")
     assert d["config"]["root"].startswith("sparse" if root == "auto" else "dense")
@@ -77,7 +77,7 @@ def test_two_processes_share_the_gpu():
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(29700 + os.getpid() % 200)]
     d = _run(["--gpus", "2", "--family", "time-coupled", "--blocks-per-gpu", "4", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-              "--no-ipm"], env={"PIPS_BENCH_SHARE_GPU": "1"}, launcher=launcher)
+              "--no-ipm", "--full"], env={"PIPS_BENCH_SHARE_GPU": "1"}, launcher=launcher)
     _check_line(d, 2)
     c = d["collective"]
     assert c is not None and c["payload_bytes_per_step"] > 0
@@ -88,8 +88,8 @@ def test_gpus_flag_starts_the_ranks_itself():
     """`python bench.py --gpus 2` with no launcher: bench.py starts one process per rank before it touches the GPU, the line says n_gpus = 2
     and the communicator the factorisation reduces through counted two ranks (here both on device 0: validation, not a measurement).
     Without --schur-dim the N > 1 default is BASELINE configs[2]'s Schur dimension."""
-    d = _run(["--gpus", "2", "--blocks-per-gpu", "2", "--n", "1000", "--rho", "0.01", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-ipm"],
-             env={"PIPS_BENCH_SHARE_GPU": "1"})
+    d = _run(["--gpus", "2", "--blocks-per-gpu", "2", "--n", "1000", "--rho", "0.01", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-ipm",
+              "--full"], env={"PIPS_BENCH_SHARE_GPU": "1"})
     _check_line(d, 2)
     assert d["collective"]["ranks_seen"] == 2
     assert "Schur dim 4000" in d["config"]["workload"]
@@ -100,7 +100,7 @@ def test_eight_ranks_hold_one_fixed_chain():
     eight ranks share device 0) - the Schur dimension is the chain's, not a function of the rank count, every rank holds its two blocks,
     the sparse root's pattern is assembled from the lists the ranks exchange, and the factorisation's communicator counted eight ranks."""
     args = ["--family", "time-coupled", "--chain-blocks", "16", "--schur-dim", "200", "--blocks-per-gpu", "2", "--n", "600", "--steps", "1", "--warmup", "1",
-            "--no-cpu-baseline", "--no-ipm"]
+            "--no-cpu-baseline", "--no-ipm", "--full"]
     d8 = _run(["--gpus", "8"] + args, env={"PIPS_BENCH_SHARE_GPU": "1"})
     _check_line(d8, 8)
     assert d8["collective"]["ranks_seen"] == 8
@@ -126,3 +126,25 @@ def test_gpus_flag_refuses_more_ranks_than_devices():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1"], cwd=ROOT, env=env, capture_output=True,
                          text=True, timeout=300)
     assert out.returncode == 2 and "device(s)" in out.stderr and not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_plain_run_is_the_headline_and_dumps_what_the_step_returned(tmp_path):
+    """Without --full the line is the headline alone (no instrumented step, CPU baseline or IPM); --dump-outputs writes the solutions of
+    the last timed step, and the same arguments give the same inputs, so a second run returns the same solutions (to rounding)."""
+    import numpy as np
+    args = ["--blocks-per-gpu", "4", "--n", "1000", "--schur-dim", "200", "--rho", "0.01", "--steps", "3", "--warmup", "1"]
+    got = []
+    for tag in ("a", "b"):
+        d = _run(args + ["--dump-outputs", str(tmp_path / tag)])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 0.02
+        assert not {"roofline", "roofline_all", "phase_ms", "collective", "cpu_baseline", "ipm_end_to_end"} & set(d), sorted(d)
+        x0, xl = np.load(tmp_path / tag / "x0.npy"), np.load(tmp_path / tag / "x_leaf.npy")
+        assert x0.dtype == np.float64 and xl.dtype == np.float64
+        assert x0.shape == (200,) and xl.shape == (4 * 1500,)            # S; blocks x (n + n / 2 equality rows)
+        assert np.isfinite(x0).all() and np.isfinite(xl).all() and np.abs(xl).max() > 0
+        got.append((x0, xl))
+    for u, v in zip(*got):
+        assert np.linalg.norm(u - v) <= 1e-8 * np.linalg.norm(u)

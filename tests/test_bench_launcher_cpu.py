@@ -34,3 +34,24 @@ def test_ranks_are_started_with_the_launcher_environment():
     out = _run(["--gpus", "3", "--steps", "1", "--blocks-per-gpu", "1", "--n", "200", "--schur-dim", "40"], env={"PIPS_BENCH_SHARE_GPU": "1"})
     assert out.returncode != 0
     assert out.stderr.count("bench.py needs a GPU") >= 1        # every rank gets as far as the device check (the others are stopped when one fails)
+
+
+def test_dump_outputs_stays_within_the_limit_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: arrays that fit are written whole; one that does not is cut to sorted, seeded positions - the same ones every
+    time - so that the files stay below 64 MB and two builds compare entry for entry."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_BYTES_MAX + 2 * 4096 <= 64 * 10**6
+    b.DUMP_BYTES_MAX = 8 * 1000
+    x0, xl = np.arange(100.0), np.arange(5000.0)
+    for tag in ("a", "b"):
+        b.dump_outputs(str(tmp_path / tag), [("x0", x0), ("x_leaf", xl)])
+    for tag in ("a", "b"):
+        y0, yl = np.load(tmp_path / tag / "x0.npy"), np.load(tmp_path / tag / "x_leaf.npy")
+        assert y0.dtype == yl.dtype == np.float64 and np.array_equal(y0, x0)
+        assert y0.nbytes + yl.nbytes <= b.DUMP_BYTES_MAX and yl.size == 900
+        assert np.all(np.diff(yl) > 0) and np.array_equal(yl, xl[yl.astype(int)])     # distinct entries, in order
+    assert np.array_equal(np.load(tmp_path / "a" / "x_leaf.npy"), np.load(tmp_path / "b" / "x_leaf.npy"))

@@ -2,7 +2,8 @@
 expected objective and iteration count; t_pips.cpp:115-119 checks EXPECT_NEAR(objective, expected, 1e-4) and
 iterations <= 1.1 * expected) through the GDX reader, the CPU restatement of the IPM and the device harness.
 
-tests/golden/gamssmall.json holds the block data extracted from the per-block GDX files (tests/golden/make_gamssmall.py)."""
+tests/golden/gamssmall.json holds the block data extracted from the per-block GDX files (tests/golden/make_gamssmall.py);
+tests/golden/gamssmall_gdx.npz holds those GDX files themselves (tests/golden/make_gamssmall_gdx.py)."""
 import json
 import os
 import warnings
@@ -15,8 +16,22 @@ from pips_ipmpp_amd.standard_form import block_standard_form, general_lp, kkt_vi
 HERE = os.path.dirname(os.path.abspath(__file__))
 DATA = json.load(open(os.path.join(HERE, "golden", "gamssmall.json")))["instances"]
 IDS = [d["name"] for d in DATA]
-REF = "/root/reference"
+GDX_ARCHIVE = os.path.join(HERE, "golden", "gamssmall_gdx.npz")
 OBJ_TOL = 1e-4   # t_pips.cpp:27,116
+
+
+@pytest.fixture(scope="module")
+def gdx_files(tmp_path_factory):
+    """tests/golden/gamssmall_gdx.npz unpacked: instance name -> path prefix P of its files P0.gdx .. P{B-1}.gdx and P.gdx"""
+    root = tmp_path_factory.mktemp("gamssmall_gdx")
+    prefix = {}
+    with np.load(GDX_ARCHIVE) as z:
+        for key in z.files:
+            name, part = key.split("/")
+            prefix[name] = str(root / name)
+            (root / (name + ("" if part == "whole" else part) + ".gdx")).write_bytes(z[key].tobytes())
+    assert sorted(prefix) == sorted(IDS)
+    return prefix
 
 
 def test_fixture_has_the_reference_instance_list():
@@ -60,11 +75,10 @@ def test_gdx_container_round_trip(tmp_path):
         gdx.GdxFile(str(tmp_path / "bad.gdx"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box): the committed fixture stands in")
-def test_fixture_is_what_the_reader_extracts_from_the_reference_files():
+def test_fixture_is_what_the_reader_extracts_from_the_reference_files(gdx_files):
     from pips_ipmpp_amd import gdx
     for d in DATA:
-        blocks = gdx.read_problem(REF + d["source"], d["num_blocks"])
+        blocks = gdx.read_problem(gdx_files[d["name"]], d["num_blocks"])
         for got, want in zip(blocks, d["blocks"]):
             for key, w in want.items():
                 gv = got[key]
@@ -75,7 +89,7 @@ def test_fixture_is_what_the_reader_extracts_from_the_reference_files():
                 else:
                     assert np.array_equal(np.asarray(gv), np.asarray(w)), (d["name"], key)
     # the whole-model file of an instance (label table present, byte-sized keys) reads as well
-    g = gdx.GdxFile(REF + DATA[0]["source"] + ".gdx")
+    g = gdx.GdxFile(gdx_files[DATA[0]["name"]] + ".gdx")
     assert len(g.uels) == 23 and g.symbol("A").keys.shape[1] == 2 and g.symbol("x").values.shape[1] == 5
 
 
@@ -202,9 +216,9 @@ def _synthetic_jacobian(path, rng, num_blocks):
     gdx.write_gdx(path, syms)
 
 
-def test_library_gdx_reader_matches_the_python_restatement(tmp_path):
-    """pips_gdx_read_block (C ABI, csrc/gdx.cpp) against pips_ipmpp_amd.gdx.read_block on synthetic jacobian files and, when the
-    reference tree is here, on every block file of the 26 instances."""
+def test_library_gdx_reader_matches_the_python_restatement(tmp_path, gdx_files):
+    """pips_gdx_read_block (C ABI, csrc/gdx.cpp) against pips_ipmpp_amd.gdx.read_block on synthetic jacobian files and on every block
+    file of the 26 instances."""
     import pips_ipmpp_amd as pa
     from pips_ipmpp_amd import gdx
     rng = np.random.default_rng(11)
@@ -219,18 +233,17 @@ def test_library_gdx_reader_matches_the_python_restatement(tmp_path):
     open(tmp_path / "junk.gdx", "wb").write(bytes(range(256)) * 3)
     with pytest.raises(RuntimeError):
         pa.capi.gdx_read_block(str(tmp_path / "junk.gdx"), 2, 0)
-    if os.path.isdir(REF):
-        whole = 0
-        for d in DATA:
-            for k in range(d["num_blocks"]):
-                _same_block(pa.capi.gdx_read_block(f"{REF}{d['source']}{k}.gdx", d["num_blocks"], k), d["blocks"][k], (d["name"], k))
-                # the unsplit model file (label table, byte-sized keys) yields the same block without the reference's split step;
-                # one instance's unsplit file carries a coefficient across blocks, which both readers reject like readBlock does
-                try:
-                    _same_block(pa.capi.gdx_read_block(f"{REF}{d['source']}.gdx", d["num_blocks"], k), d["blocks"][k], (d["name"], k, "whole"))
-                    whole += 1
-                except RuntimeError as e:
-                    assert "different blocks" in str(e)
-                    with pytest.raises(gdx.GdxError):
-                        gdx.read_block(f"{REF}{d['source']}.gdx", d["num_blocks"], k)
-        assert whole >= 100
+    whole = 0
+    for d in DATA:
+        for k in range(d["num_blocks"]):
+            _same_block(pa.capi.gdx_read_block(f"{gdx_files[d['name']]}{k}.gdx", d["num_blocks"], k), d["blocks"][k], (d["name"], k))
+            # the unsplit model file (label table, byte-sized keys) yields the same block without the reference's split step;
+            # one instance's unsplit file carries a coefficient across blocks, which both readers reject like readBlock does
+            try:
+                _same_block(pa.capi.gdx_read_block(gdx_files[d["name"]] + ".gdx", d["num_blocks"], k), d["blocks"][k], (d["name"], k, "whole"))
+                whole += 1
+            except RuntimeError as e:
+                assert "different blocks" in str(e)
+                with pytest.raises(gdx.GdxError):
+                    gdx.read_block(gdx_files[d["name"]] + ".gdx", d["num_blocks"], k)
+    assert whole >= 100

@@ -7,7 +7,8 @@ import pytest
 
 from pips_ipmpp_amd.options import apply_options, load_options
 
-REF_OPT = "/root/reference/PIPS-IPM/Drivers/gams/simple/GAMSsmall/examples_parallelRows/PIPSIPMpp.opt"
+# the options file of the GAMSsmall parallel-rows examples of PIPS-IPM++ (Drivers/gams/simple/GAMSsmall/examples_parallelRows)
+REF_OPT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "PIPSIPMpp_parallelRows.opt")
 
 
 def test_parser_follows_the_reference_rules(tmp_path):
@@ -22,7 +23,6 @@ def test_parser_follows_the_reference_rules(tmp_path):
     assert applied == [] and set(ignored) == set(o)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_OPT), reason="reference tree not present")
 def test_reads_an_options_file_of_the_reference():
     o = load_options(REF_OPT)
     assert o["PRESOLVE_PARALLEL_ROWS"] is True and o["PRESOLVE_MAX_ROUNDS"] == 1 and o["PRESOLVE_SINGLETON_ROWS"] is False

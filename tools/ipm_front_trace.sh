@@ -1,7 +1,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/ipmtrace; rm -rf $O; mkdir -p $O
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O -o ipm -- python3 $R/bench.py --family time-coupled --blocks-per-gpu 256 --n 50000 --steps 2 --warmup 1 --no-cpu-baseline > $O/log.txt 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O -o ipm -- python3 $R/bench.py --full --family time-coupled --blocks-per-gpu 256 --n 50000 --steps 2 --warmup 1 --no-cpu-baseline > $O/log.txt 2>&1
 python3 - <<PY
 import csv,glob
 f=glob.glob("$O/**/*kernel_trace.csv",recursive=True)[0]

@@ -6,7 +6,7 @@ CNT=${@:-SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS
 OUT=$R/gpurun_out/pmc_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/raw -o p -- python3 $R/bench.py --family time-coupled --blocks-per-gpu 256 --n 50000 --no-ipm --no-cpu-baseline --steps 1 --warmup 0 > $OUT/log.txt 2>&1
+timeout 900 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/raw -o p -- python3 $R/bench.py --full --family time-coupled --blocks-per-gpu 256 --n 50000 --no-ipm --no-cpu-baseline --steps 1 --warmup 0 > $OUT/log.txt 2>&1
 python3 - $OUT <<'PY'
 import csv, glob, re, sys, collections
 f = glob.glob(sys.argv[1] + "/raw/**/*counter_collection.csv", recursive=True)

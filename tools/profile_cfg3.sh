@@ -9,10 +9,10 @@ rm -rf $OUT; mkdir -p $OUT
 ARGS="--family time-coupled --blocks-per-gpu $NB --n $NI --chain-blocks $CHAIN --no-ipm"
 cd /tmp && export TMPDIR=/tmp
 # (the bench line proper also carries the end-to-end IPM of the share: 12.8 M variables at 256 x 50 000)
-timeout 1800 python3 $R/bench.py ${ARGS/ --no-ipm/} > $OUT/bench.json 2> $OUT/bench.err
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o cfg3 -- python3 $R/bench.py $ARGS --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stats.log 2>&1
-timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o cfg3 -- python3 $R/bench.py $ARGS --steps 1 --warmup 0 --no-cpu-baseline > $OUT/fetch.log 2>&1
-timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o cfg3 -- python3 $R/bench.py $ARGS --steps 1 --warmup 0 --no-cpu-baseline > $OUT/write.log 2>&1
+timeout 1800 python3 $R/bench.py --full ${ARGS/ --no-ipm/} > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o cfg3 -- python3 $R/bench.py --full $ARGS --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stats.log 2>&1
+timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o cfg3 -- python3 $R/bench.py --full $ARGS --steps 1 --warmup 0 --no-cpu-baseline > $OUT/fetch.log 2>&1
+timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o cfg3 -- python3 $R/bench.py --full $ARGS --steps 1 --warmup 0 --no-cpu-baseline > $OUT/write.log 2>&1
 python3 $R/tools/profile_cfg3_summarise.py $OUT $TAG $NB $NI $CHAIN > $OUT/summary.json 2> $OUT/summary.err
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_cfg3_kernel_stats.csv 2>/dev/null
 find $OUT -name "*counter_collection.csv" -delete

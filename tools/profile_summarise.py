@@ -69,9 +69,9 @@ for k in sorted(set(fetch) | set(write)):
     per_launch = (fb + wb) / n_pmc
     rows.append({"kernel": k, "launches_in_pmc_run": n_pmc, "hbm_read_bytes_per_launch": fb / n_pmc, "hbm_write_bytes_per_launch": wb / n_pmc,
                  "avg_launch_us": avg_ns / 1e3, "achieved_TBps": (per_launch / (avg_ns * 1e-9) / 1e12) if avg_ns > 0 else None})
-n_fact = 2   # bench.py --steps 1 --warmup 0 runs 2 factorizations (the timed step + the instrumented one for the roofline object)
+n_fact = 2   # bench.py --full --steps 1 --warmup 0 runs 2 factorizations (the timed step + the instrumented one for the roofline object)
 upd = next((r for r in rows if r["kernel"] in UPDATE), None)
-res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, with --kernel-trace only) on `python3 bench.py --steps 1 "
+res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, with --kernel-trace only) on `python3 bench.py --full --steps 1 "
                  "--warmup 0 --no-cpu-baseline --no-ipm`, durations from the --kernel-trace --stats pass, MI355X (tools/profile_bench.sh)",
        "calibration": calib, "factorizations_in_pmc_run": n_fact, "kernels": rows}
 json.dump(res, open(os.path.join(out, f"{tag}_bench_hbm_by_kernel.json"), "w"), indent=1)

@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp
 : > $O/ab.jsonl
 for v in 1 0; do
   e=""; [ $v = 0 ] && e="PIPS_HIP_AUG_SWEEPS=0"
-  env PIPS_HIP_DETERMINISTIC=1 $e python3 $R/bench.py --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --steps 3 --warmup 1 2>/dev/null | grep '^{' >> $O/ab.jsonl
-  env PIPS_HIP_DETERMINISTIC=1 $e python3 $R/bench.py --no-cpu-baseline --no-ipm --steps 3 --warmup 1 2>/dev/null | grep '^{' >> $O/ab.jsonl
+  env PIPS_HIP_DETERMINISTIC=1 $e python3 $R/bench.py --full --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --steps 3 --warmup 1 2>/dev/null | grep '^{' >> $O/ab.jsonl
+  env PIPS_HIP_DETERMINISTIC=1 $e python3 $R/bench.py --full --no-cpu-baseline --no-ipm --steps 3 --warmup 1 2>/dev/null | grep '^{' >> $O/ab.jsonl
 done
 python3 - <<PY
 import json

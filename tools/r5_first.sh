@@ -8,12 +8,12 @@ cd $R
 timeout 1500 python3 -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; echo "pytest rc $?" >> $O/pytest.log
 tail -5 $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python3 $R/bench.py --steps 10 --warmup 2 > $O/bench_c1.json 2> $O/bench_c1.err
-timeout 600 python3 $R/bench.py --steps 10 --warmup 2 --solve-check-every 0 --no-cpu-baseline --no-ipm > $O/bench_c1_nocheck.json 2> $O/bench_c1_nocheck.err
+timeout 600 python3 $R/bench.py --full --steps 10 --warmup 2 > $O/bench_c1.json 2> $O/bench_c1.err
+timeout 600 python3 $R/bench.py --full --steps 10 --warmup 2 --solve-check-every 0 --no-cpu-baseline --no-ipm > $O/bench_c1_nocheck.json 2> $O/bench_c1_nocheck.err
 C3="--family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --no-ipm --steps 6 --warmup 2"
-timeout 900 python3 $R/bench.py $C3 > $O/bench_c3.json 2> $O/bench_c3.err
-timeout 900 python3 $R/bench.py $C3 --chain-blocks 256 > $O/bench_c3_chain256.json 2> $O/bench_c3_chain256.err
-timeout 900 python3 $R/bench.py $C3 --chain-blocks 256 --solve-check-every 0 > $O/bench_c3_chain256_nocheck.json 2> $O/bench_c3_chain256_nocheck.err
+timeout 900 python3 $R/bench.py --full $C3 > $O/bench_c3.json 2> $O/bench_c3.err
+timeout 900 python3 $R/bench.py --full $C3 --chain-blocks 256 > $O/bench_c3_chain256.json 2> $O/bench_c3_chain256.err
+timeout 900 python3 $R/bench.py --full $C3 --chain-blocks 256 --solve-check-every 0 > $O/bench_c3_chain256_nocheck.json 2> $O/bench_c3_chain256_nocheck.err
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/calib_fetch -o calib -- $R/tools/pmc_calib > $O/calib.log 2>&1
 python3 - <<'PY' > $O/calib_summary.txt 2>&1
 import csv, glob, os, re

@@ -7,8 +7,8 @@ cat $O/tests.txt
 cd /tmp && export TMPDIR=/tmp
 : > $O/ab.jsonl
 for k in 1 0; do   # (the mode is opt-in: 1 = fronts on the rows of K only, 0 = the default)
-  PIPS_HIP_MF_KONLY=$k python3 $R/bench.py --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --steps 6 --warmup 2 2>$O/err_$k.txt | grep '^{' >> $O/ab.jsonl
-  PIPS_HIP_MF_KONLY=$k python3 $R/bench.py --family time-coupled --blocks-per-gpu 256 --n 50000 --chain-blocks 256 --no-cpu-baseline --no-ipm --steps 6 --warmup 2 2>>$O/err_$k.txt | grep '^{' >> $O/ab.jsonl
+  PIPS_HIP_MF_KONLY=$k python3 $R/bench.py --full --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --steps 6 --warmup 2 2>$O/err_$k.txt | grep '^{' >> $O/ab.jsonl
+  PIPS_HIP_MF_KONLY=$k python3 $R/bench.py --full --family time-coupled --blocks-per-gpu 256 --n 50000 --chain-blocks 256 --no-cpu-baseline --no-ipm --steps 6 --warmup 2 2>>$O/err_$k.txt | grep '^{' >> $O/ab.jsonl
 done
 python3 - <<PY
 import json

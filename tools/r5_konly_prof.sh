@@ -1,7 +1,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/konly; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kp -o k -- python3 $R/bench.py --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --no-ipm --steps 4 --warmup 1 > $O/prof_bench.txt 2>&1
+rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kp -o k -- python3 $R/bench.py --full --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --no-ipm --steps 4 --warmup 1 > $O/prof_bench.txt 2>&1
 python3 - <<PY
 import csv,glob,re
 fs=glob.glob('/tmp/kp/**/*kernel_stats.csv', recursive=True)

@@ -7,7 +7,7 @@ echo "# leaf factorisation (ms, phase_ms.step.leaf_factor) and work unit (ms) of
 for nb in 1 2 4 8 16 24 32 64; do
   line="blocks $nb:"
   for v in 0 1; do
-    r=$(PIPS_HIP_TAIL_SINGLE=$v timeout 300 python bench.py --blocks-per-gpu $nb --steps 5 --warmup 1 --no-ipm --no-cpu-baseline 2>/dev/null | python -c "
+    r=$(PIPS_HIP_TAIL_SINGLE=$v timeout 300 python bench.py --full --blocks-per-gpu $nb --steps 5 --warmup 1 --no-ipm --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.2f (unit %.2f)' % (d['phase_ms']['step']['leaf_factor'], d['ms_per_step']))")
     line="$line  $r"; [ $v = 0 ] && line="$line |"

@@ -9,14 +9,14 @@ echo "# the leaf tails as one dependency-driven launch (csrc/tailkernel.hip.h, P
 echo "## tools/coh_probe: does an XCD's L2 keep a line that was touched with agent-scope accesses?  (stale = a plain re-read returns the old value after a remote write-through)"
 timeout 120 ./tools/coh_probe 64
 for v in 0 1; do
-  echo "## configs[1], PIPS_HIP_TAIL_SINGLE=$v: python bench.py --steps 5 --warmup 1 --no-ipm --no-cpu-baseline"
-  PIPS_HIP_TAIL_SINGLE=$v timeout 600 python bench.py --steps 5 --warmup 1 --no-ipm --no-cpu-baseline 2>/dev/null | python -c "
+  echo "## configs[1], PIPS_HIP_TAIL_SINGLE=$v: python bench.py --full --steps 5 --warmup 1 --no-ipm --no-cpu-baseline"
+  PIPS_HIP_TAIL_SINGLE=$v timeout 600 python bench.py --full --steps 5 --warmup 1 --no-ipm --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('ms per unit', d['ms_per_step'], '| leaf factorisation', d['phase_ms']['leaf_factor'], '| solves measured / failed', d['config']['solve_checks'])"
 done
 echo "## per-task digest of one single-launch factorisation (PIPS_HIP_TAIL_TRACE, tools/tail_trace.py; the traced run also copies the trace out)"
-PIPS_HIP_TAIL_SINGLE=1 PIPS_HIP_TAIL_TRACE=$R/gpurun_out/_tailtrace.txt timeout 600 python bench.py --steps 1 --warmup 1 --no-ipm --no-cpu-baseline > /dev/null 2>&1
+PIPS_HIP_TAIL_SINGLE=1 PIPS_HIP_TAIL_TRACE=$R/${O%/*}/_tailtrace.txt timeout 600 python bench.py --full --steps 1 --warmup 1 --no-ipm --no-cpu-baseline > /dev/null 2>&1
 python tools/tail_trace.py gpurun_out/_tailtrace.txt
 rm -f gpurun_out/_tailtrace.txt
 } > $O 2>&1

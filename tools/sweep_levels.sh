@@ -1,7 +1,7 @@
 # GPU box: the launches of one forward and one backward head sweep on the configs[3] shape, level by level (supernodes, microseconds)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kp -o k -- python3 $R/bench.py --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --no-ipm --steps 2 --warmup 1 > /dev/null 2>&1
+rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kp -o k -- python3 $R/bench.py --full --family time-coupled --blocks-per-gpu 256 --n 50000 --no-cpu-baseline --no-ipm --steps 2 --warmup 1 > /dev/null 2>&1
 python3 - <<PY
 import csv,glob,re
 f=glob.glob('/tmp/kp/**/*kernel_trace.csv', recursive=True)[0]

@@ -1,7 +1,7 @@
 # GPU box: the tail factorisation of configs[1] launch by launch (one factorisation): update / diagonal / trsm kernels with start offsets, durations and the idle gaps of the main stream
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kp -o k -- python3 $R/bench.py --no-cpu-baseline --no-ipm --steps 1 --warmup 1 > /dev/null 2>&1
+rm -rf /tmp/kp; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kp -o k -- python3 $R/bench.py --full --no-cpu-baseline --no-ipm --steps 1 --warmup 1 > /dev/null 2>&1
 python3 - <<PY
 import csv,glob,re
 f=glob.glob('/tmp/kp/**/*kernel_trace.csv', recursive=True)[0]
