@@ -467,6 +467,9 @@ int pips_ipm_get_trace(void* handle, double* rows7, int max_rows, int* n_rows);
  * stats2: [0] BiCGStab iterations, [1] host synchronisations (scalar read-backs) */
 int pips_ipm_get_stats(void* handle, long long* stats4);
 int pips_ipm_get_stats2(void* handle, long long* stats2);
+/* how the leaves form their Schur contribution, as analyzed (pips_hip_batch_get_schur_mode: 1 augmented factorisation, 2 blocked solves).
+ * pips_ipm_create reads PIPS_IPM_SCHUR_MODE (0 auto, 1, 2; unset: the batch's default) before it analyzes */
+int pips_ipm_get_schur_mode(void* handle, int* mode);
 /* direct entries to the rows either side of the path, for parity tests.  pips_ipm_mult: out = J in (transposed = 0; in: nx, out:
  * my + mz = [A x | C x]) or out = J^T in (transposed = 1) - DistributedMatrix::mult / transpose_mult; with several ranks the
  * replicated rows are summed.  pips_ipm_outer_solve: factorises with the diagonals of the pair vectors G = [t|u|v|w],

@@ -465,6 +465,7 @@ struct TailCtx {
    int n_groups = 0, first_slot = 0;
    long long sc_len = 0;                // sparse Schur complement: length of its value array (one group buffer)
    bool det_defer_reduce = false;       // several ranks: the group buffers are added over ALL ranks' groups in one fixed tree by the caller
+   bool det_reduce_later = false;       // Schur mode 2: the blocked solves fill the group buffers after the tail; Engine::factor adds them then
    SweepRt* sweep = nullptr;            // single-launch solve sweeps
    bool bunch_kaufman = false;          // diagonal tiles with 1 x 1 / 2 x 2 pivoting (k_tile_diag_bk) instead of the static pivot order
    int *d_pert_cnt = nullptr, *d_pert_list = nullptr;   // ... and where they record the indices no pivot was found for inside the tile
@@ -476,6 +477,18 @@ struct TailCtx {
 };
 constexpr int GEMM_CTR_SLOTS = 4096;
 constexpr int GEMM_BAL_MIN_TASKS = 1024;   // below two full rounds of the chip a static one-task-per-workgroup launch does as well
+
+// deterministic mode: the group buffers into SC in the fixed tree of k_reduce_groups (unless the caller adds all ranks' groups itself)
+static void reduce_det_groups(const TailCtx& c, double* SC, int ldSC) {
+   const int S_ = ldSC;
+   if (c.det_defer_reduce) {
+   } else if (c.d_sctab)   // sparse Schur complement: the value array as one column
+      hipLaunchKernelGGL(k_reduce_groups, dim3((unsigned)std::max(1LL, std::min(1024LL, (c.sc_len + 255) / 256)), 1), dim3(256), 0, c.stream, SC, 0, (int)c.sc_len,
+                         c.d_gbuf, c.gstride, c.n_groups, c.first_slot);
+   else
+      hipLaunchKernelGGL(k_reduce_groups, dim3(std::max(1, std::min(64, (S_ + 255) / 256)), S_), dim3(256), 0, c.stream, SC, ldSC, S_, c.d_gbuf,
+                         c.gstride, c.n_groups, c.first_slot);
+}
 
 static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
    const TailPlan& p = *c.plan;
@@ -627,14 +640,7 @@ static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
          if (l.cnt > 0)
             hipLaunchKernelGGL(k_tile_gemm<2>, dim3((l.cnt + 7) / 8 * 8), dim3(512), 0, c.stream, c.d_det_tasks + l.off, l.cnt, c.d_blks, c.d_arena,
                                c.d_dtail, c.d_winv, c.d_bmap, SC, ldSC, c.d_sctab, c.d_uarena, c.d_gbuf, c.gstride, c.d_blk_group);
-      const int S_ = ldSC;
-      if (c.det_defer_reduce) {
-      } else if (c.d_sctab)   // sparse Schur complement: the value array as one column
-         hipLaunchKernelGGL(k_reduce_groups, dim3((unsigned)std::max(1LL, std::min(1024LL, (c.sc_len + 255) / 256)), 1), dim3(256), 0, c.stream, SC, 0, (int)c.sc_len,
-                            c.d_gbuf, c.gstride, c.n_groups, c.first_slot);
-      else
-         hipLaunchKernelGGL(k_reduce_groups, dim3(std::max(1, std::min(64, (S_ + 255) / 256)), S_), dim3(256), 0, c.stream, SC, ldSC, S_, c.d_gbuf,
-                            c.gstride, c.n_groups, c.first_slot);
+      if (!c.det_reduce_later) reduce_det_groups(c, SC, ldSC);
       if (c.timer) c.timer->end(c.stream);
    } else if (SC && c.sc_groups && !c.d_sctab) {
       if (c.timer) c.timer->begin(c.stream, 5);
@@ -2105,7 +2111,6 @@ struct Engine {
       return PIPS_OK;
    }
    int build_deterministic(int n_threads) {
-      if (schur_mode_eff != 1) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode needs Schur mode 1 (augmented factorisation)");
       if (spine_total > 0) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode: spine kernels must be off");
       const int nlev = (int)levels.size();
       g_levels.assign(nlev, GatherList());
@@ -2117,7 +2122,7 @@ struct Engine {
          long long* d_rec = nullptr;
          HIP_TRY(hipMalloc((void**)&d_rec, (size_t)slots_total * sizeof(long long)));
          HIP_TRY(hipMemsetAsync(d_rec, 0xff, (size_t)slots_total * sizeof(long long), stream));
-         double* fakeSC = d_arena;   // only offsets relative to it are formed (S > 0 blocks have border rows)
+         double* fakeSC = d_arena;   // only offsets relative to it are formed (S > 0 blocks have border rows; none in Schur mode 2, whose heads have no border)
          const ScatterCtx sx{1, d_rec, nullptr, d_arena, fakeSC};
          for (const LevelRange& L : levels) launch_head_level(L, fakeSC, S, sx);
          HIP_TRY(hipGetLastError());
@@ -2316,6 +2321,7 @@ struct Engine {
       hipLaunchKernelGGL(k_pref_tail, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_arena, d_pref, 0);
       HIP_TRY(hipGetLastError());
       TailCtx c = ctx();
+      c.det_reduce_later = schur_mode_eff == 2;   // (deterministic mode 2: the group buffers are filled by schur_by_solves, below)
       int rc = tail_factor(c, SC, ldSC);
       if (rc) return rc;
       factored = true;
@@ -2326,6 +2332,7 @@ struct Engine {
          if (timer.on) timer.end(stream);
          if (rc) return rc;
       }
+      if (SC && c.det_rounds && c.det_reduce_later) reduce_det_groups(c, SC, ldSC);   // one fixed-tree add, after every chunk
       if (timer.on) (void)hipEventRecord(timer.recs[total_rec].b, stream);
       h_amax.clear();
       if (!h_inertia_pin) {
@@ -2342,16 +2349,35 @@ struct Engine {
       return PIPS_OK;
    }
 
-   // SC -= sum_b Br_b^T K_b^-1 Br_b, chunk by chunk of 32 border columns: densify, solve (all blocks at once), multiply back
+   // SC -= sum_b Br_b^T K_b^-1 Br_b, chunk by chunk of 32 border columns: densify, solve (all blocks at once), multiply back.
+   // Deterministic mode: into the group buffers instead (k_border_tmult_chunk_det; Engine::factor adds them in the fixed tree afterwards), the
+   // chunk solved by the atomics-free sweeps - one interleaved panel (solve_once_multi, whole-panel slicing whatever the launch size) where its
+   // forward-substitution slots fit, else column by column.  A column's solution then depends on its own right-hand side only, not on the lane
+   // or chunk it lands in nor on the other blocks, so its bits do not change with the rank count
    int schur_by_solves(double* SC, int ldSC) {
       int rc = ensure_multi_buffers();
       if (rc) return rc;
+      const bool det = deterministic && d_gbuf;
+      if (det && ldSC != S) PIPS_FAIL(PIPS_ERR_ARG, "deterministic mode, Schur mode 2: ldSC %d must equal S %d (the group buffers are S x S)", ldSC, S);
+      const bool det_panel = det && det_panel_fits();
+      if (det_panel && !d_mvslot) HIP_TRY(hipMalloc((void**)&d_mvslot, (size_t)std::max<long long>(vslots_total, 1) * MQ * sizeof(double)));
       const int bs = 32, ncols = (int)schur_cols.size();
       for (int c0 = 0; c0 < ncols; c0 += bs) {
          const int nr = std::min(bs, ncols - c0);
          HIP_TRY(hipMemsetAsync(d_mx_rhs, 0, (size_t)nr * n_total * sizeof(double), stream));
          hipLaunchKernelGGL(k_border_rows_to_dense, dim3(grid_for(bt_rows_total, 256)), dim3(256), 0, stream, d_bt_rowptr, d_bt_colidx,
                             d_bval, d_bt_rowsc, d_bt_xoff, d_schur_slot, c0, nr, d_mx_rhs, n_total, bt_rows_total);
+         if (det) {
+            if (det_panel) rc = solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw, 1);
+            else
+               for (int r = 0; r < nr && !rc; ++r) rc = solve_once(d_mx_rhs + (long long)r * n_total);
+            if (rc) return rc;
+            if (g_btm_grp.n_targets > 0)
+               hipLaunchKernelGGL(k_border_tmult_chunk_det, dim3(grid_for(g_btm_grp.n_targets * 32, 256)), dim3(256), 0, stream, g_btm_grp.n_targets,
+                                  g_btm_grp.d_tgt, g_btm_grp.d_off, g_btm_grp.d_slots, d_bt_rowptr, d_bt_colidx, d_bval, d_bt_xoff, d_schur_cols + c0, nr,
+                                  d_mx_rhs, n_total, d_gbuf, det_gstride(), S, ldSC);
+            continue;
+         }
          if ((rc = use_multi(nr) ? solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw) : solve_once(d_mx_rhs, nr, n_total, d_mx_xw))) return rc;
          hipLaunchKernelGGL(k_border_tmult_chunk, dim3(grid_for(bt_rows_total, 256, 1024), nr), dim3(256), 0, stream, d_bt_rowptr,
                             d_bt_colidx, d_bval, d_bt_rowsc, d_bt_xoff, d_schur_cols + c0, nr, d_mx_rhs, n_total, SC, ldSC,
@@ -2360,6 +2386,9 @@ struct Engine {
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
    }
+   // deterministic blocked solves: the slots of one interleaved panel (MQ doubles per forward-substitution contribution of the head) within 4 GB, as
+   // solve_multi's budget.  (A rank's contributions are a part of the one-rank total: where one rank takes the panels, every rank count does)
+   bool det_panel_fits() const { return head_slots && (double)std::max<long long>(vslots_total, 1) * MQ * sizeof(double) <= 4e9; }
 
    // workgroups per block of the vector norms: slices of about 16 K rows, the launch kept near the number resident at once
    int absmax_chunks() const { return (int)std::max<long long>(1, std::min<long long>(std::min<long long>(64, 2048 / std::max(nblk, 1) + 1), n_total / std::max(nblk, 1) / 16384 + 1)); }
@@ -2462,7 +2491,7 @@ struct Engine {
 
    // nr right-hand sides at X + q * x_stride in one interleaved sweep (kernels.hip.h "multi-vector solves"): panels of MQ, every launch
    // takes all of them (grid.y / grid.z); xm holds ceil(nr / MQ) * MQ * xw_total doubles
-   int solve_once_multi(double* X, int nr, long long x_stride, double* xm) {
+   int solve_once_multi(double* X, int nr, long long x_stride, double* xm, int pin_slices = 0) {
       const int np = (nr + MQ - 1) / MQ;
       const long long ps = (long long)MQ * xw_total;
       const dim3 pg(64, nblk, np);
@@ -2477,16 +2506,18 @@ struct Engine {
          // forward substitution without atomics, like solve_once's: every contribution of a supernode goes to its slot (MQ right-hand sides
          // wide: d_mvslot, one panel at a time), every level first takes what the lower levels left for its columns, in the recorded order;
          // the simple leaves by target row where that list exists.  One panel per call (the caller cuts the right-hand sides into panels).
+         // (k_mgather_slots / k_mleaf_fwd_gather take one target per 32 threads and no grid stride: their grids are not capped - with the
+         //  4096-workgroup cap of grid_for the targets beyond 32 768 were dropped, which a batch of configs[1] blocks reaches)
          if (np != 1 || !d_mvslot) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode: several right-hand sides go panel by panel");
          auto mgather = [&](const GatherList& g) {
             if (g.n_targets > 0)
-               hipLaunchKernelGGL(k_mgather_slots, dim3(grid_for(g.n_targets * 32, 256)), dim3(256), 0, stream, g.n_targets, g.d_tgt, g.d_off, g.d_slots, d_mvslot, xm);
+               hipLaunchKernelGGL(k_mgather_slots, dim3(grid_for(g.n_targets * 32, 256, INT32_MAX)), dim3(256), 0, stream, g.n_targets, g.d_tgt, g.d_off, g.d_slots, d_mvslot, xm);
          };
          for (size_t li = 0; li < levels.size(); ++li) {
             const LevelRange& L = levels[li];
             mgather(gv_levels[li]);
             if (L.simple_cnt > 0 && lf_rows > 0)
-               hipLaunchKernelGGL(k_mleaf_fwd_gather, dim3(grid_for(lf_rows * 32, 256)), dim3(256), 0, stream, d_lf_rows, d_lf_ptr, d_lf_src, d_lf_val, xm, (int)lf_rows);
+               hipLaunchKernelGGL(k_mleaf_fwd_gather, dim3(grid_for(lf_rows * 32, 256, INT32_MAX)), dim3(256), 0, stream, d_lf_rows, d_lf_ptr, d_lf_src, d_lf_val, xm, (int)lf_rows);
             else if (L.simple_cnt > 0)
                hipLaunchKernelGGL(k_mhead, dim3((L.simple_cnt + 3) / 4, 1), dim3(256), 0, stream, d_sns, L.simple_begin, L.simple_cnt, d_blks, d_rowidx, d_arena, xm, 0, ps,
                                   d_mvslot);
@@ -2508,7 +2539,8 @@ struct Engine {
       // finest slicing that keeps the launch within 512 workgroups is taken
       const long long wg = (long long)sweep.n_tasks * np;
       const int forced = env_int("PIPS_HIP_MULTI", 1);   // (2: whole panels whatever the size, 4: half panels - tests)
-      const int sl = forced == 2 ? 1 : forced == 4 ? 2 : wg * 4 <= 512 ? 4 : wg * 2 <= 512 ? 2 : 1;
+      // (pin_slices: a fixed slicing - the blocked Schur solves of deterministic mode, whose bits must not follow sweep.n_tasks, i.e. the blocks per rank)
+      const int sl = pin_slices ? pin_slices : forced == 2 ? 1 : forced == 4 ? 2 : wg * 4 <= 512 ? 4 : wg * 2 <= 512 ? 2 : 1;
       auto tail_rows = [&](int backward) {
          const SweepArgs sa = sweep.args(0, stream);
          if (sl == 4 && !backward) hipLaunchKernelGGL(k_mtail_rows_fwd<2>, dim3(sweep.n_tasks, np * 4), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);

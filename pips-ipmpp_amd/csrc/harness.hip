@@ -1485,6 +1485,14 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
       PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: the sparse root needs the border column sets of all blocks on every rank (pips_hip_kkt_create_sparse); "
                               "the harness passes only its own - use the dense root with several ranks");
    if (sparse_root && (rc = pips_hip_batch_set_schur_mode(p->batch, 1))) return rc;
+   // PIPS_IPM_SCHUR_MODE: how the leaves form their Schur contribution (pips_hip_batch_set_schur_mode: 0 auto, 1 augmented factorisation,
+   // 2 blocked solves - the reference's SC_COMPUTE_BLOCKWISE); unset: the batch's default
+   if (const char* sm = getenv("PIPS_IPM_SCHUR_MODE")) {
+      const int mode = atoi(sm);
+      if (mode < 0 || mode > 2) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: PIPS_IPM_SCHUR_MODE=%s (0 auto, 1 augmented, 2 blocked solves)", sm);
+      if (sparse_root && mode == 2) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: the sparse root needs Schur mode 1, PIPS_IPM_SCHUR_MODE=2 asks for blocked solves");
+      if (!sparse_root && (rc = pips_hip_batch_set_schur_mode(p->batch, mode))) return rc;
+   }
    if ((rc = pips_hip_batch_analyze(p->batch, 16))) return rc;
    for (int i = 0; i < N; ++i)
       if ((rc = pips_hip_batch_set_values(p->batch, i, kvals[i].data()))) return rc;
@@ -1779,6 +1787,12 @@ int pips_ipm_get_stats(void* handle, long long* stats4) {
    if (!p || !stats4) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_get_stats: bad arguments");
    stats4[0] = p->n_factorize; stats4[1] = p->n_regularised + p->n_refactor_outer; stats4[2] = p->n_precond; stats4[3] = p->n_gondzio;
    return PIPS_OK;
+}
+
+int pips_ipm_get_schur_mode(void* handle, int* mode) {
+   Ipm* p = (Ipm*)handle;
+   if (!p || !mode) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_get_schur_mode: bad arguments");
+   return pips_hip_batch_get_schur_mode(p->batch, mode);
 }
 
 int pips_ipm_get_stats2(void* handle, long long* stats2) {

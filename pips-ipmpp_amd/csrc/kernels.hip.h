@@ -3665,6 +3665,38 @@ __global__ void k_border_tmult_chunk(const int* __restrict__ rowptr, const int* 
    }
 }
 
+// deterministic mode: the same product group by group, without atomics.  Target t of Engine::g_btm_grp is g S + srow and lists the border
+// rows of group g on Schur row srow, ascending (= block order); for right-hand side r of the chunk (Schur column col = chunk_cols[r], srow >= col)
+//   gbuf[g gstride + srow + col ldSC] = -sum over the list, in list order, of the row's dot with X_r in CSR order
+// A plain store: every (group, entry) has one target and one chunk.  Half a wave per target, a lane per right-hand side.
+__global__ __launch_bounds__(256) void k_border_tmult_chunk_det(long long n_targets, const long long* __restrict__ tgt, const long long* __restrict__ off,
+                                                               const long long* __restrict__ rows, const int* __restrict__ rowptr,
+                                                               const int* __restrict__ colidx, const double* __restrict__ val,
+                                                               const long long* __restrict__ row_xoff, const int* __restrict__ chunk_cols, int nr,
+                                                               const double* __restrict__ X, long long x_stride, double* __restrict__ gbuf,
+                                                               long long gstride, int S, int ldSC) {
+   const int r = threadIdx.x & 31;
+   if (r >= nr) return;
+   const int col = chunk_cols[r];
+   const double* x = X + r * x_stride;
+   const long long step = ((long long)gridDim.x * blockDim.x) >> 5;
+   for (long long t = (blockIdx.x * (long long)blockDim.x + threadIdx.x) >> 5; t < n_targets; t += step) {
+      const long long tg = tgt[t];
+      const long long g = tg / S;
+      const int srow = (int)(tg - g * S);
+      if (srow < col) continue;
+      double s = 0.0;
+      for (long long p = off[t]; p < off[t + 1]; ++p) {
+         const long long i = rows[p];
+         const long long xo = row_xoff[i];
+         double d = 0.0;
+         for (int q = rowptr[i]; q < rowptr[i + 1]; ++q) d += val[q] * x[xo + colidx[q]];
+         s += d;
+      }
+      gbuf[g * gstride + srow + (long long)col * ldSC] = -s;
+   }
+}
+
 // dense helpers for the root system
 __global__ void k_copy_lower_to_padded(const double* __restrict__ src, int lds, int n, double* __restrict__ dst, int ldd,
                                        int npad, int rowmajor, const int* __restrict__ perm = nullptr) {
