@@ -478,6 +478,31 @@ int pips_ipm_get_schur_mode(void* handle, int* mode);
  * 3 max iterations, 4 breakdown, 5 diverged, 6 stagnation), iterations, ||r||_2, ||rhs||_2, preconditioner applications, host
  * synchronisations} */
 int pips_ipm_mult(void* handle, int transposed, const double* in_host, double* out_host);
+/* Problem scaling (the reference's Scaler stage, ScalerType in Core/Preprocessing/PreprocessType.h; same order).  Curtis-Reid is
+ * reserved and not supported. */
+enum {
+   PIPS_SCALER_NONE = 0,
+   PIPS_SCALER_EQUILIBRIUM = 1,             /* EquilibriumScaler: one pass, max |entry| of every row and column becomes 1 */
+   PIPS_SCALER_GEOMETRIC_MEAN = 2,          /* GeometricMeanScaler: up to 10 passes of 1 / sqrt(min max), kept if it gains 15 % */
+   PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM = 3,   /* the same followed by an equilibrium pass */
+   PIPS_SCALER_CURTIS_REID = 4              /* reserved: PIPS_ERR_ARG */
+};
+/* pips_ipm_create_general with a scaler, chosen at creation (the leaf borders are fixed by the analysis).  J = [A; C] becomes
+ * R J Cs with R = diag(row_eq, row_ineq) and Cs = diag(col); c, b, the row and variable bounds and the linking right-hand sides
+ * follow (Scaler::applyScaling: c Cs, R b, R clow, R cupp, xlow / col, xupp / col); the objective is not scaled separately.
+ * The extrema sweeps run on the device.  pips_ipm_solve terminates on the UNSCALED residual (Scaler::unscale_residuals) against
+ * the data norm of the original problem, which result7[3] / [6] and the trace report; the start point uses the data norm of the
+ * scaled problem.  pips_ipm_get_solution / pips_ipm_get_iterate return the original problem's variables
+ * (Scaler::unscale_variables).  pips_ipm_mult and pips_ipm_outer_solve act on the system as the harness holds it: the scaled
+ * one.  PIPS_SCALER_NONE gives exactly pips_ipm_create_general. */
+int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL,
+                                   const double* dlow, const double* dupp, const double* idlow, const double* idupp, double dual_reg,
+                                   int device, void* comm, int rank, int n_ranks, int scaler);
+/* the factors in the harness order: col (nx) for x = [x0 | own blocks], row_eq (my) and row_ineq (mz) for [root | linking | own
+ * blocks]; any pointer may be NULL.  info8 = {scaling applied (0/1), row ratio before, column ratio before, row ratio after,
+ * column ratio after, geometric passes made, geometric stage kept (0/1), host waits of the scaler}.  A handle without scaling
+ * returns factors of 1 and zeros in info8. */
+int pips_ipm_get_scaling(void* handle, double* col, double* row_eq, double* row_ineq, double* info8);
 int pips_ipm_outer_solve(void* handle, const double* G_host, const double* L_host, const double* rhs_host, double tol, double* sol_host,
                          double* info6);
 void pips_ipm_destroy(void* handle);

@@ -33,6 +33,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <memory>
 #include <string>
 #include <vector>
@@ -213,7 +214,11 @@ __global__ __launch_bounds__(256) void k_multi_reduce(RedPack pk, double* __rest
          if (t.w) sweep([&](long long i) { return t.a[i] * t.b[i] * t.w[i]; });
          else sweep([&](long long i) { return t.a[i] * t.b[i]; });
          break;
-      case R_ABSMAX: sweep([&](long long i) { return fabs(t.a[i]); }); break;
+      case R_ABSMAX:   // w: max |a w|; d: max |a / d| (the unscaled residuals of a scaled problem, Scaler::unscale_residuals)
+         if (t.w) sweep([&](long long i) { return fabs(t.a[i] * t.w[i]); });
+         else if (t.d) sweep([&](long long i) { return fabs(t.a[i] / t.d[i]); });
+         else sweep([&](long long i) { return fabs(t.a[i]); });
+         break;
       case R_MIN_MASKED: sweep([&](long long i) { return t.c[i] != 0.0 ? t.a[i] : (double)INFINITY; }); break;
       case R_STEPBOUND: sweep([&](long long i) { return t.b[i] < 0.0 ? -t.a[i] / t.b[i] : (double)INFINITY; }); break;
       default:
@@ -245,6 +250,132 @@ __global__ __launch_bounds__(256) void k_multi_reduce_final(RedPack pk, int grid
       __syncthreads();
    }
    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// problem scaling (Scaler.cpp, EquilibriumScaler.C, GeometricMeanScaler.C).  One sweep is getRowMinMaxVec over the rows of J with the
+// column factors (or getColMinMaxVec: the rows of J^T with the row factors): per row the min of |a_ij s_j| over the entries above
+// pips_eps and the max of all of them (SparseStorage.C:1703-1773: min starts at DBL_MAX, max at 0).  Its epilogue is the ratio
+// max / min (divideSome) and, for SC_EQUI / SC_GEO, the new factor safe_invert(1.0) of max or of sqrt(max min) (applyGeoMean,
+// invertAndRound without rounding); the row ratios are reduced to their maximum in partials per workgroup and one finishing
+// workgroup.  Min and max do not depend on the order: the factors are bitwise reproducible and independent of the rank count.
+// Several ranks: the replicated rows (root and linking rows of J, x0 rows of J^T) hold local contributions only; the sweep then
+// stores the extrema, they are combined over the ranks, and the epilogue runs as a kernel of its own.
+// ---------------------------------------------------------------------------------------------------------------------------
+enum ScaleOp : int { SC_RATIO = 0, SC_EQUI, SC_GEO };
+constexpr double SC_EPS = 1e-13;                          // pips_eps (pipsdef.h:34)
+constexpr double SC_NO_ENTRY = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
+struct ScaleArgs {
+   int nrows;
+   const int* rp; const int* ci; const double* v;
+   const double* sc;       // factors of the other direction (nullptr: 1)
+   double *mn, *mx;        // extrema per row (deferred epilogue)
+   double* fac;            // factors written by SC_EQUI / SC_GEO
+   double* partial;        // ratio maximum per workgroup
+   int op, fuse;
+};
+__device__ __forceinline__ double sc_epilogue(const ScaleArgs& a, int r, double mn, double mx) {
+   if (a.op != SC_RATIO) {
+      const double g = a.op == SC_GEO ? sqrt(mx * mn) : mx;
+      a.fac[r] = g != 0.0 ? 1.0 / g : 1.0;
+   }
+   return mn != 0.0 ? mx / mn : mx;
+}
+__device__ __forceinline__ void sc_entry(const ScaleArgs& a, int p, double& mn, double& mx) {
+   const double t = fabs(a.sc ? a.v[p] * a.sc[a.ci[p]] : a.v[p]);
+   if (t < mn && t > SC_EPS) mn = t;
+   if (t > mx) mx = t;
+}
+__device__ __forceinline__ void sc_block_max(double r, double* out) {
+   __shared__ double red[256];
+   red[threadIdx.x] = r;
+   __syncthreads();
+   for (int k = 128; k > 0; k >>= 1) {
+      if ((int)threadIdx.x < k) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + k]);
+      __syncthreads();
+   }
+   if (threadIdx.x == 0) *out = red[0];
+}
+// a thread per row of at most CSR_LONG_ROW entries
+__global__ __launch_bounds__(256) void k_scale_sweep(ScaleArgs a) {
+   double rmax = 0.0;
+   for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < a.nrows; r += (long long)gridDim.x * blockDim.x) {
+      const int b = a.rp[r], e = a.rp[r + 1];
+      if (e - b > CSR_LONG_ROW) continue;   // k_scale_sweep_long
+      double mn = SC_NO_ENTRY, mx = 0.0;
+      for (int p = b; p < e; ++p) sc_entry(a, p, mn, mx);
+      if (a.fuse) rmax = fmax(rmax, sc_epilogue(a, (int)r, mn, mx));
+      else { a.mn[r] = mn; a.mx[r] = mx; }
+   }
+   if (a.fuse) sc_block_max(rmax, a.partial + blockIdx.x);
+}
+// a workgroup per long row (the linking rows of J, the x0 rows of J^T); its partial follows the short rows' ones at part0
+__global__ __launch_bounds__(256) void k_scale_sweep_long(ScaleArgs a, const int* __restrict__ long_rows, int part0) {
+   __shared__ double smn[256], smx[256];
+   const int r = long_rows[blockIdx.x];
+   double mn = SC_NO_ENTRY, mx = 0.0;
+   for (int p = a.rp[r] + threadIdx.x; p < a.rp[r + 1]; p += 256) sc_entry(a, p, mn, mx);
+   smn[threadIdx.x] = mn; smx[threadIdx.x] = mx;
+   __syncthreads();
+   for (int k = 128; k > 0; k >>= 1) {
+      if ((int)threadIdx.x < k) {
+         smn[threadIdx.x] = fmin(smn[threadIdx.x], smn[threadIdx.x + k]);
+         smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + k]);
+      }
+      __syncthreads();
+   }
+   if (threadIdx.x != 0) return;
+   if (a.fuse) a.partial[part0 + blockIdx.x] = sc_epilogue(a, r, smn[0], smx[0]);
+   else { a.mn[r] = smn[0]; a.mx[r] = smx[0]; }
+}
+// deferred epilogue over every row (several ranks, after the extrema of the replicated rows have been combined)
+__global__ __launch_bounds__(256) void k_scale_epilogue(ScaleArgs a) {
+   double rmax = 0.0;
+   for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < a.nrows; r += (long long)gridDim.x * blockDim.x)
+      rmax = fmax(rmax, sc_epilogue(a, (int)r, a.mn[r], a.mx[r]));
+   sc_block_max(rmax, a.partial + blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_scale_ratio_final(const double* __restrict__ partial, int n, double* __restrict__ out) {
+   double r = 0.0;
+   for (int i = threadIdx.x; i < n; i += 256) r = fmax(r, partial[i]);
+   sc_block_max(r, out);
+}
+// replicated rows k of [0, n_a) and [b0, b0 + n_b): one slot pair per rank in a vector the ranks sum (take = 0), then min / max over
+// the ranks' slots (take = 1)
+__global__ void k_scale_rep(int take, int n_a, int b0, int n_b, int rank, int n_ranks, double* __restrict__ mn, double* __restrict__ mx,
+                            double* __restrict__ slots) {
+   const int nrep = n_a + n_b;
+   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nrep; k += gridDim.x * blockDim.x) {
+      const int r = k < n_a ? k : b0 + (k - n_a);
+      if (!take) {
+         slots[2 * ((long long)rank * nrep + k)] = mn[r];
+         slots[2 * ((long long)rank * nrep + k) + 1] = mx[r];
+      } else {
+         double a = SC_NO_ENTRY, b = 0.0;
+         for (int q = 0; q < n_ranks; ++q) {
+            a = fmin(a, slots[2 * ((long long)q * nrep + k)]);
+            b = fmax(b, slots[2 * ((long long)q * nrep + k) + 1]);
+         }
+         mn[r] = a; mx[r] = b;
+      }
+   }
+}
+// in-place scaling of the CSR copy of J (v = (v col_j) row_i: applyScaling's columnScale, then rowScale) or of J^T (its rows are
+// columns): a thread per short row (long_rows == nullptr), a workgroup per long row
+__global__ __launch_bounds__(256) void k_scale_csr(int nrows, int transposed, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                   double* __restrict__ v, const double* __restrict__ col, const double* __restrict__ row,
+                                                   const int* __restrict__ long_rows) {
+   if (long_rows) {
+      const int r = long_rows[blockIdx.x];
+      for (int p = rp[r] + threadIdx.x; p < rp[r + 1]; p += 256)
+         v[p] = transposed ? (v[p] * col[r]) * row[ci[p]] : (v[p] * col[ci[p]]) * row[r];
+      return;
+   }
+   for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < nrows; r += (long long)gridDim.x * blockDim.x) {
+      const int b = rp[r], e = rp[r + 1];
+      if (e - b > CSR_LONG_ROW) continue;
+      for (int p = b; p < e; ++p) v[p] = transposed ? (v[p] * col[r]) * row[ci[p]] : (v[p] * col[ci[p]]) * row[r];
+   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -771,8 +902,17 @@ struct Ipm {
       pk.t[5] = term(R_DOT, my, bA, it.y, nullptr, nullptr, wY);         // b^T y
       pk.t[6] = term(R_DOT, ncp, Bd, it.L, nullptr, nullptr, wGs);       // clow^T lambda - cupp^T pi + xlow^T gamma - xupp^T phi (signs in wGs)
       pk.t[7] = term(R_DOT, ncp, it.G, it.L, nullptr, nullptr, wG);      // complementarity
-      double o[8];
+      if (scaled) {   // the norm tested and reported is the unscaled one (Scaler::unscale_residuals, Scaler.cpp:57-86), same launch
+         pk.t[0] = term(R_ABSMAX, nx, rQ, nullptr, nullptr, sc_col);                      // rQ / col
+         pk.t[1] = term(R_ABSMAX, my + mz, rAC, nullptr, nullptr, sc_row);                // [rA / row_eq | rC / row_ineq]
+         pk.t[2] = term(R_ABSMAX, mz, rz, nullptr, nullptr, nullptr, sc_row + my);        // rz * row_ineq
+         pk.t[3] = term(R_ABSMAX, 2LL * mz, rG, nullptr, nullptr, sc_ri2);                // [rt | ru] / row_ineq
+         pk.t[8] = term(R_ABSMAX, 2LL * nx, rG + 2LL * mz, nullptr, nullptr, nullptr, sc_col2);   // [rv | rw] * col
+         pk.n_terms = 9;
+      }
+      double o[9];
       TRY(reduce(pk, o));
+      if (scaled) o[3] = std::max(o[3], o[8]);
       *rnorm = std::max(std::max(o[0], o[1]), std::max(o[2], o[3]));
       for (int k = 0; k < 4; ++k) last_rparts[k] = o[k];
       *pobj = o[4];
@@ -1193,6 +1333,160 @@ struct Ipm {
       return PIPS_OK;
    }
 
+   // J, J^T and their long-row lists to the device
+   template <class H>
+   int upload_J(const H& h) {
+      std::vector<int> la, lat;
+      for (int r = 0; r < my + mz; ++r) if (h.rp[r + 1] - h.rp[r] > CSR_LONG_ROW) la.push_back(r);
+      for (int r = 0; r < nx; ++r) if (h.trp[r + 1] - h.trp[r] > CSR_LONG_ROW) lat.push_back(r);
+      nJ_long = (int)la.size(); nJt_long = (int)lat.size();
+      J_nnz = h.rp[my + mz]; Jt_nnz = h.trp[nx];
+      la.push_back(0); lat.push_back(0);
+      TRY(up(&J_long, la)); TRY(up(&Jt_long, lat));
+      TRY(alloc(&long_scratch, (long long)std::max<size_t>(std::max(la.size(), lat.size()), 1) * LONG_PARTS));
+      TRY(up(&J_rp, h.rp)); TRY(up(&J_ci, h.ci)); TRY(up(&J_v, h.v));
+      TRY(up(&Jt_rp, h.trp)); TRY(up(&Jt_ci, h.tci)); TRY(up(&Jt_v, h.tv));
+      return PIPS_OK;
+   }
+
+   // ---- problem scaling (pips_ipm_create_general_scaled) --------------------------------------------------------------------------
+   bool scaled = false;                             // factors applied to the data the harness holds
+   double dnorm_orig = 1.0;                         // data norm of the original problem (termination); dnorm: the scaled one (start point)
+   double sc_info[8] = {0};                         // see pips_ipm_get_scaling
+   double *sc_col = nullptr, *sc_row = nullptr;     // factors on the device: col (nx), [row_eq | row_ineq] (my + mz)
+   double *sc_ri2 = nullptr, *sc_col2 = nullptr;    // [row_ineq | row_ineq], [col | col]: weights of the unscaled residual norm
+   double *sc_tcol = nullptr, *sc_trow = nullptr, *sc_mn = nullptr, *sc_mx = nullptr, *sc_part = nullptr, *sc_slots = nullptr, *sc_rat = nullptr;
+   std::vector<double> h_col, h_row;                // host copies of the factors
+   int sc_waits = 0;
+   int sc_alloc() {
+      const long long nr = (long long)my + mz, nrep = std::max<long long>(n0, (long long)ry + rzr);
+      TRY(alloc(&sc_col, nx)); TRY(alloc(&sc_row, nr)); TRY(alloc(&sc_tcol, nx)); TRY(alloc(&sc_trow, nr));
+      TRY(alloc(&sc_mn, std::max<long long>(nx, nr))); TRY(alloc(&sc_mx, std::max<long long>(nx, nr)));
+      TRY(alloc(&sc_part, 2048 + std::max(nJ_long, nJt_long)));
+      TRY(alloc(&sc_slots, 2 * nrep * n_ranks)); TRY(alloc(&sc_rat, 4));
+      return PIPS_OK;
+   }
+   // one getRowMinMaxVec / getColMinMaxVec sweep with its epilogue: transposed = false sweeps the rows of J with the column factors
+   // sc and writes row factors, transposed = true the reverse; the maximum row ratio goes to *ratio_dev
+   int sc_sweep(bool transposed, const double* sc, double* fac, int op, double* ratio_dev) {
+      ScaleArgs a;
+      a.nrows = transposed ? nx : my + mz;
+      a.rp = transposed ? Jt_rp : J_rp; a.ci = transposed ? Jt_ci : J_ci; a.v = transposed ? Jt_v : J_v;
+      a.sc = sc; a.mn = sc_mn; a.mx = sc_mx; a.fac = fac; a.partial = sc_part; a.op = op; a.fuse = n_ranks == 1;
+      const int g = egrid(a.nrows), nl = transposed ? nJt_long : nJ_long;
+      hipLaunchKernelGGL(k_scale_sweep, dim3(g), dim3(256), 0, stream, a);
+      if (nl > 0) hipLaunchKernelGGL(k_scale_sweep_long, dim3(nl), dim3(256), 0, stream, a, transposed ? Jt_long : J_long, g);
+      if (!a.fuse) {   // replicated rows: extrema over the ranks, one slot pair per rank of a summed vector
+         const int na = transposed ? n0 : ry, b0 = transposed ? 0 : my, nb = transposed ? 0 : rzr;
+         const long long ns = 2LL * (na + nb) * n_ranks;
+         if (ns > 0) {
+            HIP_TRYH(hipMemsetAsync(sc_slots, 0, ns * sizeof(double), stream));
+            hipLaunchKernelGGL(k_scale_rep, dim3(egrid(na + nb)), dim3(256), 0, stream, 0, na, b0, nb, rank, n_ranks, sc_mn, sc_mx, sc_slots);
+            TRY(pips_hip_allreduce_sum(comm, sc_slots, (size_t)ns, stream));
+            hipLaunchKernelGGL(k_scale_rep, dim3(egrid(na + nb)), dim3(256), 0, stream, 1, na, b0, nb, rank, n_ranks, sc_mn, sc_mx, sc_slots);
+         }
+         hipLaunchKernelGGL(k_scale_epilogue, dim3(g), dim3(256), 0, stream, a);
+      }
+      hipLaunchKernelGGL(k_scale_ratio_final, dim3(1), dim3(256), 0, stream, (const double*)sc_part, g + (a.fuse ? nl : 0), ratio_dev);
+      HIP_TRYH(hipGetLastError());
+      return PIPS_OK;
+   }
+   // the one host read of a (half-)pass: the row and column ratios in sc_rat[0..1], maxima over the ranks
+   int sc_read(double* r2) {
+      double h[2];
+      HIP_TRYH(hipMemcpyAsync(h, sc_rat, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+      HIP_TRYH(hipStreamSynchronize(stream));
+      ++sc_waits;
+      r2[0] = h[0]; r2[1] = h[1];
+      if (n_ranks > 1) {
+         std::vector<double> slots(2 * (size_t)n_ranks, 0.0);
+         slots[2 * rank] = h[0]; slots[2 * rank + 1] = h[1];
+         TRY(reduce_host(slots.data(), 2 * n_ranks));
+         for (int q = 0; q < n_ranks; ++q) { r2[0] = std::max(r2[0], slots[2 * q]); r2[1] = std::max(r2[1], slots[2 * q + 1]); }
+      }
+      return PIPS_OK;
+   }
+   // EquilibriumScaler::scale / GeometricMeanScaler::scale (with postEquiScale) on J, J^T as uploaded; with_sides false, no
+   // bit-shifting (PreprocessFactory::make_scaler).  Ends with the factors in h_col / h_row and J, J^T scaled in place.
+   int run_scaler(int type) {
+      const long long nr = (long long)my + mz;
+      sc_waits = 0;
+      auto ones = [&]() -> int { TRY(pips_hip_vec_set(nx, 1.0, sc_col, stream)); return pips_hip_vec_set(nr, 1.0, sc_row, stream); };
+      // postEquiScale: both ratios with the current factors, whose sweeps leave 1 / max in the spare vectors; the direction with the
+      // smaller ratio keeps its spare, the other one is swept again with it
+      auto post_equi = [&](double* rr) -> int {
+         TRY(sc_sweep(false, sc_col, sc_trow, SC_EQUI, sc_rat));
+         TRY(sc_sweep(true, sc_row, sc_tcol, SC_EQUI, sc_rat + 1));
+         TRY(sc_read(rr));
+         if (rr[1] < rr[0]) { std::swap(sc_col, sc_tcol); return sc_sweep(false, sc_col, sc_row, SC_EQUI, sc_rat + 2); }
+         std::swap(sc_row, sc_trow);
+         return sc_sweep(true, sc_row, sc_col, SC_EQUI, sc_rat + 2);
+      };
+      TRY(ones());
+      double r[2];
+      bool applied = false, kept = false;
+      int passes = 0;
+      if (type == PIPS_SCALER_EQUILIBRIUM) {   // from factors of 1 the ratios of postEquiScale are the ones before scaling
+         TRY(post_equi(r));
+         sc_info[1] = r[0]; sc_info[2] = r[1];
+         applied = true;
+      } else {
+         TRY(sc_sweep(false, nullptr, nullptr, SC_RATIO, sc_rat));
+         TRY(sc_sweep(true, nullptr, nullptr, SC_RATIO, sc_rat + 1));
+         TRY(sc_read(r));
+         const double rowratio = r[0], colratio = r[1];
+         sc_info[1] = rowratio; sc_info[2] = colratio;
+         const double minImpr = 0.85, goodEnough = 500.0;
+         const int maxIters = 10;
+         const bool colfirst = colratio < rowratio;
+         const double p0start = colfirst ? colratio : rowratio, p1start = colfirst ? rowratio : colratio;
+         bool geoscale = p1start > goodEnough;
+         if (geoscale) {
+            double p0 = 0.0, p1 = 0.0, p0prev = p0start, p1prev = p1start;
+            for (int i = 0; i < maxIters; ++i) {
+               if (colfirst) {
+                  TRY(sc_sweep(true, sc_row, sc_col, SC_GEO, sc_rat));
+                  TRY(sc_sweep(false, sc_col, sc_row, SC_GEO, sc_rat + 1));
+               } else {
+                  TRY(sc_sweep(false, sc_col, sc_row, SC_GEO, sc_rat));
+                  TRY(sc_sweep(true, sc_row, sc_col, SC_GEO, sc_rat + 1));
+               }
+               TRY(sc_read(r));
+               p0 = r[0]; p1 = r[1]; passes = i + 1;
+               if (p0 > minImpr * p0prev && p1 > minImpr * p1prev) break;
+               p0prev = p0; p1prev = p1;
+            }
+            geoscale = (p0 <= minImpr * p0start || p1 <= minImpr * p1start);
+         }
+         kept = geoscale;
+         if (geoscale || type == PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM) {
+            if (type == PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM) {
+               if (!geoscale) TRY(ones());
+               TRY(post_equi(r));
+            }
+            applied = true;
+         }
+      }
+      h_col.assign(nx, 1.0); h_row.assign(nr, 1.0);
+      sc_info[3] = sc_info[1]; sc_info[4] = sc_info[2];
+      if (!applied) TRY(ones());
+      else {
+         hipLaunchKernelGGL(k_scale_csr, dim3(egrid(nr)), dim3(256), 0, stream, (int)nr, 0, J_rp, J_ci, J_v, sc_col, sc_row, (const int*)nullptr);
+         if (nJ_long > 0) hipLaunchKernelGGL(k_scale_csr, dim3(nJ_long), dim3(256), 0, stream, (int)nr, 0, J_rp, J_ci, J_v, sc_col, sc_row, (const int*)J_long);
+         hipLaunchKernelGGL(k_scale_csr, dim3(egrid(nx)), dim3(256), 0, stream, nx, 1, Jt_rp, Jt_ci, Jt_v, sc_col, sc_row, (const int*)nullptr);
+         if (nJt_long > 0) hipLaunchKernelGGL(k_scale_csr, dim3(nJt_long), dim3(256), 0, stream, nx, 1, Jt_rp, Jt_ci, Jt_v, sc_col, sc_row, (const int*)Jt_long);
+         TRY(sc_sweep(false, nullptr, nullptr, SC_RATIO, sc_rat));   // printRowColRatio
+         TRY(sc_sweep(true, nullptr, nullptr, SC_RATIO, sc_rat + 1));
+         HIP_TRYH(hipMemcpyAsync(h_col.data(), sc_col, (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, stream));
+         HIP_TRYH(hipMemcpyAsync(h_row.data(), sc_row, (size_t)nr * sizeof(double), hipMemcpyDeviceToHost, stream));
+         TRY(sc_read(r));   // also the wait for the two copies
+         sc_info[3] = r[0]; sc_info[4] = r[1];
+      }
+      scaled = applied;
+      sc_info[0] = applied ? 1.0 : 0.0; sc_info[5] = passes; sc_info[6] = kept ? 1.0 : 0.0; sc_info[7] = sc_waits;
+      return PIPS_OK;
+   }
+
    int run(int max_iter, double mutol, double artol, int verbose, double* result) {
       HIP_TRYH(hipSetDevice(device));
       verbose_run = verbose = rank == 0 ? verbose : 0;
@@ -1231,15 +1525,16 @@ struct Ipm {
       double best_merit = INFINITY, best_rnorm = INFINITY, phi_min = INFINITY;
       int n_stall = 0, n_rstall = 0;
       double prev_rnorm = INFINITY;
-      auto merit = [&](double mm, double rr) { return std::max(mm / mutol, rr / (artol * dnorm)); };
+      // termination, merit and phi measure the original problem: dnorm_orig (PIPSIPMppSolver.cpp:13,113-126); equal to dnorm unscaled
+      auto merit = [&](double mm, double rr) { return std::max(mm / mutol, rr / (artol * dnorm_orig)); };
       for (; iter < max_iter; ++iter) {
          TRY(residuals(&rnorm, &pobj, &dobj, &m));
          const bool is_nan = !(m == m) || !(rnorm == rnorm) || !(pobj == pobj);
          // a step that throws the residual up by four orders of magnitude counts as a breakdown only late in the run (best iterate
          // within 1e3 of both tolerances): early on the outer solve's tolerance is relative to a right-hand side dominated by the
          // complementarity terms, and an absolute error of 1e-9 |rhs| in the linear rows is harmless and transient
-         const bool blown = !is_nan && best_merit < 1e3 && rnorm > 1e4 * std::max(best_rnorm, artol * dnorm);
-         n_rstall = (!is_nan && m <= 1e-3 * mutol && rnorm > artol * dnorm && rnorm >= 0.99 * prev_rnorm) ? n_rstall + 1 : 0;
+         const bool blown = !is_nan && best_merit < 1e3 && rnorm > 1e4 * std::max(best_rnorm, artol * dnorm_orig);
+         n_rstall = (!is_nan && m <= 1e-3 * mutol && rnorm > artol * dnorm_orig && rnorm >= 0.99 * prev_rnorm) ? n_rstall + 1 : 0;
          prev_rnorm = rnorm;
          if ((is_nan || blown || n_stall >= 2 || n_rstall >= 3) && best_merit < INFINITY) {
             if (verbose)
@@ -1248,7 +1543,7 @@ struct Ipm {
             TRY(pips_hip_vec_copy(NP + ND, best.base, it.base, stream));
             TRY(residuals(&rnorm, &pobj, &dobj, &m));
             trace.insert(trace.end(), {m, rnorm, pobj, dobj, 0.0, 0.0, 0.0});
-            status = (m <= mutol && rnorm <= artol * dnorm) ? 0 : 3;
+            status = (m <= mutol && rnorm <= artol * dnorm_orig) ? 0 : 3;
             break;
          }
          if (!is_nan && merit(m, rnorm) < best_merit) {
@@ -1263,9 +1558,9 @@ struct Ipm {
             fflush(stdout);
          }
          if (is_nan) { status = 2; break; }
-         if (m <= mutol && rnorm <= artol * dnorm) { status = 0; break; }   // PIPSIPMppSolver.cpp:143-149
+         if (m <= mutol && rnorm <= artol * dnorm_orig) { status = 0; break; }   // PIPSIPMppSolver.cpp:143-149
          {  // "probably infeasible" (PIPSIPMppSolver.cpp:128-170)
-            const double phi = (rnorm + std::fabs(pobj - dobj)) / dnorm;
+            const double phi = (rnorm + std::fabs(pobj - dobj)) / dnorm_orig;
             phi_min = iter == 0 ? phi : std::min(phi_min, phi);
             if (iter >= 10 && phi >= 1e-8 && phi >= 1e4 * phi_min) { status = 4; break; }
          }
@@ -1293,7 +1588,7 @@ struct Ipm {
          TRY(pips_hip_vec_axpy(ND, ad, st.D, it.D, stream));
       }
       if (status == 1) TRY(residuals(&rnorm, &pobj, &dobj, &m));   // the numbers returned describe the iterate returned
-      last[0] = pobj; last[1] = iter; last[2] = m; last[3] = rnorm; last[4] = status; last[5] = dobj; last[6] = dnorm;
+      last[0] = pobj; last[1] = iter; last[2] = m; last[3] = rnorm; last[4] = status; last[5] = dobj; last[6] = dnorm_orig;
       if (result)
          for (int i = 0; i < 7; ++i) result[i] = last[i];
       return PIPS_OK;
@@ -1312,6 +1607,143 @@ namespace {
 struct View { int rows = 0, cols = 0; const int* rp = nullptr; const int* ci = nullptr; const double* v = nullptr; };
 View view(const pips_csr_view& m) { return View{m.rows, m.cols, m.rowptr, m.colidx, m.val}; }
 bool present(const View& m) { return m.rp != nullptr && m.rows > 0; }
+
+struct HostCsr { std::vector<int> rp, ci, trp, tci; std::vector<double> v, tv; };
+// J = [A; C] and J^T from the rows (sorted in place)
+void rows_to_csr(std::vector<std::vector<std::pair<int, double>>>& rows, int nx, HostCsr& h) {
+   h.rp.assign(rows.size() + 1, 0);
+   h.trp.assign((size_t)nx + 1, 0);
+   for (size_t r = 0; r < rows.size(); ++r) {
+      std::sort(rows[r].begin(), rows[r].end());
+      h.rp[r + 1] = h.rp[r] + (int)rows[r].size();
+      for (auto& e : rows[r]) ++h.trp[e.first + 1];
+   }
+   const int nnz = h.rp[rows.size()];
+   h.ci.resize(nnz); h.tci.resize(nnz); h.v.resize(nnz); h.tv.resize(nnz);
+   for (int j = 0; j < nx; ++j) h.trp[j + 1] += h.trp[j];
+   std::vector<int> fill(h.trp.begin(), h.trp.end() - 1);
+   for (size_t r = 0; r < rows.size(); ++r) {
+      int q = h.rp[r];
+      for (auto& e : rows[r]) {
+         h.ci[q] = e.first; h.v[q] = e.second; ++q;
+         const int t = fill[e.first]++;
+         h.tci[t] = (int)r; h.tv[t] = e.second;
+      }
+   }
+}
+
+// ---- scaling before assembly (pips_ipm_create_general_scaled) -----------------------------------------------------------------
+// The data as the harness reads it, scaled by the factors (Scaler::applyScaling): matrices (a col_j) row_i, c col, b / clow / cupp
+// row, xlow / xupp / col.  Host copies of O(nnz): the existing assembly reads them.
+struct ScaledData {
+   std::vector<pips_ipm_block> blk;
+   std::deque<std::vector<double>> keep;
+   const double *bL = nullptr, *dlow = nullptr, *dupp = nullptr;
+};
+void make_scaled(const Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow,
+                 const double* dupp, ScaledData& sd) {
+   const int N = n_blocks - 1, n0 = blocks[0].n, my0 = blocks[0].my, mz0 = blocks[0].mz;
+   const double* col = p->h_col.data();
+   const double* re = p->h_row.data();
+   const double* ri = re + p->my;
+   sd.blk.assign(blocks, blocks + n_blocks);
+   auto mat = [&](pips_csr_view& m, const double* rf, int c0) {   // rf: factors of the matrix' rows, c0: its first column in x
+      if (!m.rowptr || m.rows <= 0) return;
+      sd.keep.emplace_back((size_t)m.rowptr[m.rows], 0.0);
+      std::vector<double>& v = sd.keep.back();
+      for (int r = 0; r < m.rows; ++r)
+         for (int q = m.rowptr[r]; q < m.rowptr[r + 1]; ++q) v[q] = (m.val[q] * col[c0 + m.colidx[q]]) * rf[r];
+      m.val = v.data();
+   };
+   auto vec = [&](const double*& x, int n, const double* f, bool div) {
+      if (!x || n <= 0) return;
+      sd.keep.emplace_back(x, x + n);
+      std::vector<double>& v = sd.keep.back();
+      for (int k = 0; k < n; ++k) v[k] = div ? v[k] / f[k] : v[k] * f[k];
+      x = v.data();
+   };
+   int xo = n0, yo = my0 + myl, zo = mz0 + mzl;
+   for (int i = 0; i <= N; ++i) {
+      pips_ipm_block& b = sd.blk[i];
+      const int xi = i == 0 ? 0 : xo, yi = i == 0 ? 0 : yo, zi = i == 0 ? 0 : zo;
+      mat(b.A, re + yi, 0);
+      mat(b.C, ri + zi, 0);
+      if (i > 0) { mat(b.B, re + yi, xi); mat(b.D, ri + zi, xi); }
+      mat(b.BL, re + my0, xi);
+      mat(b.DL, ri + mz0, xi);
+      vec(b.c, b.n, col + xi, false); vec(b.xlow, b.n, col + xi, true); vec(b.xupp, b.n, col + xi, true);
+      vec(b.b, b.my, re + yi, false); vec(b.clow, b.mz, ri + zi, false); vec(b.cupp, b.mz, ri + zi, false);
+      if (i > 0) { xo += b.n; yo += b.my; zo += b.mz; }
+   }
+   sd.bL = bL; sd.dlow = dlow; sd.dupp = dupp;
+   vec(sd.bL, myl, re + my0, false); vec(sd.dlow, mzl, ri + mz0, false); vec(sd.dupp, mzl, ri + mz0, false);
+}
+// this rank's part of the data norm as build() forms it (every matrix entry, c, b, the bounds under their indicators)
+double data_norm(int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow, const double* dupp,
+                 const double* idlow, const double* idupp) {
+   double dn = 0.0;
+   auto m = [&](const pips_csr_view& a) {
+      if (a.rowptr && a.rows > 0) for (int q = a.rowptr[0]; q < a.rowptr[a.rows]; ++q) dn = std::max(dn, std::fabs(a.val[q]));
+   };
+   auto v = [&](const double* x, const double* ind, int n) {
+      if (x) for (int k = 0; k < n; ++k) dn = std::max(dn, std::fabs(ind ? x[k] * ind[k] : x[k]));
+   };
+   for (int i = 0; i < n_blocks; ++i) {
+      const pips_ipm_block& b = blocks[i];
+      m(b.A); m(b.C); m(b.BL); m(b.DL);
+      if (i > 0) { m(b.B); m(b.D); }
+      v(b.c, nullptr, b.n); v(b.b, nullptr, b.my);
+      v(b.xlow, b.ixlow, b.n); v(b.xupp, b.ixupp, b.n); v(b.clow, b.iclow, b.mz); v(b.cupp, b.icupp, b.mz);
+   }
+   v(bL, nullptr, myl); v(dlow, idlow, mzl); v(dupp, idupp, mzl);
+   return dn;
+}
+// J of the original data to the device, the scaler on it (J, J^T scaled in place), and the scaled host copies for build()
+int prescale(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow, const double* dupp,
+             const double* idlow, const double* idupp, int device, int scaler, ScaledData& sd) {
+   if (device >= 0) HIP_TRYH(hipSetDevice(device));
+   const int N = n_blocks - 1;
+   const pips_ipm_block& root = blocks[0];
+   p->N = N; p->n0 = root.n; p->my0 = root.my; p->mz0 = root.mz; p->myl = myl; p->mzl = mzl;
+   p->ry = root.my + myl; p->rzr = root.mz + mzl;
+   std::vector<int> xoff(N + 2, 0), yoff(N + 2, 0), zoff(N + 2, 0);
+   xoff[1] = root.n; yoff[1] = p->ry; zoff[1] = p->rzr;
+   for (int i = 1; i <= N; ++i) {
+      if (blocks[i].n < 0 || blocks[i].my < 0 || blocks[i].mz < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: negative block dimension");
+      xoff[i + 1] = xoff[i] + blocks[i].n; yoff[i + 1] = yoff[i] + blocks[i].my; zoff[i + 1] = zoff[i] + blocks[i].mz;
+   }
+   p->nx = xoff[N + 1]; p->my = yoff[N + 1]; p->mz = zoff[N + 1];
+   const int my = p->my, my0 = root.my, mz0 = root.mz;
+   std::vector<std::vector<std::pair<int, double>>> rows((size_t)p->my + p->mz);
+   auto add = [&](const pips_csr_view& m, int row0, int col0) {
+      if (!m.rowptr || m.rows <= 0) return;
+      for (int r = 0; r < m.rows; ++r)
+         for (int q = m.rowptr[r]; q < m.rowptr[r + 1]; ++q) rows[(size_t)row0 + r].push_back({col0 + m.colidx[q], m.val[q]});
+   };
+   if (p->rank == 0) { add(root.A, 0, 0); add(root.BL, my0, 0); add(root.C, my, 0); add(root.DL, my + mz0, 0); }
+   for (int i = 1; i <= N; ++i) {
+      const pips_ipm_block& b = blocks[i];
+      add(b.A, yoff[i], 0); add(b.B, yoff[i], xoff[i]); add(b.C, my + zoff[i], 0); add(b.D, my + zoff[i], xoff[i]);
+      add(b.BL, my0, xoff[i]); add(b.DL, my + mz0, xoff[i]);
+   }
+   {
+      HostCsr h;
+      rows_to_csr(rows, p->nx, h);
+      rows = {};
+      TRY(p->upload_J(h));
+   }
+   TRY(p->sc_alloc());
+   TRY(p->alloc(&p->d_red, 64 * (long long)p->n_ranks));
+   TRY(p->run_scaler(scaler));
+   p->dnorm_orig = data_norm(n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp);
+   if (p->scaled) make_scaled(p, n_blocks, blocks, myl, mzl, bL, dlow, dupp, sd);
+   std::vector<double> ri2(2 * (size_t)p->mz), col2(2 * (size_t)p->nx);
+   for (int k = 0; k < p->mz; ++k) ri2[k] = ri2[(size_t)p->mz + k] = p->h_row[(size_t)my + k];
+   for (int k = 0; k < p->nx; ++k) col2[k] = col2[(size_t)p->nx + k] = p->h_col[k];
+   TRY(p->up(&p->sc_ri2, ri2));
+   TRY(p->up(&p->sc_col2, col2));
+   return PIPS_OK;
+}
 
 int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow, const double* dupp,
           const double* idlow, const double* idupp, double dual_reg, int device) {
@@ -1458,27 +1890,8 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
    double pairs = 0.0;
    for (long long k = 0; k < p->ncp; ++k) pairs += hwG[k] * hM[k];
    // ---- CSR of J and J^T
-   std::vector<int> Jrp((size_t)my + mz + 1, 0), Jtrp((size_t)nx + 1, 0);
-   for (size_t r = 0; r < rows.size(); ++r) {
-      std::sort(rows[r].begin(), rows[r].end());
-      Jrp[r + 1] = Jrp[r] + (int)rows[r].size();
-      for (auto& e : rows[r]) ++Jtrp[e.first + 1];
-   }
-   const int nnz = Jrp[rows.size()];
-   std::vector<int> Jci(nnz), Jtci(nnz);
-   std::vector<double> Jv(nnz), Jtv(nnz);
-   for (int j = 0; j < nx; ++j) Jtrp[j + 1] += Jtrp[j];
-   {
-      std::vector<int> fill(Jtrp.begin(), Jtrp.end() - 1);
-      for (size_t r = 0; r < rows.size(); ++r) {
-         int q = Jrp[r];
-         for (auto& e : rows[r]) {
-            Jci[q] = e.first; Jv[q] = e.second; ++q;
-            const int t = fill[e.first]++;
-            Jtci[t] = (int)r; Jtv[t] = e.second;
-         }
-      }
-   }
+   HostCsr hj;
+   rows_to_csr(rows, nx, hj);
    // ---- engine: analyze, values, root system
    const bool sparse_root = getenv("PIPS_IPM_SPARSE_ROOT") && atoi(getenv("PIPS_IPM_SPARSE_ROOT")) != 0;
    if (sparse_root && p->n_ranks > 1)
@@ -1526,14 +1939,20 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
    // factorize() asks for every inertia right after the factorisation (the inertia loop): nothing would run beside a root on its own stream
    if ((rc = pips_hip_kkt_set_root_stream(p->kkt, 0))) return rc;
    HIP_TRYH(hipGetDevice(&p->device));
-   if ((rc = p->alloc(&p->d_red, 64 * (long long)p->n_ranks))) return rc;
+   if (!p->d_red && (rc = p->alloc(&p->d_red, 64 * (long long)p->n_ranks))) return rc;
+   if (p->scaled) p->dnorm_orig = p->dnorm_orig > 0 ? p->dnorm_orig : 1.0;
    if (p->n_ranks > 1) {
-      std::vector<double> slots(p->n_ranks + 1, 0.0);
+      const int ns = p->n_ranks + 1 + (p->scaled ? p->n_ranks : 0);   // scaled: the original data norm travels too
+      std::vector<double> slots(ns, 0.0);
       slots[p->rank] = p->dnorm; slots[p->n_ranks] = pairs;
-      if ((rc = p->reduce_host(slots.data(), p->n_ranks + 1))) return rc;
+      if (p->scaled) slots[p->n_ranks + 1 + p->rank] = p->dnorm_orig;
+      if ((rc = p->reduce_host(slots.data(), ns))) return rc;
       for (int r = 0; r < p->n_ranks; ++r) p->dnorm = std::max(p->dnorm, slots[r]);
+      if (p->scaled)
+         for (int r = 0; r < p->n_ranks; ++r) p->dnorm_orig = std::max(p->dnorm_orig, slots[p->n_ranks + 1 + r]);
       pairs = slots[p->n_ranks];
    }
+   if (!p->scaled) p->dnorm_orig = p->dnorm;
    p->n_pairs = pairs;
    // ---- maps: KKT right-hand sides <- [x|y|z], leaf diagonal codes
    {
@@ -1557,19 +1976,7 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
    if (e_mz0 > 0) {
       if ((rc = pips_hip_kkt_set_root_inequalities(p->kkt, e_mz0, C0.rp, C0.ci, C0.v))) return rc;
    }
-   {
-      std::vector<int> la, lat;
-      for (int r = 0; r < my + mz; ++r) if (Jrp[r + 1] - Jrp[r] > CSR_LONG_ROW) la.push_back(r);
-      for (int r = 0; r < nx; ++r) if (Jtrp[r + 1] - Jtrp[r] > CSR_LONG_ROW) lat.push_back(r);
-      p->nJ_long = (int)la.size(); p->nJt_long = (int)lat.size();
-      p->J_nnz = Jrp[my + mz]; p->Jt_nnz = Jtrp[nx];
-      la.push_back(0); lat.push_back(0);
-      if ((rc = p->up(&p->J_long, la)) || (rc = p->up(&p->Jt_long, lat))) return rc;
-      if ((rc = p->alloc(&p->long_scratch, (long long)std::max<size_t>(std::max(la.size(), lat.size()), 1) * LONG_PARTS))) return rc;
-   }
-   if ((rc = p->up(&p->J_rp, Jrp)) || (rc = p->up(&p->J_ci, Jci)) || (rc = p->up(&p->J_v, Jv)) || (rc = p->up(&p->Jt_rp, Jtrp)) ||
-       (rc = p->up(&p->Jt_ci, Jtci)) || (rc = p->up(&p->Jt_v, Jtv)))
-      return rc;
+   if (!p->J_v && (rc = p->upload_J(hj))) return rc;   // a scaled handle holds J since prescale()
    if ((rc = p->up(&p->c, hc)) || (rc = p->up(&p->bA, hb)) || (rc = p->up(&p->M, hM)) || (rc = p->up(&p->Bd, hBd)) || (rc = p->up(&p->wG, hwG)) ||
        (rc = p->up(&p->wGs, hwGs)) || (rc = p->up(&p->wXYZ, hwXYZ)))
       return rc;
@@ -1608,12 +2015,30 @@ extern "C" {
 int pips_ipm_create_general(void** handle, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow,
                             const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device, void* comm, int rank,
                             int n_ranks) {
+   return pips_ipm_create_general_scaled(handle, n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device, comm, rank, n_ranks,
+                                         PIPS_SCALER_NONE);
+}
+
+int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL,
+                                   const double* dlow, const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device,
+                                   void* comm, int rank, int n_ranks, int scaler) {
+   if (scaler == PIPS_SCALER_CURTIS_REID)
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general_scaled: scaler %d (Curtis-Reid) is not supported", scaler);
+   if (scaler < PIPS_SCALER_NONE || scaler > PIPS_SCALER_CURTIS_REID)
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general_scaled: scaler %d is not supported (0 none, 1 equilibrium, 2 geometric mean, "
+                              "3 geometric mean + equilibrium)", scaler);
    if (!handle || n_blocks < 2 || !blocks || myl < 0 || mzl < 0 || n_ranks < 1 || rank < 0 || rank >= n_ranks || (n_ranks > 1 && !comm) ||
        (myl > 0 && !bL) || (mzl > 0 && (!dlow || !dupp || !idlow || !idupp)))
       PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: bad arguments");
    auto p = std::make_unique<Ipm>();
    p->comm = comm; p->rank = rank; p->n_ranks = n_ranks;
-   int rc = build(p.get(), n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device);
+   int rc;
+   ScaledData sd;
+   if (scaler != PIPS_SCALER_NONE) {
+      if ((rc = prescale(p.get(), n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, device, scaler, sd))) return rc;
+      if (p->scaled) { blocks = sd.blk.data(); bL = sd.bL; dlow = sd.dlow; dupp = sd.dupp; }
+   }
+   rc = build(p.get(), n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device);
    if (rc) return rc;
    *handle = p.release();
    return PIPS_OK;
@@ -1673,6 +2098,10 @@ int pips_ipm_get_solution(void* handle, double* x_host, double* y_host) {
    if (!p) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
    if (x_host) HIP_TRYH(hipMemcpy(x_host, p->it.x, (size_t)p->nx * sizeof(double), hipMemcpyDeviceToHost));
    if (y_host) HIP_TRYH(hipMemcpy(y_host, p->it.y, (size_t)p->my * sizeof(double), hipMemcpyDeviceToHost));
+   if (p->scaled) {   // Scaler::get_primal_unscaled / get_dual_eq_unscaled
+      if (x_host) for (int k = 0; k < p->nx; ++k) x_host[k] *= p->h_col[k];
+      if (y_host) for (int k = 0; k < p->my; ++k) y_host[k] *= p->h_row[k];
+   }
    return PIPS_OK;
 }
 
@@ -1695,6 +2124,26 @@ int pips_ipm_get_iterate(void* handle, double* x, double* s, double* y, double* 
    TRY(get(x, p->it.x, nx)); TRY(get(s, p->it.s, mz)); TRY(get(y, p->it.y, my)); TRY(get(z, p->it.z, mz));
    TRY(get(t, p->it.G, mz)); TRY(get(u, p->it.G + mz, mz)); TRY(get(v, p->it.G + 2 * mz, nx)); TRY(get(w, p->it.G + 2 * mz + nx, nx));
    TRY(get(lambda, p->it.L, mz)); TRY(get(pi, p->it.L + mz, mz)); TRY(get(gamma, p->it.L + 2 * mz, nx)); TRY(get(phi, p->it.L + 2 * mz + nx, nx));
+   if (p->scaled) {   // Scaler::unscale_variables (Scaler.cpp:34-55)
+      const double *col = p->h_col.data(), *re = p->h_row.data(), *ri = re + my;
+      auto mul = [](double* d, const double* f, int n) { if (d) for (int k = 0; k < n; ++k) d[k] *= f[k]; };
+      auto div = [](double* d, const double* f, int n) { if (d) for (int k = 0; k < n; ++k) d[k] /= f[k]; };
+      mul(x, col, nx); div(s, ri, mz); mul(y, re, my); mul(z, ri, mz);
+      mul(v, col, nx); div(gamma, col, nx); mul(w, col, nx); div(phi, col, nx);
+      div(t, ri, mz); mul(lambda, ri, mz); div(u, ri, mz); mul(pi, ri, mz);
+   }
+   return PIPS_OK;
+}
+
+int pips_ipm_get_scaling(void* handle, double* col, double* row_eq, double* row_ineq, double* info8) {
+   Ipm* p = (Ipm*)handle;
+   if (!p) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
+   const bool have = p->scaled;
+   for (int k = 0; col && k < p->nx; ++k) col[k] = have ? p->h_col[k] : 1.0;
+   for (int k = 0; row_eq && k < p->my; ++k) row_eq[k] = have ? p->h_row[k] : 1.0;
+   for (int k = 0; row_ineq && k < p->mz; ++k) row_ineq[k] = have ? p->h_row[(size_t)p->my + k] : 1.0;
+   if (info8)
+      for (int k = 0; k < 8; ++k) info8[k] = p->sc_info[k];
    return PIPS_OK;
 }
 

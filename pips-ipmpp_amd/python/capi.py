@@ -69,11 +69,20 @@ SYMBOLS = [
     "pips_hip_vec_add_const", "pips_hip_vec_mul", "pips_hip_vec_div", "pips_hip_vec_add_product", "pips_hip_vec_add_quotient",
     "pips_hip_vec_divide_some", "pips_hip_vec_select_nonzeros", "pips_hip_vec_safe_invert", "pips_hip_vec_gondzio_projection", "pips_hip_vec_dot",
     "pips_hip_vec_one_norm", "pips_hip_vec_inf_norm", "pips_hip_vec_min", "pips_hip_vec_sumsq_scaled", "pips_hip_vec_stepbound",
-    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
+    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
     "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks",
 ]
+
+# problem scalers (pips_ipm_create_general_scaled; the order of the reference's ScalerType)
+PIPS_SCALER_NONE = 0
+PIPS_SCALER_EQUILIBRIUM = 1
+PIPS_SCALER_GEOMETRIC_MEAN = 2
+PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM = 3
+PIPS_SCALER_CURTIS_REID = 4
+SCALERS = {None: PIPS_SCALER_NONE, "none": PIPS_SCALER_NONE, "equilibrium": PIPS_SCALER_EQUILIBRIUM, "geometric": PIPS_SCALER_GEOMETRIC_MEAN,
+           "geometric_equilibrium": PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM, "curtis_reid": PIPS_SCALER_CURTIS_REID}
 
 
 def _check(rc, what):
@@ -1027,7 +1036,11 @@ class GeneralIpmSolver(IpmSolver):
     and linking rows), fed with the reader's per-block dicts (fields of GMSPIPSBlockData_t as gdx.read_block / gdx_read_block
     return them): blocks[0] is the root.  Several ranks: blocks = [root] + this rank's blocks."""
 
-    def __init__(self, blocks, dual_reg=0.0, device=-1, comm=None, rank=0, n_ranks=1):
+    def __init__(self, blocks, dual_reg=0.0, device=-1, comm=None, rank=0, n_ranks=1, scaler=None):
+        """scaler: None, "equilibrium", "geometric" or "geometric_equilibrium" (the reference's scale / scaleEqui, scaleGeo,
+        scaleGeoEqui); "curtis_reid" is reserved and raises, like any other name."""
+        if scaler not in SCALERS:
+            raise PipsHipError(f"unknown scaler {scaler!r}: one of None, 'equilibrium', 'geometric', 'geometric_equilibrium'")
         keep = []
 
         def arr(a, dtype=np.float64):
@@ -1058,10 +1071,13 @@ class GeneralIpmSolver(IpmSolver):
         self._keep = (keep, cb)
         self._comm = comm
         self._h = C.c_void_p()
-        _check(lib.pips_ipm_create_general(C.byref(self._h), C.c_int(len(blocks)), cb, C.c_int(myl), C.c_int(mzl),
-                                           C.c_void_p(arr(root["bL"])), C.c_void_p(arr(root["dlow"])), C.c_void_p(arr(root["dupp"])),
-                                           C.c_void_p(arr(root["idlow"])), C.c_void_p(arr(root["idupp"])), C.c_double(dual_reg), C.c_int(device),
-                                           comm._h if comm is not None else None, C.c_int(rank), C.c_int(n_ranks)), "pips_ipm_create_general")
+        args = (C.byref(self._h), C.c_int(len(blocks)), cb, C.c_int(myl), C.c_int(mzl), C.c_void_p(arr(root["bL"])), C.c_void_p(arr(root["dlow"])),
+                C.c_void_p(arr(root["dupp"])), C.c_void_p(arr(root["idlow"])), C.c_void_p(arr(root["idupp"])), C.c_double(dual_reg), C.c_int(device),
+                comm._h if comm is not None else None, C.c_int(rank), C.c_int(n_ranks))
+        if scaler is None:
+            _check(lib.pips_ipm_create_general(*args), "pips_ipm_create_general")
+        else:
+            _check(lib.pips_ipm_create_general_scaled(*args, C.c_int(SCALERS[scaler])), "pips_ipm_create_general_scaled")
         d = (C.c_longlong * 4)()
         _check(lib.pips_ipm_get_dims(self._h, d), "pips_ipm_get_dims")
         self.nx, self.ny, self.nzr, self.n_pairs = int(d[0]), int(d[1]), int(d[2]), int(d[3])
@@ -1094,6 +1110,15 @@ class GeneralIpmSolver(IpmSolver):
         out = (C.c_longlong * 2)()
         _check(lib.pips_ipm_get_stats2(self._h, out), "pips_ipm_get_stats2")
         return dict(bicgstab_iterations=out[0], host_syncs=out[1])
+
+    def scaling(self):
+        """The scaling factors in the harness order (col: x, row_eq: y, row_ineq: z rows) and the scaler's report (Scaler::printRowColRatio):
+        applied, row / column ratio before and after, geometric passes, whether the geometric stage was kept, host waits."""
+        col, req, rin, info = np.zeros(self.nx), np.zeros(self.ny), np.zeros(self.nzr), np.zeros(8)
+        _check(lib.pips_ipm_get_scaling(self._h, _ptr(col), _ptr(req), _ptr(rin), _ptr(info)), "pips_ipm_get_scaling")
+        return dict(col=col, row_eq=req, row_ineq=rin, applied=bool(info[0]), row_ratio_before=info[1], col_ratio_before=info[2],
+                    row_ratio_after=info[3], col_ratio_after=info[4], geometric_passes=int(info[5]), geometric_kept=bool(info[6]),
+                    host_waits=int(info[7]))
 
 
 def gdx_read_block(path, num_blocks, act_block, offset=1):

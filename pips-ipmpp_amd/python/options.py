@@ -1,7 +1,9 @@
 """The reference's options file (PIPSIPMpp.opt: lines `IDENTIFIER value type`, type in bool/boolean, int/integer, double;
 `#` and `//` comments; AbstractOptions::load_options_from_file, Core/Options/AbstractOptions.C:62-135) and the mapping of the
 identifiers that concern the KKT path onto this library's settings.  Identifiers that steer other subsystems of the reference
-(presolve, scaling, hierarchical approach, ...) are parsed and reported as ignored."""
+(presolve, hierarchical approach, ...) are parsed and reported as ignored.  Scaling is not an options-file setting in the reference
+either (gmspips takes it as a command-line word): the device harness takes it at creation, GeneralIpmSolver(..., scaler=...), and
+tools/gmspips.py accepts the reference's words scale, scaleEqui, scaleGeo and scaleGeoEqui."""
 
 _BOOL = {"true": True, "TRUE": True, "True": True, "false": False, "FALSE": False, "False": False}
 
