@@ -22,6 +22,10 @@ const char* pips_hip_last_error(void);
 long long pips_hip_host_wait_count(void);
 /* the same per call site, as lines "file:line count" written into buf (at most cap bytes, NUL-terminated); returns the bytes written */
 int pips_hip_host_wait_sites(char* buf, int cap);
+/* device and pinned host allocations the library holds right now, and their bytes (every one is made at one place: csrc/devmem.h) -
+ * a diagnostic: equal values before and after a create ... destroy sequence mean that nothing leaked */
+long long pips_hip_device_allocs_live(void);
+long long pips_hip_device_bytes_live(void);
 /* number of visible HIP devices (0 without a GPU; never fails) */
 int pips_hip_device_count(void);
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devmem.h"
 #include "kernels.hip.h"
 #include "rootkernel.hip.h"
 #include "tailkernel.hip.h"
@@ -54,15 +55,10 @@ const char* last_error() { return g_last_error.c_str(); }
       hipError_t _e = (expr);                                                                      \
       if (_e != hipSuccess) PIPS_FAIL(PIPS_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
    } while (0)
-
-template <class T>
-static int dev_upload(T** dptr, const std::vector<T>& h, hipStream_t) {
-   *dptr = nullptr;
-   const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-   HIP_TRY(hipMalloc((void**)dptr, bytes));
-   if (!h.empty()) HIP_TRY(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-   return PIPS_OK;
-}
+#define PIPS_TRY(expr)                    \
+   do {                                   \
+      if (int _rc = (expr)) return _rc;   \
+   } while (0)
 
 // environment switches: value of an integer switch, dflt when it is not set
 static int env_int(const char* name, int dflt) {
@@ -86,7 +82,7 @@ struct TailPlan {
    int ntc_max = 0;
    std::vector<TaskList> upd, upd_diag, diag, trsm, fwd, bwd, trail, trail_next;
    TaskList schur;
-   TileTask* d_tasks = nullptr;
+   DevBuf<TileTask> d_tasks;
    std::vector<TileTask> h_tasks;   // host copy (the single-launch factorisation re-lists them: TailSingle::build)
 
    // panel == 0: pure left-looking (tile column j is updated once, with everything to its left: minimal traffic on C,
@@ -212,24 +208,19 @@ struct TailPlan {
          }
       end(schur);
       h_tasks = all;
-      return dev_upload(&d_tasks, all, nullptr);
-   }
-   void release() {
-      if (d_tasks) (void)hipFree(d_tasks);
-      d_tasks = nullptr;
+      return d_tasks.upload(all);
    }
 };
 
 // Single-launch tail sweeps (kernels.hip.h k_tail_rows_fwd / _bwd): task list (block, tile row) sorted by row, ticket and flag
 // storage.  PIPS_HIP_SWEEP_LAUNCHES=1 keeps the launch-per-tile-column kernels.
 struct SweepRt {
-   TileTask* d_tasks = nullptr;
+   DevBuf<TileTask> d_tasks;
    int n_tasks = 0;
-   int* d_ints = nullptr;          // [0 .. 2 NRHS) ticket / finished per right-hand side, then the error word, then the flags
+   DevBuf<int> d_ints;             // [0 .. 2 NRHS) ticket / finished per right-hand side, then the error word, then the flags
    long long n_flags = 0;
-   long long* d_flag_off = nullptr;
-   int* d_tfirst = nullptr;
-   long long* d_tfirst_off = nullptr;
+   DevBuf<long long> d_flag_off, d_tfirst_off;
+   DevBuf<int> d_tfirst;
    int epoch = 0;
    bool enabled = false;
    long long poll_limit = SWEEP_POLL_LIMIT;
@@ -246,7 +237,7 @@ struct SweepRt {
                 who, poll_limit);
    }
    int build(const std::vector<BlkDesc>& blks, const std::vector<const std::vector<int>*>* first) {
-      release();
+      *this = SweepRt();
       if (const char* pl = getenv("PIPS_HIP_SWEEP_POLL_LIMIT")) poll_limit = atoll(pl);
       const int nblk = (int)blks.size();
       int ntc_max = 0;
@@ -267,16 +258,15 @@ struct SweepRt {
             for (int i = 0; i < blks[b].ntr; ++i) tf.push_back(i < blks[b].ntc ? std::min(i, (*(*first)[b])[i]) : (*(*first)[b])[i]);
       }
       int rc;
-      if ((rc = dev_upload(&d_tasks, tasks, nullptr))) return rc;
-      if ((rc = dev_upload(&d_flag_off, foff, nullptr))) return rc;
+      if ((rc = d_tasks.upload(tasks))) return rc;
+      if ((rc = d_flag_off.upload(foff))) return rc;
       if (first) {
-         if ((rc = dev_upload(&d_tfirst, tf, nullptr))) return rc;
-         if ((rc = dev_upload(&d_tfirst_off, tfoff, nullptr))) return rc;
+         if ((rc = d_tfirst.upload(tf))) return rc;
+         if ((rc = d_tfirst_off.upload(tfoff))) return rc;
       }
       n_flags = std::max<long long>(nf, 1);
       const size_t ints = (size_t)(2 * SWEEP_NRHS_MAX + 2 + n_flags * SWEEP_NRHS_MAX);
-      HIP_TRY(hipMalloc((void**)&d_ints, ints * sizeof(int)));
-      HIP_TRY(hipMemset(d_ints, 0, ints * sizeof(int)));
+      PIPS_TRY(d_ints.alloc_zero(ints));
       epoch = 0;
       enabled = n_tasks > 0 && !getenv("PIPS_HIP_SWEEP_LAUNCHES");
       return PIPS_OK;
@@ -286,13 +276,6 @@ struct SweepRt {
       hipLaunchKernelGGL(k_sweep_bump, dim3(1), dim3(1), 0, st, ep);
       return SweepArgs{d_tasks, n_tasks, d_ints, d_ints + 2 * SWEEP_NRHS_MAX + 2, d_flag_off, d_tfirst, d_tfirst_off, ep,
                        d_ints + 2 * SWEEP_NRHS_MAX, n_flags, xw_stride, poll_limit};
-   }
-   void release() {
-      for (void* p : {(void*)d_tasks, (void*)d_ints, (void*)d_flag_off, (void*)d_tfirst, (void*)d_tfirst_off})
-         if (p) (void)hipFree(p);
-      d_tasks = nullptr; d_ints = nullptr; d_flag_off = nullptr; d_tfirst = nullptr; d_tfirst_off = nullptr;
-      n_tasks = 0;
-      enabled = false;
    }
 };
 
@@ -347,19 +330,13 @@ struct PhaseTimer {
 // eight lists by tile row; the flags and the template they start from.
 struct TailSingle {
    TailLdlArgs args{};
-   TileTask* d_tasks = nullptr;
-   int* d_flags = nullptr;
-   int* d_flags_init = nullptr;
-   long long* d_flag_off = nullptr;
-   int* d_ctl = nullptr;
+   DevBuf<TileTask> d_tasks;
+   DevBuf<int> d_flags, d_flags_init, d_ctl;
+   DevBuf<long long> d_flag_off;
    long long n_flags = 0;
    int n_tasks = 0, n_blocks = 0;
-   void release() {
-      for (void* q : {(void*)d_tasks, (void*)d_flags, (void*)d_flags_init, (void*)d_flag_off, (void*)d_ctl}) if (q) (void)hipFree(q);
-      d_tasks = nullptr; d_flags = d_flags_init = d_ctl = nullptr; d_flag_off = nullptr;
-   }
    int build(const TailPlan& p, const std::vector<BlkDesc>& blks, hipStream_t stream) {
-      release();
+      *this = TailSingle();
       const int nblk = (int)blks.size();
       n_blocks = nblk;
       std::vector<long long> foff(nblk + 1, 0);
@@ -417,9 +394,9 @@ struct TailSingle {
       n_tasks = (int)all.size();
       if (all.empty()) all.push_back({0, 0, 0, 0});
       int rc;
-      if ((rc = dev_upload(&d_tasks, all, stream)) || (rc = dev_upload(&d_flags_init, init, stream)) || (rc = dev_upload(&d_flag_off, foff, stream))) return rc;
-      HIP_TRY(hipMalloc((void**)&d_flags, init.size() * sizeof(int)));
-      HIP_TRY(hipMalloc((void**)&d_ctl, 16 * sizeof(int)));
+      if ((rc = d_tasks.upload(all)) || (rc = d_flags_init.upload(init)) || (rc = d_flag_off.upload(foff))) return rc;
+      PIPS_TRY(d_flags.alloc(init.size()));
+      PIPS_TRY(d_ctl.alloc(16));
       HIP_TRY(hipMemsetAsync(d_ctl, 0, 16 * sizeof(int), stream));
       args.tasks = d_tasks; args.flags = d_flags; args.flag_off = d_flag_off; args.ctl = d_ctl;
       return PIPS_OK;
@@ -538,10 +515,10 @@ static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
       TailLdlArgs ta = ts.args;
       ta.n_tasks = ts.n_tasks;
       const char* trace_file = getenv("PIPS_HIP_TAIL_TRACE");   // diagnostics: per-task clocks of this launch into a file (tools/tail_trace.py)
-      long long* d_trace = nullptr;
+      DevBuf<long long> d_trace;
       const size_t n_trace = (size_t)3 * ts.n_tasks + 32 * (size_t)(p.ntc_max + 1);
       if (trace_file) {
-         HIP_TRY(hipMalloc((void**)&d_trace, n_trace * sizeof(long long)));
+         PIPS_TRY(d_trace.alloc(n_trace));
          HIP_TRY(hipMemsetAsync(d_trace, 0, n_trace * sizeof(long long), c.stream));
          ta.trace = d_trace;
       }
@@ -556,7 +533,7 @@ static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
          HIP_TRY(hipStreamSynchronize(c.stream));
          HIP_TRY(hipMemcpy(h.data(), d_trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
          HIP_TRY(hipMemcpy(ht.data(), ts.d_tasks, ht.size() * sizeof(TileTask), hipMemcpyDeviceToHost));
-         (void)hipFree(d_trace);
+         d_trace.reset();
          if (FILE* f = fopen(trace_file, "w")) {   // ticket, list, kind, block, ti, tj, K range, the three clocks
             for (int t = 0; t < ts.n_tasks; ++t) {
                int x = 0;
@@ -755,7 +732,108 @@ static void apply_tuning(AnalyzeOptions& opt) {
    if (const char* sp = getenv("PIPS_HIP_MF_SPLIT")) opt.mf_split_nb_max = atoi(sp) == 0 ? 0 : std::min(176, std::max(atoi(sp), 2));   // border split: 0 = off, else the largest nb
 }
 
-struct Engine {
+// What an analysis owns on the device and what belongs to it on the host: Engine::release() resets exactly this (a move-assignment
+// from a fresh one), so a buffer declared here is freed and reset without a second mention anywhere.  The settings that survive a
+// re-analysis, the inputs and the streams are members of Engine itself.
+struct EngineAnalysis {
+   DevBuf<double> d_norms;      // 3 * nblk: ||r||, ||rhs||, ||x|| per block
+   PinnedBuf<double> h_norms;
+   DevBuf<int> d_frowptr, d_fcol, d_fsrc;   // full row structure of K for the refinement residual
+   DevBuf<long long> d_flong;               // its rows longer than FULL_LONG_ROW
+   DevBuf<int> d_sctab;                     // sparse Schur complement (set_sc_tables): position tables, BlkDesc::sctab_off
+   DevBuf<int> d_schur_cols, d_schur_slot;
+   // fronts on the rows of K only (BlockSym::mf_konly): records and lists of k_border_rows / k_border_tail
+   DevBuf<int> d_kb_rec;
+   DevBuf<long long> d_kb_off;          // per supernode (sorted id): offset of its record, -1 none
+   DevBuf<int> d_kb_list;               // fronts with border rows, level after level
+   std::vector<int> kb_level_off;       // offsets into d_kb_list per level (size levels + 1)
+   std::vector<int> kb_level_pairs, kb_level_lds;   // per level: most pairs of one front, bytes of the largest border-row block (LDS of k_border_rows)
+   DevBuf<int> d_kb_tail;
+   int n_kb_tail = 0;
+   std::vector<MfLaunch> mf_launches;
+   DevBuf<double> d_mfU;                // update matrices of the fronts
+   DevBuf<double> d_mfLV;               // d and l of the simple leaves below fronts, front by front
+   DevBuf<int> d_roots, d_root_off;     // fronts without a head parent, per block (k_root_assemble)
+   int n_roots = 0;
+   DevBuf<BbBatch> d_bb_batches;        // border split (k_border_schur): batches of supernodes with border rows, block after block
+   DevBuf<BbMeta> d_bb_meta;
+   DevBuf<int> d_bb_off, d_bb_pos;      // batches of block b: [d_bb_off[b], d_bb_off[b + 1]); compressed border ids of the staged rows
+   int n_bb = 0;
+   long long bb_doubles = 0;            // doubles of the border-row arena (behind the panels inside d_arena)
+   DevBuf<double> d_bb_out;             // deterministic mode: the blocks' border x border triangles before they join their groups
+   DevBuf<int> d_bb_round_blk;          // deterministic mode: the blocks of round k of k_border_schur
+   DevBuf<int> d_round_blk;             // deterministic mode: the blocks of round k at [round_off[k], round_off[k + 1])
+   DevBuf<int> d_mfint;                 // front records (common.h)
+   DevBuf<long long> d_mfdbg;           // PIPS_HIP_MF_CLOCKS: phase stamps of every front (8 per supernode), dumped after the factorisation
+   DevBuf<int> d_spine, d_spine_off;
+   TailPlan plan;
+   SweepRt sweep;
+   TailSingle tsingle;                  // the tails as one dependency-driven launch (tailkernel.hip.h)
+   DevBuf<double> d_uarena;             // U = L D copies of the tails (see k_tile_gemm)
+   DevBuf<double> d_arena, d_kval, d_bval, d_winv, d_dtail, d_xw, d_rhs, d_res, d_stage, d_pref;
+   DevBuf<long long> d_kdst, d_bdst, d_kdiag, d_kptr, d_psign_off, d_perm_off, d_rowbase, d_bt_xoff;
+   DevBuf<SnDesc> d_sns;
+   DevBuf<BlkDesc> d_blks;
+   // Forward substitution of the simple leaves as a gather (k_leaf_fwd_gather): the leaves' L entries by TARGET row - row list,
+   // row pointers, source (the leaf's position in the work vector), values (written in this order by k_head_factor_simple through
+   // d_lf_pos, which is indexed like d_rowidx).  No atomics, fixed order of the sums.
+   DevBuf<int> d_lf_rows, d_lf_ptr, d_lf_src, d_lf_pos;
+   DevBuf<double> d_lf_val;
+   long long lf_rows = 0, lf_entries = 0;
+   DevBuf<LeafDesc> d_leafdesc;         // compact records of the level-0 simple leaves, in the order of d_sns (k_leaf_bwd)
+   DevBuf<int> d_lb_list;               // the simple leaves that own border rows (k_leaf_border)
+   DevBuf<int> d_rowidx, d_upd, d_sncol, d_bmap, d_perm, d_inertia, d_nprimal;
+   DevBuf<int> d_br_rowptr, d_br_sc, d_br_src;   // the border by leaf row (k_border_mult_rows)
+   DevBuf<int> d_krowptr, d_kcolidx, d_bt_rowptr, d_bt_colidx, d_bt_rowsc;
+   DevBuf<signed char> d_psign;
+   // ---- deterministic mode (see Engine): slots, gather lists, group buffers
+   struct GatherList {
+      long long n_targets = 0, n_slots = 0;
+      DevBuf<long long> d_tgt, d_off, d_slots;
+   };
+   struct SlotEntry { long long target, slot; };
+   DevBuf<double> d_slot_val, d_vslot_val;
+   DevBuf<double> d_mvslot;             // several right-hand sides: the forward substitution's slots for one panel of MQ (solve_multi)
+   std::vector<GatherList> g_levels, gv_levels;   // targets inside the head, per level (factorisation / forward substitution)
+   GatherList g_tail, g_sc, gv_tail;
+   GatherList g_sc_grp;                 // Schur targets of the head inside the group buffers
+   GatherList g_btm_grp;                // border rows per (group, Schur column): Br^T z summed group-wise, then in the fixed tree
+   DevBuf<double> d_gvec, d_tvec;
+   DevBuf<TileTask> d_det_tasks;
+   DevBuf<double> d_gbuf;
+   DevBuf<int> d_blk_group;
+   GatherList g_btm, g_bm;              // border products: rows per Schur column, entries per leaf row
+   // forward sweep of the augmented factor: the border slots of the work vector are gathered, target by target, from the border rows
+   // of the head supernodes (k_border_gather_det: no atomics, fixed order) and then group-wise into d_gvec like Br^T z
+   DevBuf<BgEntry> d_bg_ent;
+   DevBuf<long long> d_bg_ptr, d_bg_slot;
+   DevBuf<int> d_bg_idx;
+   DevBuf<double> d_bg_val;
+   long long n_bg_targets = 0, n_bg_ent = 0;
+   GatherList g_bslot_grp;
+   bool det_aug_ready = false;
+   DevBuf<double> d_bt_tmp;
+   DevBuf<int> d_gemm_ctr;              // counter slots of the persistent update kernel
+   // ---- Schur SYRK in row-panel groups, so that a multi-rank root can reduce panel p while the leaves still compute p + 1 ..
+   std::vector<TaskList> sc_groups;
+   std::vector<int> sc_row_begin;       // panel p = Schur rows [sc_row_begin[p], sc_row_begin[p + 1])
+   std::vector<hipEvent_t> ev_sc;       // (destroyed by Engine::release / set_sc_panels)
+   DevBuf<TileTask> d_sc_tasks;
+   // ---- multi-RHS solve (Engine::ensure_multi_buffers) and the host-pointer solves of a leaf handle
+   DevBuf<double> d_mx_xw, d_mx_rhs, d_mx_res;
+   int mx_cap = 0;
+   DevBuf<double> d_mmeasure;           // solve_multi: the refinement measure per right-hand side (device / pinned) ...
+   PinnedBuf<double> h_mmeasure;
+   DevBuf<int> d_midx;                  // ... and the columns that take the correction solve
+   DevBuf<double> d_hostx;              // device copy of host right-hand sides (pips_hip_ldl_solve), kept between calls
+   DevBuf<double> d_hostpack;           // packed rows + their indices of pips_hip_ldl_solve_sparse, kept between calls likewise
+   // ---- inertia counters in pinned host memory (Engine::fetch_inertia)
+   PinnedBuf<int> h_inertia_pin;
+   hipEvent_t ev_inertia = nullptr;     // (destroyed by Engine::release)
+   bool inertia_in_flight = false, inertia_on_host = false;
+};
+
+struct Engine : EngineAnalysis {
    int device = 0;
    hipStream_t stream = nullptr;
    int nblk = 0, S = 0;
@@ -765,8 +843,6 @@ struct Engine {
    double refine_tol = 0.0;    // > 0: adaptive refinement, stop as soon as the error measure of every block is <= tol
    int refine_mode = 0;        // 0: ||r_b||inf / ||rhs_b||inf ; 1: normwise backward error ||r_b||inf / (max|K_b| ||x_b||inf + ||rhs_b||inf)
    double last_refine_measure = 0.0;
-   double* d_norms = nullptr;  // 3 * nblk: ||r||, ||rhs||, ||x|| per block
-   double* h_norms = nullptr;  // pinned
    int last_refine_steps = 0;
    double thr_rel = 1e-13, repl_rel = 1e-8;
    AnalyzeOptions opt;
@@ -777,73 +853,26 @@ struct Engine {
    std::vector<long long> x_off;    // nblk+1 offsets into flat vectors
    std::vector<LevelRange> levels;
    std::vector<LevelRange> levels_top;   // the spine's levels, for the multi-vector sweeps (which are level-scheduled throughout)
-   int *d_frowptr = nullptr, *d_fcol = nullptr, *d_fsrc = nullptr;   // full row structure of K for the refinement residual
-   long long* d_flong = nullptr;   // its rows longer than FULL_LONG_ROW
    int n_flong = 0;
-   int* d_sctab = nullptr;    // sparse Schur complement (set_sc_tables): position tables, BlkDesc::sctab_off
    int schur_mode = 0;        // requested: 0 auto, 1 augmented partial factorisation, 2 blocked solves (reference K4-K6)
    int schur_mode_eff = 1;    // what analyze() settled on
    std::vector<int> schur_cols;   // non-empty Schur columns (any block), ascending
-   int *d_schur_cols = nullptr, *d_schur_slot = nullptr;
-   // fronts on the rows of K only (BlockSym::mf_konly): records and lists of k_border_rows / k_border_tail
-   int* d_kb_rec = nullptr;
-   long long* d_kb_off = nullptr;       // per supernode (sorted id): offset of its record, -1 none
-   int* d_kb_list = nullptr;            // fronts with border rows, level after level
-   std::vector<int> kb_level_off;       // offsets into d_kb_list per level (size levels + 1)
-   std::vector<int> kb_level_pairs, kb_level_lds;   // per level: most pairs of one front, bytes of the largest border-row block (LDS of k_border_rows)
-   int* d_kb_tail = nullptr;
-   int n_kb_tail = 0;
    int sn_width = 0;           // > 0: supernode width cap of this engine instead of the tuned default (the sparse root: a single block, every level is latency)
    bool mf = false;            // multifrontal head (k_front): update matrices go from child to parent front, no FP64 atomics in the head
-   std::vector<MfLaunch> mf_launches;
-   double* d_mfU = nullptr;    // update matrices of the fronts
-   double* d_mfLV = nullptr;   // d and l of the simple leaves below fronts, front by front
-   int *d_roots = nullptr, *d_root_off = nullptr;   // fronts without a head parent, per block (k_root_assemble)
-   BbBatch* d_bb_batches = nullptr;                 // border split (k_border_schur): batches of supernodes with border rows, block after block
-   BbMeta* d_bb_meta = nullptr;
-   int *d_bb_off = nullptr, *d_bb_pos = nullptr;    // batches of block b: [d_bb_off[b], d_bb_off[b + 1]); compressed border ids of the staged rows
-   long long bb_doubles = 0;                        // doubles of the border-row arena (behind the panels inside d_arena)
-   double* d_bb_out = nullptr;                      // deterministic mode: the blocks' border x border triangles before they join their groups
    std::vector<int> h_bb_off_keep;
-   int n_bb = 0, bb_stage = 3072, bb_nbmax = 0, bb_poscap = 0;
+   int bb_stage = 3072, bb_nbmax = 0, bb_poscap = 0;
    bool bb_two_per_cu = false;   // k_border_schur: staging area sized for two workgroups per compute unit (bb_plan_size)
-   int* d_bb_round_blk = nullptr;                   // deterministic mode: the blocks of round k of k_border_schur
    std::vector<int> bb_round_off;
    std::vector<int> h_root_off_keep;
-   int n_roots = 0;
-   int* d_round_blk = nullptr;                       // deterministic mode: the blocks of round k at [round_off[k], round_off[k + 1])
    std::vector<int> round_off;
-   int* d_mfint = nullptr;     // front records (common.h)
    long long mfU_total = 0;
    int spine_total = 0, n_levels_all = 0;   // supernodes handled by the per-block spine kernels; tree height before the cut
-   int *d_spine = nullptr, *d_spine_off = nullptr;
    long long n_total = 0, nnzK_total = 0, nnzB_total = 0, arena_total = 0, xw_total = 0, bt_rows_total = 0;
    int nsn_total = 0;
-   TailPlan plan;
    PhaseTimer timer;
-
-   double* d_uarena = nullptr;   // U = L D copies of the tails (see k_tile_gemm)
    long long uarena_total = 0;
-   double *d_arena = nullptr, *d_kval = nullptr, *d_bval = nullptr, *d_winv = nullptr, *d_dtail = nullptr, *d_xw = nullptr;
-   double *d_rhs = nullptr, *d_res = nullptr, *d_stage = nullptr, *d_pref = nullptr;
-   long long *d_kdst = nullptr, *d_bdst = nullptr, *d_kdiag = nullptr, *d_kptr = nullptr, *d_psign_off = nullptr,
-             *d_perm_off = nullptr, *d_rowbase = nullptr, *d_bt_xoff = nullptr;
-   SnDesc* d_sns = nullptr;
-   BlkDesc* d_blks = nullptr;
-   // Forward substitution of the simple leaves as a gather (k_leaf_fwd_gather): the leaves' L entries by TARGET row - row list,
-   // row pointers, source (the leaf's position in the work vector), values (written in this order by k_head_factor_simple through
-   // d_lf_pos, which is indexed like d_rowidx).  No atomics, fixed order of the sums.
-   int *d_lf_rows = nullptr, *d_lf_ptr = nullptr, *d_lf_src = nullptr, *d_lf_pos = nullptr;
-   double* d_lf_val = nullptr;
-   long long lf_rows = 0, lf_entries = 0;
-   LeafDesc* d_leafdesc = nullptr;   // compact records of the level-0 simple leaves, in the order of d_sns (k_leaf_bwd)
-   int* d_lb_list = nullptr;         // the simple leaves that own border rows (k_leaf_border)
    int n_lb = 0, nb_pad_max = 0;
    int head_wcap = HEAD_WMAX;   // widest head supernode of this analysis (picks the register-lean variants of the chain kernels)
-   int *d_rowidx = nullptr, *d_upd = nullptr, *d_sncol = nullptr, *d_bmap = nullptr, *d_perm = nullptr, *d_inertia = nullptr, *d_nprimal = nullptr;
-   int *d_br_rowptr = nullptr, *d_br_sc = nullptr, *d_br_src = nullptr;   // the border by leaf row (k_border_mult_rows)
-   int *d_krowptr = nullptr, *d_kcolidx = nullptr, *d_bt_rowptr = nullptr, *d_bt_colidx = nullptr, *d_bt_rowsc = nullptr;
-   signed char* d_psign = nullptr;
    std::vector<int> h_inertia;
    std::vector<double> h_amax;   // max|K_b| of the current factorisation (backward-error refinement criterion)
 
@@ -853,90 +882,13 @@ struct Engine {
       if (ev_diag_in) (void)hipEventDestroy(ev_diag_in);
       if (ev_diag_out) (void)hipEventDestroy(ev_diag_out);
    }
+   // everything the analysis owns goes; the settings, the inputs and the streams stay
    void release() {
-      if (d_uarena) (void)hipFree(d_uarena);
-      d_uarena = nullptr;
-      // the row-panel groups of the Schur SYRK belong to the analysis they were cut for (set_sc_panels)
       for (auto ev : ev_sc) (void)hipEventDestroy(ev);
-      ev_sc.clear(); sc_groups.clear(); sc_row_begin.clear();
-      if (d_sc_tasks) (void)hipFree(d_sc_tasks);
-      d_sc_tasks = nullptr;
-      for (void* q : {(void*)d_lf_rows, (void*)d_lf_ptr, (void*)d_lf_src, (void*)d_lf_pos, (void*)d_lf_val})
-         if (q) (void)hipFree(q);
-      d_lf_rows = d_lf_ptr = d_lf_src = d_lf_pos = nullptr; d_lf_val = nullptr;
-      for (void* q : {(void*)d_br_rowptr, (void*)d_br_sc, (void*)d_br_src})
-         if (q) (void)hipFree(q);
-      d_br_rowptr = d_br_sc = d_br_src = nullptr;
-      if (d_leafdesc) (void)hipFree(d_leafdesc);
-      d_leafdesc = nullptr;
-      lf_rows = 0; lf_entries = 0;
-      if (d_mfU) (void)hipFree(d_mfU);
-      if (d_mfLV) (void)hipFree(d_mfLV);
-      for (void* q : {(void*)d_bb_batches, (void*)d_bb_meta, (void*)d_bb_off, (void*)d_bb_pos, (void*)d_bb_round_blk, (void*)d_bb_out})
-         if (q) (void)hipFree(q);
-      d_bb_out = nullptr;
-      d_bb_batches = nullptr; d_bb_meta = nullptr; d_bb_off = nullptr; d_bb_pos = nullptr; d_bb_round_blk = nullptr; n_bb = 0; bb_doubles = 0;
-      for (void* q : {(void*)d_roots, (void*)d_root_off, (void*)d_round_blk})
-         if (q) (void)hipFree(q);
-      d_roots = d_root_off = d_round_blk = nullptr;
-      n_roots = 0;
-      if (d_mfint) (void)hipFree(d_mfint);
-      d_mfU = nullptr; d_mfLV = nullptr; d_mfint = nullptr;
-      mf_launches.clear();
-      if (d_gemm_ctr) (void)hipFree(d_gemm_ctr);
-      d_gemm_ctr = nullptr;
-      for (auto& g : g_levels) g.release();
-      for (auto& g : gv_levels) g.release();
-      g_levels.clear(); gv_levels.clear();
-      g_tail.release(); g_sc.release(); gv_tail.release(); g_btm.release(); g_bm.release();
-      if (d_bt_tmp) (void)hipFree(d_bt_tmp);
-      d_bt_tmp = nullptr;
-      for (void* p : {(void*)d_det_tasks, (void*)d_gbuf, (void*)d_blk_group, (void*)d_gvec, (void*)d_tvec})
-         if (p) (void)hipFree(p);
-      d_det_tasks = nullptr; d_gbuf = nullptr; d_blk_group = nullptr; d_gvec = d_tvec = nullptr;
-      g_btm_grp.release(); g_sc_grp.release(); g_bslot_grp.release();
-      for (void* q : {(void*)d_bg_ent, (void*)d_bg_ptr, (void*)d_bg_idx, (void*)d_bg_val, (void*)d_bg_slot}) if (q) (void)hipFree(q);
-      d_bg_ent = nullptr; d_bg_ptr = d_bg_slot = nullptr; d_bg_idx = nullptr; d_bg_val = nullptr; n_bg_targets = n_bg_ent = 0; det_aug_ready = false;
-      if (d_slot_val) (void)hipFree(d_slot_val);
-      if (d_vslot_val) (void)hipFree(d_vslot_val);
-      if (d_mvslot) (void)hipFree(d_mvslot);
-      d_slot_val = d_vslot_val = d_mvslot = nullptr;
-      void* ptrs[] = {d_arena, d_kval, d_bval, d_winv, d_dtail, d_xw, d_rhs, d_res, d_stage, d_pref, d_norms, d_kdst, d_bdst, d_kdiag, d_kptr,
-                      d_psign_off, d_perm_off, d_rowbase, d_bt_xoff, d_sns, d_blks, d_rowidx, d_upd, d_sncol, d_bmap, d_perm, d_spine, d_spine_off, d_schur_cols, d_schur_slot, d_sctab, d_frowptr, d_fcol, d_fsrc, d_flong,
-                      d_inertia, d_nprimal, d_krowptr, d_kcolidx, d_bt_rowptr, d_bt_colidx, d_bt_rowsc, d_psign};
-      for (void* p : ptrs)
-         if (p) (void)hipFree(p);
-      d_arena = d_kval = d_bval = d_winv = d_dtail = d_xw = d_rhs = d_res = d_stage = d_pref = d_norms = nullptr;
-      if (h_norms) (void)hipHostFree(h_norms);
-      h_norms = nullptr;
-      if (h_inertia_pin) (void)hipHostFree(h_inertia_pin);
-      h_inertia_pin = nullptr;
       if (ev_inertia) (void)hipEventDestroy(ev_inertia);
-      ev_inertia = nullptr;
-      inertia_in_flight = inertia_on_host = false;
-      for (double** q : {&d_mx_xw, &d_mx_rhs, &d_mx_res, &d_hostx, &d_hostpack, &d_mmeasure}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-      if (d_midx) (void)hipFree(d_midx);
-      d_midx = nullptr;
-      if (h_mmeasure) (void)hipHostFree(h_mmeasure);
-      h_mmeasure = nullptr;
-      mx_cap = 0;
-      hostx_cap = hostpack_cap = 0;
-      d_kdst = d_bdst = d_kdiag = d_kptr = d_psign_off = d_perm_off = d_rowbase = d_bt_xoff = nullptr;
-      d_sns = nullptr; d_blks = nullptr;
-      d_nprimal = nullptr;
-      d_spine = d_spine_off = d_schur_cols = d_schur_slot = d_sctab = nullptr;
-      for (void* q : {(void*)d_kb_rec, (void*)d_kb_off, (void*)d_kb_list, (void*)d_kb_tail}) if (q) (void)hipFree(q);
-      d_kb_rec = nullptr; d_kb_off = nullptr; d_kb_list = nullptr; d_kb_tail = nullptr; n_kb_tail = 0; kb_level_off.clear(); kb_level_pairs.clear(); kb_level_lds.clear();
-      d_frowptr = d_fcol = d_fsrc = nullptr; d_flong = nullptr;
-      d_rowidx = d_upd = d_sncol = d_bmap = d_perm = d_inertia = d_krowptr = d_kcolidx = d_bt_rowptr = d_bt_colidx = d_bt_rowsc = nullptr;
-      d_psign = nullptr;
-      plan.release();
-      sweep.release();
-      tsingle.release();
+      static_cast<EngineAnalysis&>(*this) = EngineAnalysis();
    }
 
-   SweepRt sweep;
-   TailSingle tsingle;                               // the tails as one dependency-driven launch (tailkernel.hip.h)
    bool tail_single = false;                         // ... decided at analyze time: the tails are then assembled in a scratch region (BlkDesc::T_in)
    long long tail_scratch = 0;                       // doubles of that region, behind the panels and the border-row arena
    hipStream_t side = nullptr;                       // diagonal tiles of the tail are factorised here, beside the column update
@@ -944,17 +896,6 @@ struct Engine {
    // ---- deterministic mode (pips_hip_batch_set_deterministic): no FP64 atomics on the path.  Every scattered contribution of
    // the head owns a slot; at analyze time the kernels run once in recording mode, the host groups the slots by target (per
    // elimination-tree level, then the tail, then the Schur complement) and the factorisation gathers them in that fixed order.
-   struct GatherList {
-      long long n_targets = 0, n_slots = 0;
-      long long *d_tgt = nullptr, *d_off = nullptr, *d_slots = nullptr;
-      void release() {
-         for (void* p : {(void*)d_tgt, (void*)d_off, (void*)d_slots})
-            if (p) (void)hipFree(p);
-         d_tgt = d_off = d_slots = nullptr;
-         n_targets = n_slots = 0;
-      }
-   };
-   struct SlotEntry { long long target, slot; };
    bool deterministic = false;
    // The slot / gather scheme of the head belongs to deterministic mode (without it, round 2 measured the head phase of config 2 at 5.0 ms
    // against 5.5 ms with FP64 atomics - not worth 16 bytes of device memory per contribution and the longer analysis; the switch that
@@ -963,21 +904,11 @@ struct Engine {
    bool slot_solves = false;    // single-RHS forward substitution through slots outside deterministic mode too (measured: no gain)
    static constexpr long long HEAD_SLOTS_MAX = 400LL * 1000 * 1000;
    long long slots_total = 0, vslots_total = 0;
-   double *d_slot_val = nullptr, *d_vslot_val = nullptr;
    int last_multi_path = 0;      // how the last solve(nrhs) went: 0 one sweep per right-hand side, 1 interleaved panels, 2 interleaved panels with the slot / gather forward substitution
-   double* d_mvslot = nullptr;   // deterministic mode, several right-hand sides: the forward substitution's slots for one panel of MQ (solve_multi)
-   std::vector<GatherList> g_levels, gv_levels;   // targets inside the head, per level (factorisation / forward substitution)
-   GatherList g_tail, g_sc, gv_tail;
    std::vector<SlotEntry> sc_e_keep;
    std::vector<int> sc_blk_keep;
-   GatherList g_sc_grp;            // Schur targets of the head inside the group buffers
    std::vector<int> h_bt_rowsc_keep, h_bt_rownnz_keep, h_bt_rowblk_keep;
-   GatherList g_btm_grp;           // border rows per (group, Schur column): Br^T z summed group-wise, then in the fixed tree
-   double *d_gvec = nullptr, *d_tvec = nullptr;
    std::vector<TaskList> det_rounds;
-   TileTask* d_det_tasks = nullptr;
-   double* d_gbuf = nullptr;
-   int* d_blk_group = nullptr;
    int det_n_groups = 0, det_first_slot = 0;
    // Several ranks whose count divides eight: every rank's group buffers travel to every rank (an all-reduce in which the others hold
    // zeros at these slots: exact) and ALL eight slots are added in the one fixed tree of k_reduce_groups on every rank - the sums
@@ -1019,9 +950,8 @@ struct Engine {
                if (h_root_off_keep[b + 1] > h_root_off_keep[b]) rb.push_back(b);
             round_off.push_back((int)rb.size());
          }
-         if (d_round_blk) { (void)hipFree(d_round_blk); d_round_blk = nullptr; }
          if (rb.empty()) rb.push_back(0);
-         int rcb = dev_upload(&d_round_blk, rb, stream);
+         int rcb = d_round_blk.upload(rb);
          if (rcb) return rcb;
          // ... and the same rounds over the blocks whose border x border part k_border_schur forms
          std::vector<int> bbr;
@@ -1031,9 +961,8 @@ struct Engine {
                if (n_bb > 0 && h_bb_off_keep[b + 1] > h_bb_off_keep[b]) bbr.push_back(b);
             bb_round_off.push_back((int)bbr.size());
          }
-         if (d_bb_round_blk) { (void)hipFree(d_bb_round_blk); d_bb_round_blk = nullptr; }
          if (bbr.empty()) bbr.push_back(0);
-         if ((rcb = dev_upload(&d_bb_round_blk, bbr, stream))) return rcb;
+         if ((rcb = d_bb_round_blk.upload(bbr))) return rcb;
       }
       det_rounds.clear();
       std::vector<TileTask> all;
@@ -1044,31 +973,27 @@ struct Engine {
          det_rounds.push_back(l);
       }
       if (all.empty()) all.push_back({-1, 0, 0, 0});
-      for (void* p : {(void*)d_det_tasks, (void*)d_gbuf, (void*)d_blk_group})
-         if (p) (void)hipFree(p);
-      d_det_tasks = nullptr; d_gbuf = nullptr; d_blk_group = nullptr;
+      d_det_tasks.reset(); d_gbuf.reset(); d_blk_group.reset();
       int rc;
-      if ((rc = dev_upload(&d_det_tasks, all, stream)) || (rc = dev_upload(&d_blk_group, grp, stream))) return rc;
+      if ((rc = d_det_tasks.upload(all)) || (rc = d_blk_group.upload(grp))) return rc;
       // (the group buffers themselves are allocated by the first factorisation that has a Schur complement to fill: a system with the
       //  sparse root never needs the det_n_groups x S x S doubles of the dense layout this is first called with)
       {  // the head's own Schur contributions join their block's group buffer
-         g_sc_grp.release();
+         g_sc_grp = GatherList();
          std::vector<SlotEntry> ent(sc_e_keep.size());
          for (size_t i = 0; i < sc_e_keep.size(); ++i) ent[i] = {(long long)grp[sc_blk_keep[i]] * det_gstride() + sc_e_keep[i].target, sc_e_keep[i].slot};
          if ((rc = upload_gather(ent, g_sc_grp))) return rc;
       }
       // Br^T z in the same group order: rows of group g go to slot g of an 8 x S scratch matrix
-      g_btm_grp.release();
-      if (d_gvec) (void)hipFree(d_gvec);
-      if (d_tvec) (void)hipFree(d_tvec);
-      d_gvec = d_tvec = nullptr;
+      g_btm_grp = GatherList();
+      d_gvec.reset(); d_tvec.reset();
       if (S > 0) {
          std::vector<SlotEntry> ent;
          for (long long i = 0; i < bt_rows_total; ++i)
             if (h_bt_rownnz_keep[(size_t)i] > 0) ent.push_back({(long long)grp[h_bt_rowblk_keep[(size_t)i]] * S + h_bt_rowsc_keep[(size_t)i], i});
          if ((rc = upload_gather(ent, g_btm_grp))) return rc;
-         HIP_TRY(hipMalloc((void**)&d_gvec, (size_t)8 * S * sizeof(double)));
-         HIP_TRY(hipMalloc((void**)&d_tvec, (size_t)S * sizeof(double)));
+         PIPS_TRY(d_gvec.alloc((size_t)8 * S));
+         PIPS_TRY(d_tvec.alloc((size_t)S));
          if ((rc = build_det_aug(grp))) return rc;
       }
       if (!det_aug_ready) aug_sweeps_ok = false;   // (deterministic mode takes the sweeps of the augmented factor only through forward_augmented_det)
@@ -1080,9 +1005,9 @@ struct Engine {
    // into the group slots of d_gvec.
    int build_det_aug(const std::vector<int>& grp) {
       det_aug_ready = false;
-      for (void* q : {(void*)d_bg_ent, (void*)d_bg_ptr, (void*)d_bg_idx, (void*)d_bg_val, (void*)d_bg_slot}) if (q) (void)hipFree(q);
-      d_bg_ent = nullptr; d_bg_ptr = d_bg_slot = nullptr; d_bg_idx = nullptr; d_bg_val = nullptr; n_bg_targets = n_bg_ent = 0;
-      g_bslot_grp.release();
+      d_bg_ent.reset(); d_bg_ptr.reset(); d_bg_idx.reset(); d_bg_val.reset(); d_bg_slot.reset();
+      n_bg_targets = n_bg_ent = 0;
+      g_bslot_grp = GatherList();
       if (!aug_sweeps_ok || h_sns_keep.empty()) return PIPS_OK;
       std::vector<long long> tbase(nblk + 1, 0);
       for (int b = 0; b < nblk; ++b) tbase[b + 1] = tbase[b] + h_blks[b].nb;
@@ -1130,38 +1055,21 @@ struct Engine {
             col.push_back({(long long)grp[b] * S + sym[b].bmap[(size_t)g], slot[(size_t)(tbase[b] + g)]});
          }
       int rc;
-      if ((rc = dev_upload(&d_bg_ent, ent, stream)) || (rc = dev_upload(&d_bg_ptr, cnt, stream)) || (rc = dev_upload(&d_bg_idx, idx, stream)) ||
-          (rc = dev_upload(&d_bg_slot, slot, stream)) || (rc = upload_gather(col, g_bslot_grp)))
+      if ((rc = d_bg_ent.upload(ent)) || (rc = d_bg_ptr.upload(cnt)) || (rc = d_bg_idx.upload(idx)) ||
+          (rc = d_bg_slot.upload(slot)) || (rc = upload_gather(col, g_bslot_grp)))
          return rc;
-      HIP_TRY(hipMalloc((void**)&d_bg_val, (size_t)std::max<long long>(n_ent, 1) * sizeof(double)));
+      PIPS_TRY(d_bg_val.alloc((size_t)std::max<long long>(n_ent, 1)));
       n_bg_ent = n_ent;
       n_bg_targets = nt;
       det_aug_ready = true;
       return PIPS_OK;
    }
-   GatherList g_btm, g_bm;        // border products: rows per Schur column, entries per leaf row
-   // deterministic mode, forward sweep of the augmented factor: the border slots of the work vector are gathered, target by target, from the
-   // border rows of the head supernodes (k_border_gather_det: no atomics, fixed order) and then group-wise into d_gvec like Br^T z
-   BgEntry* d_bg_ent = nullptr;
-   long long *d_bg_ptr = nullptr, *d_bg_slot = nullptr;
-   int* d_bg_idx = nullptr;
-   double* d_bg_val = nullptr;
-   long long n_bg_targets = 0, n_bg_ent = 0;
-   GatherList g_bslot_grp;
-   bool det_aug_ready = false;
-   double* d_bt_tmp = nullptr;
-   int* d_gemm_ctr = nullptr;     // counter slots of the persistent update kernel
    int gemm_ctr_cursor = 0;
-   // ---- Schur SYRK in row-panel groups, so that a multi-rank root can reduce panel p while the leaves still compute p + 1 ..
-   std::vector<TaskList> sc_groups;
-   std::vector<int> sc_row_begin;          // panel p = Schur rows [sc_row_begin[p], sc_row_begin[p + 1])
-   std::vector<hipEvent_t> ev_sc;
-   TileTask* d_sc_tasks = nullptr;
    int set_sc_panels(int n_panels) {
       if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_panels: analyze first");
       for (auto ev : ev_sc) (void)hipEventDestroy(ev);
       ev_sc.clear(); sc_groups.clear(); sc_row_begin.clear();
-      if (d_sc_tasks) { (void)hipFree(d_sc_tasks); d_sc_tasks = nullptr; }
+      d_sc_tasks.reset();
       n_panels = std::min(n_panels, std::max(1, S / (2 * TILE)));
       if (n_panels <= 1 || schur_mode_eff != 1) return PIPS_OK;
       for (int q = 0; q <= n_panels; ++q) sc_row_begin.push_back(q == n_panels ? S : (int)((long long)S * q / n_panels) / TILE * TILE);
@@ -1189,7 +1097,7 @@ struct Engine {
          ev_sc.push_back(ev);
       }
       if (all.empty()) all.push_back({-1, 0, 0, 0});
-      return dev_upload(&d_sc_tasks, all, stream);
+      return d_sc_tasks.upload(all);
    }
    TailCtx ctx() {
       TailCtx c{d_blks, &plan, d_arena, d_dtail, d_winv, d_psign, d_psign_off, d_bmap, d_inertia, stream,
@@ -1506,7 +1414,7 @@ struct Engine {
          }
          n_roots = (int)h_roots.size();
          h_root_off_keep = h_root_off;
-         if ((rc = dev_upload(&d_roots, h_roots, stream)) || (rc = dev_upload(&d_root_off, h_root_off, stream))) return rc;
+         if ((rc = d_roots.upload(h_roots)) || (rc = d_root_off.upload(h_root_off))) return rc;
          // border split: the supernodes whose border rows k_border_schur multiplies out - the fronts, and the simple leaves below a front
          // (a leaf without a front above it scatters its whole rank-one update itself), ascending; their border rows live a second
          // time in the border-row arena (per supernode w x rp doubles + w pivots, padded to even), cut into batches of up to BB_GMAX
@@ -1545,8 +1453,8 @@ struct Engine {
          }
          n_bb = (int)h_batch.size();
          if (n_bb > 0) {
-            if ((rc = dev_upload(&d_bb_batches, h_batch, stream)) || (rc = dev_upload(&d_bb_meta, h_meta, stream)) ||
-                (rc = dev_upload(&d_bb_pos, h_bbpos, stream)) || (rc = dev_upload(&d_bb_off, h_bb_off_keep, stream))) return rc;
+            if ((rc = d_bb_batches.upload(h_batch)) || (rc = d_bb_meta.upload(h_meta)) ||
+                (rc = d_bb_pos.upload(h_bbpos)) || (rc = d_bb_off.upload(h_bb_off_keep))) return rc;
          }
          bb_doubles = bb_total - arena_total;
       }
@@ -1583,8 +1491,8 @@ struct Engine {
             if (h_rec.empty()) h_rec.push_back(0);
             if (h_list.empty()) h_list.push_back(0);
             if (h_tail.empty()) h_tail.push_back(0);
-            if ((rc = dev_upload(&d_kb_rec, h_rec, stream)) || (rc = dev_upload(&d_kb_off, h_off, stream)) || (rc = dev_upload(&d_kb_list, h_list, stream)) ||
-                (rc = dev_upload(&d_kb_tail, h_tail, stream))) return rc;
+            if ((rc = d_kb_rec.upload(h_rec)) || (rc = d_kb_off.upload(h_off)) || (rc = d_kb_list.upload(h_list)) ||
+                (rc = d_kb_tail.upload(h_tail))) return rc;
          }
       }
       // spine lists: per block, ascending local index = postorder (children before parents)
@@ -1661,9 +1569,9 @@ struct Engine {
             for (int64_t pos : s.mf_fix) h_mfint[(size_t)(mfint_base[b] + pos)] = sorted_id[b][s.mf_int[(size_t)pos]];
          }
          mfU_total = mfU_base[nblk];
-         if ((rc = dev_upload(&d_mfint, h_mfint, stream))) return rc;
-         HIP_TRY(hipMalloc((void**)&d_mfU, (size_t)std::max<long long>(mfU_total, 1) * sizeof(double)));
-         HIP_TRY(hipMalloc((void**)&d_mfLV, (size_t)std::max<long long>(mfLV_base[nblk], 1) * sizeof(double)));
+         if ((rc = d_mfint.upload(h_mfint))) return rc;
+         PIPS_TRY(d_mfU.alloc((size_t)std::max<long long>(mfU_total, 1)));
+         PIPS_TRY(d_mfLV.alloc((size_t)std::max<long long>(mfLV_base[nblk], 1)));
       }
       {  // both triangles, row by row: entry (i, j) of the lower CSR also appears in row j as (j, i)
          std::vector<int> frp(n_total + 1, 0);
@@ -1688,8 +1596,8 @@ struct Engine {
          for (long long r = 0; r < n_total; ++r)
             if (frp[r + 1] - frp[r] > FULL_LONG_ROW) flong.push_back(r);
          n_flong = (int)flong.size();
-         if ((rc = dev_upload(&d_frowptr, frp, stream)) || (rc = dev_upload(&d_fcol, fcol, stream)) || (rc = dev_upload(&d_fsrc, fsrc, stream)) ||
-             (rc = dev_upload(&d_flong, flong, stream)))
+         if ((rc = d_frowptr.upload(frp)) || (rc = d_fcol.upload(fcol)) || (rc = d_fsrc.upload(fsrc)) ||
+             (rc = d_flong.upload(flong)))
             return rc;
       }
       // border CSR, global
@@ -1720,10 +1628,9 @@ struct Engine {
             if (h_bt_rowptr[i + 1] > h_bt_rowptr[i]) by_sc.push_back({(long long)h_bt_rowsc[i], i});
             for (int q = h_bt_rowptr[i]; q < h_bt_rowptr[i + 1]; ++q) by_entry.push_back({h_bt_xoff[i] + h_bt_colidx[q], (long long)q});
          }
-         g_btm.release(); g_bm.release();
+         g_btm = GatherList(); g_bm = GatherList();
          if ((rc = upload_gather(by_sc, g_btm)) || (rc = upload_gather(by_entry, g_bm))) return rc;
-         if (d_bt_tmp) (void)hipFree(d_bt_tmp);
-         HIP_TRY(hipMalloc((void**)&d_bt_tmp, (size_t)std::max<long long>(std::max(bt_rows_total, nnzB_total), 1) * sizeof(double)));
+         PIPS_TRY(d_bt_tmp.alloc((size_t)std::max<long long>(std::max(bt_rows_total, nnzB_total), 1)));
       }
       {  // non-empty Schur columns over all blocks (the reference skips empty border columns, :870-874)
          std::vector<char> used(std::max(S, 1), 0);
@@ -1735,48 +1642,47 @@ struct Engine {
          std::vector<int> slot(std::max(S, 1), -1);
          for (int s2 = 0; s2 < S; ++s2)
             if (used[s2]) { slot[s2] = (int)schur_cols.size(); schur_cols.push_back(s2); }
-         if ((rc = dev_upload(&d_schur_cols, schur_cols, stream))) return rc;
-         if ((rc = dev_upload(&d_schur_slot, slot, stream))) return rc;
+         if ((rc = d_schur_cols.upload(schur_cols))) return rc;
+         if ((rc = d_schur_slot.upload(slot))) return rc;
       }
 
       // ---- device allocation / upload
-      HIP_TRY(hipMalloc((void**)&d_arena, std::max<long long>(arena_total + bb_doubles + tail_scratch, 1) * sizeof(double)));
+      PIPS_TRY(d_arena.alloc(std::max<long long>(arena_total + bb_doubles + tail_scratch, 1)));
       if (tail_single) HIP_TRY(hipMemsetAsync(d_arena, 0, (size_t)arena_total * sizeof(double), stream));   // (tiles of the panels outside the envelopes are never written: they read as zero)
       if (bb_doubles > 0) HIP_TRY(hipMemsetAsync(d_arena + arena_total, 0, (size_t)bb_doubles * sizeof(double), stream));   // (the padding rows of the border-row arena stay zero)
-      HIP_TRY(hipMalloc((void**)&d_uarena, std::max<long long>(uarena_total, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_kval, std::max<long long>(nnzK_total, 1) * sizeof(double)));
+      PIPS_TRY(d_uarena.alloc(std::max<long long>(uarena_total, 1)));
+      PIPS_TRY(d_kval.alloc(std::max<long long>(nnzK_total, 1)));
       HIP_TRY(hipMemset(d_kval, 0, std::max<long long>(nnzK_total, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_winv, std::max<long long>(winv, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_dtail, std::max<long long>(dt, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_xw, std::max<long long>(xw_total, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_pref, std::max<long long>(xw_total, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_rhs, std::max<long long>(n_total, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_res, std::max<long long>(n_total, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_stage, std::max<long long>(n_total, 1) * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_norms, (size_t)3 * nblk * sizeof(double)));
-      HIP_TRY(hipHostMalloc((void**)&h_norms, (size_t)3 * nblk * sizeof(double), hipHostMallocDefault));
-      HIP_TRY(hipMalloc((void**)&d_inertia, (size_t)3 * nblk * sizeof(int)));
+      PIPS_TRY(d_winv.alloc(std::max<long long>(winv, 1)));
+      PIPS_TRY(d_dtail.alloc(std::max<long long>(dt, 1)));
+      PIPS_TRY(d_xw.alloc(std::max<long long>(xw_total, 1)));
+      PIPS_TRY(d_pref.alloc(std::max<long long>(xw_total, 1)));
+      PIPS_TRY(d_rhs.alloc(std::max<long long>(n_total, 1)));
+      PIPS_TRY(d_res.alloc(std::max<long long>(n_total, 1)));
+      PIPS_TRY(d_stage.alloc(std::max<long long>(n_total, 1)));
+      PIPS_TRY(d_norms.alloc((size_t)3 * nblk));
+      PIPS_TRY(h_norms.alloc((size_t)3 * nblk));
+      PIPS_TRY(d_inertia.alloc((size_t)3 * nblk));
       HIP_TRY(hipMemset(d_inertia, 0, (size_t)3 * nblk * sizeof(int)));
-      if ((rc = dev_upload(&d_bval, h_bval, stream))) return rc;
-      if ((rc = dev_upload(&d_kdst, h_kdst, stream))) return rc;
-      if ((rc = dev_upload(&d_bdst, h_bdst, stream))) return rc;
-      if ((rc = dev_upload(&d_kdiag, h_kdiag, stream))) return rc;
-      if ((rc = dev_upload(&d_kptr, kptr, stream))) return rc;
-      if ((rc = dev_upload(&d_psign_off, h_psign_off, stream))) return rc;
-      if ((rc = dev_upload(&d_perm_off, h_perm_off, stream))) return rc;
-      if ((rc = dev_upload(&d_rowbase, h_rowbase, stream))) return rc;
-      if ((rc = dev_upload(&d_bt_xoff, h_bt_xoff, stream))) return rc;
-      if ((rc = dev_upload(&d_sns, h_sns, stream))) return rc;
-      if ((rc = dev_upload(&d_blks, h_blks, stream))) return rc;
-      if ((rc = dev_upload(&d_rowidx, h_rowidx, stream))) return rc;
+      if ((rc = d_bval.upload(h_bval))) return rc;
+      if ((rc = d_kdst.upload(h_kdst))) return rc;
+      if ((rc = d_bdst.upload(h_bdst))) return rc;
+      if ((rc = d_kdiag.upload(h_kdiag))) return rc;
+      if ((rc = d_kptr.upload(kptr))) return rc;
+      if ((rc = d_psign_off.upload(h_psign_off))) return rc;
+      if ((rc = d_perm_off.upload(h_perm_off))) return rc;
+      if ((rc = d_rowbase.upload(h_rowbase))) return rc;
+      if ((rc = d_bt_xoff.upload(h_bt_xoff))) return rc;
+      if ((rc = d_sns.upload(h_sns))) return rc;
+      if ((rc = d_blks.upload(h_blks))) return rc;
+      if ((rc = d_rowidx.upload(h_rowidx))) return rc;
       {  // simple leaves that own border rows (sweeps of the augmented factor: k_leaf_border), and the widest padded border
          std::vector<int> lb;
          if (!levels.empty())
             for (int i = levels[0].simple_begin; i < levels[0].simple_begin + levels[0].simple_cnt; ++i)
                if (h_sns[i].rb < h_sns[i].r) lb.push_back(i);
          n_lb = (int)lb.size();
-         if (d_lb_list) { (void)hipFree(d_lb_list); d_lb_list = nullptr; }
-         if (n_lb > 0 && (rc = dev_upload(&d_lb_list, lb, stream))) return rc;
+         if (n_lb > 0 && (rc = d_lb_list.upload(lb))) return rc;
          nb_pad_max = 0;
          for (int b = 0; b < nblk; ++b) nb_pad_max = std::max(nb_pad_max, h_blks[b].nb_pad);
       }
@@ -1792,7 +1698,7 @@ struct Engine {
                while (r_in < sn.r && h_rowidx[sn.rows + r_in] < bd.n) ++r_in;
                h_leaf[i] = LeafDesc{sn.panel, (int)sn.rows, (int)bd.xw_off, sn.c0, r_in};
             }
-            if ((rc = dev_upload(&d_leafdesc, h_leaf, stream))) return rc;
+            if ((rc = d_leafdesc.upload(h_leaf))) return rc;
             std::vector<int> cnt((size_t)xw_total + 1, 0);
             long long nent = 0;
             for (int i = L0->simple_begin; i < L0->simple_begin + L0->simple_cnt; ++i) {
@@ -1823,26 +1729,26 @@ struct Engine {
                   }
                }
                lf_rows = (long long)h_rows.size(); lf_entries = nent;
-               if ((rc = dev_upload(&d_lf_rows, h_rows, stream))) return rc;
-               if ((rc = dev_upload(&d_lf_ptr, h_ptr, stream))) return rc;
-               if ((rc = dev_upload(&d_lf_src, h_src, stream))) return rc;
-               if ((rc = dev_upload(&d_lf_pos, h_pos, stream))) return rc;
-               HIP_TRY(hipMalloc((void**)&d_lf_val, (size_t)nent * sizeof(double)));
+               if ((rc = d_lf_rows.upload(h_rows))) return rc;
+               if ((rc = d_lf_ptr.upload(h_ptr))) return rc;
+               if ((rc = d_lf_src.upload(h_src))) return rc;
+               if ((rc = d_lf_pos.upload(h_pos))) return rc;
+               PIPS_TRY(d_lf_val.alloc((size_t)nent));
             }
          }
       }
-      if ((rc = dev_upload(&d_upd, h_upd, stream))) return rc;
-      if ((rc = dev_upload(&d_spine, h_spine, stream))) return rc;
-      if ((rc = dev_upload(&d_spine_off, h_spine_off, stream))) return rc;
-      if ((rc = dev_upload(&d_sncol, h_sncol, stream))) return rc;
-      if ((rc = dev_upload(&d_bmap, h_bmap, stream))) return rc;
-      if ((rc = dev_upload(&d_perm, h_perm, stream))) return rc;
-      if ((rc = dev_upload(&d_psign, h_psign, stream))) return rc;
-      if ((rc = dev_upload(&d_krowptr, h_krowptr, stream))) return rc;
-      if ((rc = dev_upload(&d_kcolidx, h_kcolidx, stream))) return rc;
-      if ((rc = dev_upload(&d_bt_rowptr, h_bt_rowptr, stream))) return rc;
-      if ((rc = dev_upload(&d_bt_colidx, h_bt_colidx, stream))) return rc;
-      if ((rc = dev_upload(&d_bt_rowsc, h_bt_rowsc, stream))) return rc;
+      if ((rc = d_upd.upload(h_upd))) return rc;
+      if ((rc = d_spine.upload(h_spine))) return rc;
+      if ((rc = d_spine_off.upload(h_spine_off))) return rc;
+      if ((rc = d_sncol.upload(h_sncol))) return rc;
+      if ((rc = d_bmap.upload(h_bmap))) return rc;
+      if ((rc = d_perm.upload(h_perm))) return rc;
+      if ((rc = d_psign.upload(h_psign))) return rc;
+      if ((rc = d_krowptr.upload(h_krowptr))) return rc;
+      if ((rc = d_kcolidx.upload(h_kcolidx))) return rc;
+      if ((rc = d_bt_rowptr.upload(h_bt_rowptr))) return rc;
+      if ((rc = d_bt_colidx.upload(h_bt_colidx))) return rc;
+      if ((rc = d_bt_rowsc.upload(h_bt_rowsc))) return rc;
       // ---- the border by LEAF row (t += alpha Br x0 as a gather, k_border_mult_rows): row pointers over the flat leaf space, Schur
       //      column and position in d_bval of every entry
       if (bt_rows_total > 0 && nnzB_total > 0 && nnzB_total < (1LL << 31)) {
@@ -1856,13 +1762,13 @@ struct Engine {
                const int q = fill[h_bt_xoff[r] + h_bt_colidx[p]]++;
                sc[q] = h_bt_rowsc[r]; src[q] = p;
             }
-         if ((rc = dev_upload(&d_br_rowptr, rp, stream)) || (rc = dev_upload(&d_br_sc, sc, stream)) || (rc = dev_upload(&d_br_src, src, stream)))
+         if ((rc = d_br_rowptr.upload(rp)) || (rc = d_br_sc.upload(sc)) || (rc = d_br_src.upload(src)))
             return rc;
       }
       {
          std::vector<int> np(nblk);
          for (int b = 0; b < nblk; ++b) np[b] = in[b].n_primal;
-         if ((rc = dev_upload(&d_nprimal, np, stream))) return rc;
+         if ((rc = d_nprimal.upload(np))) return rc;
       }
       // the diagonal tile of a column runs ahead on the side stream, its update first; tile rows start at their envelope (variants of the
       // tail factorisation without either: docs/HISTORY_r1_r2.md)
@@ -2028,7 +1934,7 @@ struct Engine {
          // every block at once (each supernode list in its fixed order) into a triangle of its own, then the blocks of a group in order: a walk
          // takes as long for 8 workgroups as for 256, so one launch per round of blocks made the share's factorisation 230 ms
          const long long tri = (long long)ncp;
-         if (!d_bb_out) HIP_TRY(hipMalloc((void**)&d_bb_out, (size_t)std::max(nblk, 1) * tri * sizeof(double)));
+         if (!d_bb_out) PIPS_TRY(d_bb_out.alloc((size_t)std::max(nblk, 1) * tri));
          rc = small ? go(k_border_schur<BLK, 3>, nblk, (const int*)nullptr, (double*)nullptr, 0LL, (const int*)nullptr, 1, 1, d_bb_out, tri)
                     : go(k_border_schur<BLK, 6>, nblk, (const int*)nullptr, (double*)nullptr, 0LL, (const int*)nullptr, 1, 1, d_bb_out, tri);
          for (size_t k = 0; k + 1 < bb_round_off.size() && !rc; ++k) {
@@ -2042,7 +1948,6 @@ struct Engine {
                     : go(k_border_schur<BLK, 6>, nblk, (const int*)nullptr, (double*)nullptr, 0LL, (const int*)nullptr, split, deterministic ? 1 : 0);
       return rc;
    }
-   long long* d_mfdbg = nullptr;   // PIPS_HIP_MF_CLOCKS: phase stamps of every front (8 per supernode), dumped after the factorisation
    int dump_front_clocks() {
       std::vector<long long> h((size_t)nsn_total * 8);
       HIP_TRY(hipStreamSynchronize(stream));
@@ -2107,20 +2012,20 @@ struct Engine {
       g.n_targets = (long long)tgt.size(); g.n_slots = (long long)e.size();
       if (tgt.empty()) return PIPS_OK;
       int rc;
-      if ((rc = dev_upload(&g.d_tgt, tgt, stream)) || (rc = dev_upload(&g.d_off, off, stream)) || (rc = dev_upload(&g.d_slots, sl, stream))) return rc;
+      if ((rc = g.d_tgt.upload(tgt)) || (rc = g.d_off.upload(off)) || (rc = g.d_slots.upload(sl))) return rc;
       return PIPS_OK;
    }
    int build_deterministic(int n_threads) {
       if (spine_total > 0) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode: spine kernels must be off");
       const int nlev = (int)levels.size();
-      g_levels.assign(nlev, GatherList());
-      gv_levels.assign(nlev, GatherList());
+      g_levels = std::vector<GatherList>(nlev);
+      gv_levels = std::vector<GatherList>(nlev);
       int rc = PIPS_OK;
       // ---- factorisation scatter: record where every slot goes (structure only; the numbers this pass produces are discarded)
       std::vector<long long> rec((size_t)std::max<long long>(slots_total, 1), -1);
       if (slots_total > 0) {
-         long long* d_rec = nullptr;
-         HIP_TRY(hipMalloc((void**)&d_rec, (size_t)slots_total * sizeof(long long)));
+         DevBuf<long long> d_rec;
+         PIPS_TRY(d_rec.alloc((size_t)slots_total));
          HIP_TRY(hipMemsetAsync(d_rec, 0xff, (size_t)slots_total * sizeof(long long), stream));
          double* fakeSC = d_arena;   // only offsets relative to it are formed (S > 0 blocks have border rows; none in Schur mode 2, whose heads have no border)
          const ScatterCtx sx{1, d_rec, nullptr, d_arena, fakeSC};
@@ -2128,8 +2033,8 @@ struct Engine {
          HIP_TRY(hipGetLastError());
          HIP_TRY(hipStreamSynchronize(stream));
          HIP_TRY(hipMemcpy(rec.data(), d_rec, (size_t)slots_total * sizeof(long long), hipMemcpyDeviceToHost));
-         (void)hipFree(d_rec);
-         HIP_TRY(hipMalloc((void**)&d_slot_val, (size_t)slots_total * sizeof(double)));
+         d_rec.reset();
+         PIPS_TRY(d_slot_val.alloc((size_t)slots_total));
       }
       // classify: Schur complement / tail of block b / head panel of a supernode at level l (targets of different blocks are disjoint)
       std::vector<std::vector<SlotEntry>> per_level(nlev);
@@ -2164,8 +2069,8 @@ struct Engine {
       if ((rc = upload_gather(tail_e, g_tail)) || (rc = upload_gather(sc_e, g_sc))) return rc;
       // ---- forward-substitution scatter: same recording, targets are entries of the permuted work vector
       if (vslots_total > 0) {
-         long long* d_rec = nullptr;
-         HIP_TRY(hipMalloc((void**)&d_rec, (size_t)vslots_total * sizeof(long long)));
+         DevBuf<long long> d_rec;
+         PIPS_TRY(d_rec.alloc((size_t)vslots_total));
          HIP_TRY(hipMemsetAsync(d_rec, 0xff, (size_t)vslots_total * sizeof(long long), stream));
          const ScatterCtx sxv{1, d_rec, nullptr, d_xw, nullptr};
          for (const LevelRange& L : levels) {
@@ -2181,8 +2086,8 @@ struct Engine {
          HIP_TRY(hipStreamSynchronize(stream));
          std::vector<long long> vrec((size_t)vslots_total);
          HIP_TRY(hipMemcpy(vrec.data(), d_rec, (size_t)vslots_total * sizeof(long long), hipMemcpyDeviceToHost));
-         (void)hipFree(d_rec);
-         HIP_TRY(hipMalloc((void**)&d_vslot_val, (size_t)vslots_total * sizeof(double)));
+         d_rec.reset();
+         PIPS_TRY(d_vslot_val.alloc((size_t)vslots_total));
          std::vector<std::vector<SlotEntry>> v_level(nlev);
          std::vector<SlotEntry> v_tail;
          for (int i = 0; i < nsn_total; ++i) {
@@ -2211,20 +2116,15 @@ struct Engine {
       if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_tables: analyze first");
       if (schur_mode_eff != 1) PIPS_FAIL(PIPS_ERR_STATE, "a sparse Schur complement needs Schur mode 1 (set it before analyze)");
       HIP_TRY(hipSetDevice(device));
-      if (d_sctab) { (void)hipFree(d_sctab); d_sctab = nullptr; }
-      int rc = dev_upload(&d_sctab, tab, stream);
+      int rc = d_sctab.upload(tab);
       if (rc) return rc;
       for (int b = 0; b < nblk; ++b) h_blks[b].sctab_off = off[b];
       HIP_TRY(hipMemcpy(d_blks, h_blks.data(), (size_t)nblk * sizeof(BlkDesc), hipMemcpyHostToDevice));
       sc_len = sc_nnz;
       if (head_slots) {   // the Schur targets of the head moved into the CSR value array: record again
-         for (auto& g : g_levels) g.release();
-         for (auto& g : gv_levels) g.release();
-         g_tail.release(); g_sc.release(); gv_tail.release();
-         if (d_slot_val) (void)hipFree(d_slot_val);
-         if (d_vslot_val) (void)hipFree(d_vslot_val);
-         if (d_mvslot) (void)hipFree(d_mvslot);
-         d_slot_val = d_vslot_val = d_mvslot = nullptr;
+         g_levels.clear(); gv_levels.clear();
+         g_tail = GatherList(); g_sc = GatherList(); gv_tail = GatherList();
+         d_slot_val.reset(); d_vslot_val.reset(); d_mvslot.reset();
          if ((rc = build_deterministic(1))) return rc;
       }
       return PIPS_OK;
@@ -2234,7 +2134,7 @@ struct Engine {
       if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "factor called before analyze");
       HIP_TRY(hipSetDevice(device));
       if (deterministic && SC && S > 0 && !d_gbuf && d_blk_group)
-         HIP_TRY(hipMalloc((void**)&d_gbuf, (size_t)det_n_groups * det_gstride() * sizeof(double)));
+         PIPS_TRY(d_gbuf.alloc((size_t)det_n_groups * det_gstride()));
       timer.reset();
       if (timer.on) timer.begin(stream, 6);
       if (timer.on) timer.begin(stream, 0);
@@ -2247,7 +2147,7 @@ struct Engine {
       hipLaunchKernelGGL(k_arena_clear, dim3(256, nblk), dim3(256), 0, stream, d_blks, d_arena, mf ? 1 : 0);
       HIP_TRY(hipMemsetAsync(d_inertia, 0, (size_t)3 * nblk * sizeof(int), stream));
       {
-         if (!d_gemm_ctr) HIP_TRY(hipMalloc((void**)&d_gemm_ctr, (size_t)GEMM_CTR_SLOTS * 8 * sizeof(int)));
+         if (!d_gemm_ctr) PIPS_TRY(d_gemm_ctr.alloc((size_t)GEMM_CTR_SLOTS * 8));
          HIP_TRY(hipMemsetAsync(d_gemm_ctr, 0, (size_t)GEMM_CTR_SLOTS * 8 * sizeof(int), stream));
          gemm_ctr_cursor = 0;
       }
@@ -2315,7 +2215,7 @@ struct Engine {
          if (timer.on) timer.end(stream);
       }
       if (mf && getenv("PIPS_HIP_MF_CLOCKS")) {
-         if (!d_mfdbg) HIP_TRY(hipMalloc((void**)&d_mfdbg, (size_t)std::max(nsn_total, 1) * 8 * sizeof(long long)));
+         if (!d_mfdbg) PIPS_TRY(d_mfdbg.alloc((size_t)std::max(nsn_total, 1) * 8));
          else { int drc = dump_front_clocks(); if (drc) return drc; }
       }
       hipLaunchKernelGGL(k_pref_tail, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_arena, d_pref, 0);
@@ -2336,7 +2236,7 @@ struct Engine {
       if (timer.on) (void)hipEventRecord(timer.recs[total_rec].b, stream);
       h_amax.clear();
       if (!h_inertia_pin) {
-         HIP_TRY(hipHostMalloc((void**)&h_inertia_pin, (size_t)(3 * nblk + 1) * sizeof(int), hipHostMallocDefault));
+         PIPS_TRY(h_inertia_pin.alloc((size_t)(3 * nblk + 1)));
          h_inertia_pin[3 * nblk] = 0;
          HIP_TRY(hipEventCreateWithFlags(&ev_inertia, hipEventDisableTiming));
       }
@@ -2360,7 +2260,7 @@ struct Engine {
       const bool det = deterministic && d_gbuf;
       if (det && ldSC != S) PIPS_FAIL(PIPS_ERR_ARG, "deterministic mode, Schur mode 2: ldSC %d must equal S %d (the group buffers are S x S)", ldSC, S);
       const bool det_panel = det && det_panel_fits();
-      if (det_panel && !d_mvslot) HIP_TRY(hipMalloc((void**)&d_mvslot, (size_t)std::max<long long>(vslots_total, 1) * MQ * sizeof(double)));
+      if (det_panel && !d_mvslot) PIPS_TRY(d_mvslot.alloc((size_t)std::max<long long>(vslots_total, 1) * MQ));
       const int bs = 32, ncols = (int)schur_cols.size();
       for (int c0 = 0; c0 < ncols; c0 += bs) {
          const int nr = std::min(bs, ncols - c0);
@@ -2575,30 +2475,22 @@ struct Engine {
    // multi-RHS solve (DoubleLinearSolver::solve(int nrhss, double* rhss, int*), PardisoSolver.C:276-352): all right-hand
    // sides share every launch (grid.y/z = rhs index); refine_steps unconditional refinement steps.  X_dev: nrhs vectors of
    // length n_total at distance x_stride.
-   double *d_mx_xw = nullptr, *d_mx_rhs = nullptr, *d_mx_res = nullptr;
-   int mx_cap = 0;
-   double *d_mmeasure = nullptr, *h_mmeasure = nullptr;   // solve_multi: the refinement measure per right-hand side (device / pinned)
-   int* d_midx = nullptr;                                // ... and the columns that take the correction solve
-   double* d_hostx = nullptr;   // device copy of host right-hand sides (pips_hip_ldl_solve), kept between calls
-   size_t hostx_cap = 0;
-   double* d_hostpack = nullptr;   // packed rows + their indices of pips_hip_ldl_solve_sparse, kept between calls likewise
-   size_t hostpack_cap = 0;
    static constexpr int MULTI_CHUNK_MAX = 256;   // right-hand sides per pass (eight panels)
    int ensure_multi_buffers(int want = 32) {
       want = std::min(MULTI_CHUNK_MAX, (std::max(want, 32) + MQ - 1) / MQ * MQ);
       if (mx_cap < want) {
          HIP_TRY(hipSetDevice(device));
          HIP_TRY(hipStreamSynchronize(stream));
-         for (double** p : {&d_mx_xw, &d_mx_rhs, &d_mx_res}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-         HIP_TRY(hipMalloc((void**)&d_mx_xw, (size_t)want * std::max<long long>(xw_total, 1) * sizeof(double)));
-         HIP_TRY(hipMalloc((void**)&d_mx_rhs, (size_t)want * std::max<long long>(n_total, 1) * sizeof(double)));
-         HIP_TRY(hipMalloc((void**)&d_mx_res, (size_t)want * std::max<long long>(n_total, 1) * sizeof(double)));
+         d_mx_xw.reset(); d_mx_rhs.reset(); d_mx_res.reset();   // (all three go before the larger ones come)
+         PIPS_TRY(d_mx_xw.alloc((size_t)want * std::max<long long>(xw_total, 1)));
+         PIPS_TRY(d_mx_rhs.alloc((size_t)want * std::max<long long>(n_total, 1)));
+         PIPS_TRY(d_mx_res.alloc((size_t)want * std::max<long long>(n_total, 1)));
          mx_cap = want;
       }
       if (!d_mmeasure) {   // per right-hand side: the measure of the adaptive refinement (device / pinned host, behind it the list of columns to correct)
-         HIP_TRY(hipMalloc((void**)&d_mmeasure, MULTI_CHUNK_MAX * sizeof(double)));
-         HIP_TRY(hipMalloc((void**)&d_midx, MULTI_CHUNK_MAX * sizeof(int)));
-         HIP_TRY(hipHostMalloc((void**)&h_mmeasure, MULTI_CHUNK_MAX * (sizeof(double) + sizeof(int)), hipHostMallocDefault));
+         PIPS_TRY(d_mmeasure.alloc(MULTI_CHUNK_MAX));
+         PIPS_TRY(d_midx.alloc(MULTI_CHUNK_MAX));
+         PIPS_TRY(h_mmeasure.alloc(MULTI_CHUNK_MAX + MULTI_CHUNK_MAX / 2));   // (a double and an int per right-hand side)
       }
       return PIPS_OK;
    }
@@ -2614,7 +2506,7 @@ struct Engine {
             if (int rc = solve(X_dev + (long long)r * x_stride)) return rc;
          return PIPS_OK;
       }
-      if (det_multi && !d_mvslot) HIP_TRY(hipMalloc((void**)&d_mvslot, (size_t)vslots_total * MQ * sizeof(double)));
+      if (det_multi && !d_mvslot) PIPS_TRY(d_mvslot.alloc((size_t)vslots_total * MQ));
       last_refine_steps = 0;   // (over the chunks: the steps of the last one that took any)
       const bool multi = use_multi(nrhs);
       const int chunk_max = det_multi ? MQ : multi ? MULTI_CHUNK_MAX : 32;   // (the per-right-hand-side sweeps keep their 32 work vectors)
@@ -2811,13 +2703,10 @@ struct Engine {
 
    // The inertia counters travel to pinned host memory at the end of every factorisation (factor()); a query only waits for that
    // copy - not for whatever was queued behind the factorisation (the leaf solves of an Lsolve, say).
-   int* h_inertia_pin = nullptr;
-   hipEvent_t ev_inertia = nullptr;
-   bool inertia_in_flight = false, inertia_on_host = false;
    int fetch_inertia() {
       if (inertia_in_flight && h_inertia_pin) {   // one wait per factorisation: a query per block (256 of them per IPM iteration) reads the host copy
          HIP_TRY(hipEventSynchronize(ev_inertia));
-         std::copy(h_inertia_pin, h_inertia_pin + h_inertia.size(), h_inertia.begin());
+         std::copy(h_inertia_pin.get(), h_inertia_pin + h_inertia.size(), h_inertia.begin());
          inertia_in_flight = false;
          inertia_on_host = true;
          if (tail_single && h_inertia_pin[3 * nblk]) {
@@ -3024,18 +2913,18 @@ struct DenseLdl {
    bool factored = false;
    std::vector<BlkDesc> h_blks;
    TailPlan plan;
-   BlkDesc* d_blks = nullptr;
-   double *d_R = nullptr, *d_winv = nullptr, *d_dtail = nullptr, *d_xw = nullptr, *d_in = nullptr, *d_pref = nullptr;
-   double* d_U = nullptr;   // U = L D (npad x npad), B operand of the updates
-   signed char* d_psign = nullptr;
-   long long *d_psign_off = nullptr, *d_kptr = nullptr;
-   int* d_inertia = nullptr;
+   DevBuf<BlkDesc> d_blks;
+   DevBuf<double> d_R, d_winv, d_dtail, d_xw, d_in, d_pref;
+   DevBuf<double> d_U;   // U = L D (npad x npad), B operand of the updates
+   DevBuf<signed char> d_psign;
+   DevBuf<long long> d_psign_off, d_kptr;
+   DevBuf<int> d_inertia;
    int h_inertia[3] = {0, 0, 0};
    hipStream_t side = nullptr;
    hipEvent_t ev_panel = nullptr, ev_rest = nullptr;
    // staging copy of a host matrix: only the host-pointer entry points need it (the fused KKT path hands over d_SC)
    int ensure_input_buffer() {
-      if (!d_in) HIP_TRY(hipMalloc((void**)&d_in, (size_t)std::max(n, 1) * std::max(n, 1) * sizeof(double)));
+      if (!d_in) PIPS_TRY(d_in.alloc((size_t)std::max(n, 1) * std::max(n, 1)));
       return PIPS_OK;
    }
 
@@ -3043,22 +2932,16 @@ struct DenseLdl {
       if (side) (void)hipStreamDestroy(side);
       if (ev_panel) (void)hipEventDestroy(ev_panel);
       if (ev_rest) (void)hipEventDestroy(ev_rest);
-      void* ptrs[] = {d_blks, d_R, d_U, d_winv, d_dtail, d_xw, d_in, d_pref, d_psign, d_psign_off, d_kptr, d_inertia, d_dist_tasks, d_panel, d_perm, d_pert_cnt, d_pert_list, d_flagvec,
-                      d_C, d_rtasks, d_rflags};
-      for (void* p : ptrs)
-         if (p) (void)hipFree(p);
-      plan.release();
-      sweep.release();
    }
    SweepRt sweep;
    // ---- the factorisation as ONE dependency-driven launch (rootkernel.hip.h, rootplan.cpp): static pivot order on one rank.  Bunch-Kaufman
    // (a 454-register diagonal kernel) and the root distributed over ranks keep the launch-per-step driver (tail_factor / factor_distributed);
    // PIPS_HIP_ROOT_LAUNCHES=1 keeps it everywhere (the tests run both).
    bool single_launch = !getenv("PIPS_HIP_ROOT_LAUNCHES");
-   double* d_C = nullptr;          // the accumulating tiles (scratch): L goes to d_R, U to d_U, each written once per launch
-   TileTask* d_rtasks = nullptr;
+   DevBuf<double> d_C;             // the accumulating tiles (scratch): L goes to d_R, U to d_U, each written once per launch
+   DevBuf<TileTask> d_rtasks;
    int n_rtasks = 0, n_rbulk = 0;
-   int* d_rflags = nullptr;        // ctl[8] | prog[ntc * ntc] | rowdone[ntc] | dready[ntc]
+   DevBuf<int> d_rflags;           // ctl[8] | prog[ntc * ntc] | rowdone[ntc] | dready[ntc]
    double plan_makespan_us = 0.0;
    long long root_poll_limit = 400000;   // polls before a wait inside the launch gives up (some 0.1 s: a factorisation takes 2 - 40 ms)
    bool root_error_pending = false;
@@ -3074,10 +2957,10 @@ struct DenseLdl {
       n_rbulk = (int)(t.size() / 4);
       t.insert(t.end(), tc.begin(), tc.end());
       n_rtasks = (int)(t.size() / 4);
-      HIP_TRY(hipMalloc((void**)&d_rtasks, std::max<size_t>(t.size(), 4) * sizeof(int)));
+      PIPS_TRY(d_rtasks.alloc(std::max<size_t>(t.size() / 4, 1)));
       HIP_TRY(hipMemcpy(d_rtasks, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMalloc((void**)&d_rflags, ((size_t)8 + (size_t)ntc * ntc + 2 * (size_t)ntc) * sizeof(int)));
-      HIP_TRY(hipMalloc((void**)&d_C, (size_t)npad * npad * sizeof(double)));
+      PIPS_TRY(d_rflags.alloc(((size_t)8 + (size_t)ntc * ntc + 2 * (size_t)ntc)));
+      PIPS_TRY(d_C.alloc((size_t)npad * npad));
       if (const char* pl = getenv("PIPS_HIP_ROOT_POLL_LIMIT")) root_poll_limit = atoll(pl);
       return PIPS_OK;
    }
@@ -3091,9 +2974,9 @@ struct DenseLdl {
       a.blk = d_blks; a.poll_limit = root_poll_limit;
       a.diag_blocked = getenv("PIPS_HIP_ROOT_DIAG_BARRIERS") ? 0 : 1;
       const char* trace_file = getenv("PIPS_HIP_ROOT_TRACE");   // diagnostics: per-task clocks of this launch into a file (tools/root_trace.py)
-      long long* d_trace = nullptr;
+      DevBuf<long long> d_trace;
       if (trace_file) {
-         HIP_TRY(hipMalloc((void**)&d_trace, ((size_t)3 * n_rtasks + 32 * (size_t)ntc) * sizeof(long long)));
+         PIPS_TRY(d_trace.alloc(((size_t)3 * n_rtasks + 32 * (size_t)ntc)));
          HIP_TRY(hipMemsetAsync(d_trace, 0, ((size_t)3 * n_rtasks + 32 * (size_t)ntc) * sizeof(long long), stream));
          a.trace = d_trace;
       }
@@ -3106,7 +2989,7 @@ struct DenseLdl {
          HIP_TRY(hipStreamSynchronize(stream));
          HIP_TRY(hipMemcpy(h.data(), d_trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
          HIP_TRY(hipMemcpy(ht.data(), d_rtasks, ht.size() * sizeof(int), hipMemcpyDeviceToHost));
-         (void)hipFree(d_trace);
+         d_trace.reset();
          if (FILE* f = fopen(trace_file, "w")) {
             for (int t = 0; t < n_rtasks; ++t)
                fprintf(f, "%d %d %d %d %d %lld %lld %lld\n", t, ht[4 * t], ht[4 * t + 1], ht[4 * t + 2], ht[4 * t + 3], h[3 * (size_t)t], h[3 * (size_t)t + 1], h[3 * (size_t)t + 2]);
@@ -3142,7 +3025,7 @@ struct DenseLdl {
       d.ntc = d.ntr = npad / TILE;
       d.thr_rel = 0; d.repl_rel = 1e-8; d.repl_abs = 1;
       h_blks.assign(1, d);
-      if ((rc = dev_upload(&d_blks, h_blks, stream))) return rc;
+      if ((rc = d_blks.upload(h_blks))) return rc;
       // one block only: right-looking (measured on MI355X, tools/root_probe.py: S=2000 4.3 -> 2.3 ms, S=16000 183 -> 45 ms;
       // panels of 1 tile column are best up to S = 8000, 2-3 beyond)
       const int panel = d.ntc <= 64 ? 1 : 2;
@@ -3159,17 +3042,17 @@ struct DenseLdl {
       }
       std::vector<signed char> ps(npad, 1);
       for (int i = 0; i < n; ++i) ps[i] = n_primal < 0 ? 0 : (i < n_primal ? 1 : -1);
-      if ((rc = dev_upload(&d_psign, ps, stream))) return rc;
+      if ((rc = d_psign.upload(ps))) return rc;
       std::vector<long long> zero(1, 0), kp = {0, (long long)npad};   // fallback magnitude from the diagonal only
-      if ((rc = dev_upload(&d_psign_off, zero, stream))) return rc;
-      if ((rc = dev_upload(&d_kptr, kp, stream))) return rc;
-      HIP_TRY(hipMalloc((void**)&d_R, (size_t)npad * npad * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_U, (size_t)npad * npad * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_winv, (size_t)npad * TILE * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_dtail, (size_t)npad * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_xw, (size_t)npad * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_pref, (size_t)npad * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&d_inertia, 3 * sizeof(int)));
+      if ((rc = d_psign_off.upload(zero))) return rc;
+      if ((rc = d_kptr.upload(kp))) return rc;
+      PIPS_TRY(d_R.alloc((size_t)npad * npad));
+      PIPS_TRY(d_U.alloc((size_t)npad * npad));
+      PIPS_TRY(d_winv.alloc((size_t)npad * TILE));
+      PIPS_TRY(d_dtail.alloc((size_t)npad));
+      PIPS_TRY(d_xw.alloc((size_t)npad));
+      PIPS_TRY(d_pref.alloc((size_t)npad));
+      PIPS_TRY(d_inertia.alloc(3));
       return PIPS_OK;
    }
    TailCtx ctx() {
@@ -3193,8 +3076,8 @@ struct DenseLdl {
    static constexpr int BK_RETRIES = 8;
    static constexpr int BK_MAX_COLUMNS = 2048;   // columns per round whose original entries travel to the host for the partner choice
    std::vector<int> perm;              // perm[i] = original index at position i (empty: identity)
-   int* d_perm = nullptr;
-   int *d_pert_cnt = nullptr, *d_pert_list = nullptr;
+   DevBuf<int> d_perm;
+   DevBuf<int> d_pert_cnt, d_pert_list;
    const double* last_A = nullptr;     // the matrix of the last factor_dev (the caller keeps it until the next factorisation)
    int last_lda = 0, last_rowmajor = 0;
    bool check_pending = false;
@@ -3203,7 +3086,7 @@ struct DenseLdl {
    // indices (positions in the current order) the last factorisation found no pivot for: one rank - what its tile kernels recorded, in
    // their order; a root distributed over several ranks - every rank recorded those of its own tile columns, the union (ascending) reaches
    // every rank through an all-reduce of a 0 / 1 vector, so that all ranks go on to build the SAME pivot order
-   double* d_flagvec = nullptr;
+   DevBuf<double> d_flagvec;
    int flagged_positions(std::vector<int>& pos) {
       pos.clear();
       int cnt = 0;
@@ -3218,7 +3101,7 @@ struct DenseLdl {
       }
       std::vector<double> flag((size_t)npad, 0.0);
       for (int q = 0; q < cnt; ++q) if (rec[2 * q] >= 0 && rec[2 * q] < npad) flag[rec[2 * q]] = 1.0;
-      if (!d_flagvec) HIP_TRY(hipMalloc((void**)&d_flagvec, (size_t)npad * sizeof(double)));
+      if (!d_flagvec) PIPS_TRY(d_flagvec.alloc((size_t)npad));
       HIP_TRY(hipMemcpy(d_flagvec, flag.data(), flag.size() * sizeof(double), hipMemcpyHostToDevice));
       int rc = pips_hip_allreduce_sum(dist_comm, d_flagvec, (size_t)npad, stream);
       if (rc) return rc;
@@ -3247,12 +3130,12 @@ struct DenseLdl {
          const int n_use = std::min(cnt, BK_MAX_COLUMNS);
          std::vector<double> cols((size_t)n_use * n);
          {
-            double* d_cols = nullptr;
-            HIP_TRY(hipMalloc((void**)&d_cols, cols.size() * sizeof(double)));
+            DevBuf<double> d_cols;
+            PIPS_TRY(d_cols.alloc(cols.size()));
             hipLaunchKernelGGL(k_bk_gather_columns, dim3(std::max(1, std::min(64, (n + 255) / 256)), n_use), dim3(256), 0, stream, last_A, last_lda, last_rowmajor,
                                perm.empty() ? (const int*)nullptr : (const int*)d_perm, n, d_pert_list, n_use, d_cols);
             const hipError_t ec = hipMemcpy(cols.data(), d_cols, cols.size() * sizeof(double), hipMemcpyDeviceToHost);
-            (void)hipFree(d_cols);
+            d_cols.reset();
             if (ec != hipSuccess) PIPS_FAIL(PIPS_ERR_HIP, "dense root: %s", hipGetErrorString(ec));
          }
          std::vector<int> partner(n, -1);
@@ -3290,7 +3173,7 @@ struct DenseLdl {
          }
          if ((int)next.size() != n) PIPS_FAIL(PIPS_ERR_STATE, "dense root: internal error building the pivot order (%zu of %d)", next.size(), n);
          perm.swap(next);
-         if (!d_perm) HIP_TRY(hipMalloc((void**)&d_perm, (size_t)std::max(n, 1) * sizeof(int)));
+         if (!d_perm) PIPS_TRY(d_perm.alloc((size_t)std::max(n, 1)));
          HIP_TRY(hipMemcpy(d_perm, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
          ++bk_refactorizations;
          int rc = factor_enqueue();
@@ -3322,8 +3205,8 @@ struct DenseLdl {
    void* dist_comm = nullptr;
    int dist_rank = 0, dist_P = 1;
    std::vector<TaskList> dist_diag, dist_trsm, dist_next, dist_upd;   // dist_next[j]: this rank's tiles of column j + 1 under panel j; dist_upd[j]: of its columns >= j + 2
-   TileTask* d_dist_tasks = nullptr;
-   double* d_panel = nullptr;
+   DevBuf<TileTask> d_dist_tasks;
+   DevBuf<double> d_panel;
    int set_distributed(void* comm, int rank, int P) {
       if (P <= 1 || !comm) { dist_comm = nullptr; dist_P = 1; return PIPS_OK; }
       if (rank < 0 || rank >= P) PIPS_FAIL(PIPS_ERR_ARG, "distributed root: rank %d of %d", rank, P);
@@ -3349,10 +3232,9 @@ struct DenseLdl {
                for (int ti = tk; ti < ntc; ++ti) all.push_back({0, ti, tk, j | ((j + 1) << 16)});
          dist_upd[j].cnt = (int)((long long)all.size() - dist_upd[j].off);
       }
-      if (d_dist_tasks) { (void)hipFree(d_dist_tasks); d_dist_tasks = nullptr; }
-      int rc = dev_upload(&d_dist_tasks, all, stream);
+      int rc = d_dist_tasks.upload(all);
       if (rc) return rc;
-      if (!d_panel) HIP_TRY(hipMalloc((void**)&d_panel, ((size_t)TILE * TILE + TILE + 8 + 2 * (size_t)npad * TILE) * sizeof(double)));
+      if (!d_panel) PIPS_TRY(d_panel.alloc(((size_t)TILE * TILE + TILE + 8 + 2 * (size_t)npad * TILE)));
       if (!side) {   // one column of lookahead: the bulk of a panel's update runs beside the factorisation and the broadcast of the next column
          HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
          HIP_TRY(hipEventCreateWithFlags(&ev_panel, hipEventDisableTiming));
@@ -3447,8 +3329,8 @@ struct DenseLdl {
       HIP_TRY(hipSetDevice(device));
       if (pivoting == 1) {
          if (!d_pert_cnt) {
-            HIP_TRY(hipMalloc((void**)&d_pert_cnt, sizeof(int)));
-            HIP_TRY(hipMalloc((void**)&d_pert_list, (size_t)2 * std::max(npad, 1) * sizeof(int)));
+            PIPS_TRY(d_pert_cnt.alloc(1));
+            PIPS_TRY(d_pert_list.alloc((size_t)2 * std::max(npad, 1)));
          }
          HIP_TRY(hipMemsetAsync(d_pert_cnt, 0, sizeof(int), stream));
       }
@@ -3498,12 +3380,12 @@ struct KktSystem {
    int n0 = 0, my0 = 0, myl = 0, mzl = 0, S = 0;
    int rank = 0, n_ranks = 1;
    void* comm = nullptr;
-   double *d_SC = nullptr, *d_t = nullptr, *d_fin_val = nullptr, *d_c0_val = nullptr, *d_red = nullptr, *d_packed = nullptr;
-   long long* d_fin_idx = nullptr;
+   DevBuf<double> d_SC, d_t, d_fin_val, d_c0_val, d_red, d_packed;
+   DevBuf<long long> d_fin_idx;
    long long n_fin = 0;
-   double *d_gall = nullptr, *d_gvec_all = nullptr;   // deterministic mode over several ranks: all eight group slots (8 x S x S / 8 x S)
+   DevBuf<double> d_gall, d_gvec_all;   // deterministic mode over several ranks: all eight group slots (8 x S x S / 8 x S)
    int mz0 = 0;
-   int *d_c0_rp = nullptr, *d_c0_ci = nullptr;
+   DevBuf<int> d_c0_rp, d_c0_ci;
    const double* d_zdiag0 = nullptr;   // caller-owned, set per iteration
    double root_reg_primal = 0.0, root_reg_dual = 0.0;   // pips_hip_kkt_set_root_regularization
    hipStream_t comm_stream = nullptr;   // panel-wise Schur reduction beside the leaf work
@@ -3537,7 +3419,6 @@ struct KktSystem {
       }
       return PIPS_OK;
    }
-   size_t packed_cap = 0;
    bool use_rsag = false, force_reduce = false;
    bool solve_graph = false;                // pips_hip_kkt_set_solve_graph
    hipGraphExec_t graph_exec = nullptr;
@@ -3577,12 +3458,12 @@ struct KktSystem {
    // right-hand side and all go the refined way (a rank's inaccurate -Br^T K^-1 b taints x0 for everybody).
    int solve_check_every = 1, sweeps_since_check = 0;
    long long solves_since_factor = 0;   // equal on every rank: which solveCompressed calls are scheduled for a measure (every solve_check_every-th)
-   double* h_flag = nullptr;            // pinned: the one-number exchange of settle() without a host wait before the collective
+   PinnedBuf<double> h_flag;            // pinned: the one-number exchange of settle() without a host wait before the collective
    long long checked_solves = 0, failed_checks = 0;
-   double* d_flag = nullptr;
+   DevBuf<double> d_flag;
    bool joint_aug_any = false;        // several ranks: some rank's analysis chose the sweeps (all-reduced once per analysis)
    long long joint_aug_gen = -1;
-   double *d_bsave = nullptr, *d_b0save = nullptr;
+   DevBuf<double> d_bsave, d_b0save;
    bool root_pivoting_set = false;   // pips_hip_kkt_set_root_pivoting decided; else: Bunch-Kaufman iff root inequality rows are eliminated
    // phase times of one factorize and the solveCompressed calls after it (pips_hip_kkt_get_timing; on with the batch's timing switch):
    // 0 diagonals + zero SC, 1 leaf factorisation, 2 Schur reduction, 3 finalize, 4 root factorisation (its own stream),
@@ -3595,8 +3476,8 @@ struct KktSystem {
    std::unique_ptr<Engine> root_sp;
    std::vector<int> sc_rowptr, sc_colidx, root_perm, root_colcount;
    int root_order_mode = 0;   // sparse root: 0 minimum degree, 1 dense-tile band, 2 dissection around the hubs
-   long long *d_xdiag_pos = nullptr, *d_zlink_pos = nullptr;
-   int* d_sc_rowptr = nullptr;
+   DevBuf<long long> d_xdiag_pos, d_zlink_pos;
+   DevBuf<int> d_sc_rowptr;
    ~KktSystem() {
       if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
       if (graph_stream) (void)hipStreamDestroy(graph_stream);
@@ -3605,10 +3486,6 @@ struct KktSystem {
       if (ev_root_done) (void)hipEventDestroy(ev_root_done);
       if (comm_stream) (void)hipStreamDestroy(comm_stream);
       if (ev_reduced) (void)hipEventDestroy(ev_reduced);
-      if (h_flag) (void)hipHostFree(h_flag);
-      void* ptrs[] = {d_SC, d_t, d_fin_val, d_fin_idx, d_c0_val, d_red, d_c0_rp, d_c0_ci, d_packed, d_xdiag_pos, d_zlink_pos, d_sc_rowptr, d_gall, d_gvec_all, d_bsave, d_b0save, d_flag};
-      for (void* p : ptrs)
-         if (p) (void)hipFree(p);
    }
 };
 
@@ -3711,6 +3588,8 @@ extern "C" {
 
 const char* pips_hip_last_error(void) { return pips::last_error(); }
 long long pips_hip_host_wait_count(void) { return pips::g_host_waits.load(std::memory_order_relaxed); }
+long long pips_hip_device_allocs_live(void) { return pips::g_mem_allocs_live.load(std::memory_order_relaxed); }
+long long pips_hip_device_bytes_live(void) { return pips::g_mem_bytes_live.load(std::memory_order_relaxed); }
 int pips_hip_host_wait_sites(char* buf, int cap) {
    int used = 0;
    if (buf && cap > 0) buf[0] = 0;
@@ -4041,9 +3920,9 @@ struct LdlGroup;
 // stream synchronisation; 64 handles with an array each were 32 GB at S = 8000), and only the compact nb x nb block travels to the host.
 struct SchurScratch {
    std::mutex mu;
-   std::map<int, std::pair<double*, size_t>> per_device;   // device -> (array, doubles)
+   std::map<int, DevBuf<double>> per_device;   // device -> array
 };
-static SchurScratch g_schur_scratch;
+static SchurScratch& g_schur_scratch = *new SchurScratch;   // (never destroyed: nothing is freed while the process exits)
 
 // C[i + j * nb] = SC[bm[i] + bm[j] * ld] (the block of a leaf's border columns, column-major; the lower triangle is what the caller reads) -
 // and SC is left zero on the whole block, whichever triangle a Schur mode wrote
@@ -4059,7 +3938,7 @@ __global__ void k_schur_take_block(double* __restrict__ SC, int ld, const int* _
 struct LdlHandle {
    Engine eng;
    bool have_perm = false;
-   double* d_sc = nullptr;        // compact nb x nb Schur term of this leaf (pips_hip_ldl_factor_schur)
+   DevBuf<double> d_sc;           // compact nb x nb Schur term of this leaf (pips_hip_ldl_factor_schur)
    std::vector<double> h_sc;
    std::shared_ptr<LdlGroup> group;   // the leaves of a rank bound into one batch engine (pips_hip_ldl_factor_schur_batch)
    int group_index = -1;
@@ -4077,14 +3956,12 @@ struct LdlHandle {
 struct LdlGroup {
    Engine eng;
    std::vector<LdlHandle*> members;
-   double *d_sc = nullptr, *d_x = nullptr;
+   DevBuf<double> d_sc, d_x;
    std::vector<double> h_sc;
-   ~LdlGroup() { if (d_sc) (void)hipFree(d_sc); if (d_x) (void)hipFree(d_x); }
 };
 // a handle that goes away leaves an empty slot in its group: the siblings keep the batch's factors (their own solves go through
 // group_solve_rows, which needs no sibling), the next array-of-handles call sees another array and binds anew
 LdlHandle::~LdlHandle() {
-   if (d_sc) (void)hipFree(d_sc);
    if (group && group_index >= 0 && group_index < (int)group->members.size() && group->members[group_index] == this) group->members[group_index] = nullptr;
 }
 // array-of-handles solves / queries answer from the batch's factors: refuse if a member has been factorised alone since
@@ -4102,7 +3979,7 @@ static inline bool ldl_uses_group(const LdlHandle* h) { return h->group && h->ne
 static int group_solve_rows(LdlGroup& g, int index, int nrhs, double* rhs, long long ld, bool on_device, const char* who) {
    Engine& e = g.eng;
    HIP_TRY(hipSetDevice(e.device));
-   if (!g.d_x) HIP_TRY(hipMalloc((void**)&g.d_x, (size_t)std::max<long long>(e.n_total, 1) * sizeof(double)));
+   if (!g.d_x) PIPS_TRY(g.d_x.alloc((size_t)std::max<long long>(e.n_total, 1)));
    const size_t cnt = (size_t)(e.x_off[index + 1] - e.x_off[index]) * sizeof(double);
    for (int r = 0; r < nrhs; ++r) {
       HIP_TRY(hipMemsetAsync(g.d_x, 0, (size_t)e.n_total * sizeof(double), e.stream));
@@ -4230,18 +4107,9 @@ int pips_hip_ldl_factor_schur(void* handle, const double* K_vals_host, const dou
    // the device's shared S x S scratch array: zero on entry (allocated zeroed; every call takes its block out again and leaves zeros)
    // (held to the end of the call: host threads that factorise their leaves side by side take turns on the scratch array)
    std::lock_guard<std::mutex> scratch_lock(g_schur_scratch.mu);
-   double* scratch = nullptr;
-   {
-      auto& slot = g_schur_scratch.per_device[e.device];
-      if (slot.second < (size_t)S * S) {
-         if (slot.first) (void)hipFree(slot.first);
-         slot = {nullptr, 0};
-         HIP_TRY(hipMalloc((void**)&slot.first, (size_t)S * S * sizeof(double)));
-         slot.second = (size_t)S * S;
-         HIP_TRY(hipMemset(slot.first, 0, (size_t)S * S * sizeof(double)));
-      }
-      scratch = slot.first;
-   }
+   DevBuf<double>& slot = g_schur_scratch.per_device[e.device];
+   if (slot.size() < (size_t)S * S) PIPS_TRY(slot.alloc_zero((size_t)S * S));
+   double* scratch = slot;
    if ((rc = e.factor(scratch, S))) {   // (whatever reached the scratch array must not meet the next handle)
       (void)hipStreamSynchronize(e.stream);
       (void)hipMemset(scratch, 0, (size_t)S * S * sizeof(double));
@@ -4249,7 +4117,7 @@ int pips_hip_ldl_factor_schur(void* handle, const double* K_vals_host, const dou
    }
    h->newest_in_group = false;
    if (nb > 0) {
-      if (!h->d_sc) HIP_TRY(hipMalloc((void**)&h->d_sc, (size_t)nb * nb * sizeof(double)));
+      if (!h->d_sc) PIPS_TRY(h->d_sc.alloc((size_t)nb * nb));
       hipLaunchKernelGGL(k_schur_take_block, dim3(std::max(1, std::min(16, (nb + 255) / 256)), nb), dim3(256), 0, e.stream, scratch, S, e.d_bmap, nb, h->d_sc);
       h->h_sc.resize((size_t)nb * nb);
       HIP_TRY(hipMemcpyAsync(h->h_sc.data(), h->d_sc, (size_t)nb * nb * sizeof(double), hipMemcpyDeviceToHost, e.stream));
@@ -4297,13 +4165,13 @@ int pips_hip_ldl_solve(void* handle, int nrhs, double* rhs, int ld) {
    // (the device copy of the right-hand sides stays with the handle: the reference's loop calls this hundreds of times per factorisation
    // with the same chunk size, an allocation and a release per call were a fifth of a millisecond each)
    const size_t flag_bytes = ((size_t)nrhs * sizeof(int) + 15) & ~(size_t)15;
-   if (e.hostx_cap < (size_t)nrhs * row + flag_bytes) {
-      if (e.d_hostx) { HIP_TRY(hipStreamSynchronize(e.stream)); (void)hipFree(e.d_hostx); e.d_hostx = nullptr; e.hostx_cap = 0; }
-      HIP_TRY(hipMalloc((void**)&e.d_hostx, (size_t)nrhs * row + flag_bytes));
-      e.hostx_cap = (size_t)nrhs * row + flag_bytes;
+   const size_t hostx_doubles = ((size_t)nrhs * row + flag_bytes) / sizeof(double);
+   if (e.d_hostx.size() < hostx_doubles) {
+      if (e.d_hostx) HIP_TRY(hipStreamSynchronize(e.stream));
+      PIPS_TRY(e.d_hostx.reserve(hostx_doubles));
    }
    double* d_X = e.d_hostx;
-   int* d_flags = (int*)((char*)e.d_hostx + (size_t)nrhs * row);
+   int* d_flags = (int*)(d_X + (size_t)nrhs * e.n_total);
    std::vector<int> flags((size_t)nrhs), nz;
    HIP_TRY(hipMemcpy2DAsync(d_X, row, rhs, (size_t)ld * sizeof(double), row, nrhs, hipMemcpyHostToDevice, e.stream));
    hipLaunchKernelGGL(k_columns_nonzero, dim3(nrhs), dim3(256), 0, e.stream, d_X, (long long)e.n_total, (int)e.n_total, d_flags);
@@ -4383,15 +4251,14 @@ int pips_hip_ldl_solve_sparse(void* handle, int nrhs, double* rhs, int ld, const
    }
    // (device copies kept with the handle, like pips_hip_ldl_solve's: no allocation and release per call)
    const size_t row = (size_t)n * sizeof(double), pack_bytes = packed.size() * sizeof(double) + (size_t)nr * sizeof(int);
-   if (e.hostx_cap < (size_t)nq * row) {
-      if (e.d_hostx) { HIP_TRY(hipStreamSynchronize(e.stream)); (void)hipFree(e.d_hostx); e.d_hostx = nullptr; e.hostx_cap = 0; }
-      HIP_TRY(hipMalloc((void**)&e.d_hostx, (size_t)nq * row));
-      e.hostx_cap = (size_t)nq * row;
+   const size_t pack_doubles = (pack_bytes + sizeof(double) - 1) / sizeof(double);
+   if (e.d_hostx.size() < (size_t)nq * n) {
+      if (e.d_hostx) HIP_TRY(hipStreamSynchronize(e.stream));
+      PIPS_TRY(e.d_hostx.reserve((size_t)nq * n));
    }
-   if (e.hostpack_cap < pack_bytes) {
-      if (e.d_hostpack) { HIP_TRY(hipStreamSynchronize(e.stream)); (void)hipFree(e.d_hostpack); e.d_hostpack = nullptr; e.hostpack_cap = 0; }
-      HIP_TRY(hipMalloc((void**)&e.d_hostpack, pack_bytes));
-      e.hostpack_cap = pack_bytes;
+   if (e.d_hostpack.size() < pack_doubles) {
+      if (e.d_hostpack) HIP_TRY(hipStreamSynchronize(e.stream));
+      PIPS_TRY(e.d_hostpack.reserve(pack_doubles));
    }
    double *d_X = e.d_hostx, *d_packed = e.d_hostpack;
    int* d_rows = (int*)(e.d_hostpack + packed.size());
@@ -4473,7 +4340,7 @@ int pips_hip_ldl_factor_schur_batch(void* const* handles, int n, const double* c
       }
    }
    if (schur) {
-      if (!g->d_sc) HIP_TRY(hipMalloc((void**)&g->d_sc, (size_t)S * S * sizeof(double)));
+      if (!g->d_sc) PIPS_TRY(g->d_sc.alloc((size_t)S * S));
       HIP_TRY(hipMemsetAsync(g->d_sc, 0, (size_t)S * S * sizeof(double), e.stream));
    }
    if ((rc = e.factor(schur ? g->d_sc : nullptr, S))) return rc;
@@ -4513,7 +4380,7 @@ int pips_hip_ldl_solve_batch(void* const* handles, int n, double* const* rhs_ino
    Engine& e = g->eng;
    if ((rc = ldl_group_is_current(*g, "pips_hip_ldl_solve_batch"))) return rc;
    HIP_TRY(hipSetDevice(e.device));
-   if (!g->d_x) HIP_TRY(hipMalloc((void**)&g->d_x, (size_t)std::max<long long>(e.n_total, 1) * sizeof(double)));
+   if (!g->d_x) PIPS_TRY(g->d_x.alloc((size_t)std::max<long long>(e.n_total, 1)));
    // a leaf without a right-hand side this time (NULL) is solved with zeros: the batch runs every block in every launch
    HIP_TRY(hipMemsetAsync(g->d_x, 0, (size_t)e.n_total * sizeof(double), e.stream));
    for (int i = 0; i < n; ++i)
@@ -4663,13 +4530,21 @@ int pips_hip_dense_ldl_inertia(void* handle, int* pos, int* neg, int* zero) {
 void pips_hip_dense_ldl_destroy(void* handle) { delete (DenseLdl*)handle; }
 
 // ---- plain device buffers ------------------------------------------------------------------------------------------
+// (what the caller holds is owned here under its address, so that it is counted like every other allocation)
+static std::mutex g_user_mu;
+static std::map<void*, DevBuf<char>>& g_user_bufs = *new std::map<void*, DevBuf<char>>;   // (never destroyed, like the Schur scratch)
 int pips_hip_malloc(void** dev_ptr, size_t bytes) {
    if (!dev_ptr) PIPS_FAIL(PIPS_ERR_ARG, "null pointer");
-   HIP_TRY(hipMalloc(dev_ptr, bytes ? bytes : 8));
+   DevBuf<char> b;
+   PIPS_TRY(b.alloc(bytes ? bytes : 8));
+   *dev_ptr = b.get();
+   std::lock_guard<std::mutex> lock(g_user_mu);
+   g_user_bufs[*dev_ptr] = std::move(b);
    return PIPS_OK;
 }
 int pips_hip_free(void* dev_ptr) {
-   if (dev_ptr) HIP_TRY(hipFree(dev_ptr));
+   std::lock_guard<std::mutex> lock(g_user_mu);
+   if (dev_ptr && !g_user_bufs.erase(dev_ptr)) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_free: not a pointer of pips_hip_malloc");
    return PIPS_OK;
 }
 int pips_hip_memcpy_h2d(void* dst, const void* src, size_t bytes) {
@@ -4714,8 +4589,8 @@ int pips_hip_kkt_create(void** handle, void* batch, int n0, int my0, int myl, in
    // several ranks: the dense root factorised column-cyclically over the ranks instead of redundantly on every one of them
    // (PIPS_HIP_ROOT_DISTRIBUTED=1; untimed - see DenseLdl::set_distributed)
    if (comm && n_ranks > 1 && env_int("PIPS_HIP_ROOT_DISTRIBUTED", 0) != 0 && (rc = k->root->set_distributed(comm, rank, n_ranks))) return rc;
-   HIP_TRY(hipMalloc((void**)&k->d_SC, (size_t)S * S * sizeof(double)));
-   HIP_TRY(hipMalloc((void**)&k->d_t, std::max<size_t>((size_t)e->n_total, 1) * sizeof(double)));
+   PIPS_TRY(k->d_SC.alloc((size_t)S * S));
+   PIPS_TRY(k->d_t.alloc(std::max<size_t>((size_t)e->n_total, 1)));
    // constant root blocks added by finalizeKKTdense: A0 at row n0, F0 at row n0+my0, G0 at row n0+my0+myl
    // (sLinsysRootAug.C:270-320, 1782-1796).  SC is column-major with the lower triangle valid: (r,c) -> r + c*S.
    std::vector<long long> idx;
@@ -4729,8 +4604,8 @@ int pips_hip_kkt_create(void** handle, void* batch, int n0, int my0, int myl, in
    add(F0_rowptr, F0_colidx, F0_val, myl, n0 + my0);
    add(G0_rowptr, G0_colidx, G0_val, mzl, n0 + my0 + myl);
    k->n_fin = (long long)idx.size();
-   if ((rc = dev_upload(&k->d_fin_idx, idx, nullptr))) return rc;
-   if ((rc = dev_upload(&k->d_fin_val, val, nullptr))) return rc;
+   if ((rc = k->d_fin_idx.upload(idx))) return rc;
+   if ((rc = k->d_fin_val.upload(val))) return rc;
    // several ranks: Schur SYRK in row panels, each reduced as soon as it is final (PIPS_HIP_SC_PANELS, default 4 for S >= 1024; 1 =
    // one reduction after all leaf work); PIPS_HIP_SC_REDUCE=rsag: reduce-scatter + all-gather instead of the all-reduce
    if (e->deterministic && (rc = e->set_det_groups(rank, n_ranks))) return rc;
@@ -4913,12 +4788,12 @@ int pips_hip_kkt_create_sparse(void** handle, void* batch, int n0, int my0, int 
    for (int i = 0; i < n0; ++i) xpos[i] = pos_of(i, i);
    for (int i = 0; i < mzl; ++i) zpos[i] = pos_of(n0 + my0 + myl + i, n0 + my0 + myl + i);
    k->n_fin = (long long)idx.size();
-   if ((rc = dev_upload(&k->d_fin_idx, idx, nullptr))) return rc;
-   if ((rc = dev_upload(&k->d_fin_val, val, nullptr))) return rc;
-   if ((rc = dev_upload(&k->d_xdiag_pos, xpos, nullptr))) return rc;
-   if ((rc = dev_upload(&k->d_zlink_pos, zpos, nullptr))) return rc;
-   if ((rc = dev_upload(&k->d_sc_rowptr, k->sc_rowptr, nullptr))) return rc;
-   HIP_TRY(hipMalloc((void**)&k->d_t, std::max<size_t>((size_t)e->n_total, 1) * sizeof(double)));
+   if ((rc = k->d_fin_idx.upload(idx))) return rc;
+   if ((rc = k->d_fin_val.upload(val))) return rc;
+   if ((rc = k->d_xdiag_pos.upload(xpos))) return rc;
+   if ((rc = k->d_zlink_pos.upload(zpos))) return rc;
+   if ((rc = k->d_sc_rowptr.upload(k->sc_rowptr))) return rc;
+   PIPS_TRY(k->d_t.alloc(std::max<size_t>((size_t)e->n_total, 1)));
    *handle = k.release();
    return PIPS_OK;
 }
@@ -4945,7 +4820,7 @@ static int kkt_factorize_sparse(KktSystem* k, const double* leaf_diag_dev, const
    if (reduce && e->deterministic && e->det_global && e->d_gbuf) {
       // deterministic mode over several ranks: all eight group slots of the value array on every rank, one fixed tree (as in pips_hip_kkt_factorize)
       if (!k->comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: n_ranks > 1 needs a communicator");
-      if (!k->d_gall) HIP_TRY(hipMalloc((void**)&k->d_gall, 8 * nnz * sizeof(double)));
+      if (!k->d_gall) PIPS_TRY(k->d_gall.alloc(8 * nnz));
       HIP_TRY(hipMemsetAsync(k->d_gall, 0, 8 * nnz * sizeof(double), e->stream));
       HIP_TRY(hipMemcpyAsync(k->d_gall + (size_t)e->det_first_slot * nnz, e->d_gbuf, (size_t)e->det_n_groups * nnz * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
       if ((rc = pips_hip_all_gather(k->comm, k->d_gall, (size_t)e->det_slots * nnz, 8 / e->det_slots, e->stream))) return rc;   // every rank's slots to every rank: 1 x the bytes
@@ -5043,7 +4918,7 @@ int pips_hip_kkt_factorize(void* handle, const double* leaf_diag_dev, const doub
       // leaf engine left its groups unreduced, Engine::det_global) - equal bits for 1, 2, 4 and 8 ranks
       if (!k->comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: n_ranks > 1 needs a communicator");
       const size_t gs = (size_t)k->S * k->S;
-      if (!k->d_gall) HIP_TRY(hipMalloc((void**)&k->d_gall, 8 * gs * sizeof(double)));
+      if (!k->d_gall) PIPS_TRY(k->d_gall.alloc(8 * gs));
       HIP_TRY(hipMemsetAsync(k->d_gall, 0, 8 * gs * sizeof(double), e->stream));
       HIP_TRY(hipMemcpyAsync(k->d_gall + (size_t)e->det_first_slot * gs, e->d_gbuf, (size_t)e->det_n_groups * gs * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
       if ((rc = pips_hip_all_gather(k->comm, k->d_gall, (size_t)e->det_slots * gs, 8 / e->det_slots, e->stream))) return rc;   // (the all-reduce of zeros it replaces moved 8 x the bytes)
@@ -5056,11 +4931,7 @@ int pips_hip_kkt_factorize(void* handle, const double* leaf_diag_dev, const doub
       const size_t n_groups = std::max<size_t>(e->sc_groups.size(), 1);
       const size_t P = (size_t)std::max(1, pips_hip_comm_size(k->comm));
       const size_t cap = np + (n_groups + 1) * P;   // reduce-scatter pads every piece to a multiple of the rank count
-      if (!k->d_packed || k->packed_cap < cap) {
-         if (k->d_packed) (void)hipFree(k->d_packed);
-         HIP_TRY(hipMalloc((void**)&k->d_packed, cap * sizeof(double)));
-         k->packed_cap = cap;
-      }
+      PIPS_TRY(k->d_packed.reserve(cap));
       auto reduce_piece = [&](double* buf, size_t cnt, hipStream_t st) -> int {
          return k->use_rsag ? pips_hip_allreduce_sum_rsag(k->comm, buf, cnt, st) : pips_hip_allreduce_sum(k->comm, buf, cnt, st);
       };
@@ -5181,7 +5052,7 @@ static int kkt_solve_compressed_enqueue(KktSystem* k, double* b0_dev, double* b_
    // (whether the ranks exchange the outcome may depend only on what is equal on every rank: the settings the host gives all ranks alike,
    // and "some rank's analysis chose the sweeps" - the cost model decides per rank - settled once per analysis by an all-reduce)
    if (joint && can_measure && k->solve_check_every > 0 && k->joint_aug_gen != e->analysis_gen) {
-      if (!k->d_flag) HIP_TRY(hipMalloc((void**)&k->d_flag, sizeof(double)));
+      if (!k->d_flag) PIPS_TRY(k->d_flag.alloc(1));
       double any = e->aug_sweeps_ok ? 1.0 : 0.0;
       HIP_TRY(hipMemcpyAsync(k->d_flag, &any, sizeof(double), hipMemcpyHostToDevice, e->stream));
       HIP_TRY(hipStreamSynchronize(e->stream));
@@ -5208,8 +5079,8 @@ static int kkt_solve_compressed_enqueue(KktSystem* k, double* b0_dev, double* b_
       }
    }
    if (verify || joint_check) {   // the right-hand side as the caller gave it: needed for the check, and for the refined pass if a check fails
-      if (!k->d_bsave) HIP_TRY(hipMalloc((void**)&k->d_bsave, std::max<size_t>((size_t)e->n_total, 1) * sizeof(double)));
-      if (!k->d_b0save) HIP_TRY(hipMalloc((void**)&k->d_b0save, (size_t)(k->S + k->mz0 + 1) * sizeof(double)));
+      if (!k->d_bsave) PIPS_TRY(k->d_bsave.alloc(std::max<size_t>((size_t)e->n_total, 1)));
+      if (!k->d_b0save) PIPS_TRY(k->d_b0save.alloc((size_t)(k->S + k->mz0 + 1)));
       HIP_TRY(hipMemcpyAsync(k->d_bsave, b_leaf_dev, (size_t)e->n_total * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
       HIP_TRY(hipMemcpyAsync(k->d_b0save, b0_dev, (size_t)(k->S + k->mz0) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
    }
@@ -5217,8 +5088,8 @@ static int kkt_solve_compressed_enqueue(KktSystem* k, double* b0_dev, double* b_
    auto settle = [&](bool my_check_failed) -> int {
       bool redo = my_check_failed;
       if (joint_check) {
-         if (!k->d_flag) HIP_TRY(hipMalloc((void**)&k->d_flag, sizeof(double)));
-         if (!k->h_flag) HIP_TRY(hipHostMalloc((void**)&k->h_flag, 2 * sizeof(double), hipHostMallocDefault));
+         if (!k->d_flag) PIPS_TRY(k->d_flag.alloc(1));
+         if (!k->h_flag) PIPS_TRY(k->h_flag.alloc(2));
          k->h_flag[0] = my_check_failed ? 1.0 : 0.0;   // (pinned: the copy is queued, nothing waits before the collective)
          HIP_TRY(hipMemcpyAsync(k->d_flag, k->h_flag, sizeof(double), hipMemcpyHostToDevice, e->stream));
          int rcf = pips_hip_allreduce_sum(k->comm, k->d_flag, 1, e->stream);
@@ -5256,7 +5127,7 @@ static int kkt_solve_compressed_enqueue(KktSystem* k, double* b0_dev, double* b_
          e->gather(e->g_btm_grp, e->d_bt_tmp, e->d_gvec);
       }
       if (e->det_global && k->n_ranks > 1) {   // all eight group slots on every rank, one tree (see pips_hip_kkt_factorize)
-         if (!k->d_gvec_all) HIP_TRY(hipMalloc((void**)&k->d_gvec_all, (size_t)8 * k->S * sizeof(double)));
+         if (!k->d_gvec_all) PIPS_TRY(k->d_gvec_all.alloc((size_t)8 * k->S));
          HIP_TRY(hipMemsetAsync(k->d_gvec_all, 0, (size_t)8 * k->S * sizeof(double), e->stream));
          HIP_TRY(hipMemcpyAsync(k->d_gvec_all + (size_t)e->det_first_slot * k->S, e->d_gvec, (size_t)e->det_n_groups * k->S * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
          if ((rc = pips_hip_all_gather(k->comm, k->d_gvec_all, (size_t)e->det_slots * k->S, 8 / e->det_slots, e->stream))) return rc;
@@ -5515,8 +5386,8 @@ int pips_hip_kkt_set_root_inequalities(void* handle, int mz0, const int* C0_rowp
    std::vector<int> rp(C0_rowptr, C0_rowptr + mz0 + 1), ci(C0_colidx, C0_colidx + C0_rowptr[mz0]);
    std::vector<double> v(C0_val, C0_val + C0_rowptr[mz0]);
    int rc;
-   if ((rc = dev_upload(&k->d_c0_rp, rp, nullptr)) || (rc = dev_upload(&k->d_c0_ci, ci, nullptr)) || (rc = dev_upload(&k->d_c0_val, v, nullptr))) return rc;
-   HIP_TRY(hipMalloc((void**)&k->d_red, (size_t)std::max(k->S, 1) * sizeof(double)));
+   if ((rc = k->d_c0_rp.upload(rp)) || (rc = k->d_c0_ci.upload(ci)) || (rc = k->d_c0_val.upload(v))) return rc;
+   PIPS_TRY(k->d_red.alloc((size_t)std::max(k->S, 1)));
    return PIPS_OK;
 }
 

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devmem.h"
 #include "pips_hip.h"
 
 extern "C" {
@@ -765,8 +766,9 @@ struct Ipm {
    double* zd0 = nullptr;                       // eliminated root inequality rows: nOmegaInv - dual regularisation (dual_inequality_diagonal_regularized)
    double *rhs = nullptr, *sol = nullptr, *w_r = nullptr, *w_r0 = nullptr, *w_best = nullptr, *w_v = nullptr, *w_t = nullptr, *w_p = nullptr,
           *w_dx = nullptr, *w_tmp = nullptr;
-   double *d_partial = nullptr, *d_out = nullptr, *h_out = nullptr, *d_bst = nullptr, *h_bst = nullptr;
-   int* d_pred = nullptr;
+   double *d_partial = nullptr, *d_out = nullptr, *d_bst = nullptr;
+   PinnedBuf<double> h_out, h_bst;
+   DevBuf<int> d_pred;
    // options / counters
    int max_gondzio = 2;
    long long n_gondzio = 0, n_precond = 0, n_bicg_iter = 0, n_host_syncs = 0;
@@ -777,7 +779,7 @@ struct Ipm {
    double outer_tol = 1e-10, last_outer_res = 0.0, last_outer_abs = 0.0;
    int n_regularised = 0, n_factorize = 0, n_refactor_outer = 0, verbose_run = 0;
    double last_reg = 0.0;
-   std::vector<void*> owned;
+   std::vector<DevBuf<char>> owned;   // what up() and alloc() hand out views of
    double last[8] = {0};
    std::vector<double> trace;
    // ranks
@@ -789,22 +791,19 @@ struct Ipm {
    ~Ipm() {
       if (kkt) pips_hip_kkt_destroy(kkt);
       if (batch) pips_hip_batch_destroy(batch);
-      for (void* p : owned)
-         if (p) (void)hipFree(p);
-      if (h_out) (void)hipHostFree(h_out);
-      if (h_bst) (void)hipHostFree(h_bst);
    }
    template <class T>
    int up(T** d, const std::vector<T>& h) {
-      HIP_TRYH(hipMalloc((void**)d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-      owned.push_back(*d);
+      owned.emplace_back();
+      TRY(owned.back().alloc(std::max<size_t>(h.size(), 1) * sizeof(T)));
+      *d = (T*)owned.back().get();
       if (!h.empty()) HIP_TRYH(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
       return PIPS_OK;
    }
    int alloc(double** d, long long n) {
-      HIP_TRYH(hipMalloc((void**)d, std::max<long long>(n, 1) * sizeof(double)));
-      HIP_TRYH(hipMemset(*d, 0, std::max<long long>(n, 1) * sizeof(double)));
-      owned.push_back(*d);
+      owned.emplace_back();
+      TRY(owned.back().alloc_zero((size_t)std::max<long long>(n, 1) * sizeof(double)));
+      *d = (double*)owned.back().get();
       return PIPS_OK;
    }
 
@@ -1999,11 +1998,9 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
    p->bl = p->b0 + S + e_mz0;
    if ((rc = p->alloc(&p->d_partial, (long long)RED_MAX * RED_GRID)) || (rc = p->alloc(&p->d_out, 2 * RED_MAX)) || (rc = p->alloc(&p->d_bst, B_SLOTS)))
       return rc;
-   HIP_TRYH(hipHostMalloc((void**)&p->h_out, 2 * RED_MAX * sizeof(double), hipHostMallocDefault));
-   HIP_TRYH(hipHostMalloc((void**)&p->h_bst, B_SLOTS * sizeof(double), hipHostMallocDefault));
-   HIP_TRYH(hipMalloc((void**)&p->d_pred, P_COUNT * sizeof(int)));
-   p->owned.push_back(p->d_pred);
-   HIP_TRYH(hipMemset(p->d_pred, 0, P_COUNT * sizeof(int)));
+   TRY(p->h_out.alloc(2 * RED_MAX));
+   TRY(p->h_bst.alloc(B_SLOTS));
+   TRY(p->d_pred.alloc_zero(P_COUNT));
    if (e_mz0 > 0 && ((rc = p->alloc(&p->zd0, e_mz0)) || (rc = pips_hip_kkt_set_zdiag0_dev(p->kkt, p->zd0)))) return rc;   // nOmegaInv of the root rows, regularised
    return PIPS_OK;
 }

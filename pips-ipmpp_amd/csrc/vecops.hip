@@ -235,6 +235,8 @@ static double red_identity_host(int op) { return (op == RED_MIN || op == RED_STE
 // Reduction workspace: one per (thread, device).  The entry points take device pointers only, so the workspace of the device
 // that is current at the call is used - a workspace allocated on another device would be written across the fabric (or
 // fault without peer access).  Freed when a worker thread ends.
+// These two allocations stay raw pointers, outside the owner types of devmem.h (and its live counters): their destructor would free
+// on the main thread at process exit and knows nothing of the device switch below.
 struct VecWorkspace {
    double* d_partial = nullptr;  // 2048 partials + 8 result slots
    double* h_out = nullptr;      // pinned

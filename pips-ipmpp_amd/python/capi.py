@@ -42,6 +42,8 @@ _vp = C.c_void_p
 lib.pips_hip_last_error.restype = C.c_char_p
 lib.pips_hip_device_count.restype = C.c_int
 lib.pips_hip_host_wait_count.restype = C.c_longlong
+lib.pips_hip_device_allocs_live.restype = C.c_longlong
+lib.pips_hip_device_bytes_live.restype = C.c_longlong
 
 # every symbol include/pips_hip.h declares (tests/test_capi_symbols.py checks the header against this list)
 SYMBOLS = [
@@ -52,7 +54,7 @@ SYMBOLS = [
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
     "pips_hip_ldl_inertia_batch",
     "pips_hip_dense_ldl_create", "pips_hip_dense_ldl_factor", "pips_hip_dense_ldl_factor_dev", "pips_hip_dense_ldl_solve",
-    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_hip_host_wait_count", "pips_hip_host_wait_sites",
+    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
     "pips_hip_batch_create", "pips_hip_batch_set_block", "pips_hip_batch_set_options", "pips_hip_batch_set_schur_mode", "pips_hip_batch_set_deterministic", "pips_hip_batch_get_schur_mode", "pips_hip_batch_add_regularization", "pips_hip_batch_set_refinement",
     "pips_hip_batch_last_refinement_steps", "pips_hip_batch_set_refinement_backward_error",
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
@@ -98,6 +100,16 @@ def device_count():
 def host_wait_count():
     """host waits for the device inside the library so far (a diagnostic: take the difference around a call sequence)"""
     return int(lib.pips_hip_host_wait_count())
+
+
+def device_allocs_live():
+    """device and pinned host allocations the library holds right now"""
+    return int(lib.pips_hip_device_allocs_live())
+
+
+def device_bytes_live():
+    """... and their bytes"""
+    return int(lib.pips_hip_device_bytes_live())
 
 
 def host_wait_sites():
