@@ -542,6 +542,22 @@ int pips_symbolic_probe(int n, int n_primal, const int* krow, const int* jcol, i
 int pips_symbolic_probe_hubs(int n, int n_primal, const int* krow, const int* jcol, int n_hubs, const int* hubs, int min_size,
                              int64_t* what, int n_what, int* perm, int* colcount);
 
+/* The host layout pass of a batch analysis, without a device (csrc/layout.cpp; tests): symbolic analysis of every block with the
+ * switches read from the environment as pips_hip_batch_analyze reads them, then the layout the engine would upload.  K per block as
+ * lower-triangular CSR (n[b] + 1 row pointers), the border as CSR with S rows over the block's n[b] rows (bt_rowptr or bt_rowptr[b]
+ * NULL: no border).  free_device_bytes stands in for the free device memory that decides the single-launch tails.  The properties
+ * the kernels rely on are checked (disjoint block regions; supernode order and level ranges; front launches and their LDS; border-split
+ * batches; scatter targets, diagonal positions and the two-triangle row structure; the border by leaf row; the simple leaves' gather):
+ * PIPS_ERR_STATE with a message that names the first one that fails.
+ * what[0] arena doubles, [1] work-vector doubles, [2] U-arena doubles, [3] head supernodes, [4] levels kept for the level launches,
+ * [5] levels of the spine, [6] front launches, [7] fronts in the device-memory classes, [8] border-split batches, [9] staging doubles of a
+ * batch, [10] single-launch tails, [11] border-backward sweep, [12] sweeps of the augmented factor, [13] / [14] slots of the
+ * factorisation / forward substitution (deterministic mode), [15] sum of n, [16] multifrontal head, [17] Schur mode taken,
+ * [18] doubles of the border-row arena, [19] doubles of update matrices, [20] supernodes of the spine */
+int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol,
+                      int S, const int* const* bt_rowptr, const int* const* bt_colidx,
+                      int deterministic, long long free_device_bytes, int64_t* what, int n_what);
+
 /* ---- 6. input files ---------------------------------------------------------------------------------------------------
  * One block of a block-structured LP from a "jacobian" GDX file, the format gmspips_reader opens per block
  * (Drivers/gams/gmspips/gmspips_reader.cpp:30-60; extraction rules of readBlock, gmspipsio.c:1357-2033; fields of

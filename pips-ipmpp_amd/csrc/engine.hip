@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "devmem.h"
+#include "layout.h"
 #include "kernels.hip.h"
 #include "rootkernel.hip.h"
 #include "tailkernel.hip.h"
@@ -64,6 +65,12 @@ const char* last_error() { return g_last_error.c_str(); }
 static int env_int(const char* name, int dflt) {
    const char* v = getenv(name);
    return v ? atoi(v) : dflt;
+}
+
+// ... of an on / off switch: -1 when it is not set, else whether its value is non-zero
+static int env_flag(const char* name) {
+   const char* v = getenv(name);
+   return v ? (atoi(v) != 0 ? 1 : 0) : -1;
 }
 
 static inline int grid_for(long long n, int block, int cap = 4096) {
@@ -681,56 +688,15 @@ static int tail_bwd(const TailCtx& c, double* xw, int nrhs = 1, long long xw_str
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// batched leaf engine
+// batched leaf engine (BlockInput, LevelRange, MfLaunch and the host pass of the analysis: layout.h)
 // ---------------------------------------------------------------------------------------------------------------
-struct BlockInput {
-   int n = 0, n_primal = -1;
-   std::vector<int> krow, kcol;
-   std::vector<int> btrow, btcol;  // S+1 / nnz ; empty if no border
-   std::vector<double> btval;
+// What one analyze() call reads from the environment: the layout's switches, and the two of the single-launch tail factorisation
+struct AnalyzeKnobs : LayoutKnobs {
+   long long tail_poll_limit = 0;
+   int tail_diag_blocked = 1;
 };
-
-// The head solve sweeps use the register-lean "chain" kernels (k_head_fwd_chain / k_head_bwd_chain: all loads up front, partial sums in
-// registers, one LDS transpose) at every launch size (round 2 drew a line at 1024 waves; with supernodes capped at 16 columns they win
-// everywhere: configs[3] share, leaf solve 13.5 -> 11.6 ms).  Deterministic mode takes k_head_fwd (it writes slots) forward, the chain
-// kernel backward.
-struct LevelRange {
-   int simple_begin, simple_cnt, small_begin, small_cnt, large_begin, large_cnt;
-   int small_lds = 0, large_lds = 0;   // doubles of LDS the widest L21 panel of the class needs (r * (w | 1)), capped at the kernel's capacity
-};
-
-// Multifrontal head: one launch per (level, front class); class = (workgroup size, width bound) of k_front.
-struct MfLaunch { int level, cls, begin, cnt, lds_doubles; };
-// doubles of the update matrix a front keeps: all r columns, or (border split) those of its rb rows of K
-// rows a front holds below its pivot block: all, or (fronts on the rows of K only, BlockSym::mf_konly) its rows of K
-static inline int mf_rows(const BlockSym& bs, const HeadSupernode& s) { return bs.mf_konly ? s.rb : s.r; }
-static inline long long mf_unp(const BlockSym& bs, const HeadSupernode& s) {
-   const long long uc = bs.mf_split ? s.rb : s.r, r = mf_rows(bs, s);
-   return uc * r - uc * (uc - 1) / 2;
-}
-static inline int mf_class(int w, long long nf, long long unp, long long lds_budget) {
-   const long long r = nf - w, pw = std::max<long long>(w * nf - (long long)w * (w - 1) / 2, (long long)w * ((r + 3) / 4 * 4));
-   if (pw + unp + 8 > lds_budget) return 6 + (nf <= 256 ? 0 : 1);   // update matrix stays in device memory
-   // more than one wave: 256 threads - the phases around the pivots are spread over them (128 threads up to 128 rows - twice the fronts
-   // per compute unit where the registers set the limit - measured 15.3 against 15.0 ms on the 256-block chain: docs/HISTORY_r4.md)
-   return (nf <= 64 ? 0 : 2) + 3 * (w <= 16 ? 0 : 1);
-}
-
-// Tile geometry + the cost-model / amalgamation knobs (environment overrides are for tuning runs only).
-static void apply_tuning(AnalyzeOptions& opt) {
-   opt.tile = TILE;
-   // Supernode width cap.  16 instead of the kernels' limit of 32: on the time-coupled family (tools/config3_probe.py, 64 x 50 000)
-   // narrower supernodes carry fewer explicit zeros (nnz(L) 164 M -> 151 M), halve the dependent pivot chain of a front and the
-   // registers its rows take; factorisation 13.4 -> 12.5 ms, solveCompressed 9.3 -> 8.9 ms.  Random sparsity (config 2) has no
-   // supernodes wider than one column in the head.
-   opt.max_sn_width = 16;
-   if (const char* sw = getenv("PIPS_HIP_SN_WIDTH")) opt.max_sn_width = std::max(1, std::min(HEAD_WMAX, atoi(sw)));
-   if (const char* rz = getenv("PIPS_HIP_RELAX_ZEROS")) opt.relax_zeros = atof(rz);   // share of explicit zeros per panel
-   if (const char* ndd = getenv("PIPS_HIP_ND_DEPTH")) opt.nd_depth = atoi(ndd);        // dissection levels (0 = off)
-   if (const char* ndm = getenv("PIPS_HIP_ND_MIN")) opt.nd_min_size = atoi(ndm);      // smallest segment that is still dissected
-   if (const char* ml = getenv("PIPS_HIP_MF_LDS")) opt.mf_lds_doubles = atoll(ml);   // LDS budget of a front in doubles (tests: small values force the device-memory variant)
-   if (const char* sp = getenv("PIPS_HIP_MF_SPLIT")) opt.mf_split_nb_max = atoi(sp) == 0 ? 0 : std::min(176, std::max(atoi(sp), 2));   // border split: 0 = off, else the largest nb
-}
+struct Engine;
+static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs& knobs);
 
 // What an analysis owns on the device and what belongs to it on the host: Engine::release() resets exactly this (a move-assignment
 // from a fresh one), so a buffer declared here is freed and reset without a second mention anywhere.  The settings that survive a
@@ -746,20 +712,13 @@ struct EngineAnalysis {
    DevBuf<int> d_kb_rec;
    DevBuf<long long> d_kb_off;          // per supernode (sorted id): offset of its record, -1 none
    DevBuf<int> d_kb_list;               // fronts with border rows, level after level
-   std::vector<int> kb_level_off;       // offsets into d_kb_list per level (size levels + 1)
-   std::vector<int> kb_level_pairs, kb_level_lds;   // per level: most pairs of one front, bytes of the largest border-row block (LDS of k_border_rows)
    DevBuf<int> d_kb_tail;
-   int n_kb_tail = 0;
-   std::vector<MfLaunch> mf_launches;
    DevBuf<double> d_mfU;                // update matrices of the fronts
    DevBuf<double> d_mfLV;               // d and l of the simple leaves below fronts, front by front
    DevBuf<int> d_roots, d_root_off;     // fronts without a head parent, per block (k_root_assemble)
-   int n_roots = 0;
    DevBuf<BbBatch> d_bb_batches;        // border split (k_border_schur): batches of supernodes with border rows, block after block
    DevBuf<BbMeta> d_bb_meta;
    DevBuf<int> d_bb_off, d_bb_pos;      // batches of block b: [d_bb_off[b], d_bb_off[b + 1]); compressed border ids of the staged rows
-   int n_bb = 0;
-   long long bb_doubles = 0;            // doubles of the border-row arena (behind the panels inside d_arena)
    DevBuf<double> d_bb_out;             // deterministic mode: the blocks' border x border triangles before they join their groups
    DevBuf<int> d_bb_round_blk;          // deterministic mode: the blocks of round k of k_border_schur
    DevBuf<int> d_round_blk;             // deterministic mode: the blocks of round k at [round_off[k], round_off[k + 1])
@@ -779,7 +738,6 @@ struct EngineAnalysis {
    // d_lf_pos, which is indexed like d_rowidx).  No atomics, fixed order of the sums.
    DevBuf<int> d_lf_rows, d_lf_ptr, d_lf_src, d_lf_pos;
    DevBuf<double> d_lf_val;
-   long long lf_rows = 0, lf_entries = 0;
    DevBuf<LeafDesc> d_leafdesc;         // compact records of the level-0 simple leaves, in the order of d_sns (k_leaf_bwd)
    DevBuf<int> d_lb_list;               // the simple leaves that own border rows (k_leaf_border)
    DevBuf<int> d_rowidx, d_upd, d_sncol, d_bmap, d_perm, d_inertia, d_nprimal;
@@ -833,7 +791,9 @@ struct EngineAnalysis {
    bool inertia_in_flight = false, inertia_on_host = false;
 };
 
-struct Engine : EngineAnalysis {
+// The host side of the analysis - offsets, sorted supernodes, launch lists, the decisions - is the BatchLayout (layout.h) the engine is
+// built on; its big index arrays are dropped once they are uploaded.
+struct Engine : EngineAnalysis, BatchLayout {
    int device = 0;
    hipStream_t stream = nullptr;
    int nblk = 0, S = 0;
@@ -848,31 +808,11 @@ struct Engine : EngineAnalysis {
    AnalyzeOptions opt;
    std::vector<BlockInput> in;
    std::vector<BlockSym> sym;
-   std::vector<BlkDesc> h_blks;
-   std::vector<long long> kptr;     // nblk+1 offsets into kval
-   std::vector<long long> x_off;    // nblk+1 offsets into flat vectors
-   std::vector<LevelRange> levels;
-   std::vector<LevelRange> levels_top;   // the spine's levels, for the multi-vector sweeps (which are level-scheduled throughout)
-   int n_flong = 0;
    int schur_mode = 0;        // requested: 0 auto, 1 augmented partial factorisation, 2 blocked solves (reference K4-K6)
-   int schur_mode_eff = 1;    // what analyze() settled on
-   std::vector<int> schur_cols;   // non-empty Schur columns (any block), ascending
    int sn_width = 0;           // > 0: supernode width cap of this engine instead of the tuned default (the sparse root: a single block, every level is latency)
-   bool mf = false;            // multifrontal head (k_front): update matrices go from child to parent front, no FP64 atomics in the head
-   std::vector<int> h_bb_off_keep;
-   int bb_stage = 3072, bb_nbmax = 0, bb_poscap = 0;
-   bool bb_two_per_cu = false;   // k_border_schur: staging area sized for two workgroups per compute unit (bb_plan_size)
    std::vector<int> bb_round_off;
-   std::vector<int> h_root_off_keep;
    std::vector<int> round_off;
-   long long mfU_total = 0;
-   int spine_total = 0, n_levels_all = 0;   // supernodes handled by the per-block spine kernels; tree height before the cut
-   long long n_total = 0, nnzK_total = 0, nnzB_total = 0, arena_total = 0, xw_total = 0, bt_rows_total = 0;
-   int nsn_total = 0;
    PhaseTimer timer;
-   long long uarena_total = 0;
-   int n_lb = 0, nb_pad_max = 0;
-   int head_wcap = HEAD_WMAX;   // widest head supernode of this analysis (picks the register-lean variants of the chain kernels)
    std::vector<int> h_inertia;
    std::vector<double> h_amax;   // max|K_b| of the current factorisation (backward-error refinement criterion)
 
@@ -882,15 +822,15 @@ struct Engine : EngineAnalysis {
       if (ev_diag_in) (void)hipEventDestroy(ev_diag_in);
       if (ev_diag_out) (void)hipEventDestroy(ev_diag_out);
    }
-   // everything the analysis owns goes; the settings, the inputs and the streams stay
+   // everything the analysis owns goes, on the device and on the host; the settings, the inputs and the streams stay
    void release() {
       for (auto ev : ev_sc) (void)hipEventDestroy(ev);
       if (ev_inertia) (void)hipEventDestroy(ev_inertia);
       static_cast<EngineAnalysis&>(*this) = EngineAnalysis();
+      static_cast<BatchLayout&>(*this) = BatchLayout();
+      analyzed = factored = head_slots = false;
    }
 
-   bool tail_single = false;                         // ... decided at analyze time: the tails are then assembled in a scratch region (BlkDesc::T_in)
-   long long tail_scratch = 0;                       // doubles of that region, behind the panels and the border-row arena
    hipStream_t side = nullptr;                       // diagonal tiles of the tail are factorised here, beside the column update
    hipEvent_t ev_diag_in = nullptr, ev_diag_out = nullptr;
    // ---- deterministic mode (pips_hip_batch_set_deterministic): no FP64 atomics on the path.  Every scattered contribution of
@@ -903,11 +843,9 @@ struct Engine : EngineAnalysis {
    bool head_slots = false;
    bool slot_solves = false;    // single-RHS forward substitution through slots outside deterministic mode too (measured: no gain)
    static constexpr long long HEAD_SLOTS_MAX = 400LL * 1000 * 1000;
-   long long slots_total = 0, vslots_total = 0;
    int last_multi_path = 0;      // how the last solve(nrhs) went: 0 one sweep per right-hand side, 1 interleaved panels, 2 interleaved panels with the slot / gather forward substitution
    std::vector<SlotEntry> sc_e_keep;
    std::vector<int> sc_blk_keep;
-   std::vector<int> h_bt_rowsc_keep, h_bt_rownnz_keep, h_bt_rowblk_keep;
    std::vector<TaskList> det_rounds;
    int det_n_groups = 0, det_first_slot = 0;
    // Several ranks whose count divides eight: every rank's group buffers travel to every rank (an all-reduce in which the others hold
@@ -947,7 +885,7 @@ struct Engine : EngineAnalysis {
          round_off.assign(1, 0);
          for (int k = 0; k < gs; ++k) {
             for (int b = k; b < nblk; b += gs)
-               if (h_root_off_keep[b + 1] > h_root_off_keep[b]) rb.push_back(b);
+               if (h_root_off[b + 1] > h_root_off[b]) rb.push_back(b);
             round_off.push_back((int)rb.size());
          }
          if (rb.empty()) rb.push_back(0);
@@ -958,7 +896,7 @@ struct Engine : EngineAnalysis {
          bb_round_off.assign(1, 0);
          for (int k = 0; k < gs; ++k) {
             for (int b = k; b < nblk; b += gs)
-               if (n_bb > 0 && h_bb_off_keep[b + 1] > h_bb_off_keep[b]) bbr.push_back(b);
+               if (n_bb > 0 && h_bb_off[b + 1] > h_bb_off[b]) bbr.push_back(b);
             bb_round_off.push_back((int)bbr.size());
          }
          if (bbr.empty()) bbr.push_back(0);
@@ -990,7 +928,7 @@ struct Engine : EngineAnalysis {
       if (S > 0) {
          std::vector<SlotEntry> ent;
          for (long long i = 0; i < bt_rows_total; ++i)
-            if (h_bt_rownnz_keep[(size_t)i] > 0) ent.push_back({(long long)grp[h_bt_rowblk_keep[(size_t)i]] * S + h_bt_rowsc_keep[(size_t)i], i});
+            if (h_bt_rownnz[(size_t)i] > 0) ent.push_back({(long long)grp[h_bt_rowblk[(size_t)i]] * S + h_bt_rowsc[(size_t)i], i});
          if ((rc = upload_gather(ent, g_btm_grp))) return rc;
          PIPS_TRY(d_gvec.alloc((size_t)8 * S));
          PIPS_TRY(d_tvec.alloc((size_t)S));
@@ -1008,15 +946,15 @@ struct Engine : EngineAnalysis {
       d_bg_ent.reset(); d_bg_ptr.reset(); d_bg_idx.reset(); d_bg_val.reset(); d_bg_slot.reset();
       n_bg_targets = n_bg_ent = 0;
       g_bslot_grp = GatherList();
-      if (!aug_sweeps_ok || h_sns_keep.empty()) return PIPS_OK;
+      if (!aug_sweeps_ok || h_sns.empty()) return PIPS_OK;
       std::vector<long long> tbase(nblk + 1, 0);
       for (int b = 0; b < nblk; ++b) tbase[b + 1] = tbase[b] + h_blks[b].nb;
       const long long nt = tbase[nblk];
       if (nt == 0) return PIPS_OK;
       std::vector<long long> cnt((size_t)nt + 1, 0);
       auto for_rows = [&](auto&& fn) {
-         for (size_t i = 0; i < h_sns_keep.size(); ++i) {
-            const SnDesc& sn = h_sns_keep[i];
+         for (size_t i = 0; i < h_sns.size(); ++i) {
+            const SnDesc& sn = h_sns[i];
             if (sn.rb >= sn.r) continue;
             const BlockSym& bs = sym[sn.blk];
             const int loc = bs.sn_of_col[(size_t)sn.c0];
@@ -1118,699 +1056,42 @@ struct Engine : EngineAnalysis {
       return c;
    }
 
-   int analyze_host(int n_threads, bool with_border = true) {
-      sym.assign(nblk, BlockSym());
-      std::vector<int> rc(nblk, 0);
-      std::vector<std::string> msgs(nblk);
-      n_threads = std::max(1, std::min(n_threads, nblk));
-      auto work = [&](int t) {
-         for (int b = t; b < nblk; b += n_threads) {
-            CsrPattern K{in[b].n, in[b].n, in[b].krow.data(), in[b].kcol.data()};
-            CsrPattern B{0, in[b].n, nullptr, nullptr};
-            if (with_border && !in[b].btrow.empty()) B = CsrPattern{S, in[b].n, in[b].btrow.data(), in[b].btcol.data()};
-            rc[b] = analyze_block(K, B, in[b].n_primal, opt, sym[b]);
-            if (rc[b]) msgs[b] = last_error();
-         }
-      };
-      std::vector<std::thread> th;
-      for (int t = 1; t < n_threads; ++t) th.emplace_back(work, t);
-      work(0);
-      for (auto& t : th) t.join();
-      for (int b = 0; b < nblk; ++b)
-         if (rc[b]) PIPS_FAIL(rc[b], "block %d: %s", b, msgs[b].c_str());
-      return PIPS_OK;
-   }
-
-   // Schur contribution by the augmented partial factorisation (border rows ride in every panel: dense work, right when
-   // the factor is dense anyway) or by blocked solves with the plain factor (the reference's way: 4 nnz(L) flops per border
-   // column, right when L is sparse and L^-1 Br would fill in).  Estimated from the bordered symbolic analysis.
-   bool blocked_solves_cheaper() const {
-      double t_aug = 0.0, l_bytes = 0.0;
-      int max_levels = 0, max_ntc = 0;
-      std::vector<char> used(S, 0);
-      for (int b = 0; b < nblk; ++b) {
-         const BlockSym& s = sym[b];
-         double pairs = 0.0, border_entries = 0.0;
-         for (const HeadSupernode& sn : s.sn) {
-            const double rbd = sn.r - sn.rb;
-            // every scattered pair costs a w-long dot product besides its atomic (calibrated: 8e-11 s at w = 1, 1e-9 s at w = 25)
-            pairs += (rbd * (sn.r - rbd) + 0.5 * rbd * rbd) * std::max(1.0, 0.5 * sn.w);
-            border_entries += rbd * sn.w;
-         }
-         t_aug += opt.head_cost * pairs + s.flops_border / opt.mfma_rate;
-         l_bytes += 8.0 * ((double)s.nnzL - border_entries);
-         max_levels = std::max(max_levels, s.n_levels);
-         max_ntc = std::max(max_ntc, s.m_pad / TILE);
-         for (int c : s.bmap) used[c] = 1;
-      }
-      double ncols = 0;
-      for (char u : used) ncols += u;
-      const double launches = 2.0 * (max_levels + 2 * max_ntc) + 8;
-      // multi-RHS sweeps over a sparse factor run at ~0.8 TB/s effective (measured, tools/banded_schur_probe.py)
-      const double t_sol = ncols * 2.0 * l_bytes / 0.8e12 + std::ceil(ncols / 32.0) * launches * 12e-6;
-      return t_sol < t_aug;
-   }
-
+   // check inputs; read knobs; symbolic analysis with its two retries; host layout; upload; task plans; streams; deterministic mode.
+   // What the previous analysis held goes first, whatever comes of this one (sym is overwritten: the old buffers would not match it);
+   // the free memory that decides tail_single is thereby read as it always was, without the old buffers.
    int analyze(int n_threads) {
       for (int b = 0; b < nblk; ++b)
          if (in[b].n <= 0) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_batch_analyze: block %d was never set", b);
-      apply_tuning(opt);
-      if (sn_width > 0 && !getenv("PIPS_HIP_SN_WIDTH")) opt.max_sn_width = std::min(HEAD_WMAX, sn_width);
-      bool any_border = false;
-      for (int b = 0; b < nblk; ++b) any_border = any_border || !in[b].btrow.empty();
-      {  // the border split (compact front panels) only exists with the multifrontal head
-         if (env_int("PIPS_HIP_MF", 1) == 0) opt.mf_split_nb_max = 0;
-      }
-      // fronts on the rows of K only where the border split applies (PIPS_HIP_MF_KONLY=1; off by default: on the configs[3] share the fronts fall
-      // from 9.7 to 4.0 ms, forming the border rows afterwards costs 8.0 - DESIGN.md 4.1c): not in deterministic mode (the border rows of the dense
-      // tail take their head contributions with atomics, k_border_tail) and with supernodes of at most 16 columns (k_border_rows<., 16>)
-      opt.mf_konly = opt.mf_split_nb_max > 0 && !deterministic && opt.max_sn_width <= 16 && env_int("PIPS_HIP_MF_KONLY", 0) != 0;
-      int rc = analyze_host(n_threads, schur_mode != 2);
-      if (rc) return rc;
-      schur_mode_eff = (schur_mode == 2 && any_border) ? 2 : 1;
-      if (schur_mode == 0 && any_border && blocked_solves_cheaper()) {
-         schur_mode_eff = 2;
-         if ((rc = analyze_host(n_threads, false))) return rc;
-      }
+      AnalyzeKnobs knobs;
+      read_layout_knobs(this, opt, knobs);
       HIP_TRY(hipSetDevice(device));
       release();
-      {  // multifrontal head: every block's fronts must fit the LDS; the slot machinery of deterministic mode records scatters
-         mf = env_int("PIPS_HIP_MF", 1) != 0;
-         const bool mf_wanted = mf;
-         auto fronts_fit = [&]() {
-            bool ok = mf_wanted;
-            for (int b = 0; b < nblk && ok; ++b) {
-               ok = sym[b].mf_ok;
-               // fronts with very many leaves below them: the staged leaf data must fit beside the front
-               for (size_t l = 0; l < sym[b].sn.size() && ok; ++l) {
-                  if (sym[b].mf_meta[l] < 0) continue;
-                  const HeadSupernode& s = sym[b].sn[l];
-                  const int* H = sym[b].mf_int.data() + sym[b].mf_meta[l];
-                  const long long fr = mf_rows(sym[b], s), nf = s.w + fr, pw = std::max<long long>(s.w * nf - (long long)s.w * (s.w - 1) / 2, (long long)s.w * ((fr + 3) / 4 * 4));
-                  const long long packed = pw + mf_unp(sym[b], s) + 8, panel = pw + 8;
-                  const long long extra = H[5] + (H[6] + H[3] + 1) / 2 + 2;
-                  if ((packed > opt.mf_lds_doubles ? panel : packed) + extra > 20352) ok = false;   // 159 KB of the 160
-               }
-            }
-            return ok;
-         };
-         mf = fronts_fit();
-         bool any_split = false;
-         for (int b = 0; b < nblk; ++b) any_split = any_split || sym[b].mf_split;
-         // ... or k_border_schur's triangle + staged batch + row positions exceed the LDS (nb close to the cap under wide fronts whose
-         // below-rows are nearly all border rows): the same formula the launch uses, evaluated here so that such an input is analysed with
-         // whole update matrices instead of failing in every factor()
-         const bool bb_too_big = mf && any_split && !bb_fits(bb_plan_size());
-         if ((!mf && any_split) || bb_too_big) {   // every block back to full panels
-            opt.mf_split_nb_max = 0;
-            if ((rc = analyze_host(n_threads, schur_mode_eff != 2))) return rc;
-            if (bb_too_big) mf = fronts_fit();   // (the fronts grew by their border columns: they must still fit)
-         }
-      }
-
-      // ---- offsets
-      h_blks.assign(nblk, BlkDesc());
-      kptr.assign(nblk + 1, 0);
-      x_off.assign(nblk + 1, 0);
-      std::vector<long long> bptr(nblk + 1, 0), rows_base(nblk + 1, 0), sn_base(nblk + 1, 0), bmap_off(nblk + 1, 0),
-         upd_base(nblk + 1, 0), mfU_base(nblk + 1, 0), mfint_base(nblk + 1, 0), mfLV_base(nblk + 1, 0);
-      long long arena = 0, xw = 0, winv = 0, dt = 0, sncol = 0, uar = 0;
-      for (int b = 0; b < nblk; ++b) {
-         const BlockSym& s = sym[b];
-         BlkDesc& d = h_blks[b];
-         d.arena_off = arena;
-         d.T = arena + s.T_off;
-         d.sncol_off = sncol;
-         d.xw_off = xw;
-         d.x_off = x_off[b];
-         d.bmap_off = bmap_off[b];
-         d.winv_off = winv;
-         d.dt_off = dt;
-         d.n = s.n; d.n_head = s.n_head; d.m = s.m; d.m_pad = s.m_pad; d.nb = s.nb; d.nb_pad = s.nb_pad; d.ldT = s.ldT;
-         d.ntc = s.m_pad / TILE;
-         d.ntr = s.m > 0 ? s.ldT / TILE : 0;
-         d.mf_split = (mf && s.mf_split) ? (s.mf_konly ? 2 : 1) : 0;   // 2: fronts on the rows of K only (k_border_rows forms their border rows)
-         d.U = uar;
-         uar += (long long)s.m_pad * s.m_pad;
-         d.thr_rel = 0; d.repl_rel = 1e-8; d.repl_abs = 1;
-         arena += s.arena;
-         xw += s.n_head + s.m_pad + s.nb_pad;   // [head | padded tail | border rows (border-backward sweep only)]
-         winv += (long long)d.ntc * TILE * TILE;
-         dt += s.m_pad;
-         sncol += s.n_head;
-         kptr[b + 1] = kptr[b] + (long long)in[b].kcol.size();
-         bptr[b + 1] = bptr[b] + (long long)in[b].btcol.size();
-         x_off[b + 1] = x_off[b] + s.n;
-         rows_base[b + 1] = rows_base[b] + (long long)s.rowidx.size();
-         upd_base[b + 1] = upd_base[b] + (long long)s.upd.size();
-         mfU_base[b + 1] = mfU_base[b] + (mf ? s.mf_U_total : 0);
-         mfint_base[b + 1] = mfint_base[b] + (mf ? (long long)s.mf_int.size() : 0);
-         mfLV_base[b + 1] = mfLV_base[b] + (mf ? s.mf_LV_total : 0);
-         d.lv_off = mfLV_base[b];
-         d.k_off = kptr[b]; d.b_off = bptr[b];
-         sn_base[b + 1] = sn_base[b] + (long long)s.sn.size();
-         bmap_off[b + 1] = bmap_off[b] + s.nb;
-      }
-      arena_total = arena; uarena_total = uar; xw_total = xw; n_total = x_off[nblk]; nnzK_total = kptr[nblk]; nnzB_total = bptr[nblk];
-      // the concatenated CSR copies of K (refinement residual: both triangles) and of the borders are indexed with int32
-      if (2 * nnzK_total > (long long)INT32_MAX || nnzB_total > (long long)INT32_MAX || n_total > (long long)INT32_MAX)
-         PIPS_FAIL(PIPS_ERR_ARG, "batch too large for the 32-bit index arrays of one rank: sum nnz(K) %lld (limit 2^30), sum nnz(border) %lld, sum n %lld - "
-                                 "use more ranks or fewer blocks per batch", nnzK_total, nnzB_total, n_total);
-      nsn_total = (int)sn_base[nblk];
-
-      // ---- supernodes sorted by (level, size class); multifrontal head: by (level, kernel variant, LDS need)
-      struct Key { int level, cls, lds, blk, loc; };
-      std::vector<Key> keys;
-      keys.reserve(nsn_total);
-      int nlev = 0;
-      auto is_simple = [](const HeadSupernode& s) { return s.w == 1 && s.r <= SIMPLE_RMAX && s.level == 0; };
-      // multifrontal: a level with few fronts is latency, not throughput - all its (LDS-resident) fronts go into ONE launch of the
-      // largest variant any of them needs instead of one launch per variant
-      constexpr int MF_MERGE_MAX = 1024;
-      std::vector<int> lev_cnt, lev_b, lev_w;
-      if (mf)
-         for (int b = 0; b < nblk; ++b)
-            for (const HeadSupernode& s : sym[b].sn) {
-               if (is_simple(s)) continue;
-               if ((int)lev_cnt.size() <= s.level) { lev_cnt.resize(s.level + 1, 0); lev_b.resize(s.level + 1, 0); lev_w.resize(s.level + 1, 0); }
-               const int c = mf_class(s.w, s.w + mf_rows(sym[b], s), mf_unp(sym[b], s), opt.mf_lds_doubles);
-               ++lev_cnt[s.level];
-               if (c < 6) { lev_b[s.level] = std::max(lev_b[s.level], c % 3); lev_w[s.level] = std::max(lev_w[s.level], c / 3); }
-            }
-      for (int b = 0; b < nblk; ++b)
-         for (int l = 0; l < (int)sym[b].sn.size(); ++l) {
-            const HeadSupernode& s = sym[b].sn[l];
-            // class 0: "simple leaf" (w = 1, r <= 16, level 0) -> one thread each;
-            // class 1: small (one wave); class 2: large (256 threads)
-            int cls = (s.w <= 8 && s.r <= 64) ? 1 : 2, lds = 0;
-            if (mf && !is_simple(s)) {
-               const long long fr = mf_rows(sym[b], s);
-               int c = mf_class(s.w, s.w + fr, mf_unp(sym[b], s), opt.mf_lds_doubles);
-               if (c < 6 && lev_cnt[s.level] <= MF_MERGE_MAX) c = lev_b[s.level] + 3 * lev_w[s.level];
-               cls = 1 + c;
-               // LDS of a front: the packed front (or its panel columns) + 8 doubles of slack, the leaves' values, and as ints the
-               // children's position lists and the leaf part of the record (common.h "Front record")
-               const long long nf = s.w + fr;
-               const int* H = sym[b].mf_int.data() + sym[b].mf_meta[l];
-               const long long pw = std::max<long long>(s.w * nf - (long long)s.w * (s.w - 1) / 2, (long long)s.w * ((fr + 3) / 4 * 4));   // packed panel / aligned L21 copy
-               lds = (int)(pw + (c >= 6 ? 0 : mf_unp(sym[b], s)) + 8 + H[5] + (H[6] + H[3] + 1) / 2 + 2);
-            }
-            if (is_simple(s)) cls = 0;
-            keys.push_back({s.level, cls, lds, b, l});
-            nlev = std::max(nlev, s.level + 1);
-         }
-      std::stable_sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
-         return a.level != b.level ? a.level < b.level : (a.cls != b.cls ? a.cls < b.cls : a.lds < b.lds);
-      });
-      if (getenv("PIPS_HIP_DUMP_LEVELS")) {   // development aid: shape of the head, level by level
-         std::vector<long long> cnt(nlev * 3, 0), rmax(nlev, 0), wsum(nlev, 0), pairs(nlev, 0);
-         for (const Key& k : keys) {
-            const HeadSupernode& s = sym[k.blk].sn[k.loc];
-            ++cnt[k.level * 3 + std::min(k.cls, 2)];
-            rmax[k.level] = std::max<long long>(rmax[k.level], s.r);
-            wsum[k.level] += s.w;
-            pairs[k.level] += (long long)s.r * (s.r + 1) / 2;
-         }
-         for (int l = 0; l < nlev; ++l)
-            fprintf(stderr, "level %3d: simple %lld small %lld large %lld  columns %lld  max r %lld  update pairs %lld\n", l, cnt[3 * l], cnt[3 * l + 1],
-                    cnt[3 * l + 2], wsum[l], rmax[l], pairs[l]);
-      }
-      // ---- spine: the top levels that hold at most two supernodes of every block (chain-like trees of time-coupled
-      //      blocks).  One launch per level would be pure latency there; they go to the per-block spine kernels instead.
-      n_levels_all = nlev;
-      int lstar = nlev;
       {
-         std::vector<int> width(nlev, 0);   // max over blocks of the supernode count per level
-         std::vector<int> cnt(nlev);
-         for (int b = 0; b < nblk; ++b) {
-            std::fill(cnt.begin(), cnt.end(), 0);
-            for (const HeadSupernode& s : sym[b].sn) ++cnt[s.level];
-            for (int l = 0; l < nlev; ++l) width[l] = std::max(width[l], cnt[l]);
-         }
-         while (lstar > 0 && width[lstar - 1] <= 2) --lstar;
-         const char* env = getenv("PIPS_HIP_SPINE");
-         if (nlev - lstar < 8 || (env && atoi(env) == 0) || deterministic || mf) lstar = nlev;   // the spine kernels hand over through atomics
-      }
-      std::vector<SnDesc> h_sns(nsn_total);
-      std::vector<std::vector<int>> roots_of(nblk);   // multifrontal head: fronts without a head parent, ascending
-      long long slots_acc = 0, vslots_acc = 0;
-      std::vector<std::vector<int>> sorted_id(nblk);
-      for (int b = 0; b < nblk; ++b) sorted_id[b].resize(sym[b].sn.size());
-      levels.assign(lstar, LevelRange{0, 0, 0, 0, 0, 0, 0, 0});
-      levels_top.assign(nlev - lstar, LevelRange{0, 0, 0, 0, 0, 0, 0, 0});
-      head_wcap = 1;
-      for (int i = 0; i < nsn_total; ++i) {
-         const Key& k = keys[i];
-         const HeadSupernode& s = sym[k.blk].sn[k.loc];
-         head_wcap = std::max(head_wcap, s.w);
-         h_sns[i] = SnDesc{h_blks[k.blk].arena_off + s.panel, rows_base[k.blk] + s.rows, upd_base[k.blk] + s.upd, s.w, s.r, s.c0, k.blk,
-                           s.n_useg, s.rb, s.ld, 0, slots_acc, vslots_acc, -1, -1, -1};
-         if (mf && k.cls > 0 && s.r > 0 && sym[k.blk].sn_parent[k.loc] < 0) roots_of[k.blk].push_back(i);
-         if (mf) {
-            const BlockSym& bs = sym[k.blk];
-            if (bs.mf_U[k.loc] >= 0) h_sns[i].U = (k.cls == 0 ? mfLV_base[k.blk] : mfU_base[k.blk]) + bs.mf_U[k.loc];
-            if (bs.mf_meta[k.loc] >= 0) h_sns[i].mf = mfint_base[k.blk] + bs.mf_meta[k.loc];
-         }
-         // factorisation slots: every scattering supernode; multifrontal head: only the simple leaves without a front above them scatter
-         // (the fronts hand their update matrices on, k_root_assemble adds the last ones in a fixed order)
-         if (!mf || (k.cls == 0 && s.n_useg == 0)) slots_acc += (long long)s.r * (s.r + 1) / 2;
-         vslots_acc += s.r;
-         sorted_id[k.blk][k.loc] = i;
-         LevelRange& L = k.level >= lstar ? levels_top[k.level - lstar] : levels[k.level];
-         if (k.cls == 0) { if (L.simple_cnt++ == 0) L.simple_begin = i; }
-         else if (k.cls == 1 || mf) { if (L.small_cnt++ == 0) L.small_begin = i; }   // multifrontal: one contiguous range of fronts per level
-         else { if (L.large_cnt++ == 0) L.large_begin = i; }
-         if (mf && k.cls > 0) {
-            // one launch per (level, variant, LDS bucket): the dynamic LDS of a launch is that of its largest front, and it decides how
-            // many fronts share a compute unit
-            bool open = mf_launches.empty() || mf_launches.back().level != k.level || mf_launches.back().cls != k.cls - 1;
-            if (!open) {
-               const MfLaunch& m = mf_launches.back();
-               const int first_lds = keys[m.begin].lds;
-               {
-                  // how many fronts of the variant share a compute unit: the LDS decides up to the limit the registers set (123 VGPRs: four
-                  // waves per SIMD - four workgroups of 256 threads, sixteen of 64); a bucket = one such class, since inside a class a
-                  // smaller front gains nothing from a launch of its own and across a boundary every front of the launch loses a slot
-                  auto cls_of = [&](int lds_doubles) {
-                     const int c = k.cls - 1, kmax = c == 0 ? 16 : c == 3 ? 12 : c == 1 ? 8 : c == 4 ? 6 : c == 2 ? 4 : 3;   // (154 VGPRs for the 32-wide variants)
-                     return std::min(kmax, (int)(163840 / ((long long)lds_doubles * 8 + 1024)));
-                  };
-                  if (m.cnt >= 256 && cls_of(k.lds) < cls_of(first_lds)) open = true;
-               }
-            }
-            if (open) mf_launches.push_back({k.level, k.cls - 1, i, 0, 0});
-            ++mf_launches.back().cnt;
-            mf_launches.back().lds_doubles = std::max(mf_launches.back().lds_doubles, k.lds);
-         }
-         const long long need = (long long)s.r * (s.w | 1);
-         if (k.cls == 1) L.small_lds = (int)std::max<long long>(L.small_lds, std::min<long long>(need, 640));
-         else if (k.cls == 2) L.large_lds = (int)std::max<long long>(L.large_lds, std::min<long long>(need, 6144));
-      }
-      if (mf) {
-         std::vector<int> h_roots, h_root_off(nblk + 1, 0);
-         for (int b = 0; b < nblk; ++b) {
-            h_roots.insert(h_roots.end(), roots_of[b].begin(), roots_of[b].end());
-            h_root_off[b + 1] = (int)h_roots.size();
-         }
-         n_roots = (int)h_roots.size();
-         h_root_off_keep = h_root_off;
-         if ((rc = d_roots.upload(h_roots)) || (rc = d_root_off.upload(h_root_off))) return rc;
-         // border split: the supernodes whose border rows k_border_schur multiplies out - the fronts, and the simple leaves below a front
-         // (a leaf without a front above it scatters its whole rank-one update itself), ascending; their border rows live a second
-         // time in the border-row arena (per supernode w x rp doubles + w pivots, padded to even), cut into batches of up to BB_GMAX
-         // supernodes / bb_stage doubles that the kernel stages as one contiguous piece
-         std::vector<BbMeta> h_meta;
-         std::vector<BbBatch> h_batch;
-         std::vector<int> h_bbpos;
-         h_bb_off_keep.assign(nblk + 1, 0);
-         bb_stage = 3072; bb_nbmax = 0; bb_poscap = 0;
-         // staging area: as much of the LDS as the packed triangle of the widest border leaves (a batch is one barrier pair and one request
-         // latency whatever it holds; the supernodes of the upper levels take 2000+ doubles each), at most 6144 doubles, at least the largest
-         // single supernode (bb_plan_size)
-         { const BbPlanSize z = bb_plan_size(); bb_stage = z.stage; bb_two_per_cu = z.two_per_cu; }
-         long long bb_total = arena_total;   // the border-row arena lives behind the panels in the same allocation (offsets like SnDesc::panel)
-         for (int b = 0; b < nblk; ++b) {
-            const BlockSym& bs = sym[b];
-            if (bs.mf_split) {
-               bb_nbmax = std::max(bb_nbmax, bs.nb);
-               BbBatch cur{0, 0, 0, 0, 0, 0, 0, 0};
-               auto flush = [&]() { if (cur.cnt > 0) { h_batch.push_back(cur); bb_poscap = std::max(bb_poscap, cur.npos); } cur = BbBatch{0, 0, 0, 0, 0, 0, 0, 0}; };
-               for (int l = 0; l < (int)bs.sn.size(); ++l) {
-                  const HeadSupernode& hs = bs.sn[l];
-                  if (hs.rb >= hs.r || (is_simple(hs) && bs.sn_parent[l] < 0)) continue;
-                  const int nbj = hs.r - hs.rb, rp = (nbj + 3) & ~3, sz = hs.w * rp + ((hs.w + 1) & ~1);
-                  if (cur.cnt == BB_GMAX || cur.ndoubles + sz > bb_stage) flush();
-                  if (cur.cnt == 0) { cur.src = bb_total; cur.pos = (long long)h_bbpos.size(); cur.first = (int)h_meta.size(); }
-                  h_meta.push_back(BbMeta{cur.ndoubles, cur.npos, hs.w, nbj, cur.ntiles, 0, 0, 0});
-                  h_sns[sorted_id[b][l]].bb = bb_total;
-                  for (int a = hs.rb; a < hs.r; ++a) h_bbpos.push_back(bs.rowidx[hs.rows + a] - bs.n);
-                  ++cur.cnt; cur.ndoubles += sz; cur.ntiles += bb_tile_count(rp); cur.npos += nbj;
-                  bb_total += sz;
-               }
-               flush();
-            }
-            h_bb_off_keep[b + 1] = (int)h_batch.size();
-         }
-         n_bb = (int)h_batch.size();
-         if (n_bb > 0) {
-            if ((rc = d_bb_batches.upload(h_batch)) || (rc = d_bb_meta.upload(h_meta)) ||
-                (rc = d_bb_pos.upload(h_bbpos)) || (rc = d_bb_off.upload(h_bb_off_keep))) return rc;
-         }
-         bb_doubles = bb_total - arena_total;
-      }
-      {  // gather-form metadata of the blocks whose fronts hold the rows of K only
-         std::vector<int> h_rec, h_list, h_tail;
-         std::vector<long long> h_off((size_t)std::max(nsn_total, 1), -1);
-         std::vector<std::vector<int>> by_level(levels.size());
-         kb_level_pairs.assign(levels.size(), 0); kb_level_lds.assign(levels.size(), 0);
-         bool any = false;
-         for (int b = 0; b < nblk && mf; ++b) {
-            const BlockSym& bs = sym[b];
-            if (!bs.mf_konly) continue;
-            any = true;
-            for (int l = 0; l < (int)bs.sn.size(); ++l) {
-               if (bs.kb_off[l] < 0) continue;
-               const int* R = bs.kb_rec.data() + bs.kb_off[l];
-               const int np = R[0], ne = R[1];
-               h_off[sorted_id[b][l]] = (long long)h_rec.size();
-               h_rec.push_back(np); h_rec.push_back(ne);
-               for (int q = 0; q < np; ++q) { h_rec.push_back(sorted_id[b][R[2 + 2 * q]]); h_rec.push_back(R[3 + 2 * q]); }
-               h_rec.insert(h_rec.end(), R + 2 + 2 * np, R + 2 + 2 * np + 2 * ne);
-               const HeadSupernode& sj = bs.sn[l];
-               if (sj.level >= (int)by_level.size()) PIPS_FAIL(PIPS_ERR_STATE, "analyze: internal error, level of a front with border rows");
-               by_level[sj.level].push_back(sorted_id[b][l]);
-               kb_level_pairs[sj.level] = std::max(kb_level_pairs[sj.level], np);
-               kb_level_lds[sj.level] = std::max(kb_level_lds[sj.level], (int)(sj.w * ((sj.r - sj.rb + 3) / 4 * 4) * sizeof(double)));
-            }
-            for (size_t q = 0; q + 1 < bs.kb_tail.size(); q += 2) { h_tail.push_back(sorted_id[b][bs.kb_tail[q]]); h_tail.push_back(bs.kb_tail[q + 1]); }
-         }
-         kb_level_off.assign(levels.size() + 1, 0);
-         for (size_t l = 0; l < by_level.size(); ++l) { h_list.insert(h_list.end(), by_level[l].begin(), by_level[l].end()); kb_level_off[l + 1] = (int)h_list.size(); }
-         n_kb_tail = (int)(h_tail.size() / 2);
-         if (any) {
-            if (h_rec.empty()) h_rec.push_back(0);
-            if (h_list.empty()) h_list.push_back(0);
-            if (h_tail.empty()) h_tail.push_back(0);
-            if ((rc = d_kb_rec.upload(h_rec)) || (rc = d_kb_off.upload(h_off)) || (rc = d_kb_list.upload(h_list)) ||
-                (rc = d_kb_tail.upload(h_tail))) return rc;
-         }
-      }
-      // spine lists: per block, ascending local index = postorder (children before parents)
-      std::vector<int> h_spine, h_spine_off(nblk + 1, 0);
-      for (int b = 0; b < nblk; ++b) {
-         for (int l = 0; l < (int)sym[b].sn.size(); ++l)
-            if (sym[b].sn[l].level >= lstar) h_spine.push_back(sorted_id[b][l]);
-         h_spine_off[b + 1] = (int)h_spine.size();
-      }
-      spine_total = (int)h_spine.size();
-      // ---- the tails as one launch (tailkernel.hip.h; the default for batches of up to 16 blocks, slower than the column launches for the
-      // large ones: DESIGN.md 4.2a): multifrontal head (every producer of the tail panel goes by BlkDesc::T_in), no deterministic mode (its slot records hold
-      // panel addresses), room for a second copy of the tail panels
-      {
-         long long scratch = 0;
-         for (int b = 0; b < nblk; ++b) scratch += sym[b].arena - sym[b].T_off;
          size_t free_b = 0, total_b = 0;
          (void)hipMemGetInfo(&free_b, &total_b);
-         const double need = 8.0 * (double)(arena_total + bb_doubles + scratch + uarena_total) + 4e9;
-         // few blocks: the column launches are a chain of ~4 launches per tile column whatever the batch holds, and the one launch wins
-         // (leaf factorisation of configs[1] blocks, profiles/r6_tail_single_by_blocks.txt: 1 block 8.41 -> 7.48 ms, 4: 13.2 -> 12.1,
-         // 8: 19.3 -> 17.8, 16: 31.1 -> 30.4; from 24 blocks on it loses: 43.0 -> 43.7, 32: 54.2 -> 56.4, 64: 101 -> 110).
-         // PIPS_HIP_TAIL_SINGLE=0 / 1 forces one side.
-         const int want_single = env_int("PIPS_HIP_TAIL_SINGLE", nblk <= 16 ? 1 : 0);
-         tail_single = mf && !deterministic && scratch > 0 && want_single != 0 && need < (double)free_b;
-         tail_scratch = tail_single ? scratch : 0;
-         long long at = arena_total + bb_doubles;
-         for (int b = 0; b < nblk; ++b) {
-            h_blks[b].T_in = tail_single ? at : h_blks[b].T;
-            at += sym[b].arena - sym[b].T_off;
-         }
+         knobs.free_device_bytes = (long long)free_b;
       }
-      // ---- concatenated index arrays
-      std::vector<int> h_rowidx, h_sncol, h_bmap, h_perm, h_upd;
-      h_upd.reserve(upd_base[nblk]);
-      std::vector<signed char> h_psign;
-      std::vector<long long> h_psign_off(nblk), h_perm_off(nblk), h_kdst(nnzK_total), h_bdst(nnzB_total), h_kdiag(n_total),
-         h_rowbase(n_total);
-      std::vector<int> h_krowptr(n_total + 1), h_kcolidx(nnzK_total);
-      h_rowidx.reserve(rows_base[nblk]);
-      h_sncol.reserve(sncol);
-      for (int b = 0; b < nblk; ++b) {
-         const BlockSym& s = sym[b];
-         h_rowidx.insert(h_rowidx.end(), s.rowidx.begin(), s.rowidx.end());
-         h_upd.insert(h_upd.end(), s.upd.begin(), s.upd.end());
-         for (int c = 0; c < s.n_head; ++c) h_sncol.push_back(sorted_id[b][s.sn_of_col[c]]);
-         h_bmap.insert(h_bmap.end(), s.bmap.begin(), s.bmap.end());
-         h_psign_off[b] = (long long)h_psign.size();
-         h_psign.insert(h_psign.end(), s.psign.begin(), s.psign.end());
-         h_perm_off[b] = (long long)h_perm.size();
-         h_perm.insert(h_perm.end(), s.perm.begin(), s.perm.end());
-         // multifrontal head: the fronts read their panel entries from the value arrays (k_front), nobody reads them from the arena
-         // (entries of the tail panel land where the tail is assembled: BlkDesc::T_in)
-         auto dst = [&](long long rel) { return rel >= s.T_off ? h_blks[b].T_in + (rel - s.T_off) : h_blks[b].arena_off + rel; };
-         for (size_t p = 0; p < s.a_dst.size(); ++p) h_kdst[kptr[b] + p] = (mf && s.a_front[p]) ? -1 : dst(s.a_dst[p]);
-         for (size_t p = 0; p < s.b_dst.size(); ++p) h_bdst[bptr[b] + p] = (mf && s.b_front[p]) ? -1 : dst(s.b_dst[p]);
-         for (int i = 0; i < s.n; ++i) {
-            long long dp = -1;
-            for (int p = in[b].krow[i]; p < in[b].krow[i + 1]; ++p)
-               if (in[b].kcol[p] == i) dp = kptr[b] + p;
-            if (dp < 0) PIPS_FAIL(PIPS_ERR_ARG, "block %d row %d has no explicit diagonal entry (create_kkt always stores one)", b, i);
-            h_kdiag[x_off[b] + i] = dp;
-            h_rowbase[x_off[b] + i] = x_off[b];
-            h_krowptr[x_off[b] + i] = (int)(kptr[b] + in[b].krow[i]);
-         }
-         std::copy(in[b].kcol.begin(), in[b].kcol.end(), h_kcolidx.begin() + kptr[b]);
+      int rc = analyze_symbolic(in, S, n_threads, opt, knobs, sym);
+      if (rc) return rc;
+      {  // an input error is met here, before the first allocation
+         BatchLayout lay;
+         if ((rc = build_batch_layout(in, sym, S, knobs, lay))) return rc;
+         static_cast<BatchLayout&>(*this) = std::move(lay);
       }
-      h_krowptr[n_total] = (int)nnzK_total;
-      if (mf) {
-         std::vector<int> h_mfint((size_t)mfint_base[nblk]);
-         for (int b = 0; b < nblk; ++b) {
-            const BlockSym& s = sym[b];
-            std::copy(s.mf_int.begin(), s.mf_int.end(), h_mfint.begin() + mfint_base[b]);
-            for (int64_t pos : s.mf_fix) h_mfint[(size_t)(mfint_base[b] + pos)] = sorted_id[b][s.mf_int[(size_t)pos]];
-         }
-         mfU_total = mfU_base[nblk];
-         if ((rc = d_mfint.upload(h_mfint))) return rc;
-         PIPS_TRY(d_mfU.alloc((size_t)std::max<long long>(mfU_total, 1)));
-         PIPS_TRY(d_mfLV.alloc((size_t)std::max<long long>(mfLV_base[nblk], 1)));
-      }
-      {  // both triangles, row by row: entry (i, j) of the lower CSR also appears in row j as (j, i)
-         std::vector<int> frp(n_total + 1, 0);
-         for (int b = 0; b < nblk; ++b)
-            for (int i = 0; i < sym[b].n; ++i)
-               for (int p = in[b].krow[i]; p < in[b].krow[i + 1]; ++p) {
-                  const int j = in[b].kcol[p];
-                  ++frp[x_off[b] + i + 1];
-                  if (j != i) ++frp[x_off[b] + j + 1];
-               }
-         for (long long r = 0; r < n_total; ++r) frp[r + 1] += frp[r];
-         std::vector<int> fcol(frp[n_total]), fsrc(frp[n_total]), fill(frp.begin(), frp.end() - 1);
-         for (int b = 0; b < nblk; ++b)
-            for (int i = 0; i < sym[b].n; ++i)
-               for (int p = in[b].krow[i]; p < in[b].krow[i + 1]; ++p) {
-                  const int j = in[b].kcol[p], src = (int)(kptr[b] + p);
-                  int q = fill[x_off[b] + i]++;
-                  fcol[q] = j; fsrc[q] = src;
-                  if (j != i) { q = fill[x_off[b] + j]++; fcol[q] = i; fsrc[q] = src; }
-               }
-         std::vector<long long> flong;
-         for (long long r = 0; r < n_total; ++r)
-            if (frp[r + 1] - frp[r] > FULL_LONG_ROW) flong.push_back(r);
-         n_flong = (int)flong.size();
-         if ((rc = d_frowptr.upload(frp)) || (rc = d_fcol.upload(fcol)) || (rc = d_fsrc.upload(fsrc)) ||
-             (rc = d_flong.upload(flong)))
-            return rc;
-      }
-      // border CSR, global
-      std::vector<int> h_bt_rowptr, h_bt_colidx(nnzB_total), h_bt_rowsc;
-      std::vector<long long> h_bt_xoff;
-      std::vector<double> h_bval(nnzB_total);
-      h_bt_rowptr.push_back(0);
-      for (int b = 0; b < nblk; ++b) {
-         if (in[b].btrow.empty()) continue;
-         for (int s2 = 0; s2 < S; ++s2) {
-            h_bt_rowptr.push_back((int)(bptr[b] + in[b].btrow[s2 + 1]));
-            h_bt_rowsc.push_back(s2);
-            h_bt_xoff.push_back(x_off[b]);
-         }
-         std::copy(in[b].btcol.begin(), in[b].btcol.end(), h_bt_colidx.begin() + bptr[b]);
-         std::copy(in[b].btval.begin(), in[b].btval.end(), h_bval.begin() + bptr[b]);
-      }
-      bt_rows_total = (long long)h_bt_rowsc.size();
-      h_bt_rowsc_keep = h_bt_rowsc;
-      h_bt_rownnz_keep.assign((size_t)bt_rows_total, 0);
-      for (long long i = 0; i < bt_rows_total; ++i) h_bt_rownnz_keep[(size_t)i] = h_bt_rowptr[i + 1] - h_bt_rowptr[i];
-      h_bt_rowblk_keep.clear();
-      for (int b = 0; b < nblk; ++b)
-         if (!in[b].btrow.empty()) h_bt_rowblk_keep.insert(h_bt_rowblk_keep.end(), (size_t)S, b);
-      if (deterministic && bt_rows_total > 0) {   // gather lists of the border products (see k_border_rowdot)
-         std::vector<SlotEntry> by_sc, by_entry;
-         for (long long i = 0; i < bt_rows_total; ++i) {
-            if (h_bt_rowptr[i + 1] > h_bt_rowptr[i]) by_sc.push_back({(long long)h_bt_rowsc[i], i});
-            for (int q = h_bt_rowptr[i]; q < h_bt_rowptr[i + 1]; ++q) by_entry.push_back({h_bt_xoff[i] + h_bt_colidx[q], (long long)q});
-         }
-         g_btm = GatherList(); g_bm = GatherList();
-         if ((rc = upload_gather(by_sc, g_btm)) || (rc = upload_gather(by_entry, g_bm))) return rc;
-         PIPS_TRY(d_bt_tmp.alloc((size_t)std::max<long long>(std::max(bt_rows_total, nnzB_total), 1)));
-      }
-      {  // non-empty Schur columns over all blocks (the reference skips empty border columns, :870-874)
-         std::vector<char> used(std::max(S, 1), 0);
-         for (int b = 0; b < nblk; ++b)
-            if (!in[b].btrow.empty())
-               for (int s2 = 0; s2 < S; ++s2)
-                  if (in[b].btrow[s2 + 1] > in[b].btrow[s2]) used[s2] = 1;
-         schur_cols.clear();
-         std::vector<int> slot(std::max(S, 1), -1);
-         for (int s2 = 0; s2 < S; ++s2)
-            if (used[s2]) { slot[s2] = (int)schur_cols.size(); schur_cols.push_back(s2); }
-         if ((rc = d_schur_cols.upload(schur_cols))) return rc;
-         if ((rc = d_schur_slot.upload(slot))) return rc;
-      }
-
-      // ---- device allocation / upload
-      PIPS_TRY(d_arena.alloc(std::max<long long>(arena_total + bb_doubles + tail_scratch, 1)));
-      if (tail_single) HIP_TRY(hipMemsetAsync(d_arena, 0, (size_t)arena_total * sizeof(double), stream));   // (tiles of the panels outside the envelopes are never written: they read as zero)
-      if (bb_doubles > 0) HIP_TRY(hipMemsetAsync(d_arena + arena_total, 0, (size_t)bb_doubles * sizeof(double), stream));   // (the padding rows of the border-row arena stay zero)
-      PIPS_TRY(d_uarena.alloc(std::max<long long>(uarena_total, 1)));
-      PIPS_TRY(d_kval.alloc(std::max<long long>(nnzK_total, 1)));
-      HIP_TRY(hipMemset(d_kval, 0, std::max<long long>(nnzK_total, 1) * sizeof(double)));
-      PIPS_TRY(d_winv.alloc(std::max<long long>(winv, 1)));
-      PIPS_TRY(d_dtail.alloc(std::max<long long>(dt, 1)));
-      PIPS_TRY(d_xw.alloc(std::max<long long>(xw_total, 1)));
-      PIPS_TRY(d_pref.alloc(std::max<long long>(xw_total, 1)));
-      PIPS_TRY(d_rhs.alloc(std::max<long long>(n_total, 1)));
-      PIPS_TRY(d_res.alloc(std::max<long long>(n_total, 1)));
-      PIPS_TRY(d_stage.alloc(std::max<long long>(n_total, 1)));
-      PIPS_TRY(d_norms.alloc((size_t)3 * nblk));
-      PIPS_TRY(h_norms.alloc((size_t)3 * nblk));
-      PIPS_TRY(d_inertia.alloc((size_t)3 * nblk));
-      HIP_TRY(hipMemset(d_inertia, 0, (size_t)3 * nblk * sizeof(int)));
-      if ((rc = d_bval.upload(h_bval))) return rc;
-      if ((rc = d_kdst.upload(h_kdst))) return rc;
-      if ((rc = d_bdst.upload(h_bdst))) return rc;
-      if ((rc = d_kdiag.upload(h_kdiag))) return rc;
-      if ((rc = d_kptr.upload(kptr))) return rc;
-      if ((rc = d_psign_off.upload(h_psign_off))) return rc;
-      if ((rc = d_perm_off.upload(h_perm_off))) return rc;
-      if ((rc = d_rowbase.upload(h_rowbase))) return rc;
-      if ((rc = d_bt_xoff.upload(h_bt_xoff))) return rc;
-      if ((rc = d_sns.upload(h_sns))) return rc;
-      if ((rc = d_blks.upload(h_blks))) return rc;
-      if ((rc = d_rowidx.upload(h_rowidx))) return rc;
-      {  // simple leaves that own border rows (sweeps of the augmented factor: k_leaf_border), and the widest padded border
-         std::vector<int> lb;
-         if (!levels.empty())
-            for (int i = levels[0].simple_begin; i < levels[0].simple_begin + levels[0].simple_cnt; ++i)
-               if (h_sns[i].rb < h_sns[i].r) lb.push_back(i);
-         n_lb = (int)lb.size();
-         if (n_lb > 0 && (rc = d_lb_list.upload(lb))) return rc;
-         nb_pad_max = 0;
-         for (int b = 0; b < nblk; ++b) nb_pad_max = std::max(nb_pad_max, h_blks[b].nb_pad);
-      }
-      // ---- the simple leaves' L entries by target row (forward substitution as a gather, see d_lf_rows)
-      {
-         const LevelRange* L0 = levels.empty() ? nullptr : &levels[0];
-         if (L0 && L0->simple_cnt > 0 && xw_total < (1LL << 31) && h_rowidx.size() < (1ull << 31)) {
-            std::vector<LeafDesc> h_leaf((size_t)L0->simple_cnt);
-            for (int i = 0; i < L0->simple_cnt; ++i) {
-               const SnDesc& sn = h_sns[L0->simple_begin + i];
-               const BlkDesc& bd = h_blks[sn.blk];
-               int r_in = 0;
-               while (r_in < sn.r && h_rowidx[sn.rows + r_in] < bd.n) ++r_in;
-               h_leaf[i] = LeafDesc{sn.panel, (int)sn.rows, (int)bd.xw_off, sn.c0, r_in};
-            }
-            if ((rc = d_leafdesc.upload(h_leaf))) return rc;
-            std::vector<int> cnt((size_t)xw_total + 1, 0);
-            long long nent = 0;
-            for (int i = L0->simple_begin; i < L0->simple_begin + L0->simple_cnt; ++i) {
-               const SnDesc& sn = h_sns[i];
-               const BlkDesc& bd = h_blks[sn.blk];
-               for (int a = 0; a < sn.r; ++a) {
-                  const int ra = h_rowidx[sn.rows + a];
-                  if (ra >= bd.n) break;
-                  ++cnt[bd.xw_off + ra];
-                  ++nent;
-               }
-            }
-            if (nent > 0 && nent < (1LL << 31)) {
-               std::vector<int> h_rows, h_ptr(1, 0), h_src((size_t)nent), h_pos(h_rowidx.size(), -1);
-               std::vector<int> slot((size_t)xw_total, -1);   // target row -> its index in the compact list
-               for (long long t = 0; t < xw_total; ++t)
-                  if (cnt[t] > 0) { slot[t] = (int)h_rows.size(); h_rows.push_back((int)t); h_ptr.push_back(h_ptr.back() + cnt[t]); }
-               std::vector<int> fill(h_ptr.begin(), h_ptr.end() - 1);
-               for (int i = L0->simple_begin; i < L0->simple_begin + L0->simple_cnt; ++i) {   // ascending leaves: the order of every sum
-                  const SnDesc& sn = h_sns[i];
-                  const BlkDesc& bd = h_blks[sn.blk];
-                  for (int a = 0; a < sn.r; ++a) {
-                     const int ra = h_rowidx[sn.rows + a];
-                     if (ra >= bd.n) break;
-                     const int q = fill[slot[bd.xw_off + ra]]++;
-                     h_src[q] = (int)(bd.xw_off + sn.c0);
-                     h_pos[sn.rows + a] = q;
-                  }
-               }
-               lf_rows = (long long)h_rows.size(); lf_entries = nent;
-               if ((rc = d_lf_rows.upload(h_rows))) return rc;
-               if ((rc = d_lf_ptr.upload(h_ptr))) return rc;
-               if ((rc = d_lf_src.upload(h_src))) return rc;
-               if ((rc = d_lf_pos.upload(h_pos))) return rc;
-               PIPS_TRY(d_lf_val.alloc((size_t)nent));
-            }
-         }
-      }
-      if ((rc = d_upd.upload(h_upd))) return rc;
-      if ((rc = d_spine.upload(h_spine))) return rc;
-      if ((rc = d_spine_off.upload(h_spine_off))) return rc;
-      if ((rc = d_sncol.upload(h_sncol))) return rc;
-      if ((rc = d_bmap.upload(h_bmap))) return rc;
-      if ((rc = d_perm.upload(h_perm))) return rc;
-      if ((rc = d_psign.upload(h_psign))) return rc;
-      if ((rc = d_krowptr.upload(h_krowptr))) return rc;
-      if ((rc = d_kcolidx.upload(h_kcolidx))) return rc;
-      if ((rc = d_bt_rowptr.upload(h_bt_rowptr))) return rc;
-      if ((rc = d_bt_colidx.upload(h_bt_colidx))) return rc;
-      if ((rc = d_bt_rowsc.upload(h_bt_rowsc))) return rc;
-      // ---- the border by LEAF row (t += alpha Br x0 as a gather, k_border_mult_rows): row pointers over the flat leaf space, Schur
-      //      column and position in d_bval of every entry
-      if (bt_rows_total > 0 && nnzB_total > 0 && nnzB_total < (1LL << 31)) {
-         std::vector<int> rp((size_t)n_total + 1, 0);
-         for (long long r = 0; r < bt_rows_total; ++r)
-            for (int p = h_bt_rowptr[r]; p < h_bt_rowptr[r + 1]; ++p) ++rp[h_bt_xoff[r] + h_bt_colidx[p] + 1];
-         for (long long i = 0; i < n_total; ++i) rp[i + 1] += rp[i];
-         std::vector<int> sc((size_t)nnzB_total), src((size_t)nnzB_total), fill(rp.begin(), rp.end() - 1);
-         for (long long r = 0; r < bt_rows_total; ++r)   // ascending (block, Schur column): the order of every row's sum
-            for (int p = h_bt_rowptr[r]; p < h_bt_rowptr[r + 1]; ++p) {
-               const int q = fill[h_bt_xoff[r] + h_bt_colidx[p]]++;
-               sc[q] = h_bt_rowsc[r]; src[q] = p;
-            }
-         if ((rc = d_br_rowptr.upload(rp)) || (rc = d_br_sc.upload(sc)) || (rc = d_br_src.upload(src)))
-            return rc;
-      }
-      {
-         std::vector<int> np(nblk);
-         for (int b = 0; b < nblk; ++b) np[b] = in[b].n_primal;
-         if ((rc = d_nprimal.upload(np))) return rc;
-      }
+      if ((rc = upload_layout())) return rc;
       // the diagonal tile of a column runs ahead on the side stream, its update first; tile rows start at their envelope (variants of the
       // tail factorisation without either: docs/HISTORY_r1_r2.md)
-      std::vector<const std::vector<int>*> firsts(nblk);
-      for (int b = 0; b < nblk; ++b) firsts[b] = &sym[b].tile_first;
       // tile columns per launch of the left-looking tail update (TailPlan::build, pair2).  configs[1], ms per unit / ms of update, two boxes:
       // 1 column 125.0 - 126.8 / 73.8 - 74.7; 2: 123.6 - 124.0 / 72.4; 3: 122.0 / 70.8; 4: 120.0 - 121.7 / 70.3 - 71.0; 6: 120.5 / 70.3; 8: 120.8 / 70.9
       const int pair2 = 4;   // (1: a column per launch; the switch that chose it went with round 6)
-      if ((rc = plan.build(h_blks, 0, false, true, &firsts, true, pair2))) return rc;
-      if ((rc = sweep.build(h_blks, &firsts))) return rc;
+      if ((rc = plan.build(h_blks, 0, false, true, &tile_first, true, pair2))) return rc;
+      if ((rc = sweep.build(h_blks, &tile_first))) return rc;
       if (tail_single) {
          if ((rc = tsingle.build(plan, h_blks, stream))) return rc;
-         tsingle.args.poll_limit = env_int("PIPS_HIP_ROOT_POLL_LIMIT", 400000) > 0 ? (long long)env_int("PIPS_HIP_ROOT_POLL_LIMIT", 400000) * 50 : 0;   // (a deep update runs a millisecond)
-         tsingle.args.diag_blocked = env_int("PIPS_HIP_ROOT_DIAG_BARRIERS", 0) ? 0 : 1;
+         tsingle.args.poll_limit = knobs.tail_poll_limit;
+         tsingle.args.diag_blocked = knobs.tail_diag_blocked;
       }
-      {
-         // border-backward sweep: worth it where the border rows of the factor (what it reads on top of a backward sweep) are no
-         // more than what the forward sweep it saves would read, with a margin for the chain and the launches it also saves
-         double fwd_entries = 0.0, border_entries = 0.0;
-         for (int b = 0; b < nblk; ++b) {
-            const BlockSym& sb = sym[b];
-            fwd_entries += 0.5 * (double)sb.m_pad * sb.m_pad;
-            border_entries += (double)sb.nb_pad * sb.m_pad;
-            for (const HeadSupernode& sn : sb.sn) {
-               const int nbord = sn.r - sn.rb;
-               fwd_entries += (double)sn.w * (sn.r - nbord) + 0.5 * sn.w * sn.w;
-               border_entries += (double)sn.w * nbord;
-            }
-         }
-         // (round 4: 3 x instead of 1.25 x - with compact front panels and the border-row arena the sweep reads the border rows as one piece per supernode;
-         //  on the configs[3] share, ratio 1.23, the witness pass of a factorisation drops from two refined solves to one + this sweep)
-         border_backward_ok = schur_mode_eff == 1 && nnzB_total > 0 && (sweep.enabled || plan.ntc_max == 0) && !deterministic && border_entries <= 3.0 * fwd_entries;
-         if (const char* bb = getenv("PIPS_HIP_BORDER_BACKWARD"))
-            border_backward_ok = atoi(bb) != 0 && schur_mode_eff == 1 && nnzB_total > 0 && sweep.enabled && !deterministic;
-         // Both halves of solveCompressed from the augmented factor (forward_augmented / backward_augmented): one forward and one backward
-         // sweep that also read the border rows, instead of two full solves (two sweeps each, a residual check each, two border
-         // products) - pays as long as the border rows are not several times what a sweep reads anyway
-         const bool aug_paths = schur_mode_eff == 1 && nnzB_total > 0 && (sweep.enabled || plan.ntc_max == 0) && spine_total == 0 &&
-                                (deterministic || !head_slots);   // (deterministic mode: forward_augmented_det, if set_det_groups can build its lists)
-         aug_sweeps_ok = aug_paths && border_entries <= 3.0 * fwd_entries;
-         if (const char* as = getenv("PIPS_HIP_AUG_SWEEPS")) aug_sweeps_ok = atoi(as) != 0 && aug_paths;
-      }
+      drop_uploaded();
       if (!side) {
          // highest priority: the few workgroups of the diagonal chain must not queue behind the thousands of the column update
          int prio_lo = 0, prio_hi = 0;
@@ -1820,23 +1101,117 @@ struct Engine : EngineAnalysis {
          HIP_TRY(hipEventCreateWithFlags(&ev_diag_out, hipEventDisableTiming));
       }
       h_inertia.assign(3 * nblk, 0);
-      slots_total = slots_acc; vslots_total = vslots_acc;
-      h_sns_keep = h_sns;
       analyzed = true;
       ++analysis_gen;
-      factored = false;
-      head_slots = false;
-      const bool want_slots = deterministic;
-      if (want_slots && slots_total + vslots_total <= HEAD_SLOTS_MAX) {
+      if (deterministic) {
+         if (slots_total + vslots_total > HEAD_SLOTS_MAX)
+            PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode: %lld head contributions exceed the slot budget of %lld", slots_total + vslots_total, HEAD_SLOTS_MAX);
          if ((rc = build_deterministic(n_threads))) return rc;
          head_slots = true;
-      } else if (deterministic)
-         PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode: %lld head contributions exceed the slot budget of %lld", slots_total + vslots_total, HEAD_SLOTS_MAX);
-      if (deterministic && (rc = set_det_groups(0, 1))) return rc;
+         if ((rc = set_det_groups(0, 1))) return rc;
+      }
       return PIPS_OK;
    }
 
-   std::vector<SnDesc> h_sns_keep;
+   // Allocation and upload of an analysis: one line per buffer, from the layout's arrays.  (The order is the one the allocations always
+   // had: the addresses of the arenas, and with them the timings, stay what they were.)
+   int upload_layout() {
+      if (mf) {
+         PIPS_TRY(d_roots.upload(h_roots));
+         PIPS_TRY(d_root_off.upload(h_root_off));
+      }
+      if (n_bb > 0) {   // border split
+         PIPS_TRY(d_bb_batches.upload(h_bb_batches));
+         PIPS_TRY(d_bb_meta.upload(h_bb_meta));
+         PIPS_TRY(d_bb_pos.upload(h_bb_pos));
+         PIPS_TRY(d_bb_off.upload(h_bb_off));
+      }
+      if (kb_any) {   // fronts on the rows of K only
+         PIPS_TRY(d_kb_rec.upload(h_kb_rec));
+         PIPS_TRY(d_kb_off.upload(h_kb_off));
+         PIPS_TRY(d_kb_list.upload(h_kb_list));
+         PIPS_TRY(d_kb_tail.upload(h_kb_tail));
+      }
+      if (mf) {
+         PIPS_TRY(d_mfint.upload(h_mfint));
+         PIPS_TRY(d_mfU.alloc((size_t)std::max<long long>(mfU_total, 1)));
+         PIPS_TRY(d_mfLV.alloc((size_t)std::max<long long>(mfLV_total, 1)));
+      }
+      PIPS_TRY(d_frowptr.upload(h_frowptr));
+      PIPS_TRY(d_fcol.upload(h_fcol));
+      PIPS_TRY(d_fsrc.upload(h_fsrc));
+      PIPS_TRY(d_flong.upload(h_flong));
+      if (deterministic && bt_rows_total > 0) {   // gather lists of the border products (see k_border_rowdot)
+         std::vector<SlotEntry> by_sc, by_entry;
+         for (long long i = 0; i < bt_rows_total; ++i) {
+            if (h_bt_rowptr[i + 1] > h_bt_rowptr[i]) by_sc.push_back({(long long)h_bt_rowsc[i], i});
+            for (int q = h_bt_rowptr[i]; q < h_bt_rowptr[i + 1]; ++q) by_entry.push_back({h_bt_xoff[i] + h_bt_colidx[q], (long long)q});
+         }
+         PIPS_TRY(upload_gather(by_sc, g_btm));
+         PIPS_TRY(upload_gather(by_entry, g_bm));
+         PIPS_TRY(d_bt_tmp.alloc((size_t)std::max<long long>(std::max(bt_rows_total, nnzB_total), 1)));
+      }
+      PIPS_TRY(d_schur_cols.upload(schur_cols));
+      PIPS_TRY(d_schur_slot.upload(h_schur_slot));
+      PIPS_TRY(d_arena.alloc(std::max<long long>(arena_total + bb_doubles + tail_scratch, 1)));
+      if (tail_single) HIP_TRY(hipMemsetAsync(d_arena, 0, (size_t)arena_total * sizeof(double), stream));   // (tiles of the panels outside the envelopes are never written: they read as zero)
+      if (bb_doubles > 0) HIP_TRY(hipMemsetAsync(d_arena + arena_total, 0, (size_t)bb_doubles * sizeof(double), stream));   // (the padding rows of the border-row arena stay zero)
+      PIPS_TRY(d_uarena.alloc(std::max<long long>(uarena_total, 1)));
+      PIPS_TRY(d_kval.alloc(std::max<long long>(nnzK_total, 1)));
+      HIP_TRY(hipMemset(d_kval, 0, std::max<long long>(nnzK_total, 1) * sizeof(double)));
+      PIPS_TRY(d_winv.alloc(std::max<long long>(winv_total, 1)));
+      PIPS_TRY(d_dtail.alloc(std::max<long long>(dtail_total, 1)));
+      PIPS_TRY(d_xw.alloc(std::max<long long>(xw_total, 1)));
+      PIPS_TRY(d_pref.alloc(std::max<long long>(xw_total, 1)));
+      PIPS_TRY(d_rhs.alloc(std::max<long long>(n_total, 1)));
+      PIPS_TRY(d_res.alloc(std::max<long long>(n_total, 1)));
+      PIPS_TRY(d_stage.alloc(std::max<long long>(n_total, 1)));
+      PIPS_TRY(d_norms.alloc((size_t)3 * nblk));
+      PIPS_TRY(h_norms.alloc((size_t)3 * nblk));
+      PIPS_TRY(d_inertia.alloc((size_t)3 * nblk));
+      HIP_TRY(hipMemset(d_inertia, 0, (size_t)3 * nblk * sizeof(int)));
+      PIPS_TRY(d_bval.upload(h_bval));
+      PIPS_TRY(d_kdst.upload(h_kdst));
+      PIPS_TRY(d_bdst.upload(h_bdst));
+      PIPS_TRY(d_kdiag.upload(h_kdiag));
+      PIPS_TRY(d_kptr.upload(kptr));
+      PIPS_TRY(d_psign_off.upload(h_psign_off));
+      PIPS_TRY(d_perm_off.upload(h_perm_off));
+      PIPS_TRY(d_rowbase.upload(h_rowbase));
+      PIPS_TRY(d_bt_xoff.upload(h_bt_xoff));
+      PIPS_TRY(d_sns.upload(h_sns));
+      PIPS_TRY(d_blks.upload(h_blks));
+      PIPS_TRY(d_rowidx.upload(h_rowidx));
+      if (n_lb > 0) PIPS_TRY(d_lb_list.upload(h_lb_list));
+      if (!h_leafdesc.empty()) PIPS_TRY(d_leafdesc.upload(h_leafdesc));
+      if (lf_entries > 0) {   // the simple leaves' forward substitution as a gather
+         PIPS_TRY(d_lf_rows.upload(h_lf_rows));
+         PIPS_TRY(d_lf_ptr.upload(h_lf_ptr));
+         PIPS_TRY(d_lf_src.upload(h_lf_src));
+         PIPS_TRY(d_lf_pos.upload(h_lf_pos));
+         PIPS_TRY(d_lf_val.alloc((size_t)lf_entries));
+      }
+      PIPS_TRY(d_upd.upload(h_upd));
+      PIPS_TRY(d_spine.upload(h_spine));
+      PIPS_TRY(d_spine_off.upload(h_spine_off));
+      PIPS_TRY(d_sncol.upload(h_sncol));
+      PIPS_TRY(d_bmap.upload(h_bmap));
+      PIPS_TRY(d_perm.upload(h_perm));
+      PIPS_TRY(d_psign.upload(h_psign));
+      PIPS_TRY(d_krowptr.upload(h_krowptr));
+      PIPS_TRY(d_kcolidx.upload(h_kcolidx));
+      PIPS_TRY(d_bt_rowptr.upload(h_bt_rowptr));
+      PIPS_TRY(d_bt_colidx.upload(h_bt_colidx));
+      PIPS_TRY(d_bt_rowsc.upload(h_bt_rowsc));
+      if (!h_br_rowptr.empty()) {   // the border by leaf row (k_border_mult_rows)
+         PIPS_TRY(d_br_rowptr.upload(h_br_rowptr));
+         PIPS_TRY(d_br_sc.upload(h_br_sc));
+         PIPS_TRY(d_br_src.upload(h_br_src));
+      }
+      PIPS_TRY(d_nprimal.upload(h_nprimal));
+      return PIPS_OK;
+   }
+
    ScatterCtx sx_atomic() const { return ScatterCtx{0, nullptr, nullptr, nullptr, nullptr}; }
    void launch_head_level(const LevelRange& L, double* SC, int ldSC, const ScatterCtx& sx) {
       if (L.simple_cnt > 0)
@@ -1861,52 +1236,6 @@ struct Engine : EngineAnalysis {
                          d_psign_off, d_bmap, d_arena, d_mfU, SC, ldSC, d_inertia, d_pref, d_sctab, d_mfdbg, d_mfLV, d_kval, d_bval, deterministic ? 1 : 0, d_arena);
       return PIPS_OK;
    }
-   // ---- k_border_schur's LDS need, from the symbolic analysis alone (the same rules as the batching loop of analyze()): staging area,
-   //      most row positions of a batch, widest border.  Evaluated at analyze time: a block set whose border rows do not fit (nb near 176
-   //      under wide fronts that are nearly all border rows) goes back to whole update matrices there instead of failing in every factor()
-   struct BbPlanSize { int stage = 3072, poscap = 0, nbmax = 0; bool two_per_cu = false; };
-   BbPlanSize bb_plan_size() const {
-      BbPlanSize z;
-      for (int b = 0; b < nblk; ++b) if (sym[b].mf_split) z.nbmax = std::max(z.nbmax, sym[b].nb);
-      const long long tri = ((long long)z.nbmax * (z.nbmax + 1) / 2 + 1) & ~1LL;
-      const long long room = 19200 - tri - 4 * 512 / 2 - 64;   // (positions: up to 4 * 512 ints; supernode records)
-      z.stage = (int)std::max<long long>(3072, std::min<long long>(6144, room)) & ~1;
-      // two workgroups on a compute unit where half the LDS leaves a staging area of 3072 doubles or more: the walk is a chain of
-      // barriers and request latencies per batch, a second workgroup fills them (configs[3] shape, nb = 103: k_border_schur 3.3 -> 2.1 ms
-      // with 3072 - 4096 doubles and two workgroups per block; 2048 doubles and two or three: 2.7 - 3.2 ms)
-      const long long room2 = 9600 - tri - 4 * 512 / 2 - 64;
-      if (room2 >= 3072) { z.stage = (int)std::min<long long>(4096, room2) & ~1; z.two_per_cu = true; }
-      for (int b = 0; b < nblk; ++b) {
-         const BlockSym& bs = sym[b];
-         if (!bs.mf_split) continue;
-         for (const HeadSupernode& hs : bs.sn)
-            if (hs.rb < hs.r) {
-               const int need = hs.w * ((hs.r - hs.rb + 3) / 4 * 4) + ((hs.w + 1) & ~1);
-               if (need > z.stage) { z.stage = need; z.two_per_cu = false; }   // (a supernode beyond the half-LDS area: back to one workgroup's rule)
-            }
-      }
-      if (!z.two_per_cu) z.stage = std::max<int>(z.stage, (int)std::max<long long>(3072, std::min<long long>(6144, room)) & ~1);
-      for (int b = 0; b < nblk; ++b) {
-         const BlockSym& bs = sym[b];
-         if (!bs.mf_split) continue;
-         int cnt = 0, nd = 0, np = 0;
-         for (int l = 0; l < (int)bs.sn.size(); ++l) {
-            const HeadSupernode& hs = bs.sn[l];
-            const bool simple = hs.w == 1 && hs.r <= SIMPLE_RMAX && hs.level == 0;    // (analyze()'s is_simple)
-            if (hs.rb >= hs.r || (simple && bs.sn_parent[l] < 0)) continue;
-            const int nbj = hs.r - hs.rb, rp = (nbj + 3) & ~3, sz = hs.w * rp + ((hs.w + 1) & ~1);
-            if (cnt == BB_GMAX || nd + sz > z.stage) { z.poscap = std::max(z.poscap, np); cnt = nd = np = 0; }
-            ++cnt; nd += sz; np += nbj;
-         }
-         z.poscap = std::max(z.poscap, np);
-      }
-      return z;
-   }
-   static size_t bb_lds_bytes(const BbPlanSize& z) {
-      const long long ncp = ((long long)z.nbmax * (z.nbmax + 1) / 2 + 1) & ~1LL;
-      return (size_t)(ncp + z.stage) * sizeof(double) + (size_t)((z.poscap + 3) & ~3) * sizeof(int) + BB_GMAX * sizeof(BbMeta);
-   }
-   static bool bb_fits(const BbPlanSize& z) { return bb_lds_bytes(z) <= 160 * 1024 && z.poscap <= 4 * 512 && z.stage <= 2 * 6 * 512; }
    int launch_border_schur(double* SC, int ldSC) {
       // LDS: packed nb x nb triangle + one staged batch + its rows' positions + the batch's supernode records
       constexpr int BLK = 512;
@@ -1957,7 +1286,7 @@ struct Engine : EngineAnalysis {
          double ph[8] = {0}; long long nfs = 0, ws = 0;
          for (int i = m.begin; i < m.begin + m.cnt; ++i) {
             for (int q = 0; q < 7; ++q) ph[q] += (double)(h[(size_t)i * 8 + q + 1] - h[(size_t)i * 8 + q]);
-            nfs += h_sns_keep[i].w + h_sns_keep[i].r; ws += h_sns_keep[i].w;
+            nfs += h_sns[i].w + h_sns[i].r; ws += h_sns[i].w;
          }
          fprintf(stderr, "[mf clocks] level %2d variant %d fronts %6d lds %6d  avg nf %5.1f w %4.1f | ", m.level, m.cls, m.cnt, m.lds_doubles * 8, (double)nfs / m.cnt, (double)ws / m.cnt);
          for (int q = 0; q < 7; ++q) fprintf(stderr, "%s %.1f%s", names[q], ph[q] / m.cnt * 0.01, q == 6 ? " us\n" : ", ");
@@ -2046,7 +1375,7 @@ struct Engine : EngineAnalysis {
          std::sort(panel_level[b].begin(), panel_level[b].end());
       }
       for (int i = 0; i < nsn_total; ++i) {
-         const SnDesc& sn = h_sns_keep[i];
+         const SnDesc& sn = h_sns[i];
          if (mf && !(sn.mf < 0 && sn.n_useg == 0)) continue;   // multifrontal head: only the leaves without a front above them own slots
          const long long cnt = (long long)sn.r * (sn.r + 1) / 2;
          const BlkDesc& bd = h_blks[sn.blk];
@@ -2091,7 +1420,7 @@ struct Engine : EngineAnalysis {
          std::vector<std::vector<SlotEntry>> v_level(nlev);
          std::vector<SlotEntry> v_tail;
          for (int i = 0; i < nsn_total; ++i) {
-            const SnDesc& sn = h_sns_keep[i];
+            const SnDesc& sn = h_sns[i];
             const BlkDesc& bd = h_blks[sn.blk];
             for (int a = 0; a < sn.r; ++a) {
                const long long t = vrec[(size_t)(sn.vslot + a)];
@@ -2732,8 +2061,6 @@ struct Engine : EngineAnalysis {
    // border product, no forward sweep, no diagonal scaling.  Pays where the border rows of the factor are no larger than what a
    // forward sweep reads (decided at analyze time, border_backward_ok); needs Schur mode 1 and the single-launch tail sweeps.
    // There is no refinement in it: the caller uses it only while the factorisation has no perturbed pivot (perturbed_leaf_pivots).
-   bool border_backward_ok = false;
-   bool aug_sweeps_ok = false;   // solveCompressed by one forward + one backward sweep of the augmented factor (decided at analyze time)
    long long aug_passes = 0;     // passes (forward + backward) of those sweeps so far
    int perturbed_cache = -1;   // perturbed pivots of the current factorisation over all blocks; -1 = not fetched yet
    int perturbed_leaf_pivots(int* out) {
@@ -2832,6 +2159,7 @@ struct Engine : EngineAnalysis {
    // ... and the backward sweep from where forward_augmented stopped: border slots = x0, x = L^-T (D^-1 y - L_b^T x0) = K^-1 (b - Br x0)
    // in original order at out_dev (Ltsolve, sLinsysRootAug.C:346-365 / LniTransMult, with nothing left to combine)
    int backward_augmented(const double* x0_dev, double* out_dev) {
+      if (!factored) PIPS_FAIL(PIPS_ERR_STATE, "solve called before factor");
       HIP_TRY(hipSetDevice(device));
       timer.begin(stream, 10);
       hipLaunchKernelGGL(k_border_fill, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, x0_dev, d_xw, 1.0);
@@ -2888,6 +2216,44 @@ struct Engine : EngineAnalysis {
       return PIPS_OK;
    }
 };
+
+// Every switch an analysis depends on, read in one place at every analyze() call (tests set them before
+// analysing).  e == nullptr: the CPU probes - no engine settings, no deterministic mode.
+static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs& knobs) {
+   // Tile geometry + the cost-model / amalgamation knobs (environment overrides are for tuning runs only).
+   opt.tile = TILE;
+   // Supernode width cap.  16 instead of the kernels' limit of 32: on the time-coupled family (tools/config3_probe.py, 64 x 50 000)
+   // narrower supernodes carry fewer explicit zeros (nnz(L) 164 M -> 151 M), halve the dependent pivot chain of a front and the
+   // registers its rows take; factorisation 13.4 -> 12.5 ms, solveCompressed 9.3 -> 8.9 ms.  Random sparsity (config 2) has no
+   // supernodes wider than one column in the head.
+   opt.max_sn_width = 16;
+   if (const char* sw = getenv("PIPS_HIP_SN_WIDTH")) opt.max_sn_width = std::max(1, std::min(HEAD_WMAX, atoi(sw)));
+   else if (e && e->sn_width > 0) opt.max_sn_width = std::min(HEAD_WMAX, e->sn_width);
+   if (const char* rz = getenv("PIPS_HIP_RELAX_ZEROS")) opt.relax_zeros = atof(rz);   // share of explicit zeros per panel
+   if (const char* ndd = getenv("PIPS_HIP_ND_DEPTH")) opt.nd_depth = atoi(ndd);        // dissection levels (0 = off)
+   if (const char* ndm = getenv("PIPS_HIP_ND_MIN")) opt.nd_min_size = atoi(ndm);      // smallest segment that is still dissected
+   if (const char* ml = getenv("PIPS_HIP_MF_LDS")) opt.mf_lds_doubles = atoll(ml);   // LDS budget of a front in doubles (tests: small values force the device-memory variant)
+   if (const char* sp = getenv("PIPS_HIP_MF_SPLIT")) opt.mf_split_nb_max = atoi(sp) == 0 ? 0 : std::min(176, std::max(atoi(sp), 2));   // border split: 0 = off, else the largest nb
+   knobs.deterministic = e && e->deterministic;
+   knobs.schur_mode = e ? e->schur_mode : 0;
+   knobs.mf_lds_doubles = opt.mf_lds_doubles;
+   knobs.mf_wanted = env_int("PIPS_HIP_MF", 1) != 0;
+   if (!knobs.mf_wanted) opt.mf_split_nb_max = 0;   // the border split (compact front panels) only exists with the multifrontal head
+   // fronts on the rows of K only where the border split applies (value 1; off by default: on the configs[3] share the fronts fall
+   // from 9.7 to 4.0 ms, forming the border rows afterwards costs 8.0 - DESIGN.md 4.1c): not in deterministic mode (the border rows of the dense
+   // tail take their head contributions with atomics, k_border_tail) and with supernodes of at most 16 columns (k_border_rows<., 16>)
+   opt.mf_konly = opt.mf_split_nb_max > 0 && !knobs.deterministic && opt.max_sn_width <= 16 && env_int("PIPS_HIP_MF_KONLY", 0) != 0;
+   knobs.spine = env_flag("PIPS_HIP_SPINE");                      // 0: no spine kernels
+   knobs.tail_single = env_flag("PIPS_HIP_TAIL_SINGLE");          // 0 / 1 forces one side (default: batches of up to 16 blocks)
+   knobs.border_backward = env_flag("PIPS_HIP_BORDER_BACKWARD");  // 0 / 1 instead of the cost rule of the border-backward sweep
+   knobs.aug_sweeps = env_flag("PIPS_HIP_AUG_SWEEPS");            // 0 / 1 instead of the cost rule of the sweeps of the augmented factor
+   knobs.dump_levels = getenv("PIPS_HIP_DUMP_LEVELS") != nullptr;    // development aid: shape of the head, level by level
+   knobs.sweep_launches = getenv("PIPS_HIP_SWEEP_LAUNCHES") != nullptr;   // (SweepRt::build: the single-launch sweeps are off)
+   const int poll = env_int("PIPS_HIP_ROOT_POLL_LIMIT", 400000);
+   knobs.tail_poll_limit = poll > 0 ? (long long)poll * 50 : 0;   // (a deep update runs a millisecond)
+   knobs.tail_diag_blocked = env_int("PIPS_HIP_ROOT_DIAG_BARRIERS", 0) ? 0 : 1;
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // dense root solver (DeSymIndefSolver replacement) on the same tile kernels
@@ -5457,9 +4823,9 @@ int pips_symbolic_probe(int n, int n_primal, const int* krow, const int* jcol, i
                         const int* Bt_colidx, int force_n_head, int64_t* what, int n_what, int* perm, int* colcount) {
    if (n <= 0 || !krow || !jcol) PIPS_FAIL(PIPS_ERR_ARG, "pips_symbolic_probe: bad arguments");
    AnalyzeOptions opt;
-   apply_tuning(opt);
+   AnalyzeKnobs knobs;
+   read_layout_knobs(nullptr, opt, knobs);
    opt.force_n_head = force_n_head;
-   opt.mf_konly = opt.mf_split_nb_max > 0 && opt.max_sn_width <= 16 && env_int("PIPS_HIP_MF_KONLY", 0) != 0;   // (as Engine::analyze outside deterministic mode)
    CsrPattern K{n, n, krow, jcol};
    CsrPattern B{0, n, nullptr, nullptr};
    if (Bt_rowptr && S > 0) B = CsrPattern{S, n, Bt_rowptr, Bt_colidx};
@@ -5542,7 +4908,9 @@ int pips_symbolic_probe_hubs(int n, int n_primal, const int* krow, const int* jc
    std::vector<int> hv(hubs, hubs + n_hubs), pv, cc;
    if (!hub_dissected_order(n, ap, ai, hv, min_size, pv, cc)) PIPS_FAIL(PIPS_ERR_STATE, "pips_symbolic_probe_hubs: no separators");
    AnalyzeOptions opt;
-   apply_tuning(opt);
+   AnalyzeKnobs knobs;
+   read_layout_knobs(nullptr, opt, knobs);
+   opt.mf_konly = false;   // (the sparse root's order: plain fronts)
    opt.user_perm = pv.data();
    opt.user_colcount = cc.data();
    {  // (the cut pips_hip_kkt_create_sparse takes)
@@ -5558,6 +4926,44 @@ int pips_symbolic_probe_hubs(int n, int n_primal, const int* krow, const int* jc
    if (what) sym_info(sym, what, n_what);
    if (perm) std::copy(sym[0].perm.begin(), sym[0].perm.end(), perm);
    if (colcount) std::copy(sym[0].colcount.begin(), sym[0].colcount.end(), colcount);
+   return PIPS_OK;
+}
+
+// ---- layout probe (CPU only): symbolic analysis and host layout of a batch as Engine::analyze forms them, and the layout's invariants
+int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
+                      const int* const* bt_rowptr, const int* const* bt_colidx, int deterministic, long long free_device_bytes,
+                      int64_t* what, int n_what) {
+   if (nblk <= 0 || !n || !krow || !kcol || S < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_layout_probe: bad arguments");
+   std::vector<BlockInput> in(nblk);
+   for (int b = 0; b < nblk; ++b) {
+      if (n[b] <= 0 || !krow[b] || !kcol[b]) PIPS_FAIL(PIPS_ERR_ARG, "pips_layout_probe: block %d is empty", b);
+      in[b].n = n[b];
+      in[b].n_primal = n_primal ? n_primal[b] : -1;
+      in[b].krow.assign(krow[b], krow[b] + n[b] + 1);
+      in[b].kcol.assign(kcol[b], kcol[b] + krow[b][n[b]]);
+      if (S > 0 && bt_rowptr && bt_colidx && bt_rowptr[b] && bt_colidx[b]) {
+         in[b].btrow.assign(bt_rowptr[b], bt_rowptr[b] + S + 1);
+         in[b].btcol.assign(bt_colidx[b], bt_colidx[b] + bt_rowptr[b][S]);
+         in[b].btval.assign(in[b].btcol.size(), 0.0);
+      }
+   }
+   AnalyzeOptions opt;
+   AnalyzeKnobs knobs;
+   read_layout_knobs(nullptr, opt, knobs);
+   if (deterministic) { knobs.deterministic = true; opt.mf_konly = false; }
+   knobs.free_device_bytes = free_device_bytes;
+   std::vector<BlockSym> sym;
+   BatchLayout lay;
+   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+   int rc = analyze_symbolic(in, S, n_threads, opt, knobs, sym);
+   if (!rc) rc = build_batch_layout(in, sym, S, knobs, lay);
+   if (!rc) rc = check_batch_layout(in, sym, S, knobs, lay);
+   if (rc) return rc;
+   int64_t v[21] = {lay.arena_total, lay.xw_total, lay.uarena_total, lay.nsn_total, (int64_t)lay.levels.size(), (int64_t)lay.levels_top.size(),
+                    (int64_t)lay.mf_launches.size(), 0, lay.n_bb, lay.bb_stage, lay.tail_single, lay.border_backward_ok, lay.aug_sweeps_ok,
+                    lay.slots_total, lay.vslots_total, lay.n_total, lay.mf, lay.schur_mode_eff, lay.bb_doubles, lay.mfU_total, lay.spine_total};
+   for (const MfLaunch& m : lay.mf_launches) if (m.cls >= 6) v[7] += m.cnt;
+   for (int i = 0; what && i < n_what && i < 21; ++i) what[i] = v[i];
    return PIPS_OK;
 }
 

@@ -12,52 +12,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "records.h"
+
 namespace pips {
 
-constexpr int TILE = 128;
 constexpr int KB = 16;          // k-depth of one LDS stage of the tile GEMM (16; 32 needs 132 KB of LDS: one workgroup per CU)
 constexpr int LDS_PAD = 16;     // LDS row padding (doubles): 144*8 B = 1152 B -> half-wave k-groups hit disjoint banks
 constexpr int LDSW = TILE + LDS_PAD;
-
-struct SnDesc {
-   long long panel;  // global arena offset of the ld x w panel
-   long long rows;   // global offset into rowidx
-   long long upd;    // global offset into upd (head-to-head update segments)
-   int w, r, c0, blk;
-   int n_useg, rb;   // number of update segments; index of the first border row among the r below-rows
-   int ld, pad_;     // leading dimension of the stored panel: w + r, or w + rb for a front under the border split (its border rows live
-                     // only in the border-row arena at bb: Lt[k * rpb + a - rb], rpb = r - rb rounded up to 4)
-   long long slot;   // deterministic mode: first contribution slot of the factorisation scatter (r (r + 1) / 2 slots: pair (a, b),
-                     // a >= b, has slot + b r - b (b - 1) / 2 + a - b)
-   long long vslot;  // ... and of the forward-substitution scatter (r slots)
-   long long U;      // multifrontal head: offset of the packed r x r update matrix inside the update arena, -1 if none
-   long long mf;     // multifrontal head: offset of the front record inside mfint (common.h "Front record"), -1 for simple leaves
-   long long bb;     // border split: offset of the supernode's border rows inside the border-row arena (k_border_schur), -1 if none
-};
-
-
-struct BlkDesc {
-   long long arena_off;  // block arena base (doubles)
-   long long T;          // global arena offset of the tail panel
-   long long sncol_off;  // offset into sn_of_col (values are global supernode ids)
-   long long xw_off;     // offset of the permuted work vector (length n_head + m_pad)
-   long long x_off;      // offset into flat original-order vectors (sum of n over preceding blocks)
-   long long bmap_off;   // offset into bmap
-   long long winv_off;   // offset into winv (ntc tiles of TILE*TILE)
-   long long dt_off;     // offset into dtail (m_pad)
-   long long sctab_off;  // offset of this block's nb x nb position table inside sctab (sparse Schur complement), else 0
-   int n, n_head, m, m_pad, nb, nb_pad, ldT, ntc, ntr;
-   int mf_split;         // multifrontal head with the border split (BlockSym::mf_split)
-   long long U;          // offset of the block's scaled tail copy U = L D (m_pad x m_pad, ld = m_pad) inside the U arena
-   double thr_rel, repl_rel;  // pivot threshold / replacement relative to the pivot's reference magnitude pref[k]
-   double repl_abs;           // replacement when no reference magnitude exists (structurally zero diagonal)
-   long long lv_off;          // multifrontal head: offset of the block's leaf values inside the leaf-value arena
-   long long k_off, b_off;    // offsets of the block's K values / border values (Engine::d_kval, d_bval): k_front reads its panel entries there
-   long long T_in;            // where the tail panel is ASSEMBLED (scatter, root fronts, border rows of the head) and accumulated: = T when the tail is
-                              // factorised in place (launch per step), a scratch region behind the panels when it is one launch (tailkernel.hip.h)
-};
-
-struct TileTask { int blk, ti, tj, pad; };
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -298,8 +259,6 @@ __global__ void k_block_absmax_finish(BlkDesc* blks, int nblk, double thr_rel, d
 // ------------------------------------------------------------------------------------------------
 // head supernode factorisation (one workgroup per supernode)
 // ------------------------------------------------------------------------------------------------
-constexpr int HEAD_WMAX = 32;   // widest head supernode (solve kernels)
-
 // Head-to-head update segments (symbolic.cpp "update segments"): 8-int header + positions, read-only on the device.
 constexpr int USEG_HDR = 8;
 constexpr int MF_HDR_DEV = 4;
@@ -509,8 +468,6 @@ __global__ __launch_bounds__(BLOCK) void k_head_factor_spine(const int* __restri
 // the positions come from the segment tables).  One THREAD per supernode:
 // the launch is throughput-bound instead of paying a workgroup's dependent-load latency chain per 21-flop supernode.
 // ------------------------------------------------------------------------------------------------
-constexpr int SIMPLE_RMAX = 16;
-
 __global__ __launch_bounds__(256) void k_head_factor_simple(const SnDesc* __restrict__ sns, int sn_begin, int cnt,
                                                            const BlkDesc* __restrict__ blks, const int* __restrict__ rowidx,
                                                            const int* __restrict__ upd, const signed char* __restrict__ psign,
@@ -1213,29 +1170,7 @@ __global__ __launch_bounds__(64) void k_border_tail(const int* __restrict__ list
 // return value, no wait).  ordered != 0 (deterministic mode): the supernodes of a batch one after the other with a barrier between
 // them - inside a supernode the targets are distinct, so every sum has a fixed order.  At the end C is added to the Schur complement:
 // FP64 atomics (targets shared between blocks and shares), or - gbuf != nullptr - plain adds into the group's buffer by launches that
-// hold at most one block of every group.
-constexpr int BB_GMAX = 8;
-// register tile of k_border_schur: BB_TR rows x 4 columns of L_b D L_b^T per thread and step (BB_TR = 4: square tiles over the lower triangle;
-// 8: two row groups per tile - six LDS reads per 32 multiply-adds instead of four per 16)
-constexpr int BB_TR = 4;
-// tiles of a supernode with rp (a multiple of 4) padded border rows; tile t -> (column group tb of 4, row group ta of BB_TR)
-__host__ __device__ inline int bb_tile_count(int rp) {
-   const int nt4 = rp >> 2;
-   if (BB_TR == 4) return nt4 * (nt4 + 1) / 2;
-   const int nt8 = (rp + 7) >> 3;
-   int cnt = 0;
-   for (int tb = 0; tb < nt4; ++tb) cnt += nt8 - (tb >> 1);
-   return cnt;
-}
-struct BbMeta { int lt_off, pos_off, w, nbj, tile0, pad0, pad1, pad2; };   // staging offset of Lt (doubles; the pivots follow at + w * rp),
-                                                                          // offset of the rows' positions inside the batch's list, tiles before it
-struct BbBatch {
-   long long src;     // offset of the batch inside the border-row arena
-   long long pos;     // offset of its rows' positions (compressed border ids) inside bbpos
-   int first, cnt;    // its supernodes inside the BbMeta array
-   int ndoubles, ntiles, npos, pad;
-};
-
+// hold at most one block of every group.  (BB_GMAX, BB_TR, bb_tile_count, BbMeta, BbBatch: records.h)
 template <int BLOCK, int NPF>
 __global__ __launch_bounds__(BLOCK) void k_border_schur(const int* __restrict__ blk_list, const int* __restrict__ batch_off,
                                                        const BbBatch* __restrict__ batches, const BbMeta* __restrict__ metas,
@@ -1452,16 +1387,7 @@ __global__ __launch_bounds__(256) void k_leaf_fwd_gather(const int* __restrict__
    if (row) x[target] -= s;
 }
 
-// Backward substitution of the simple leaves from a compact record (24 bytes instead of the 88-byte SnDesc + BlkDesc the general
-// kernel reads - on the time-coupled blocks the descriptors were most of this kernel's traffic): x_c = x_c / d - sum_a l_a x[rows_a]
-struct LeafDesc {
-   long long panel;   // d, l_0 .. l_{r-1} in the arena
-   int rows;          // offset into rowidx
-   int xoff;          // the block's offset in the work vector
-   int c0;            // the leaf's column (block-local, permuted)
-   int r_in;          // rows inside the block (the border rows behind them take no part in solves with K_i)
-};
-
+// Backward substitution of the simple leaves from a compact record (LeafDesc, records.h)
 __global__ __launch_bounds__(256) void k_leaf_bwd(const LeafDesc* __restrict__ leaves, int cnt, const int* __restrict__ rowidx,
                                                   const double* __restrict__ arena, double* __restrict__ xw, long long xw_stride, int dscale) {
    const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2858,7 +2784,6 @@ __global__ __launch_bounds__(256) void k_leaf_border(const int* __restrict__ lis
 // (entry p of the list on lane p % 64: a fixed assignment; the lanes' sums in the fixed tree of the shuffles): equal bits from run to run.
 // Entry: where the w factors of the row lie (stride between them) and the first of J's columns in the work vector.
 // (A first version gathered the factors per target: 1560 entries per wave, every factor a sector of its own - 10 ms per sweep on the configs[3] share.)
-struct BgEntry { long long off; unsigned y; unsigned short stride, w; };
 __global__ void k_border_rowdot_det(long long n_ent, const BgEntry* __restrict__ ent, const double* __restrict__ arena, const double* __restrict__ xw,
                                     double* __restrict__ val) {
    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n_ent; p += (long long)gridDim.x * blockDim.x) {
@@ -3409,8 +3334,7 @@ __global__ __launch_bounds__(256) void k_mrefine_measure(const BlkDesc* __restri
 
 // refinement residual r = b - K x (r holds b on entry): the full (both triangles) row structure is built at analyze time -
 // frowptr / fcol (block-local column) / fsrc (index of the value inside kval) - so the product is gather-only, no atomics:
-//   y_i -= sum_j K_ij x_j
-constexpr int FULL_LONG_ROW = 512;
+//   y_i -= sum_j K_ij x_j   (rows longer than FULL_LONG_ROW, records.h, go to k_full_spmv_sub_long)
 
 // y0 != nullptr: y = y0 - K x (every row must then be short: the caller checks that no row goes to k_full_spmv_sub_long)
 __global__ void k_full_spmv_sub(const int* __restrict__ frowptr, const int* __restrict__ fcol, const int* __restrict__ fsrc,

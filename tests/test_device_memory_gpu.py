@@ -158,8 +158,8 @@ def test_front_clock_buffer_goes_with_its_analysis(monkeypatch):
 
 
 def test_analyze_that_fails_part_way_leaves_nothing_behind():
-    """A block whose pattern lacks a diagonal entry is refused in the middle of analyze(), after the previous analysis was released and
-    the first buffers of the new one exist: once the handle is destroyed the counters are where they were."""
+    """A block whose pattern lacks a diagonal entry is refused in the middle of analyze(), by the host layout pass: after the previous
+    analysis was released and before the first buffer of the new one exists.  Once the handle is destroyed the counters are where they were."""
     prob = Problem(1, 2, 400, 200, 24, 16, 0.02)
     _batch(prob, prob, deterministic=False)   # (warm-up)
     want = _live()
