@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace pips {
@@ -201,6 +202,21 @@ struct RootPlanParams {
 };
 // tasks / chain_tasks: (kind 0 UPD / 1 TRSM / 2 DIAG, i, j, k0 | k1 << 16) quadruples in ticket order
 int build_root_plan(int ntc, const RootPlanParams& p, std::vector<int>& tasks, std::vector<int>& chain_tasks, double* makespan_us);
+
+
+// ---- sparse root of the KKT system: pattern and elimination order (rootplan.cpp; device side: kkt.hip.h) --------------
+// One of the constant root blocks A0 / F0 / G0: CSR rows (rowptr == nullptr: none) that sit at row row0 of the Schur complement.
+struct RootRows { const int* rowptr; const int* colidx; const double* val; int nrows, row0; };
+// Pattern of SC (lower CSR, sorted, every row ends with its diagonal): the dense x0 block, the root rows, a full diagonal and for every
+// (cols, count) in cliques - the non-empty border columns of a block, ascending - the clique on them.
+void sc_lower_pattern(int S, int n0, const RootRows (&root)[3], const std::vector<std::pair<const int*, int>>& cliques, std::vector<int>& rowptr,
+                      std::vector<int>& colidx);
+// Elimination order of that pattern; the rows [0, n_hubs) are the hubs x0 / y0.  Returns 0 minimum degree (the engine orders; perm is
+// not needed), 1 dense-tile band (perm: linking rows, then the hubs), 2 dissection around the hubs (perm, colcount; the first head_cut
+// columns have at most max_head_colcount entries below the diagonal: the multifrontal head).  force_mode != nullptr: that mode instead
+// of the choice by the tile envelope (2 still falls back to 1 without separators).
+int sparse_root_order(int S, int n_hubs, const std::vector<int>& rowptr, const std::vector<int>& colidx, int tile, int max_head_colcount,
+                      const int* force_mode, std::vector<int>& perm, std::vector<int>& colcount, int& head_cut);
 
 }  // namespace pips
 

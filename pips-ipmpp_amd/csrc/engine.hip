@@ -2733,165 +2733,6 @@ struct DenseLdl {
    }
 };
 
-// ---------------------------------------------------------------------------------------------------------------
-// fused two-level KKT system of one rank: leaves (Engine) + replicated dense root (DenseLdl) + Schur reduction.
-// Mirrors DistributedRootLinearSystem::factor2 (:206-243) and DistributedLinearSystem::solveCompressed (:409-420)
-// with sLinsysRootAug::{finalizeKKTdense, Lsolve, Dsolve, Ltsolve} (sLinsysRootAug.C:1769-1796, 323-365).
-// ---------------------------------------------------------------------------------------------------------------
-typedef int (*allreduce_fn)(void* comm, double* buf, size_t n, void* stream);
-
-struct KktSystem {
-   Engine* leaves = nullptr;
-   std::unique_ptr<DenseLdl> root;
-   int n0 = 0, my0 = 0, myl = 0, mzl = 0, S = 0;
-   int rank = 0, n_ranks = 1;
-   void* comm = nullptr;
-   DevBuf<double> d_SC, d_t, d_fin_val, d_c0_val, d_red, d_packed;
-   DevBuf<long long> d_fin_idx;
-   long long n_fin = 0;
-   DevBuf<double> d_gall, d_gvec_all;   // deterministic mode over several ranks: all eight group slots (8 x S x S / 8 x S)
-   int mz0 = 0;
-   DevBuf<int> d_c0_rp, d_c0_ci;
-   const double* d_zdiag0 = nullptr;   // caller-owned, set per iteration
-   double root_reg_primal = 0.0, root_reg_dual = 0.0;   // pips_hip_kkt_set_root_regularization
-   hipStream_t comm_stream = nullptr;   // panel-wise Schur reduction beside the leaf work
-   hipEvent_t ev_reduced = nullptr;
-   // The dense root is factorised on a stream of its own: it is a latency chain (S = 2000: 16 diagonal tiles, 1.9 ms with the chip
-   // nearly idle) and nothing needs its factors before the Dsolve of the next solveCompressed - the leaf solves of that call's
-   // Lsolve run beside it.  root_wait() joins the main stream with it (before Dsolve, the next factorisation, an inertia query).
-   hipStream_t root_stream = nullptr;
-   hipEvent_t ev_sc_final = nullptr, ev_root_done = nullptr;
-   bool root_pending = false;
-   bool root_own_stream = true;   // pips_hip_kkt_set_root_stream: a caller that asks for the root's inertia after every factorisation (the IPM
-                                  // harness) has nothing to run beside the root - the second stream then only costs (measured: section 4.3b)
-   int root_wait() {
-      if (root_pending) {
-         if (root && root->check_pending) {   // Bunch-Kaufman root: were there indices without a pivot inside their tile?  (host wait for the
-                                              // root's stream - the work queued on the main stream meanwhile keeps the device busy)
-            hipStream_t keep = root->stream;
-            root->stream = root_stream;
-            const int rc = root->check_pivots();
-            root->stream = keep;
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(ev_root_done, root_stream));
-         }
-         HIP_TRY(hipStreamWaitEvent(leaves->stream, ev_root_done, 0));
-         root_pending = false;
-      } else if (root && root->check_pending) {
-         // the root was factorised on the main stream (pips_hip_kkt_set_root_stream(0)): the pivot check is still owed, and it reads from the
-         // device and waits - it must happen here, before a capture of the solve sequence begins, not inside DenseLdl::solve_dev
-         const int rc = root->check_pivots();
-         if (rc) return rc;
-      }
-      return PIPS_OK;
-   }
-   bool use_rsag = false, force_reduce = false;
-   bool solve_graph = false;                // pips_hip_kkt_set_solve_graph
-   hipGraphExec_t graph_exec = nullptr;
-   hipStream_t graph_stream = nullptr;
-   // everything a captured launch sequence has baked in: buffer addresses, the Ltsolve path, the number of refinement launches, the
-   // elimination of root inequality rows (zdiag0, C0), the root's pivoting mode, the analysis the leaf buffers belong to
-   struct GraphKey {
-      const void *b0 = nullptr, *bl = nullptr, *zdiag0 = nullptr, *c0_val = nullptr, *c0_rp = nullptr, *c0_ci = nullptr;
-      int from_factor = 0, refine_steps = 0, refine_mode = 0, mz0 = 0, pivoting = 0, bk_gen = 0;
-      long long analysis_gen = 0;
-      bool operator==(const GraphKey& o) const {
-         return b0 == o.b0 && bl == o.bl && zdiag0 == o.zdiag0 && c0_val == o.c0_val && c0_rp == o.c0_rp && c0_ci == o.c0_ci &&
-                from_factor == o.from_factor && refine_steps == o.refine_steps && refine_mode == o.refine_mode && mz0 == o.mz0 &&
-                pivoting == o.pivoting && bk_gen == o.bk_gen && analysis_gen == o.analysis_gen;
-      }
-   } graph_key;
-   long long graph_captures = 0, graph_replays = 0;
-   bool last_ltsolve_from_factor = false;   // which Ltsolve the last solveCompressed took (reported per solve, not only at analyze time)
-   // Sweeps of the augmented factor for both halves of solveCompressed (Engine::forward_augmented / backward_augmented).  They carry no
-   // refinement, so they are taken only on evidence that this factorisation is accurate: no perturbed pivot, and an earlier
-   // solveCompressed on the SAME factors went the refined way and every refined leaf solve in it met the backward-error tolerance
-   // without a step (aug_validated_gen == factor_gen).  The first solveCompressed after every factorisation is that witness.
-   long long factor_gen = 0, aug_validated_gen = -1;
-   int last_solve_path = 0;   // 0: two refined leaf solves, 1: refined Lsolve + Ltsolve from the factor, 2: augmented sweeps, 3: augmented sweeps
-                              // whose result was checked (below)
-   // One rank: the witness is the first sweep pair itself - its result x_i is put into the leaf rows, r_i = b_i - Br_i x0 - K_i x_i, and
-   // accepted where the measure of the adaptive refinement is within the tolerance (one product with K instead of a refined solve and
-   // its extra backward sweep); a result that fails is thrown away, the saved right-hand side goes the refined way and the sweeps stay
-   // off for these factors (aug_failed_gen).  Several ranks keep the refined witness: the decision to repeat a solveCompressed would
-   // have to be taken by all ranks together.  PIPS_HIP_AUG_WITNESS=0: the refined witness everywhere.
-   long long aug_failed_gen = -1;
-   bool checked_witness = env_int("PIPS_HIP_AUG_WITNESS", 1) != 0;
-   // Every solveCompressed that goes by sweeps is measured like that (pips_hip_kkt_set_solve_check: every k-th one; 0 = the witness
-   // only, rounds 4's behaviour): the reference's PARDISO measures and refines EVERY leaf solve (iparm[7] = 2,
-   // PardisoProjectSolver.C:72), and one clean right-hand side does not bound the backward error of the next.  Several ranks decide
-   // together: each solveCompressed ends with a one-number all-reduce "did any rank's check fail"; if so every rank restores its
-   // right-hand side and all go the refined way (a rank's inaccurate -Br^T K^-1 b taints x0 for everybody).
-   int solve_check_every = 1, sweeps_since_check = 0;
-   long long solves_since_factor = 0;   // equal on every rank: which solveCompressed calls are scheduled for a measure (every solve_check_every-th)
-   PinnedBuf<double> h_flag;            // pinned: the one-number exchange of settle() without a host wait before the collective
-   long long checked_solves = 0, failed_checks = 0;
-   DevBuf<double> d_flag;
-   bool joint_aug_any = false;        // several ranks: some rank's analysis chose the sweeps (all-reduced once per analysis)
-   long long joint_aug_gen = -1;
-   DevBuf<double> d_bsave, d_b0save;
-   bool root_pivoting_set = false;   // pips_hip_kkt_set_root_pivoting decided; else: Bunch-Kaufman iff root inequality rows are eliminated
-   // phase times of one factorize and the solveCompressed calls after it (pips_hip_kkt_get_timing; on with the batch's timing switch):
-   // 0 diagonals + zero SC, 1 leaf factorisation, 2 Schur reduction, 3 finalize, 4 root factorisation (its own stream),
-   // 5 Lsolve leaf solves, 6 Lsolve border product + b0 reduction, 7 Dsolve, 8 Ltsolve, 9 x_i = z_i - u_i,
-   // 10 panel-wise Schur reduction on its own stream (sum over the panels; phase 2 is then only what the main stream waited for it)
-   PhaseTimer timer;
-   // sparse root: SC lives as the value array of a lower-triangular CSR pattern inside a one-block sparse
-   // engine, which factorises and solves it with the leaf machinery (ordering, head / dense tail, refinement)
-   bool sparse = false;
-   std::unique_ptr<Engine> root_sp;
-   std::vector<int> sc_rowptr, sc_colidx, root_perm, root_colcount;
-   int root_order_mode = 0;   // sparse root: 0 minimum degree, 1 dense-tile band, 2 dissection around the hubs
-   DevBuf<long long> d_xdiag_pos, d_zlink_pos;
-   DevBuf<int> d_sc_rowptr;
-   ~KktSystem() {
-      if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-      if (graph_stream) (void)hipStreamDestroy(graph_stream);
-      if (root_stream) { (void)hipStreamSynchronize(root_stream); (void)hipStreamDestroy(root_stream); }
-      if (ev_sc_final) (void)hipEventDestroy(ev_sc_final);
-      if (ev_root_done) (void)hipEventDestroy(ev_root_done);
-      if (comm_stream) (void)hipStreamDestroy(comm_stream);
-      if (ev_reduced) (void)hipEventDestroy(ev_reduced);
-   }
-};
-
-// vals[pos[i]] += d[i]
-__global__ void k_add_at(double* __restrict__ vals, const long long* __restrict__ pos, const double* __restrict__ d, int n) {
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) vals[pos[i]] += d[i];
-}
-
-// SC[0:n0,0:n0] -= C0^T diag(zdiag)^-1 C0 (lower triangle; zdiag < 0): schur_complement_add_CTDC_block
-// (sLinsysRootAug.C:1276-1338, SparseStorage::matTransDinvMultMat SparseStorage.C:1257).  One thread per row of C0.
-// sc_rowptr != nullptr: SC is the value array of the sparse root's CSR pattern, whose x0 block is dense: (i, j), j <= i < n0,
-// sits at sc_rowptr[i] + j
-__global__ void k_ctdc(int mz0, const int* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v,
-                       const double* __restrict__ zdiag, double* __restrict__ SC, int ld, const int* __restrict__ sc_rowptr) {
-   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < mz0; k += gridDim.x * blockDim.x) {
-      const double dinv = 1.0 / zdiag[k];
-      for (int p = rp[k]; p < rp[k + 1]; ++p)
-         for (int q = rp[k]; q < rp[k + 1]; ++q) {
-            const int i = ci[p], j = ci[q];
-            if (i >= j) atomic_add_f64(sc_rowptr ? SC + sc_rowptr[i] + j : SC + i + (long long)j * ld, -v[p] * v[q] * dinv);
-         }
-   }
-}
-
-// solveReducedLinkCons (sLinsysRootAug.C:384-466), z0 elimination: mode 0: t_k = b3_k / zdiag_k ; rhs1 -= C0^T t
-//                                                                     mode 1: b3_k = (b3_k - (C0 x1)_k) / zdiag_k
-__global__ void k_z0_elim(int mode, int mz0, const int* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v,
-                          const double* __restrict__ zdiag, double* __restrict__ b3, double* __restrict__ x1) {
-   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < mz0; k += gridDim.x * blockDim.x) {
-      if (mode == 0) {
-         const double t = b3[k] / zdiag[k];
-         for (int p = rp[k]; p < rp[k + 1]; ++p) atomic_add_f64(x1 + ci[p], -v[p] * t);
-      } else {
-         double s = b3[k];
-         for (int p = rp[k]; p < rp[k + 1]; ++p) s -= v[p] * x1[ci[p]];
-         b3[k] = s / zdiag[k];
-      }
-   }
-}
-
 // add_regularization_local_kkt (DistributedLeafLinearSystem.C:108-143): K diag += primal on the leading n_primal rows,
 // -= dual on the rest
 __global__ void k_add_regularization(const BlkDesc* __restrict__ blks, const int* __restrict__ n_primal,
@@ -2902,46 +2743,7 @@ __global__ void k_add_regularization(const BlkDesc* __restrict__ blks, const int
       kval[kdiag[bd.x_off + i]] += (np < 0 || i < np) ? primal : -dual;
 }
 
-// pack / unpack the lower triangle of the column-major S x S Schur complement (column c holds S - c entries):
-// the reference reduces packed triangles too (submatrixAllReduceDiagLower, DistributedRootLinearSystem.C:1661-1707)
-__global__ void k_pack_lower(const double* __restrict__ M, int ld, int S, double* __restrict__ packed, int unpack) {
-   const int c = blockIdx.y;
-   const long long base = (long long)c * S - (long long)c * (c - 1) / 2;
-   double* col = const_cast<double*>(M) + (long long)c * ld;
-   for (int r = c + blockIdx.x * blockDim.x + threadIdx.x; r < S; r += gridDim.x * blockDim.x) {
-      if (unpack) col[r] = packed[base + (r - c)];
-      else packed[base + (r - c)] = col[r];
-   }
-}
-
-// the same for a row panel [R0, R1) of the lower triangle: column c < R1 contributes its rows max(c, R0) .. R1 - 1
-__global__ void k_pack_rows(const double* __restrict__ M, int ld, int R0, int R1, double* __restrict__ packed, int unpack) {
-   const int c = blockIdx.y;
-   const long long h = R1 - R0;
-   const long long base = c <= R0 ? (long long)c * h
-                                  : (long long)R0 * h + (long long)(c - R0) * R1 - ((long long)c * (c - 1) / 2 - (long long)R0 * (R0 - 1) / 2);
-   const int r_first = c > R0 ? c : R0;
-   double* col = const_cast<double*>(M) + (long long)c * ld;
-   for (int r = r_first + blockIdx.x * blockDim.x + threadIdx.x; r < R1; r += gridDim.x * blockDim.x) {
-      if (unpack) col[r] = packed[base + (r - r_first)];
-      else packed[base + (r - r_first)] = col[r];
-   }
-}
-
-// diagonal_add_constant_from: dense column-major SC (rowptr == nullptr) or the CSR lower pattern of the sparse SC, whose rows end
-// with their diagonal entry
-__global__ void k_add_const_diag(double* __restrict__ M, int ld, const int* __restrict__ rowptr, int first, int n, double value) {
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-      const int r = first + i;
-      if (rowptr) M[rowptr[r + 1] - 1] += value;
-      else M[(long long)r * ld + r] += value;
-   }
-}
-
-__global__ void k_add_diag(double* __restrict__ M, int ld, int off, const double* __restrict__ d, int n) {
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-      M[(long long)(off + i) * ld + off + i] += d[i];
-}
+#include "kkt.hip.h"
 
 }  // namespace pips
 
@@ -3926,77 +3728,21 @@ int pips_hip_memset(void* dst, int value, size_t bytes) {
    return PIPS_OK;
 }
 
-// ---- fused KKT system ---------------------------------------------------------------------------------------------
-int pips_hip_allreduce_sum(void* comm, double* buf_dev, size_t n, void* stream);
-
+// ---- fused KKT system (kkt.hip.h) ---------------------------------------------------------------------------------
 int pips_hip_kkt_create(void** handle, void* batch, int n0, int my0, int myl, int mzl, const int* A0_rowptr,
                         const int* A0_colidx, const double* A0_val, const int* F0_rowptr, const int* F0_colidx,
                         const double* F0_val, const int* G0_rowptr, const int* G0_colidx, const double* G0_val, void* comm,
                         int rank, int n_ranks) {
    Engine* e = (Engine*)batch;
    if (!handle || !e || !e->analyzed) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_create: the leaf batch must be analyzed first");
-   const int S = n0 + my0 + myl + mzl;
-   if (S != e->S) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_create: n0+my0+myl+mzl = %d but the batch was created with S = %d", S, e->S);
-   auto k = std::make_unique<KktSystem>();
-   k->leaves = e;
-   k->n0 = n0; k->my0 = my0; k->myl = myl; k->mzl = mzl; k->S = S;
-   k->comm = comm; k->rank = rank; k->n_ranks = n_ranks;
-   k->force_reduce = comm && getenv("PIPS_HIP_FORCE_REDUCE") != nullptr;
    HIP_TRY(hipSetDevice(e->device));
-   k->root = std::make_unique<DenseLdl>();
-   k->root->n = S;
-   k->root->n_primal = n0;
-   k->root->device = e->device;
-   k->root->stream = e->stream;
-   k->root->thr_rel = e->thr_rel;
-   k->root->repl_rel = e->repl_rel;
-   int rc = k->root->init();
-   if (rc) return rc;
-   // several ranks: the dense root factorised column-cyclically over the ranks instead of redundantly on every one of them
-   // (PIPS_HIP_ROOT_DISTRIBUTED=1; untimed - see DenseLdl::set_distributed)
-   if (comm && n_ranks > 1 && env_int("PIPS_HIP_ROOT_DISTRIBUTED", 0) != 0 && (rc = k->root->set_distributed(comm, rank, n_ranks))) return rc;
-   PIPS_TRY(k->d_SC.alloc((size_t)S * S));
-   PIPS_TRY(k->d_t.alloc(std::max<size_t>((size_t)e->n_total, 1)));
-   // constant root blocks added by finalizeKKTdense: A0 at row n0, F0 at row n0+my0, G0 at row n0+my0+myl
-   // (sLinsysRootAug.C:270-320, 1782-1796).  SC is column-major with the lower triangle valid: (r,c) -> r + c*S.
-   std::vector<long long> idx;
-   std::vector<double> val;
-   auto add = [&](const int* rp, const int* ci, const double* v, int rows, int r0) {
-      if (!rp) return;
-      for (int r = 0; r < rows; ++r)
-         for (int p = rp[r]; p < rp[r + 1]; ++p) { idx.push_back((long long)(r0 + r) + (long long)ci[p] * S); val.push_back(v[p]); }
-   };
-   add(A0_rowptr, A0_colidx, A0_val, my0, n0);
-   add(F0_rowptr, F0_colidx, F0_val, myl, n0 + my0);
-   add(G0_rowptr, G0_colidx, G0_val, mzl, n0 + my0 + myl);
-   k->n_fin = (long long)idx.size();
-   if ((rc = k->d_fin_idx.upload(idx))) return rc;
-   if ((rc = k->d_fin_val.upload(val))) return rc;
-   // several ranks: Schur SYRK in row panels, each reduced as soon as it is final (PIPS_HIP_SC_PANELS, default 4 for S >= 1024; 1 =
-   // one reduction after all leaf work); PIPS_HIP_SC_REDUCE=rsag: reduce-scatter + all-gather instead of the all-reduce
-   if (e->deterministic && (rc = e->set_det_groups(rank, n_ranks))) return rc;
-   if (comm && (n_ranks > 1 || k->force_reduce) && !e->deterministic) {
-      // default: panels only where the reduction is worth hiding (S >= 4096: >= 64 MB packed; splitting the SYRK costs ~1 ms)
-      int panels = S >= 4096 ? 4 : 1;
-      if (const char* pp = getenv("PIPS_HIP_SC_PANELS")) panels = atoi(pp);
-      if ((rc = e->set_sc_panels(panels))) return rc;
-      if (const char* m = getenv("PIPS_HIP_SC_REDUCE")) k->use_rsag = std::string(m) == "rsag";
-   }
-   *handle = k.release();
-   return PIPS_OK;
+   const RootRows rows[3] = {{A0_rowptr, A0_colidx, A0_val, my0, n0}, {F0_rowptr, F0_colidx, F0_val, myl, n0 + my0}, {G0_rowptr, G0_colidx, G0_val, mzl, n0 + my0 + myl}};
+   return KktSystem::create(handle, e, "pips_hip_kkt_create", false, n0, my0, myl, mzl, rows, 0, nullptr, nullptr, comm, rank, n_ranks);
 }
 
-// Largest column count the dissected sparse root admits in its head: a front of colcount + 1 rows must fit the LDS as a packed triangle
-// (19 200 doubles: 195 rows).  Measured (tools/sparse_root_probe.py, 64 blocks): 31 linking rows per pair (fronts <= 188 rows) factorize
-// 4.3 ms as a band, 2.6 ms dissected; 100 rows per pair (fronts of 308 rows: update matrices in device memory) 10.1 ms as a band, 11.1 ms
-// dissected and solveCompressed 2.1 -> 4.3 ms - those stay a band.
-constexpr int ROOT_ND_MAX_COLCOUNT = 192;
-
-// Sparse-root variant (createSchurCompSymbSparseUpper, DistributedProblem.cpp:2235+; finalizeKKTsparse, sLinsysRootAug.C:
-// 1629-1739).  Pattern of SC (lower): the dense x0 block, for every block the clique on its non-empty border columns, the
-// root rows A0 / F0 / G0 and a full diagonal.  With 2-link structure (a linking row touches two blocks) it stays sparse.
-// blk_cols_ptr / blk_cols (optional): the border column sets of ALL blocks of the problem (needed with n_ranks > 1, where a
-// rank only knows its own blocks but every rank must reduce the same value array); NULL: the blocks of this batch.
+// Sparse root (KktSystem::init_sparse_root).  blk_cols_ptr / blk_cols (optional): the border column sets of ALL blocks of the problem
+// (needed with n_ranks > 1, where a rank only knows its own blocks but every rank must reduce the same value array); NULL: the blocks
+// of this batch.
 int pips_hip_kkt_create_sparse(void** handle, void* batch, int n0, int my0, int myl, int mzl, const int* A0_rowptr,
                                const int* A0_colidx, const double* A0_val, const int* F0_rowptr, const int* F0_colidx,
                                const double* F0_val, const int* G0_rowptr, const int* G0_colidx, const double* G0_val,
@@ -4004,389 +3750,16 @@ int pips_hip_kkt_create_sparse(void** handle, void* batch, int n0, int my0, int 
                                int n_ranks) {
    Engine* e = (Engine*)batch;
    if (!handle || !e || !e->analyzed) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_create_sparse: the batch must be analyzed");
-   const int S = n0 + my0 + myl + mzl;
-   if (S != e->S) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_create_sparse: n0+my0+myl+mzl = %d but the batch was created with S = %d", S, e->S);
-   if (n_ranks > 1 && !blk_cols_ptr) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_create_sparse: n_ranks > 1 needs the border column sets of all blocks");
-   auto k = std::make_unique<KktSystem>();
-   k->leaves = e;
-   k->n0 = n0; k->my0 = my0; k->myl = myl; k->mzl = mzl; k->S = S;
-   k->comm = comm; k->rank = rank; k->n_ranks = n_ranks;
-   k->force_reduce = comm && getenv("PIPS_HIP_FORCE_REDUCE") != nullptr;
-   k->sparse = true;
    HIP_TRY(hipSetDevice(e->device));
-   // ---- pattern, row by row (lower triangle, sorted, explicit diagonal)
-   std::vector<std::vector<int>> rows(S);
-   for (int r = 0; r < S; ++r) rows[r].push_back(r);
-   for (int r = 0; r < n0; ++r)
-      for (int c = 0; c < r; ++c) rows[r].push_back(c);
-   auto add_rows = [&](const int* rp, const int* ci, int nrows, int r0) {
-      if (!rp) return;
-      for (int r = 0; r < nrows; ++r)
-         for (int p = rp[r]; p < rp[r + 1]; ++p) rows[r0 + r].push_back(ci[p]);
-   };
-   add_rows(A0_rowptr, A0_colidx, my0, n0);
-   add_rows(F0_rowptr, F0_colidx, myl, n0 + my0);
-   add_rows(G0_rowptr, G0_colidx, mzl, n0 + my0 + myl);
-   auto add_clique = [&](const int* cols, int nc) {
-      for (int a = 0; a < nc; ++a)
-         for (int b = 0; b <= a; ++b) rows[cols[a]].push_back(cols[b]);   // cols ascending: cols[a] >= cols[b]
-   };
-   if (blk_cols_ptr) {
-      for (int b = 0; b < n_blocks_global; ++b) add_clique(blk_cols + blk_cols_ptr[b], blk_cols_ptr[b + 1] - blk_cols_ptr[b]);
-   }
-   for (int b = 0; b < e->nblk; ++b) add_clique(e->sym[b].bmap.data(), (int)e->sym[b].bmap.size());
-   k->sc_rowptr.assign(S + 1, 0);
-   for (int r = 0; r < S; ++r) {
-      std::sort(rows[r].begin(), rows[r].end());
-      rows[r].erase(std::unique(rows[r].begin(), rows[r].end()), rows[r].end());
-      k->sc_rowptr[r + 1] = k->sc_rowptr[r] + (int)rows[r].size();
-   }
-   k->sc_colidx.reserve(k->sc_rowptr[S]);
-   for (int r = 0; r < S; ++r) k->sc_colidx.insert(k->sc_colidx.end(), rows[r].begin(), rows[r].end());
-   auto pos_of = [&](int r, int c) -> long long {
-      const int* b0 = k->sc_colidx.data() + k->sc_rowptr[r];
-      const int* b1 = k->sc_colidx.data() + k->sc_rowptr[r + 1];
-      const int* it = std::lower_bound(b0, b1, c);
-      return (it != b1 && *it == c) ? (long long)(it - k->sc_colidx.data()) : -1;
-   };
-   // ---- per-block position tables for the leaf kernels
-   std::vector<int> tab;
-   std::vector<long long> off(e->nblk, 0);
-   for (int b = 0; b < e->nblk; ++b) {
-      const std::vector<int>& bm = e->sym[b].bmap;
-      const int nb = (int)bm.size();
-      off[b] = (long long)tab.size();
-      tab.resize(tab.size() + (size_t)nb * nb, 0);
-      for (int la = 0; la < nb; ++la)
-         for (int lb = 0; lb <= la; ++lb) tab[off[b] + (long long)la * nb + lb] = (int)pos_of(bm[la], bm[lb]);
-   }
-   int rc = e->set_sc_tables(tab, off, (long long)k->sc_rowptr[S]);
-   if (rc) return rc;
-   if (e->deterministic && (rc = e->set_det_groups(rank, n_ranks))) return rc;   // group buffers as long as the value array
-   // ---- the root as a one-block sparse engine; its value array is the Schur complement
-   k->root_sp = std::make_unique<Engine>();
-   Engine* r = k->root_sp.get();
-   r->nblk = 1; r->S = 0; r->device = e->device; r->stream = e->stream;
-   r->thr_rel = e->thr_rel; r->repl_rel = e->repl_rel;
-   r->deterministic = e->deterministic;   // (the root's own factorisation and sweeps: slots and fixed-order gathers instead of atomics)
-   r->in.assign(1, BlockInput());
-   r->in[0].n = S; r->in[0].n_primal = n0;
-   r->in[0].krow = k->sc_rowptr; r->in[0].kcol = k->sc_colidx;
-   // Elimination order.  The link-link block of SC is negative definite on its own (-sum F_i (K_i^-1)_xx F_i^T), so the linking
-   // rows can go first with their expected signs, then x0, then the root equality rows y0 (zero diagonal block: they need x0
-   // before them).  In that order a 2-link Schur complement is banded: if its tile envelope is thin the root is factorised as
-   // an all-dense-tile band (TailPlan envelope: band^2 work per column on the MFMA kernels) - otherwise minimum degree with
-   // the usual head / tail split decides (linking rows still before x0 unless y0 rows exist).
-   k->root_perm.clear();
-   for (int i = n0 + my0; i < S; ++i) k->root_perm.push_back(i);
-   for (int i = 0; i < n0 + my0; ++i) k->root_perm.push_back(i);
-   {
-      std::vector<int> ipos(S);
-      for (int t = 0; t < S; ++t) ipos[k->root_perm[t]] = t;
-      const int nt = (S + TILE - 1) / TILE;
-      std::vector<int> first(nt);
-      for (int t = 0; t < nt; ++t) first[t] = t;
-      for (int rr = 0; rr < S; ++rr)
-         for (int p = k->sc_rowptr[rr]; p < k->sc_rowptr[rr + 1]; ++p) {
-            const int a = ipos[rr], b = ipos[k->sc_colidx[p]];
-            const int tr = std::max(a, b) / TILE, tc = std::min(a, b) / TILE;
-            first[tr] = std::min(first[tr], tc);
-         }
-      double env = 0;
-      for (int t = 0; t < nt; ++t) env += t - first[t] + 1;
-      bool banded = env <= 0.25 * 0.5 * nt * (nt + 1.0);
-      // A thin band is a chain: as dense tiles its diagonal tiles are factorised one after the other (63 tiles of 86 us at S = 8000 -
-      // as long as the dense root).  Dissected around the hubs x0 / y0 (ordered last) the linking rows become a tree of small fronts
-      // for the multifrontal head, a dozen dependent launches deep; only the hubs and the top separators stay dense.
-      int mode = banded ? 2 : 0;   // 0 minimum degree, 1 dense-tile band, 2 dissection (falls back to 1 without separators)
-      if (const char* f = getenv("PIPS_HIP_SPARSE_ROOT_BAND")) mode = atoi(f);   // tests: force a path
-      if (mode == 2) {
-         std::vector<int> ap(S + 1, 0), ai, hubs, nd_perm;
-         for (int rr = 0; rr < S; ++rr)
-            for (int p = k->sc_rowptr[rr]; p < k->sc_rowptr[rr + 1]; ++p)
-               if (k->sc_colidx[p] != rr) { ++ap[rr + 1]; ++ap[k->sc_colidx[p] + 1]; }
-         for (int i = 0; i < S; ++i) ap[i + 1] += ap[i];
-         ai.resize(ap[S]);
-         {
-            std::vector<int> fill(ap.begin(), ap.end() - 1);
-            for (int rr = 0; rr < S; ++rr)
-               for (int p = k->sc_rowptr[rr]; p < k->sc_rowptr[rr + 1]; ++p) {
-                  const int c = k->sc_colidx[p];
-                  if (c != rr) { ai[fill[rr]++] = c; ai[fill[c]++] = rr; }
-               }
-         }
-         for (int i = 0; i < n0 + my0; ++i) hubs.push_back(i);
-         // head = the dissected rows as long as their fronts stay LDS-resident in k_front (ROOT_ND_MAX_COLCOUNT); the cost model is no
-         // guide here (it prices a scattering head against MFMA throughput, and the band's cost is the latency of its chain of diagonal tiles)
-         int cut = 0;
-         const bool dissected = hub_dissected_order(S, ap, ai, hubs, 48, nd_perm, k->root_colcount) && (int)nd_perm.size() == S;
-         if (dissected) {
-            const int n_rest = S - (int)hubs.size();
-            while (cut < n_rest && k->root_colcount[cut] <= ROOT_ND_MAX_COLCOUNT) ++cut;
-         }
-         // (without separators - one linking row or none, say - nd_perm is empty: never take it, whatever the threshold says)
-         if (dissected && cut > 0 && cut >= (S - (int)hubs.size()) / 2) { k->root_perm = nd_perm; r->opt.force_n_head = cut; r->sn_width = HEAD_WMAX; }
-         else mode = 1;   // (the band order - linking rows, then x0 - is always built above: root_perm holds it)
-      }
-      if (mode == 2) {
-         r->opt.user_perm = k->root_perm.data();
-         r->opt.user_colcount = k->root_colcount.data();
-      } else if (mode == 1) {
-         r->opt.user_perm = k->root_perm.data();
-         r->opt.force_n_head = 0;
-      } else {
-         r->opt.constrain_order = my0 > 0;
-      }
-      k->root_order_mode = mode;
-   }
-   if ((rc = r->analyze(4))) return rc;
-   // ---- constant root entries and the diagonals added by finalizeKKT
-   std::vector<long long> idx, xpos(n0), zpos(mzl);
-   std::vector<double> val;
-   auto add = [&](const int* rp, const int* ci, const double* v, int nrows, int r0) {
-      if (!rp) return;
-      for (int rr = 0; rr < nrows; ++rr)
-         for (int p = rp[rr]; p < rp[rr + 1]; ++p) { idx.push_back(pos_of(r0 + rr, ci[p])); val.push_back(v[p]); }
-   };
-   add(A0_rowptr, A0_colidx, A0_val, my0, n0);
-   add(F0_rowptr, F0_colidx, F0_val, myl, n0 + my0);
-   add(G0_rowptr, G0_colidx, G0_val, mzl, n0 + my0 + myl);
-   for (int i = 0; i < n0; ++i) xpos[i] = pos_of(i, i);
-   for (int i = 0; i < mzl; ++i) zpos[i] = pos_of(n0 + my0 + myl + i, n0 + my0 + myl + i);
-   k->n_fin = (long long)idx.size();
-   if ((rc = k->d_fin_idx.upload(idx))) return rc;
-   if ((rc = k->d_fin_val.upload(val))) return rc;
-   if ((rc = k->d_xdiag_pos.upload(xpos))) return rc;
-   if ((rc = k->d_zlink_pos.upload(zpos))) return rc;
-   if ((rc = k->d_sc_rowptr.upload(k->sc_rowptr))) return rc;
-   PIPS_TRY(k->d_t.alloc(std::max<size_t>((size_t)e->n_total, 1)));
-   *handle = k.release();
-   return PIPS_OK;
-}
-
-static int kkt_factorize_sparse(KktSystem* k, const double* leaf_diag_dev, const double* xdiag0_dev, const double* zdiag_link_dev) {
-   Engine* e = k->leaves;
-   Engine* r = k->root_sp.get();
-   int rc;
-   if (leaf_diag_dev && (rc = pips_hip_batch_set_diagonals_dev(e, leaf_diag_dev))) return rc;
-   const size_t nnz = (size_t)k->sc_rowptr[k->S];
-   PhaseTimer& tm = k->timer;
-   tm.on = e->timer.on;
-   tm.reset();
-   if ((rc = k->root_wait())) return rc;                                         // the previous root factorisation still reads the value array
-   HIP_TRY(hipMemsetAsync(r->d_kval, 0, nnz * sizeof(double), e->stream));
-   tm.begin(e->stream, 1);
-   e->defer_group_reduce = (k->n_ranks > 1 || k->force_reduce) && e->deterministic && e->det_global;
-   rc = e->factor(r->d_kval, 0);
-   e->defer_group_reduce = false;
-   if (rc) return rc;
-   tm.end(e->stream);
-   const bool reduce = k->n_ranks > 1 || k->force_reduce;
-   tm.begin(e->stream, 2);
-   if (reduce && e->deterministic && e->det_global && e->d_gbuf) {
-      // deterministic mode over several ranks: all eight group slots of the value array on every rank, one fixed tree (as in pips_hip_kkt_factorize)
-      if (!k->comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: n_ranks > 1 needs a communicator");
-      if (!k->d_gall) PIPS_TRY(k->d_gall.alloc(8 * nnz));
-      HIP_TRY(hipMemsetAsync(k->d_gall, 0, 8 * nnz * sizeof(double), e->stream));
-      HIP_TRY(hipMemcpyAsync(k->d_gall + (size_t)e->det_first_slot * nnz, e->d_gbuf, (size_t)e->det_n_groups * nnz * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      if ((rc = pips_hip_all_gather(k->comm, k->d_gall, (size_t)e->det_slots * nnz, 8 / e->det_slots, e->stream))) return rc;   // every rank's slots to every rank: 1 x the bytes
-      hipLaunchKernelGGL(k_reduce_groups, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(1024, (nnz + 255) / 256)), 1), dim3(256), 0, e->stream, r->d_kval, 0, (int)nnz,
-                         k->d_gall, (long long)nnz, 8, 0);
-   } else if (reduce) {
-      if (!k->comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: n_ranks > 1 needs a communicator");
-      if ((rc = pips_hip_allreduce_sum(k->comm, r->d_kval, nnz, e->stream))) return rc;
-   }
-   tm.end(e->stream);
-   if (xdiag0_dev && k->n0 > 0)
-      hipLaunchKernelGGL(k_add_at, dim3(grid_for(k->n0, 256)), dim3(256), 0, e->stream, r->d_kval, k->d_xdiag_pos, xdiag0_dev, k->n0);
-   if (k->n_fin > 0)
-      hipLaunchKernelGGL(k_add_entries, dim3(grid_for(k->n_fin, 256)), dim3(256), 0, e->stream, r->d_kval, k->d_fin_idx, k->d_fin_val,
-                         k->n_fin);
-   if (k->mz0 > 0) {
-      if (!k->d_zdiag0) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: mz0 > 0 needs pips_hip_kkt_set_root_inequalities + a zdiag0 vector");
-      hipLaunchKernelGGL(k_ctdc, e->deterministic ? dim3(1) : dim3(grid_for(k->mz0, 128)), e->deterministic ? dim3(1) : dim3(128), 0, e->stream, k->mz0, k->d_c0_rp,
-                         k->d_c0_ci, k->d_c0_val, k->d_zdiag0, r->d_kval, 0, k->d_sc_rowptr);
-   }
-   if (zdiag_link_dev && k->mzl > 0)
-      hipLaunchKernelGGL(k_add_at, dim3(grid_for(k->mzl, 256)), dim3(256), 0, e->stream, r->d_kval, k->d_zlink_pos, zdiag_link_dev, k->mzl);
-   if (k->root_reg_primal != 0.0 && k->n0 > 0)
-      hipLaunchKernelGGL(k_add_const_diag, dim3(grid_for(k->n0, 256)), dim3(256), 0, e->stream, r->d_kval, 0, k->d_sc_rowptr, 0, k->n0, k->root_reg_primal);
-   if (k->root_reg_dual != 0.0 && k->S > k->n0)
-      hipLaunchKernelGGL(k_add_const_diag, dim3(grid_for(k->S - k->n0, 256)), dim3(256), 0, e->stream, r->d_kval, 0, k->d_sc_rowptr, k->n0,
-                         k->S - k->n0, -k->root_reg_dual);
-   HIP_TRY(hipGetLastError());
-   // The root engine's factorisation is a chain of small launches (the dissected root: 26 levels of fronts + the hubs' tile): on a stream
-   // of its own it runs beside the leaf sweeps of the next solveCompressed's Lsolve, as the dense root does (root_wait() joins before
-   // Dsolve, the next factorisation, queries): 39.9 -> 38.9 ms per unit on the configs[3] shape, 43.5 -> 42.7 on the 256-block chain
-   // (tools/ab_async_root.sh, alternating on one box).  Default since round 5 (PIPS_HIP_SPARSE_ROOT_ASYNC=0 / PIPS_HIP_ROOT_SYNC keep the
-   // main stream): round 4 had one bench run of about two dozen with it not finish inside its time limit and made it opt-in; 148 full-size
-   // runs and 60 small ones in round 5 (tools/stress_exit.sh, tools/stress_async.sh, every run under a watchdog) all ended, and the
-   // mechanism is the dense root's, which has been the default since round 2.
-   static const bool root_async_env = env_int("PIPS_HIP_SPARSE_ROOT_ASYNC", 1) != 0 && !getenv("PIPS_HIP_ROOT_SYNC");
-   const bool root_async = root_async_env && k->root_own_stream;
-   if (!root_async) {
-      const int rec_main = tm.begin_i(e->stream, 13);     // (phase 13 = the root factorisation where it sits on the main stream: critical path)
-      tm.begin(e->stream, 4);
-      rc = r->factor(nullptr, 0);
-      tm.end(e->stream);
-      tm.end_i(rec_main, e->stream);
-      return rc;
-   }
-   if (!k->root_stream) {
-      int prio_lo = 0, prio_hi = 0;
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-      HIP_TRY(hipStreamCreateWithPriority(&k->root_stream, hipStreamNonBlocking, prio_hi));
-      HIP_TRY(hipEventCreateWithFlags(&k->ev_sc_final, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&k->ev_root_done, hipEventDisableTiming));
-   }
-   HIP_TRY(hipEventRecord(k->ev_sc_final, e->stream));
-   HIP_TRY(hipStreamWaitEvent(k->root_stream, k->ev_sc_final, 0));
-   r->stream = k->root_stream;
-   tm.begin(k->root_stream, 4);
-   rc = r->factor(nullptr, 0);
-   tm.end(k->root_stream);
-   r->stream = e->stream;                                                         // solves and queries run on the main stream
-   if (rc) return rc;
-   HIP_TRY(hipEventRecord(k->ev_root_done, k->root_stream));
-   k->root_pending = true;
-   return PIPS_OK;
+   const RootRows rows[3] = {{A0_rowptr, A0_colidx, A0_val, my0, n0}, {F0_rowptr, F0_colidx, F0_val, myl, n0 + my0}, {G0_rowptr, G0_colidx, G0_val, mzl, n0 + my0 + myl}};
+   return KktSystem::create(handle, e, "pips_hip_kkt_create_sparse", true, n0, my0, myl, mzl, rows, n_blocks_global, blk_cols_ptr, blk_cols, comm, rank, n_ranks);
 }
 
 int pips_hip_kkt_factorize(void* handle, const double* leaf_diag_dev, const double* xdiag0_dev, const double* zdiag_link_dev) {
    KktSystem* k = (KktSystem*)handle;
    if (!k) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   Engine* e = k->leaves;
-   HIP_TRY(hipSetDevice(e->device));
-   ++k->factor_gen;
-   k->solves_since_factor = 0;
-   if (k->sparse) return kkt_factorize_sparse(k, leaf_diag_dev, xdiag0_dev, zdiag_link_dev);
-   int rc;
-   PhaseTimer& tm = k->timer;
-   tm.on = e->timer.on;
-   tm.reset();
-   tm.begin(e->stream, 0);
-   if (leaf_diag_dev && (rc = pips_hip_batch_set_diagonals_dev(e, leaf_diag_dev))) return rc;
-   const size_t n = (size_t)k->S * k->S;
-   if ((rc = k->root_wait())) return rc;                                         // the previous root factorisation still reads d_SC
-   HIP_TRY(hipMemsetAsync(k->d_SC, 0, n * sizeof(double), e->stream));            // initializeKKT (:840-847)
-   tm.end(e->stream);
-   tm.begin(e->stream, 1);
-   e->defer_group_reduce = (k->n_ranks > 1 || k->force_reduce) && e->deterministic && e->det_global;
-   rc = e->factor(k->d_SC, k->S);                                                // children factor2 + assembleLocalKKT
-   e->defer_group_reduce = false;
-   if (rc) return rc;
-   tm.end(e->stream);
-   // reduceKKT (:860-881).  PIPS_HIP_FORCE_REDUCE exercises the reduction path with a one-rank communicator (tests).
-   const bool reduce = k->n_ranks > 1 || k->force_reduce;
-   const int rec_reduce = tm.begin_i(e->stream, 2);   // what the main stream waits for the reduction: its exposed part
-   if (reduce && e->deterministic && e->det_global && e->d_gbuf) {
-      // deterministic mode over several ranks: every rank's group buffers to every rank, then ALL eight slots in the one fixed tree (the
-      // leaf engine left its groups unreduced, Engine::det_global) - equal bits for 1, 2, 4 and 8 ranks
-      if (!k->comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: n_ranks > 1 needs a communicator");
-      const size_t gs = (size_t)k->S * k->S;
-      if (!k->d_gall) PIPS_TRY(k->d_gall.alloc(8 * gs));
-      HIP_TRY(hipMemsetAsync(k->d_gall, 0, 8 * gs * sizeof(double), e->stream));
-      HIP_TRY(hipMemcpyAsync(k->d_gall + (size_t)e->det_first_slot * gs, e->d_gbuf, (size_t)e->det_n_groups * gs * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      if ((rc = pips_hip_all_gather(k->comm, k->d_gall, (size_t)e->det_slots * gs, 8 / e->det_slots, e->stream))) return rc;   // (the all-reduce of zeros it replaces moved 8 x the bytes)
-      hipLaunchKernelGGL(k_reduce_groups, dim3(std::max(1, std::min(64, (k->S + 255) / 256)), k->S), dim3(256), 0, e->stream, k->d_SC, k->S, k->S, k->d_gall,
-                         (long long)gs, 8, 0);
-   } else if (reduce) {
-      if (!k->comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: n_ranks > 1 needs a communicator");
-      // only the lower triangle is authoritative: reduce S(S+1)/2 packed doubles instead of S^2
-      const size_t np = (size_t)k->S * (k->S + 1) / 2;
-      const size_t n_groups = std::max<size_t>(e->sc_groups.size(), 1);
-      const size_t P = (size_t)std::max(1, pips_hip_comm_size(k->comm));
-      const size_t cap = np + (n_groups + 1) * P;   // reduce-scatter pads every piece to a multiple of the rank count
-      PIPS_TRY(k->d_packed.reserve(cap));
-      auto reduce_piece = [&](double* buf, size_t cnt, hipStream_t st) -> int {
-         return k->use_rsag ? pips_hip_allreduce_sum_rsag(k->comm, buf, cnt, st) : pips_hip_allreduce_sum(k->comm, buf, cnt, st);
-      };
-      if (!e->sc_groups.empty()) {
-         // Panel-wise: the Schur SYRK ran in row-panel groups (Engine::set_sc_panels); the rows of panel q are final on this rank
-         // once group q has run, so their reduction goes out on a second stream while the leaves compute the later groups -
-         // the overlap of leaf work with MPI_Allreduce that DistributedRootLinearSystem.C:860-881 cannot have (it reduces
-         // after all children are done).  Everything was enqueued by e->factor(); here only the reductions are issued, in order.
-         if (!k->comm_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&k->comm_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&k->ev_reduced, hipEventDisableTiming));
-         }
-         size_t off = 0;
-         for (size_t q = 0; q < e->sc_groups.size(); ++q) {
-            const int R0 = e->sc_row_begin[q], R1 = e->sc_row_begin[q + 1];
-            if (R1 <= R0) continue;
-            const size_t h = (size_t)(R1 - R0);
-            const size_t cnt = (size_t)R0 * h + h * (h + 1) / 2;
-            HIP_TRY(hipStreamWaitEvent(k->comm_stream, e->ev_sc[q], 0));
-            const dim3 pg(std::max(1, std::min(64, (R1 - R0 + 255) / 256)), R1);
-            const int rec_panel = tm.begin_i(k->comm_stream, 10);   // pack + collective + unpack of this panel, beside the leaf work
-            hipLaunchKernelGGL(k_pack_rows, pg, dim3(256), 0, k->comm_stream, k->d_SC, k->S, R0, R1, k->d_packed + off, 0);
-            if ((rc = reduce_piece(k->d_packed + off, cnt, k->comm_stream))) return rc;
-            hipLaunchKernelGGL(k_pack_rows, pg, dim3(256), 0, k->comm_stream, k->d_SC, k->S, R0, R1, k->d_packed + off, 1);
-            tm.end_i(rec_panel, k->comm_stream);
-            off += (cnt + P - 1) / P * P;
-         }
-         HIP_TRY(hipEventRecord(k->ev_reduced, k->comm_stream));
-         HIP_TRY(hipStreamWaitEvent(e->stream, k->ev_reduced, 0));
-      } else {
-         const dim3 pg(std::max(1, std::min(64, (k->S + 255) / 256)), k->S);
-         hipLaunchKernelGGL(k_pack_lower, pg, dim3(256), 0, e->stream, k->d_SC, k->S, k->S, k->d_packed, 0);
-         if ((rc = reduce_piece(k->d_packed, np, e->stream))) return rc;
-         hipLaunchKernelGGL(k_pack_lower, pg, dim3(256), 0, e->stream, k->d_SC, k->S, k->S, k->d_packed, 1);
-      }
-   }
-   tm.end_i(rec_reduce, e->stream);
-   // finalizeKKTdense
-   tm.begin(e->stream, 3);
-   if (xdiag0_dev && k->n0 > 0)
-      hipLaunchKernelGGL(k_add_diag, dim3(grid_for(k->n0, 256)), dim3(256), 0, e->stream, k->d_SC, k->S, 0, xdiag0_dev, k->n0);
-   if (k->n_fin > 0)
-      hipLaunchKernelGGL(k_add_entries, dim3(grid_for(k->n_fin, 256)), dim3(256), 0, e->stream, k->d_SC, k->d_fin_idx,
-                         k->d_fin_val, k->n_fin);
-   if (k->mz0 > 0) {
-      if (!k->d_zdiag0) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: mz0 > 0 needs pips_hip_kkt_set_root_inequalities + a zdiag0 vector");
-      // deterministic mode: one thread walks the rows of C0 (the kernel's atomics then arrive in row order)
-      hipLaunchKernelGGL(k_ctdc, e->deterministic ? dim3(1) : dim3(grid_for(k->mz0, 128)), e->deterministic ? dim3(1) : dim3(128), 0, e->stream, k->mz0,
-                         k->d_c0_rp, k->d_c0_ci, k->d_c0_val, k->d_zdiag0, k->d_SC, k->S, (const int*)nullptr);
-   }
-   if (zdiag_link_dev && k->mzl > 0)
-      hipLaunchKernelGGL(k_add_diag, dim3(grid_for(k->mzl, 256)), dim3(256), 0, e->stream, k->d_SC, k->S,
-                         k->n0 + k->my0 + k->myl, zdiag_link_dev, k->mzl);
-   if (k->root_reg_primal != 0.0 && k->n0 > 0)
-      hipLaunchKernelGGL(k_add_const_diag, dim3(grid_for(k->n0, 256)), dim3(256), 0, e->stream, k->d_SC, k->S, (const int*)nullptr, 0, k->n0,
-                         k->root_reg_primal);
-   if (k->root_reg_dual != 0.0 && k->S > k->n0)
-      hipLaunchKernelGGL(k_add_const_diag, dim3(grid_for(k->S - k->n0, 256)), dim3(256), 0, e->stream, k->d_SC, k->S, (const int*)nullptr, k->n0,
-                         k->S - k->n0, -k->root_reg_dual);
-   HIP_TRY(hipGetLastError());
-   tm.end(e->stream);
-   static const bool root_async_env = !getenv("PIPS_HIP_ROOT_SYNC");
-   const bool root_async = root_async_env && k->root_own_stream && k->root->dist_P <= 1;   // the distributed root issues collectives: main stream
-   if (!root_async) {
-      const int rec_main = tm.begin_i(e->stream, 13);
-      tm.begin(e->stream, 4);
-      rc = k->root->factor_dev(k->d_SC, k->S, 0);                                  // factorizeKKT (:1436-1464)
-      tm.end(e->stream);
-      tm.end_i(rec_main, e->stream);
-      return rc;
-   }
-   if (!k->root_stream) {
-      int prio_lo = 0, prio_hi = 0;
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-      HIP_TRY(hipStreamCreateWithPriority(&k->root_stream, hipStreamNonBlocking, prio_hi));
-      HIP_TRY(hipEventCreateWithFlags(&k->ev_sc_final, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&k->ev_root_done, hipEventDisableTiming));
-   }
-   HIP_TRY(hipEventRecord(k->ev_sc_final, e->stream));
-   HIP_TRY(hipStreamWaitEvent(k->root_stream, k->ev_sc_final, 0));
-   k->root->stream = k->root_stream;
-   tm.begin(k->root_stream, 4);
-   rc = k->root->factor_dev(k->d_SC, k->S, 0);
-   tm.end(k->root_stream);
-   k->root->stream = e->stream;                                                   // solves and queries run on the main stream
-   if (rc) return rc;
-   HIP_TRY(hipEventRecord(k->ev_root_done, k->root_stream));
-   k->root_pending = true;
-   return PIPS_OK;
+   HIP_TRY(hipSetDevice(k->leaves->device));
+   return k->factorize(leaf_diag_dev, xdiag0_dev, zdiag_link_dev);
 }
 
 int pips_hip_kkt_set_root_regularization(void* handle, double primal, double dual) {
@@ -4397,278 +3770,11 @@ int pips_hip_kkt_set_root_regularization(void* handle, double primal, double dua
    return PIPS_OK;
 }
 
-// the launch sequence of one solveCompressed; `capturing`: inside a stream capture (no host-side decisions, no waits on events recorded outside)
-static int kkt_solve_compressed_enqueue(KktSystem* k, double* b0_dev, double* b_leaf_dev, bool capturing) {
-   Engine* e = k->leaves;
-   int rc;
-   bool use_aug = false, verify = false;
-   int lsolve_steps = 0;
-   // with mz0 > 0 the caller's vector is [x0 | y0 | z0 | ylink | zlink]; the Schur system lives on the reduced vector
-   // [x0 | y0 | ylink | zlink] (solveReducedLinkCons, sLinsysRootAug.C:397-433)
-   double* red = b0_dev;
-   const int head = k->n0 + k->my0, tailn = k->myl + k->mzl;
-   if (k->mz0 > 0) {
-      red = k->d_red;
-      HIP_TRY(hipMemcpyAsync(red, b0_dev, (size_t)head * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      HIP_TRY(hipMemcpyAsync(red + head, b0_dev + head + k->mz0, (size_t)tailn * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-   }
-   // several ranks (or the forced reduction of the tests): the checks are decided together - see KktSystem::solve_check_every
-   const bool joint = k->n_ranks > 1 || k->force_reduce;
-   const bool can_measure = !capturing && e->refine_tol > 0.0 && e->refine_steps > 0;
-   // (whether the ranks exchange the outcome may depend only on what is equal on every rank: the settings the host gives all ranks alike,
-   // and "some rank's analysis chose the sweeps" - the cost model decides per rank - settled once per analysis by an all-reduce)
-   if (joint && can_measure && k->solve_check_every > 0 && k->joint_aug_gen != e->analysis_gen) {
-      if (!k->d_flag) PIPS_TRY(k->d_flag.alloc(1));
-      double any = e->aug_sweeps_ok ? 1.0 : 0.0;
-      HIP_TRY(hipMemcpyAsync(k->d_flag, &any, sizeof(double), hipMemcpyHostToDevice, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-      if ((rc = pips_hip_allreduce_sum(k->comm, k->d_flag, 1, e->stream))) return rc;
-      HIP_TRY(hipMemcpyAsync(&any, k->d_flag, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-      k->joint_aug_any = any > 0.0;
-      k->joint_aug_gen = e->analysis_gen;
-   }
-   const bool joint_check = joint && can_measure && k->solve_check_every > 0 && k->joint_aug_any;
-   // Which calls measure is decided by a counter that is equal on every rank (solveCompressed calls since the factorisation; the first one
-   // is always scheduled): several ranks then exchange the outcome only on scheduled calls - none could have measured on the others -
-   // instead of ending every call with a latency-bound collective and two host waits.
-   const bool scheduled = k->solve_check_every > 0 && (k->solves_since_factor++ % k->solve_check_every) == 0;
-   if (can_measure && e->aug_sweeps_ok && k->aug_failed_gen != k->factor_gen) {
-      const bool validated = k->aug_validated_gen == k->factor_gen;
-      const bool may_check = !joint || joint_check;      // (a measure may fail: several ranks must be able to act on it together)
-      if (validated || (k->checked_witness && may_check && (!joint || scheduled))) {   // the first solve after a factorisation: a checked sweep pair, or the refined pass
-         int pert = 1;
-         if ((rc = e->perturbed_leaf_pivots(&pert))) return rc;
-         use_aug = pert == 0;
-         const bool due = use_aug && validated && may_check && scheduled;
-         verify = use_aug && (!validated || due);
-      }
-   }
-   if (verify || joint_check) {   // the right-hand side as the caller gave it: needed for the check, and for the refined pass if a check fails
-      if (!k->d_bsave) PIPS_TRY(k->d_bsave.alloc(std::max<size_t>((size_t)e->n_total, 1)));
-      if (!k->d_b0save) PIPS_TRY(k->d_b0save.alloc((size_t)(k->S + k->mz0 + 1)));
-      HIP_TRY(hipMemcpyAsync(k->d_bsave, b_leaf_dev, (size_t)e->n_total * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      HIP_TRY(hipMemcpyAsync(k->d_b0save, b0_dev, (size_t)(k->S + k->mz0) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-   }
-   // the joint decision at the end of the call: any rank's failed check sends every rank back to its saved right-hand side
-   auto settle = [&](bool my_check_failed) -> int {
-      bool redo = my_check_failed;
-      if (joint_check) {
-         if (!k->d_flag) PIPS_TRY(k->d_flag.alloc(1));
-         if (!k->h_flag) PIPS_TRY(k->h_flag.alloc(2));
-         k->h_flag[0] = my_check_failed ? 1.0 : 0.0;   // (pinned: the copy is queued, nothing waits before the collective)
-         HIP_TRY(hipMemcpyAsync(k->d_flag, k->h_flag, sizeof(double), hipMemcpyHostToDevice, e->stream));
-         int rcf = pips_hip_allreduce_sum(k->comm, k->d_flag, 1, e->stream);
-         if (rcf) return rcf;
-         HIP_TRY(hipMemcpyAsync(k->h_flag + 1, k->d_flag, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-         HIP_TRY(hipStreamSynchronize(e->stream));
-         redo = k->h_flag[1] > 0.0;
-      }
-      if (!redo) return PIPS_OK;
-      ++k->failed_checks;
-      k->aug_failed_gen = k->factor_gen;   // no sweeps on these factors any more, on any rank
-      HIP_TRY(hipMemcpyAsync(b_leaf_dev, k->d_bsave, (size_t)e->n_total * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      HIP_TRY(hipMemcpyAsync(b0_dev, k->d_b0save, (size_t)(k->S + k->mz0) * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      return kkt_solve_compressed_enqueue(k, b0_dev, b_leaf_dev, capturing);
-   };
-   if (e->deterministic && e->d_gvec) {
-      // deterministic Lsolve: t = -sum_i Br_i^T K_i^-1 b_i is formed on its own - group-wise in block order, the (at most eight)
-      // groups in the fixed tree of k_reduce_groups, the ranks' parts by the all-reduce - and added to b0 on every rank.  Guarantee:
-      // run-to-run reproducibility for any rank count, and equal bits for 1 and 2 ranks (a two-operand all-reduce has one order);
-      // with 4 or 8 ranks the association of the per-rank partial sums is the all-reduce's (ring / tree, per chunk), not this tree
-      k->timer.begin(e->stream, 5);
-      if (use_aug) { if ((rc = e->forward_augmented_det(b_leaf_dev))) return rc; }   // (the blocks' border slots hold -L_b y = -Br^T K^-1 b)
-      else {
-         if ((rc = e->solve(b_leaf_dev))) return rc;
-         lsolve_steps = e->last_refine_steps;
-      }
-      k->timer.end(e->stream);
-      k->timer.begin(e->stream, 6);
-      HIP_TRY(hipMemsetAsync(e->d_gvec, 0, (size_t)8 * k->S * sizeof(double), e->stream));
-      HIP_TRY(hipMemsetAsync(e->d_tvec, 0, (size_t)k->S * sizeof(double), e->stream));
-      if (use_aug) e->gather(e->g_bslot_grp, e->d_xw, e->d_gvec);
-      else if (e->bt_rows_total > 0) {
-         hipLaunchKernelGGL(k_border_rowdot, dim3(grid_for(e->bt_rows_total, 256)), dim3(256), 0, e->stream, e->d_bt_rowptr, e->d_bt_colidx, e->d_bval,
-                            e->d_bt_xoff, b_leaf_dev, e->d_bt_tmp, e->bt_rows_total, -1.0);
-         e->gather(e->g_btm_grp, e->d_bt_tmp, e->d_gvec);
-      }
-      if (e->det_global && k->n_ranks > 1) {   // all eight group slots on every rank, one tree (see pips_hip_kkt_factorize)
-         if (!k->d_gvec_all) PIPS_TRY(k->d_gvec_all.alloc((size_t)8 * k->S));
-         HIP_TRY(hipMemsetAsync(k->d_gvec_all, 0, (size_t)8 * k->S * sizeof(double), e->stream));
-         HIP_TRY(hipMemcpyAsync(k->d_gvec_all + (size_t)e->det_first_slot * k->S, e->d_gvec, (size_t)e->det_n_groups * k->S * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-         if ((rc = pips_hip_all_gather(k->comm, k->d_gvec_all, (size_t)e->det_slots * k->S, 8 / e->det_slots, e->stream))) return rc;
-         hipLaunchKernelGGL(k_reduce_groups, dim3(std::max(1, std::min(64, (k->S + 255) / 256)), 1), dim3(256), 0, e->stream, e->d_tvec, k->S, k->S, k->d_gvec_all,
-                            (long long)k->S, 8, 0);
-      } else {
-      hipLaunchKernelGGL(k_reduce_groups, dim3(std::max(1, std::min(64, (k->S + 255) / 256)), 1), dim3(256), 0, e->stream, e->d_tvec, k->S, k->S, e->d_gvec,
-                         (long long)k->S, e->det_n_groups, e->det_first_slot);
-      if ((k->n_ranks > 1 || k->force_reduce) && (rc = pips_hip_allreduce_sum(k->comm, e->d_tvec, (size_t)k->S, e->stream))) return rc;
-      }
-      hipLaunchKernelGGL(k_axpy, dim3(grid_for(k->S, 256)), dim3(256), 0, e->stream, red, e->d_tvec, 1.0, (long long)k->S);
-      k->timer.end(e->stream);
-   } else {
-   // Lsolve: ranks > 0 zero b0, every child adds -Br^T K^-1 b_i, all-reduce (sLinsysRootAug.C:323-344)
-   if (k->n_ranks > 1 && k->rank > 0) HIP_TRY(hipMemsetAsync(red, 0, (size_t)k->S * sizeof(double), e->stream));
-   k->timer.begin(e->stream, 5);
-   if (use_aug) { if ((rc = e->forward_augmented(b_leaf_dev, red))) return rc; }
-   else {
-      if ((rc = e->solve(b_leaf_dev))) return rc;
-      lsolve_steps = e->last_refine_steps;
-   }
-   k->timer.end(e->stream);
-   k->timer.begin(e->stream, 6);
-   if (!use_aug && (rc = pips_hip_batch_border_tmult_dev(e, b_leaf_dev, red, -1.0))) return rc;
-   if ((k->n_ranks > 1 || k->force_reduce) && (rc = pips_hip_allreduce_sum(k->comm, red, (size_t)k->S, e->stream)))
-      return rc;
-   k->timer.end(e->stream);
-   }
-   // Dsolve: eliminate z0 through C0, solve with the Schur complement, recover z0 (solveReducedLinkCons :384-466)
-   // the join with the root's stream is a phase of its own (11): what the main stream waits there is the part of the root factorisation
-   // that the first Lsolve did not hide - the exposed root time, measured instead of estimated
-   if (!capturing) {   // (a captured sequence: joined before the capture began)
-      const bool pending = k->root_pending;
-      if (pending) k->timer.begin(e->stream, 11);
-      if ((rc = k->root_wait())) return rc;
-      if (pending) k->timer.end(e->stream);
-   }
-   k->timer.begin(e->stream, 7);
-   if (k->mz0 > 0)
-      hipLaunchKernelGGL(k_z0_elim, e->deterministic ? dim3(1) : dim3(grid_for(k->mz0, 128)), e->deterministic ? dim3(1) : dim3(128), 0, e->stream, 0, k->mz0, k->d_c0_rp, k->d_c0_ci, k->d_c0_val,
-                         k->d_zdiag0, b0_dev + head, red);
-   if (k->sparse) {
-      if ((rc = k->root_sp->solve(red))) return rc;
-   } else {
-      if ((rc = k->root->solve_dev(red))) return rc;
-   }
-   if (k->mz0 > 0) {
-      hipLaunchKernelGGL(k_z0_elim, dim3(grid_for(k->mz0, 128)), dim3(128), 0, e->stream, 1, k->mz0, k->d_c0_rp, k->d_c0_ci, k->d_c0_val,
-                         k->d_zdiag0, b0_dev + head, red);
-      HIP_TRY(hipMemcpyAsync(b0_dev, red, (size_t)head * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-      HIP_TRY(hipMemcpyAsync(b0_dev + head + k->mz0, red + head, (size_t)tailn * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-   }
-   // Ltsolve: b_i -= K_i^-1 Br_i x0 (LniTransMult, DistributedLinearSystem.C:430-483).  Where the stored border rows are thin
-   // enough and no pivot of the factorisation was perturbed: from the augmented factor with one backward sweep
-   // (Engine::solve_border_backward); else border product + full solve with refinement.
-   k->timer.end(e->stream);
-   k->timer.begin(e->stream, 8);
-   // The sweep carries no refinement, so it is taken only on evidence that the factors are accurate: no perturbed pivot (the
-   // counters reached pinned memory with the factorisation: no wait for the solves queued behind it) AND, with adaptive refinement,
-   // the refined leaf solve of this call's Lsolve - same factors - was satisfied by its first solve (backward error below the
-   // tolerance without a step).  A pivot that kept its sign but is rounding noise passes the first test, not the second.
-   if (use_aug) {
-      if ((rc = e->backward_augmented(red, b_leaf_dev))) return rc;
-      k->last_ltsolve_from_factor = true;
-      k->last_solve_path = 2;
-      bool failed = false;
-      if (verify) {
-         k->timer.end(e->stream);
-         k->timer.begin(e->stream, 12);   // (phase 12: the measure of the sweeps' result)
-         // r_i = (b_i - Br_i x0) - K_i x_i over the blocks, measured like a refinement step would measure it
-         double worst = 0.0;
-         if (e->can_measure_fused()) {
-            if ((rc = e->residual_measure_fused(k->d_bsave, red, b_leaf_dev, &worst))) return rc;
-         } else {
-            HIP_TRY(hipMemcpyAsync(k->d_t, k->d_bsave, (size_t)e->n_total * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-            if ((rc = pips_hip_batch_border_mult_dev(e, red, k->d_t, -1.0))) return rc;
-            if ((rc = e->residual_measure(k->d_t, b_leaf_dev, &worst))) return rc;
-         }
-         ++k->checked_solves;
-         k->sweeps_since_check = 0;
-         if (worst <= e->refine_tol) {
-            k->aug_validated_gen = k->factor_gen;
-            k->last_solve_path = 3;
-         } else
-            failed = true;   // not good enough without refinement: the refined path on the saved right-hand side, no sweeps on these factors
-      }
-      k->timer.end(e->stream);
-      if (failed || (joint_check && scheduled)) return settle(failed);
-      HIP_TRY(hipGetLastError());
-      return PIPS_OK;
-   } else {
-   if (!capturing) {
-      int pert = 1;
-      if ((e->border_backward_ok || e->aug_sweeps_ok) && (rc = e->perturbed_leaf_pivots(&pert))) return rc;
-      const bool lsolve_clean = e->refine_tol > 0.0 ? e->last_refine_steps == 0 : true;
-      k->last_ltsolve_from_factor = e->border_backward_ok && pert == 0 && lsolve_clean;   // (dense or sparse root: x0 comes in Schur numbering either way)
-   }
-   int ltsolve_steps = 0;
-   if (k->last_ltsolve_from_factor) {
-      if ((rc = e->solve_border_backward(red, k->d_t))) return rc;
-   } else {
-      HIP_TRY(hipMemsetAsync(k->d_t, 0, (size_t)e->n_total * sizeof(double), e->stream));
-      if ((rc = pips_hip_batch_border_mult_dev(e, red, k->d_t, 1.0))) return rc;
-      if ((rc = e->solve(k->d_t))) return rc;
-      ltsolve_steps = e->last_refine_steps;
-   }
-   k->last_solve_path = k->last_ltsolve_from_factor ? 1 : 0;
-   // this refined pass is the witness for the factors it ran on (see KktSystem::aug_validated_gen)
-   // (a pass that was allowed no step proves nothing: refine_steps > 0)
-   if (can_measure && e->aug_sweeps_ok && lsolve_steps == 0 && ltsolve_steps == 0) k->aug_validated_gen = k->factor_gen;
-   k->timer.end(e->stream);
-   k->timer.begin(e->stream, 9);
-   hipLaunchKernelGGL(k_axpy, dim3(grid_for(e->n_total, 256)), dim3(256), 0, e->stream, b_leaf_dev, k->d_t, -1.0, e->n_total);
-   k->timer.end(e->stream);
-   if (joint_check && scheduled) return settle(false);   // (another rank's check may have failed)
-   }
-   HIP_TRY(hipGetLastError());
-   return PIPS_OK;
-}
-
-// solveCompressed as a replayed HIP graph (pips_hip_kkt_set_solve_graph): the launch sequence of one call is
-// fixed between factorisations - dozens of launches on a launch-bound problem (configs[0]: ~50 kernels of a few microseconds each) -
-// so it is captured once per (right-hand-side pointers, Ltsolve path) and replayed.  What a capture cannot contain keeps the
-// direct path: adaptive refinement (it reads norms on the host between steps), reductions over several ranks, the sparse root,
-// deterministic mode, phase timing.  The single-launch sweeps take their epoch from device memory for this (k_sweep_bump).
-static bool kkt_graph_eligible(const KktSystem* k) {
-   const Engine* e = k->leaves;
-   return k->solve_graph && !k->sparse && k->n_ranks <= 1 && !k->force_reduce && e->refine_tol == 0.0 && !e->deterministic && !e->timer.on &&
-          !k->timer.on;
-}
-
 int pips_hip_kkt_solve_compressed(void* handle, double* b0_dev, double* b_leaf_dev) {
    KktSystem* k = (KktSystem*)handle;
    if (!k || !b0_dev || !b_leaf_dev) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_compressed: bad arguments");
-   Engine* e = k->leaves;
-   HIP_TRY(hipSetDevice(e->device));
-   if (!kkt_graph_eligible(k)) return kkt_solve_compressed_enqueue(k, b0_dev, b_leaf_dev, false);
-   int rc;
-   // host-side decisions and joins first: they are part of the key, not of the graph
-   if ((rc = k->root_wait())) return rc;
-   int pert = 1;
-   if (e->border_backward_ok && (rc = e->perturbed_leaf_pivots(&pert))) return rc;
-   k->last_ltsolve_from_factor = e->border_backward_ok && pert == 0;
-   KktSystem::GraphKey key;
-   key.b0 = b0_dev; key.bl = b_leaf_dev; key.zdiag0 = k->d_zdiag0; key.c0_val = k->d_c0_val; key.c0_rp = k->d_c0_rp; key.c0_ci = k->d_c0_ci;
-   key.from_factor = k->last_ltsolve_from_factor ? 1 : 0; key.refine_steps = e->refine_steps; key.refine_mode = e->refine_mode; key.mz0 = k->mz0;
-   key.pivoting = k->root ? k->root->pivoting : 0; key.analysis_gen = e->analysis_gen;
-   key.bk_gen = k->root ? k->root->bk_refactorizations : 0;   // (a new pivot order: the solve permutes its right-hand side)
-   if (k->graph_exec && !(k->graph_key == key)) {
-      (void)hipGraphExecDestroy(k->graph_exec);
-      k->graph_exec = nullptr;
-   }
-   if (!k->graph_exec) {
-      // The capture runs on a stream of its own (the handle's stream may be the legacy default stream, which cannot be captured):
-      // the engine's and the root's stream members point there for the duration of the enqueue; the graph is then launched into the
-      // handle's own stream like any other work.
-      if (!k->graph_stream) HIP_TRY(hipStreamCreateWithFlags(&k->graph_stream, hipStreamNonBlocking));
-      hipGraph_t g = nullptr;
-      hipStream_t keep_e = e->stream, keep_r = k->root->stream;
-      e->stream = k->graph_stream; k->root->stream = k->graph_stream;
-      hipError_t eb = hipStreamBeginCapture(k->graph_stream, hipStreamCaptureModeRelaxed);
-      rc = eb == hipSuccess ? kkt_solve_compressed_enqueue(k, b0_dev, b_leaf_dev, true) : PIPS_OK;
-      const hipError_t ec = eb == hipSuccess ? hipStreamEndCapture(k->graph_stream, &g) : eb;
-      e->stream = keep_e; k->root->stream = keep_r;
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      if (ec != hipSuccess || !g) PIPS_FAIL(PIPS_ERR_HIP, "pips_hip_kkt_solve_compressed: stream capture failed: %s", hipGetErrorString(ec));
-      const hipError_t ei = hipGraphInstantiate(&k->graph_exec, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (ei != hipSuccess) { k->graph_exec = nullptr; PIPS_FAIL(PIPS_ERR_HIP, "pips_hip_kkt_solve_compressed: hipGraphInstantiate: %s", hipGetErrorString(ei)); }
-      k->graph_key = key;
-      ++k->graph_captures;
-   }
-   HIP_TRY(hipGraphLaunch(k->graph_exec, e->stream));
-   ++k->graph_replays;
-   return PIPS_OK;
+   HIP_TRY(hipSetDevice(k->leaves->device));
+   return k->solve_compressed(b0_dev, b_leaf_dev);
 }
 
 int pips_hip_kkt_set_root_stream(void* handle, int own_stream) {
@@ -4744,17 +3850,7 @@ int pips_hip_kkt_set_root_inequalities(void* handle, int mz0, const int* C0_rowp
    KktSystem* k = (KktSystem*)handle;
    if (!k || mz0 < 0 || (mz0 > 0 && (!C0_rowptr || !C0_colidx || !C0_val))) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_set_root_inequalities: bad arguments");
    HIP_TRY(hipSetDevice(k->leaves->device));
-   k->mz0 = mz0;
-   // -C0^T Omega^-1 C0 in the x0 block (sLinsysRootAug.C:1276-1294): an active row makes it a huge low-rank matrix plus an O(1) rest,
-   // the static pivot rule then takes the cancelled pivots for zeros - the reference leaves that to dsytrf, so does the root here
-   if (k->root && !k->root_pivoting_set) k->root->pivoting = mz0 > 0 ? 1 : 0;
-   if (mz0 == 0) return PIPS_OK;
-   std::vector<int> rp(C0_rowptr, C0_rowptr + mz0 + 1), ci(C0_colidx, C0_colidx + C0_rowptr[mz0]);
-   std::vector<double> v(C0_val, C0_val + C0_rowptr[mz0]);
-   int rc;
-   if ((rc = k->d_c0_rp.upload(rp)) || (rc = k->d_c0_ci.upload(ci)) || (rc = k->d_c0_val.upload(v))) return rc;
-   PIPS_TRY(k->d_red.alloc((size_t)std::max(k->S, 1)));
-   return PIPS_OK;
+   return k->set_root_inequalities(mz0, C0_rowptr, C0_colidx, C0_val);
 }
 
 int pips_hip_kkt_set_root_pivoting(void* handle, int mode) {

@@ -14,6 +14,7 @@
 // polls a little.  tools/root_schedule_sim.py is the prototype this restates.
 #include <algorithm>
 #include <queue>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -148,6 +149,94 @@ int build_root_plan(int ntc, const RootPlanParams& p, std::vector<int>& tasks, s
       *makespan_us = t;
    }
    return PIPS_OK;
+}
+
+// ---- sparse root: pattern and elimination order (host side of KktSystem::init_sparse_root, kkt.hip.h) --------------------------
+void sc_lower_pattern(int S, int n0, const RootRows (&root)[3], const std::vector<std::pair<const int*, int>>& cliques, std::vector<int>& rowptr,
+                      std::vector<int>& colidx) {
+   // row by row (lower triangle, sorted, explicit diagonal)
+   std::vector<std::vector<int>> rows(S);
+   for (int r = 0; r < S; ++r) rows[r].push_back(r);
+   for (int r = 0; r < n0; ++r)
+      for (int c = 0; c < r; ++c) rows[r].push_back(c);
+   for (const RootRows& b : root) {
+      if (!b.rowptr) continue;
+      for (int r = 0; r < b.nrows; ++r)
+         for (int p = b.rowptr[r]; p < b.rowptr[r + 1]; ++p) rows[b.row0 + r].push_back(b.colidx[p]);
+   }
+   for (const auto& q : cliques)
+      for (int a = 0; a < q.second; ++a)
+         for (int b = 0; b <= a; ++b) rows[q.first[a]].push_back(q.first[b]);   // cols ascending: cols[a] >= cols[b]
+   rowptr.assign(S + 1, 0);
+   for (int r = 0; r < S; ++r) {
+      std::sort(rows[r].begin(), rows[r].end());
+      rows[r].erase(std::unique(rows[r].begin(), rows[r].end()), rows[r].end());
+      rowptr[r + 1] = rowptr[r] + (int)rows[r].size();
+   }
+   colidx.clear();
+   colidx.reserve(rowptr[S]);
+   for (int r = 0; r < S; ++r) colidx.insert(colidx.end(), rows[r].begin(), rows[r].end());
+}
+
+// The link-link block of SC is negative definite on its own (-sum F_i (K_i^-1)_xx F_i^T), so the linking rows can go first with their
+// expected signs, then x0, then the root equality rows y0 (zero diagonal block: they need x0 before them).  In that order a 2-link
+// Schur complement is banded: if its tile envelope is thin the root is factorised as an all-dense-tile band (TailPlan envelope: band^2
+// work per column on the MFMA kernels) - otherwise minimum degree with the usual head / tail split decides (linking rows still before
+// x0 unless y0 rows exist).
+int sparse_root_order(int S, int n_hubs, const std::vector<int>& rowptr, const std::vector<int>& colidx, int tile, int max_head_colcount,
+                      const int* force_mode, std::vector<int>& perm, std::vector<int>& colcount, int& head_cut) {
+   perm.clear();
+   for (int i = n_hubs; i < S; ++i) perm.push_back(i);
+   for (int i = 0; i < n_hubs; ++i) perm.push_back(i);
+   head_cut = 0;
+   std::vector<int> ipos(S);
+   for (int t = 0; t < S; ++t) ipos[perm[t]] = t;
+   const int nt = (S + tile - 1) / tile;
+   std::vector<int> first(nt);
+   for (int t = 0; t < nt; ++t) first[t] = t;
+   for (int rr = 0; rr < S; ++rr)
+      for (int p = rowptr[rr]; p < rowptr[rr + 1]; ++p) {
+         const int a = ipos[rr], b = ipos[colidx[p]];
+         const int tr = std::max(a, b) / tile, tc = std::min(a, b) / tile;
+         first[tr] = std::min(first[tr], tc);
+      }
+   double env = 0;
+   for (int t = 0; t < nt; ++t) env += t - first[t] + 1;
+   const bool banded = env <= 0.25 * 0.5 * nt * (nt + 1.0);
+   // A thin band is a chain: as dense tiles its diagonal tiles are factorised one after the other (63 tiles of 86 us at S = 8000 -
+   // as long as the dense root).  Dissected around the hubs x0 / y0 (ordered last) the linking rows become a tree of small fronts
+   // for the multifrontal head, a dozen dependent launches deep; only the hubs and the top separators stay dense.
+   int mode = banded ? 2 : 0;   // 0 minimum degree, 1 dense-tile band, 2 dissection (falls back to 1 without separators)
+   if (force_mode) mode = *force_mode;   // tests: force a path
+   if (mode != 2) return mode;
+   std::vector<int> ap(S + 1, 0), ai, hubs, nd_perm;
+   for (int rr = 0; rr < S; ++rr)
+      for (int p = rowptr[rr]; p < rowptr[rr + 1]; ++p)
+         if (colidx[p] != rr) { ++ap[rr + 1]; ++ap[colidx[p] + 1]; }
+   for (int i = 0; i < S; ++i) ap[i + 1] += ap[i];
+   ai.resize(ap[S]);
+   {
+      std::vector<int> fill(ap.begin(), ap.end() - 1);
+      for (int rr = 0; rr < S; ++rr)
+         for (int p = rowptr[rr]; p < rowptr[rr + 1]; ++p) {
+            const int c = colidx[p];
+            if (c != rr) { ai[fill[rr]++] = c; ai[fill[c]++] = rr; }
+         }
+   }
+   for (int i = 0; i < n_hubs; ++i) hubs.push_back(i);
+   // head = the dissected rows as long as their fronts stay LDS-resident in k_front (max_head_colcount); the cost model is no
+   // guide here (it prices a scattering head against MFMA throughput, and the band's cost is the latency of its chain of diagonal tiles)
+   int cut = 0;
+   const bool dissected = hub_dissected_order(S, ap, ai, hubs, 48, nd_perm, colcount) && (int)nd_perm.size() == S;
+   if (dissected) {
+      const int n_rest = S - (int)hubs.size();
+      while (cut < n_rest && colcount[cut] <= max_head_colcount) ++cut;
+   }
+   // (without separators - one linking row or none, say - nd_perm is empty: never take it, whatever the threshold says)
+   if (!(dissected && cut > 0 && cut >= (S - (int)hubs.size()) / 2)) return 1;   // (the band order - linking rows, then x0 - is in perm)
+   perm = nd_perm;
+   head_cut = cut;
+   return 2;
 }
 
 }  // namespace pips
