@@ -6,6 +6,7 @@ import scipy.sparse.linalg as spl
 import pips_ipmpp_amd as pa
 from oracle import oracle as orc
 from tests.util import Problem, hip_lower_as_rowmajor
+from tests.util import TimeCoupledProblem as _TimeCoupledProblem
 
 pytestmark = pytest.mark.gpu
 
@@ -410,30 +411,6 @@ def test_structured_matrices_without_inertia_hint(kind):
     assert np.linalg.norm(A @ x - rhs) / np.linalg.norm(rhs) < 1e-11
     info = s.info()
     assert info["n_levels"] >= 3 or info["m"] > 0
-
-
-class _TimeCoupledProblem(Problem):
-    """Same as Problem but W_i is banded (time-coupled constraints): chain-like elimination trees, hundreds of levels,
-    wide amalgamated supernodes, head-to-head update segments."""
-
-    def __init__(self, seed, N, n_i, my_i, n0, myl, bw):
-        import scipy.sparse as sp
-        super().__init__(seed, N, n_i, my_i, n0, myl, 0.02)
-        rng = np.random.default_rng(seed)
-        for b, blk in enumerate(self.blocks):
-            rows, cols = [], []
-            for r in range(my_i):
-                center = int(r * n_i / my_i)
-                cs = np.union1d(np.clip(center + rng.integers(-bw, bw + 1, 5), 0, n_i - 1), [center])
-                rows += [r] * len(cs)
-                cols += list(cs)
-            W = sp.csr_matrix((rng.uniform(-1, 1, len(rows)), (rows, cols)), shape=(my_i, n_i))
-            W.sum_duplicates()
-            W.sort_indices()
-            Wp = pa.Csr(my_i, n_i, W.indptr, W.indices, W.data)
-            K, dpos = pa.kkt_leaf_assemble(n_i, Wp)
-            K.val[dpos] = blk["diag"]
-            blk.update(W=Wp, K=K, dpos=dpos)
 
 
 @pytest.mark.parametrize("head", ["multifrontal", "multifrontal_devmem", "multifrontal_k_only", "scatter"])

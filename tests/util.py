@@ -56,7 +56,180 @@ class Problem:
         return orc.finalize_kkt_dense(SC, self.n0, 0, self.myl, 0, self.x_diag0, F0=self.F0.to_scipy())
 
 
+class TimeCoupledProblem(Problem):
+    """Same as Problem but W_i is banded (time-coupled constraints): chain-like elimination trees, hundreds of levels,
+    wide amalgamated supernodes, head-to-head update segments."""
+
+    def __init__(self, seed, N, n_i, my_i, n0, myl, bw):
+        super().__init__(seed, N, n_i, my_i, n0, myl, 0.02)
+        rng = np.random.default_rng(seed)
+        for b, blk in enumerate(self.blocks):
+            rows, cols = [], []
+            for r in range(my_i):
+                center = int(r * n_i / my_i)
+                cs = np.union1d(np.clip(center + rng.integers(-bw, bw + 1, 5), 0, n_i - 1), [center])
+                rows += [r] * len(cs)
+                cols += list(cs)
+            W = sp.csr_matrix((rng.uniform(-1, 1, len(rows)), (rows, cols)), shape=(my_i, n_i))
+            W.sum_duplicates()
+            W.sort_indices()
+            Wp = pa.Csr(my_i, n_i, W.indptr, W.indices, W.data)
+            K, dpos = pa.kkt_leaf_assemble(n_i, Wp)
+            K.val[dpos] = blk["diag"]
+            blk.update(W=Wp, K=K, dpos=dpos)
+
+
 def hip_lower_as_rowmajor(buf, S):
     """The HIP path writes SC column-major with the lower triangle valid; return the row-major lower triangle."""
     A = np.asarray(buf).reshape(S, S)   # A[c][r] = SC(r, c)
     return np.tril(A.T)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the sweeps judged without iterative refinement (tests/test_unrefined_reference_cpu.py, tests/test_unrefined_sweeps_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------------
+UNIT_ROUNDOFF = 2.0 ** -53
+UNREFINED_M_CAP = 64      # the largest margin the predicate may ever be given
+
+
+class UnrefinedReference:
+    """One K (a block of a Problem) and a set of right-hand sides (one per row of B): the oracle's unrefined solutions X0, its twice
+    refined ones XS, and the oracle's own measures.  Everything is computed once and read-only, tests share it."""
+
+    def __init__(self, prob, b, B):
+        self.prob, self.b = prob, b
+        Kf = prob.K_full(b).tocsr()
+        Kf.sort_indices()
+        assert np.all(np.diff(Kf.indptr) > 0)              # (every row has its diagonal: reduceat below needs no empty segment)
+        self._indptr, self._indices = Kf.indptr[:-1].copy(), Kf.indices.copy()
+        self._data = Kf.data.astype(np.longdouble)
+        self.norm_K = float(np.abs(Kf).sum(axis=1).max())
+        self.B = np.ascontiguousarray(np.atleast_2d(B), dtype=np.float64)
+        o0 = prob.oracle_leaf(b, refine_steps=0)
+        self.inertia = o0.get_inertia()
+        self.X0 = o0.solve(self.B.copy())
+        self.XS = prob.oracle_leaf(b, refine_steps=2).solve(self.B.copy())
+        self.eta_ref = self.backward_errors(self.X0)
+        self.fwd_ref = np.abs(self.X0 - self.XS).max(axis=1)
+        self.xs_norm = np.abs(self.XS).max(axis=1)
+        for a in (self.B, self.X0, self.XS, self.eta_ref, self.fwd_ref, self.xs_norm):
+            a.setflags(write=False)
+
+    def backward_errors(self, X):
+        """eta(x) = ||b - K x||inf / (||K||inf ||x||inf + ||b||inf) per right-hand side, the residual formed in long double from the
+        full symmetric K.  A zero right-hand side with a zero solution has eta = 0 (0 / 0 otherwise), anything non-finite has eta = inf."""
+        X = np.atleast_2d(X)
+        R = self.B.astype(np.longdouble) - np.add.reduceat(self._data[None, :] * X.astype(np.longdouble)[:, self._indices], self._indptr, axis=1)
+        num = np.abs(R).max(axis=1).astype(np.float64)
+        den = self.norm_K * np.abs(X).max(axis=1) + np.abs(self.B).max(axis=1)
+        eta = np.where(num == 0.0, 0.0, num / np.where(den > 0.0, den, 1.0))
+        return np.where(np.isfinite(eta), eta, np.inf)
+
+    def backward_ratios(self, X):
+        """eta(x) / max(eta_ref, 2^-53) per right-hand side: what the margin M bounds"""
+        return self.backward_errors(X) / np.maximum(self.eta_ref, UNIT_ROUNDOFF)
+
+    def forward_ratios(self, X):
+        """||x - x*||inf / max(||x_ref0 - x*||inf, 2^-53 ||x*||inf) per right-hand side (0 where x = x* = 0)"""
+        err = np.abs(np.atleast_2d(X) - self.XS).max(axis=1)
+        den = np.maximum(self.fwd_ref, UNIT_ROUNDOFF * self.xs_norm)
+        q = np.where(err == 0.0, 0.0, err / np.where(den > 0.0, den, 1.0))
+        return np.where(np.isfinite(q), q, np.inf)
+
+    def accepts(self, X, M):
+        """the predicate, per right-hand side: backward and forward"""
+        assert M <= UNREFINED_M_CAP
+        return (self.backward_ratios(X) <= M) & (self.forward_ratios(X) <= M)
+
+
+# the cases: which K, which right-hand sides.  Shapes are the smallest that still select each kernel (see the GPU module's docstring).
+UNREFINED_SINGLE_SHAPES = {
+    # id: (kind, n_i, my_i) - the time-coupled blocks of test_leaf_gpu.py's chain_and_spine / dissected cases (banded W, half width 6)
+    "chain_and_spine": ("time_coupled", 600, 300),
+    "dissected": ("time_coupled", 3000, 1500),
+    # leaf dimensions 127, 128, 129, 257 for the all-tail cut: the last 128-row tile empty / full / one row / one row past two tiles
+    "tail127": ("random", 85, 42),
+    "tail128": ("random", 86, 42),
+    "tail129": ("random", 86, 43),
+    "tail257": ("random", 171, 86),
+}
+UNREFINED_MULTI_NRHS = (2, 7, 8, 31, 32, 33, 64, 65, 256, 257)
+UNREFINED_BATCH_SHAPES = {"three_large": (3, 2600, 1300, 20, 10, 0.004), "seventy_small": (70, 400, 200, 10, 10, 0.03)}
+UNREFINED_BATCH_NRHS = 33
+
+
+def unrefined_single_problem(shape):
+    kind, n_i, my_i = UNREFINED_SINGLE_SHAPES[shape]
+    return TimeCoupledProblem(5, 1, n_i, my_i, 0, 0, 6) if kind == "time_coupled" else Problem(17, 1, n_i, my_i, 0, 0, 0.1)
+
+
+def unrefined_multi_problem():
+    n_i = 1500       # the block of test_leaf_many_rhs_on_the_matrix_pipe: a dense tail of several tiles under a sparse head
+    return Problem(5, 1, n_i, n_i // 2, 4, 4, 6.0 / n_i)
+
+
+def unrefined_batch_problem(shape):
+    # the primal diagonal spans 1e-2 .. 1e2 instead of the default 1e-4 .. 1e4: in 70 random blocks there are primal variables without
+    # a constraint entry and a diagonal near 1e-4 - x_j = b_j / d_j then carries ||x||inf while its rounding error leaves a residual
+    # of d_j * error, and ||K||inf ||x||inf hides it: the float32-rounded solution passed the predicate (ratio 39 at block 61)
+    return Problem(77, *UNREFINED_BATCH_SHAPES[shape], diag_lo=-2.0, diag_hi=2.0)
+
+
+def unrefined_rhs_rows(prob, b, nrhs, seed, units=True):
+    """nrhs right-hand sides, one per row, and which row is what: Gaussian rows, of which the last is scaled by 1e6; from 7 rows on row 1
+    is all zero and rows 2 and 3 are unit vectors whose index lies in the head and in the tail of the device's elimination order (2 rows:
+    the scaled one and the zero one; units=False: no unit vectors)."""
+    n = prob.n_leaf
+    R = np.random.default_rng(seed).standard_normal((nrhs, n))
+    what = {}
+    if nrhs >= 2:
+        what["scaled"] = nrhs - 1 if nrhs > 2 else 0
+        R[what["scaled"]] *= 1e6
+        what["zero"] = 1
+        R[1] = 0.0
+    if nrhs >= 7 and units:
+        probe = pa.symbolic_probe(prob.blocks[b]["K"], prob.n_i, want_perm=True)
+        n_head, m, perm = probe["n_head"], probe["m"], probe["perm"]
+        assert n_head > 0 and m > 0 and n_head + m == n, probe
+        what["unit_head"], what["unit_tail"] = 2, 3
+        R[2:4] = 0.0
+        R[2, perm[n_head // 2]] = 1.0             # perm[k] = the row of K that the device eliminates k-th; the tail is the last m of them
+        R[3, perm[n_head + m // 2]] = 1.0
+    return R, what
+
+
+_unrefined_cache = {}
+
+
+def unrefined_reference(kind, key):
+    """The shared references: ("single", shape) one Gaussian right-hand side; ("multi", nrhs) the rows of unrefined_rhs_rows;
+    ("batch", (shape, block, rep)) one Gaussian right-hand side per block and repetition; ("batch_multi", shape) block 0, 33 rows (Gaussian, one scaled, one zero)."""
+    k = (kind, key)
+    if k not in _unrefined_cache:
+        if kind == "single":
+            prob = _unrefined_cached_problem(kind, key)
+            ref = UnrefinedReference(prob, 0, np.random.default_rng(1).standard_normal((1, prob.n_leaf)))
+        elif kind == "multi":
+            prob = _unrefined_cached_problem(kind, None)
+            R, what = unrefined_rhs_rows(prob, 0, key, key)
+            ref = UnrefinedReference(prob, 0, R)
+            ref.what = what
+        elif kind == "batch":
+            shape, b = key
+            prob = _unrefined_cached_problem(kind, shape)
+            ref = UnrefinedReference(prob, b, np.random.default_rng(1000 + b).standard_normal((3, prob.n_leaf)))   # row = repetition
+        else:
+            prob = _unrefined_cached_problem("batch", key)
+            R, what = unrefined_rhs_rows(prob, 0, UNREFINED_BATCH_NRHS, 7, units=False)
+            ref = UnrefinedReference(prob, 0, R)
+            ref.what = what
+        _unrefined_cache[k] = ref
+    return _unrefined_cache[k]
+
+
+def _unrefined_cached_problem(kind, key):
+    k = ("problem", kind, key)
+    if k not in _unrefined_cache:
+        _unrefined_cache[k] = (unrefined_single_problem(key) if kind == "single" else unrefined_multi_problem() if kind == "multi"
+                               else unrefined_batch_problem(key))
+    return _unrefined_cache[k]
