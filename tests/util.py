@@ -233,3 +233,124 @@ def _unrefined_cached_problem(kind, key):
         _unrefined_cache[k] = (unrefined_single_problem(key) if kind == "single" else unrefined_multi_problem() if kind == "multi"
                                else unrefined_batch_problem(key))
     return _unrefined_cache[k]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the Schur contribution judged against a long-double reference (tests/test_schur_reference_cpu.py, tests/test_schur_judged_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------------
+class SchurReference:
+    """SC = - sum_b Br_b^T K_b^-1 Br_b of a Problem, twice: SC_star from the oracle's twice refined solves of the densified border columns,
+    Br^T X and the sum over the blocks accumulated in long double and rounded to float64 once; SC_ref0 by the oracle's plain FP64 algorithm
+    (add_term_to_schur_compl_blocked over unrefined solves, the sign convention of Problem.oracle_schur).  Row-major, only the lower triangle
+    counts.  finalized: with the constant root entries and diagonals of finalizeKKTdense in both (what a KktSystem hands out).  The same pair
+    is kept per block (block_star, block_ref0: the term of that block alone, non-zero on bmaps[b] x bmaps[b] only).  Computed once, read-only."""
+
+    def __init__(self, prob, finalized=False):
+        self.prob, S = prob, prob.S
+        total = np.zeros((S, S), np.longdouble)
+        self.SC_ref0 = np.zeros((S, S))
+        self.inertia, self.bmaps, self.block_star, self.block_ref0 = [], [], [], []
+        for b in range(prob.N):
+            Bt = prob.Bt_scipy(b)
+            Bt.sort_indices()
+            cols = np.nonzero(np.diff(Bt.indptr) > 0)[0]          # the block's non-empty border columns: its bmap
+            o0 = prob.oracle_leaf(b, refine_steps=0)
+            self.inertia.append(o0.get_inertia())
+            t0 = orc.add_term_to_schur_compl_blocked(np.zeros((S, S)), o0, Bt)
+            X = prob.oracle_leaf(b, refine_steps=2).solve(np.ascontiguousarray(Bt[cols].toarray()))      # (len(cols), n_leaf): K^-1 Br e_col per row
+            term = np.zeros((S, S), np.longdouble)
+            if len(cols):
+                # (Br^T x)[r] = sum of Bt's row r against x, in long double: the rows between two non-empty ones hold no entry, so the segments
+                # that start at the non-empty rows are exactly their entries
+                term[np.ix_(cols, cols)] = -np.add.reduceat(Bt.data.astype(np.longdouble)[None, :] * X.astype(np.longdouble)[:, Bt.indices], Bt.indptr[cols], axis=1)
+            total += term
+            self.SC_ref0 += t0
+            self.bmaps.append(cols)
+            self.block_star.append(np.tril(term.astype(np.float64)))
+            self.block_ref0.append(np.tril(t0))
+        if finalized:
+            total += prob.oracle_finalize(np.zeros((S, S))).astype(np.longdouble)     # (constants put into zeros: exact)
+            prob.oracle_finalize(self.SC_ref0)
+        self.SC_star = np.tril(total.astype(np.float64))
+        self.SC_ref0 = np.tril(self.SC_ref0)
+        self.scale = float(np.abs(self.SC_star).max())
+        self.err_ref0 = float(np.abs(self.SC_ref0 - self.SC_star).max())
+        self.block_scale = [float(np.abs(t).max()) for t in self.block_star]
+        self.block_err_ref0 = [float(np.abs(r - t).max()) for r, t in zip(self.block_ref0, self.block_star)]
+        for a in [self.SC_star, self.SC_ref0] + self.bmaps + self.block_star + self.block_ref0:
+            a.setflags(write=False)
+
+    @staticmethod
+    def _quotient(err, den):
+        q = 0.0 if err == 0.0 else err / (den if den > 0.0 else 1.0)
+        return float(q) if np.isfinite(q) else float("inf")
+
+    def ratio(self, SC, times=1):
+        """max|SC - SC*| / max(err_ref0, 2^-53 scale) over the lower triangle.  times = 2: a contribution accumulated twice, judged against
+        2 SC* - the reference doubles exactly and its own error with it, so the denominator doubles too."""
+        return self._quotient(float(np.abs(np.tril(SC) - times * self.SC_star).max()), times * max(self.err_ref0, UNIT_ROUNDOFF * self.scale))
+
+    def accepts(self, SC, M, times=1):
+        assert M <= UNREFINED_M_CAP
+        return self.ratio(SC, times) <= M
+
+    def block_ratio(self, b, SC):
+        """the same quotient for block b factored alone, over the rows and columns of its bmap (inf if anything outside them is touched)"""
+        idx = np.ix_(self.bmaps[b], self.bmaps[b])
+        L = np.tril(SC)
+        outside = L.copy()
+        outside[idx] = 0.0
+        if outside.any():
+            return float("inf")
+        return self._quotient(float(np.abs(L[idx] - self.block_star[b][idx]).max()) if len(self.bmaps[b]) else 0.0,
+                              max(self.block_err_ref0[b], UNIT_ROUNDOFF * self.block_scale[b]))
+
+    def block_accepts(self, b, SC, M):
+        assert M <= UNREFINED_M_CAP
+        return self.block_ratio(b, SC) <= M
+
+
+# the cases: (n_i, S, N, borders).  my_i = n_i // 2 (leaves of dimension 255 and 600: 2 and 5 tail tiles when all of K is in the tail), S is
+# split n0 = S // 2, myl = S - n0; the widths sit at the chunk of the blocked solves (32) and at the tile (128).  borders = "hetero":
+# block 1 has only the n0 border columns, block 2 only the myl ones - bmaps that differ and are proper subsets.
+SCHUR_N_I = (170, 400)
+SCHUR_WIDTHS = (1, 31, 32, 33, 127, 128, 129, 257)
+SCHUR_WIDTHS_THREE_BLOCKS = (32, 33, 129)
+SCHUR_PROBLEMS = [(n_i, S, 1, "full") for n_i in SCHUR_N_I for S in SCHUR_WIDTHS] + \
+                 [(n_i, S, 3, "full") for n_i in SCHUR_N_I for S in SCHUR_WIDTHS_THREE_BLOCKS] + [(n_i, 129, 3, "hetero") for n_i in SCHUR_N_I]
+
+
+def schur_problem(n_i, S, N, borders):
+    # primal diagonals within 1e-2 .. 1e2, as unrefined_batch_problem (and for its reason: nothing badly scaled hides an error)
+    n0 = S // 2
+    prob = Problem(300 + S, N, n_i, n_i // 2, n0, S - n0, 8.0 / n_i, diag_lo=-2.0, diag_hi=2.0)
+    rng = np.random.default_rng(300 + S)
+    for blk in prob.blocks:
+        # the generator's T_i leaves some of the n0 columns without an entry; the widths under test are those of the non-empty border columns,
+        # so every column gets one: two random entries per row as the generator's, and one in row j mod my_i of column j
+        rows = np.concatenate([np.repeat(np.arange(prob.my_i), min(2, n0)), np.arange(n0) % prob.my_i]).astype(np.int64)
+        cols = np.concatenate([rng.integers(0, max(n0, 1), prob.my_i * min(2, n0)), np.arange(n0)]).astype(np.int64)
+        T = sp.csr_matrix((rng.uniform(0.5, 1.5, len(rows)) * rng.choice([-1.0, 1.0], len(rows)), (rows, cols)), shape=(prob.my_i, n0))
+        T.sum_duplicates()
+        T.sort_indices()
+        blk["T"] = pa.Csr(prob.my_i, n0, T.indptr, T.indices, T.data)
+        blk["Bt"] = pa.border_assemble(n_i, prob.my_i, 0, n0, 0, A=blk["T"] if n0 else None, F=blk["F"])
+    if borders == "hetero":
+        blk = prob.blocks[1]
+        top = pa.border_assemble(n_i, prob.my_i, 0, n0, 0, A=blk["T"], F=None)          # n0 rows; the myl linking ones follow, empty
+        blk["Bt"] = pa.Csr(S, prob.n_leaf, np.concatenate([top.rowptr, np.full(S - n0, top.rowptr[-1], np.int32)]), top.colidx, top.val)
+        blk = prob.blocks[2]
+        blk["Bt"] = pa.border_assemble(n_i, prob.my_i, 0, n0, 0, A=None, F=blk["F"])    # S rows, the first n0 empty
+    return prob
+
+
+_schur_cache = {}
+
+
+def schur_reference(key, finalized=False):
+    """The shared SchurReference of a case of SCHUR_PROBLEMS (and its Problem: .prob)."""
+    if ("problem", key) not in _schur_cache:
+        _schur_cache[("problem", key)] = schur_problem(*key)
+    if (key, finalized) not in _schur_cache:
+        _schur_cache[(key, finalized)] = SchurReference(_schur_cache[("problem", key)], finalized)
+    return _schur_cache[(key, finalized)]
