@@ -195,6 +195,11 @@ int pips_hip_batch_border_tmult_dev(void* handle, const double* z_dev, double* b
 /* t_b += alpha * Br_b x0 for every block   (LniTransMult) */
 int pips_hip_batch_border_mult_dev(void* handle, const double* x0_dev, double* t_dev, double alpha);
 int pips_hip_batch_inertia(void* handle, int b, int* pos, int* neg, int* zero);
+/* the factorised dense tail of block b as it lies in device memory (tests compare two kernels' factors entry for entry): which = 0 the tail
+ * panel, column-major ldT x m_pad (m_pad tail rows - D on the diagonal, L below it - then the border rows), 1 its scaled copy U = L D,
+ * m_pad x m_pad (tiles strictly below the tile diagonal only), 2 the pivots d (m_pad).  dims[0..3] = m, m_pad, nb, ldT; out may be NULL
+ * (dimensions only), n_out = the doubles it holds.  Waits for the handle's stream. */
+int pips_hip_batch_tail_to_host(void* handle, int b, int which, double* out, int64_t n_out, int* dims);
 /* what[0]=sum nnz(L) what[1]=sum n what[2]=sum n_head what[3]=sum tail m what[4]=#head supernodes what[5]=max levels
  * what[6]=factor flops what[7]=border (TRSM+SYRK) flops what[8]=arena bytes what[9]=max tail tile columns
  * what[10]=bytes of the head-to-head update position tables what[11]=sum of non-empty border columns what[12]=sum nnz(K lower)

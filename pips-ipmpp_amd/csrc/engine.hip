@@ -513,6 +513,9 @@ static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
       }
       return PIPS_OK;
    };
+   // trsm of the leaf tails in the static pivot order: Winv is lower triangular, k_tile_gemm<5> skips the products with its zeros
+   // (PIPS_HIP_TRSM_DENSE=1: the dense product, for A/B runs and the test that compares the two bit for bit)
+   const bool trsm_tri = !c.bunch_kaufman && !c.is_root && env_int("PIPS_HIP_TRSM_DENSE", 0) == 0;
    int rc;
    if (c.single && c.single->n_tasks > 0) {
       const TailSingle& ts = *c.single;
@@ -590,8 +593,12 @@ static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
       }
       if (p.trsm[j].cnt > 0) {
          if (c.timer) c.timer->begin(c.stream, 4);
-         hipLaunchKernelGGL(k_tile_gemm<1>, dim3((p.trsm[j].cnt + 7) / 8 * 8), dim3(512), 0, c.stream, p.d_tasks + p.trsm[j].off, p.trsm[j].cnt,
-                            c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
+         if (trsm_tri)
+            hipLaunchKernelGGL(k_tile_gemm<5>, dim3((p.trsm[j].cnt + 7) / 8 * 8), dim3(512), 0, c.stream, p.d_tasks + p.trsm[j].off, p.trsm[j].cnt,
+                               c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
+         else
+            hipLaunchKernelGGL(k_tile_gemm<1>, dim3((p.trsm[j].cnt + 7) / 8 * 8), dim3(512), 0, c.stream, p.d_tasks + p.trsm[j].off, p.trsm[j].cnt,
+                               c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
          if (c.timer) c.timer->end(c.stream);
          // Bunch-Kaufman root that will be looked at (DenseLdl::check_pivots): multipliers beyond what a whole-column search allows?
          if (c.bunch_kaufman && c.is_root && c.d_pert_cnt)
@@ -2247,7 +2254,6 @@ static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs
    knobs.tail_single = env_flag("PIPS_HIP_TAIL_SINGLE");          // 0 / 1 forces one side (default: batches of up to 16 blocks)
    knobs.border_backward = env_flag("PIPS_HIP_BORDER_BACKWARD");  // 0 / 1 instead of the cost rule of the border-backward sweep
    knobs.aug_sweeps = env_flag("PIPS_HIP_AUG_SWEEPS");            // 0 / 1 instead of the cost rule of the sweeps of the augmented factor
-   knobs.dump_levels = getenv("PIPS_HIP_DUMP_LEVELS") != nullptr;    // development aid: shape of the head, level by level
    knobs.sweep_launches = getenv("PIPS_HIP_SWEEP_LAUNCHES") != nullptr;   // (SweepRt::build: the single-launch sweeps are off)
    const int poll = env_int("PIPS_HIP_ROOT_POLL_LIMIT", 400000);
    knobs.tail_poll_limit = poll > 0 ? (long long)poll * 50 : 0;   // (a deep update runs a millisecond)
@@ -3001,6 +3007,21 @@ int pips_hip_batch_inertia(void* handle, int b, int* pos, int* neg, int* zero) {
    if (pos) *pos = e->h_inertia[3 * b];
    if (neg) *neg = e->h_inertia[3 * b + 1];
    if (zero) *zero = e->h_inertia[3 * b + 2];
+   return PIPS_OK;
+}
+
+int pips_hip_batch_tail_to_host(void* handle, int b, int which, double* out, int64_t n_out, int* dims) {
+   Engine* e = (Engine*)handle;
+   if (!e || !e->factored || b < 0 || b >= e->nblk || which < 0 || which > 2) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_batch_tail_to_host: factor first");
+   const BlkDesc& bd = e->h_blks[b];
+   if (dims) { dims[0] = bd.m; dims[1] = bd.m_pad; dims[2] = bd.nb; dims[3] = bd.ldT; }
+   if (!out) return PIPS_OK;
+   const double* src = which == 0 ? e->d_arena + bd.T : which == 1 ? e->d_uarena + bd.U : e->d_dtail + bd.dt_off;
+   const int64_t n = which == 0 ? (int64_t)bd.ldT * bd.m_pad : which == 1 ? (int64_t)bd.m_pad * bd.m_pad : bd.m_pad;
+   if (n_out < n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_batch_tail_to_host: %lld doubles needed, %lld given", (long long)n, (long long)n_out);
+   HIP_TRY(hipSetDevice(e->device));
+   HIP_TRY(hipStreamSynchronize(e->stream));
+   if (n > 0) HIP_TRY(hipMemcpy(out, src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
    return PIPS_OK;
 }
 

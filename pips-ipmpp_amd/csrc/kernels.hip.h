@@ -1458,6 +1458,13 @@ __global__ __launch_bounds__(256) void k_head_solve_simple(const SnDesc* __restr
 //   MODE 2 (schur) : SC[bmap(ti), bmap(tj)] -= A(ti,0:K) diag(d) B(tj,0:K)^T   ti,tj border tile rows, K = m_pad
 //   MODE 3 / 4     : MODE 0 under names of their own - 3 the dense root, 4 the diagonal tiles of a leaf column that are
 //                    updated ahead of the rest (so that profiles keep the leaf update kernel apart)
+//   MODE 5 (trsm, triangular Winv): MODE 1 for the static pivot order, where Winv = D^-1 L^-1 is lower triangular (k_tile_diag):
+//                    in the staged [k][n] image every entry with k > n is an exact zero, so the MFMA of a 4-column fragment is
+//                    skipped for the k-steps right of it (wc*32 + 4c + 3 < k4) and a wave leaves a k-step whose fragments are all
+//                    skipped before its LDS reads: 528 of the 1024 MFMAs of a row of four waves remain.  The sums keep their order, the
+//                    skipped terms are +-0.  Bunch-Kaufman's Winv = Lambda^-1 G is dense and stays on MODE 1.
+// MODE 2 on a diagonal tile pair (ti == tj): the waves whose 64 x 32 sub-tile lies strictly above the diagonal (wr == 0, wc >= 2)
+// only stage - the epilogue would discard everything they compute.
 // 512 threads = 8 waves in a 2 x 4 grid, each wave owns a 64 x 32 sub-tile (32 accumulators): ~110 VGPRs, so four
 // waves share a SIMD and hide each other's LDS / barrier / DMA-issue stalls (two 256-thread workgroups per CU).
 //
@@ -1500,6 +1507,7 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
                                                double* __restrict__ gbuf = nullptr, long long gstride = 0,
                                                const int* __restrict__ blk_group = nullptr) {
    constexpr bool SCALE = (MODE == 2);   // in-loop diagonal scaling: only the Schur SYRK (border rows have no U copy)
+   constexpr bool UPD = (MODE == 0 || MODE == 3 || MODE == 4), TRSM = (MODE == 1 || MODE == 5), TRI = (MODE == 5);
    auto& As = sh.As;
    auto& Bs = sh.Bs;
    auto& Ds = sh.Ds;
@@ -1508,7 +1516,10 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
    if (task.blk < 0) return;
    const BlkDesc bd = blks[task.blk];
    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int wr = wave & 1, wc = wave >> 1;   // 8 waves: 2 (rows) x 4 (cols), each 64 rows x 32 columns
+   // 8 waves: 2 (rows) x 4 (cols), each 64 rows x 32 columns.  (The triangular trsm keeps 36 / 100 / 164 / 228 of 256 MFMAs in wave
+   // columns 0 .. 3; a map that gives waves w and w + 4 a light and a heavy column, wc = (wave >> 1) ^ (wave >> 2), measured the same
+   // 146.5 us per launch: the kernel is on its memory side by then - profiles/trsm_triangular_ab.txt)
+   const int wr = wave & 1, wc = wave >> 1;
    const int ld = bd.ldT;
    double* T = arena + bd.T;
 
@@ -1517,14 +1528,14 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
    const double* Bp;  // B panel: columns of C
    long long ldb;
    const double* dv = nullptr;
-   if (MODE == 0 || MODE >= 3) {
+   if (UPD) {
       // K range in tile columns [k0, k1): pad = k0 | k1 << 16, k1 == 0 meaning "up to the tile's own column"
       const int k0 = task.pad & 0xffff, k1 = (task.pad >> 16) ? (task.pad >> 16) : task.tj;
       K = (k1 - k0) * TILE;
       Ap = T + (long long)task.ti * TILE + (long long)k0 * TILE * ld;
       Bp = uarena + bd.U + (long long)task.tj * TILE + (long long)k0 * TILE * bd.m_pad;
       ldb = bd.m_pad;
-   } else if (MODE == 1) {
+   } else if (TRSM) {
       K = TILE;
       Ap = T + (long long)task.ti * TILE + (long long)task.tj * TILE * ld;
       Bp = winv + bd.winv_off + (long long)task.tj * TILE * TILE;
@@ -1564,6 +1575,8 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
    }
    const int rlane = wr * 64 + (lane & 15);   // row-panel fragment offset
    const int clane = wc * 32 + (lane & 3);    // column-panel fragment offset (broadcast over the 4 blocks)
+   // Schur SYRK, diagonal tile pair: this wave's sub-tile is strictly above the diagonal (it stages and takes the barriers, no more)
+   const bool above = MODE == 2 && wr * 64 + 63 < wc * 32 && __builtin_amdgcn_readfirstlane(task.ti == task.tj);
    for (int st = 0; st < nst; ++st) {
       const int buf = st & 1;
       dma_wait();        // own DMA of this stage retired
@@ -1576,6 +1589,11 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
          // matrix pipe is already busy when the address arithmetic and the four LDS-DMA instructions go out (+1.5 %; issuing
          // later still, or one instruction per quarter, loses 6-8 %: profiles/r1_fp64_issue_rates.txt)
          if (q == KB / 16 && st + 1 < nst) { issue(st + 1, buf ^ 1); load_d(st + 1, buf ^ 1); }
+         if (above) continue;
+         // triangular Winv: fragment c (columns wc*32 + 4c .. + 3) meets only zeros from k-step k4 > wc*32 + 4c + 3 on, i.e. the
+         // fragments c < c_lo; all wave-uniform (st and wc at run time, q and c unrolled)
+         const int c_lo = TRI ? (st * KB + 4 * q - wc * 32) >> 2 : 0;
+         if (TRI && c_lo > 7) continue;
          double fr[4], fc[8];
 #pragma unroll
          for (int i = 0; i < 4; ++i) fr[i] = Ab[(4 * q) * LDSW + i * 16];
@@ -1586,6 +1604,15 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
 #pragma unroll
             for (int i = 0; i < 4; ++i) fr[i] *= dq;   // A diag(d) B^T: scale the 4 row fragments, not the column ones
          }
+         if (TRI) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+               if (c < c_lo) continue;
+#pragma unroll
+               for (int i = 0; i < 4; ++i) acc[i][c] = __builtin_amdgcn_mfma_f64_4x4x4f64(fc[c], fr[i], acc[i][c], 0, 0, 0);
+            }
+            continue;
+         }
 #pragma unroll
          for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1595,7 +1622,7 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
    }
 
    // epilogue: lane holds C(row = wr*64 + 16 i + (lane&15), col = wc*32 + 4 c + (lane>>4))
-   if (MODE == 0 || MODE >= 3) {
+   if (UPD) {
       // read-modify-write of the C tile: all 32 loads go out before the first store (written as `*cp -= v` per element the
       // compiler serialises load -> wait -> store 32 times, a global round trip each)
       double* c0 = T + (long long)task.ti * TILE + wr * 64 + (lane & 15) + ((long long)task.tj * TILE + wc * 32 + (lane >> 4)) * ld;
@@ -1615,7 +1642,7 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
       }
       return;
    }
-   if (MODE == 1) {
+   if (TRSM) {
       // L tile, and for tail rows its scaled copy U = L D (B operand of the updates); the eight d_j a lane needs are
       // fetched in one go before the stores
       const int col0 = task.tj * TILE + wc * 32 + (lane >> 4), row0 = task.ti * TILE + wr * 64 + (lane & 15);
@@ -1639,6 +1666,7 @@ __device__ __forceinline__ void tile_gemm_body(int tix, GemmShared& sh, const Ti
       }
       return;
    }
+   if (above) return;
 #pragma unroll
    for (int i = 0; i < 4; ++i) {
       const int row = wr * 64 + i * 16 + (lane & 15);

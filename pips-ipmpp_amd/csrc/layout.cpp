@@ -255,7 +255,7 @@ int layout_offsets(const std::vector<BlockInput>& in, const std::vector<BlockSym
 }
 
 // ---- supernodes sorted by (level, size class); multifrontal head: by (level, kernel variant, LDS need)
-std::vector<Key> layout_sort_keys(const std::vector<BlockSym>& sym, bool mf, long long lds_budget, bool dump_levels, int nsn_total, int& nlev) {
+std::vector<Key> layout_sort_keys(const std::vector<BlockSym>& sym, bool mf, long long lds_budget, int nsn_total, int& nlev) {
    const int nblk = (int)sym.size();
    std::vector<Key> keys;
    keys.reserve(nsn_total);
@@ -293,19 +293,6 @@ std::vector<Key> layout_sort_keys(const std::vector<BlockSym>& sym, bool mf, lon
    std::stable_sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
       return a.level != b.level ? a.level < b.level : (a.cls != b.cls ? a.cls < b.cls : a.lds < b.lds);
    });
-   if (dump_levels) {   // development aid: shape of the head, level by level
-      std::vector<long long> cnt(nlev * 3, 0), rmax(nlev, 0), wsum(nlev, 0), pairs(nlev, 0);
-      for (const Key& k : keys) {
-         const HeadSupernode& s = sym[k.blk].sn[k.loc];
-         ++cnt[k.level * 3 + std::min(k.cls, 2)];
-         rmax[k.level] = std::max<long long>(rmax[k.level], s.r);
-         wsum[k.level] += s.w;
-         pairs[k.level] += (long long)s.r * (s.r + 1) / 2;
-      }
-      for (int l = 0; l < nlev; ++l)
-         fprintf(stderr, "level %3d: simple %lld small %lld large %lld  columns %lld  max r %lld  update pairs %lld\n", l, cnt[3 * l], cnt[3 * l + 1],
-                 cnt[3 * l + 2], wsum[l], rmax[l], pairs[l]);
-   }
    return keys;
 }
 
@@ -741,7 +728,7 @@ int build_batch_layout(const std::vector<BlockInput>& in, const std::vector<Bloc
    Bases B;
    int rc, nlev = 0;
    if ((rc = layout_offsets(in, sym, out.mf, out, B))) return rc;
-   const std::vector<Key> keys = layout_sort_keys(sym, out.mf, knobs.mf_lds_doubles, knobs.dump_levels, out.nsn_total, nlev);
+   const std::vector<Key> keys = layout_sort_keys(sym, out.mf, knobs.mf_lds_doubles, out.nsn_total, nlev);
    out.n_levels_all = nlev;
    const int lstar = layout_spine_cut(sym, nlev, knobs);
    std::vector<std::vector<int>> sorted_id, roots_of;

@@ -66,7 +66,6 @@ struct LayoutKnobs {
    int spine = -1;              // 0: no spine kernels
    int tail_single = -1;        // 0 / 1 forces one side of the single-launch tail factorisation
    int border_backward = -1, aug_sweeps = -1;   // 0 / 1 instead of the cost rules of the sweeps of the augmented factor
-   bool dump_levels = false;    // development aid: shape of the head, level by level, to stderr
    bool sweep_launches = false; // the launch-per-tile-column solve sweeps are selected (the single-launch sweeps are off)
    long long free_device_bytes = 0;   // the one runtime input: free device memory, decides tail_single
    // settled by analyze_symbolic

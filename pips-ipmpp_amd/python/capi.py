@@ -60,7 +60,7 @@ SYMBOLS = [
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
     "pips_hip_batch_set_values", "pips_hip_batch_set_diagonals_dev", "pips_hip_batch_set_diagonals", "pips_hip_batch_factor",
     "pips_hip_batch_solve_dev", "pips_hip_batch_solve", "pips_hip_batch_border_tmult_dev", "pips_hip_batch_border_mult_dev",
-    "pips_hip_batch_inertia", "pips_hip_batch_info", "pips_hip_batch_sync", "pips_hip_batch_set_timing",
+    "pips_hip_batch_inertia", "pips_hip_batch_tail_to_host", "pips_hip_batch_info", "pips_hip_batch_sync", "pips_hip_batch_set_timing",
     "pips_hip_batch_get_timing", "pips_hip_batch_destroy",
     "pips_hip_kkt_create", "pips_hip_kkt_create_sparse", "pips_hip_kkt_get_schur_sparse", "pips_hip_kkt_sparse_root_info", "pips_hip_kkt_factorize", "pips_hip_kkt_set_root_regularization", "pips_hip_kkt_solve_compressed", "pips_hip_kkt_get_schur",
     "pips_hip_kkt_set_root_inequalities", "pips_hip_kkt_set_zdiag0_dev",
@@ -548,6 +548,17 @@ class LeafBatch:
         p, n, z = C.c_int(), C.c_int(), C.c_int()
         _check(lib.pips_hip_batch_inertia(self._h, C.c_int(b), C.byref(p), C.byref(n), C.byref(z)), "batch inertia")
         return p.value, n.value, z.value
+
+    def tail_to_host(self, b, which):
+        """block b's factorised tail: which = "panel" (ldT x m_pad), "U" (m_pad x m_pad) or "d" (m_pad), with (m, m_pad, nb, ldT)"""
+        w = {"panel": 0, "U": 1, "d": 2}[which]
+        dims = (C.c_int * 4)()
+        _check(lib.pips_hip_batch_tail_to_host(self._h, C.c_int(b), C.c_int(w), None, C.c_int64(0), dims), "pips_hip_batch_tail_to_host")
+        m, m_pad, nb, ldT = (int(v) for v in dims)
+        shape = {0: (m_pad, ldT), 1: (m_pad, m_pad), 2: (m_pad,)}[w]   # (column, row): the device arrays are column-major
+        out = np.zeros(shape, np.float64)
+        _check(lib.pips_hip_batch_tail_to_host(self._h, C.c_int(b), C.c_int(w), _ptr(out), C.c_int64(out.size), dims), "pips_hip_batch_tail_to_host")
+        return (out.T if w < 2 else out), (m, m_pad, nb, ldT)
 
     def info(self):
         what = np.zeros(26, np.int64)
