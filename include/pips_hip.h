@@ -204,7 +204,9 @@ int pips_hip_batch_tail_to_host(void* handle, int b, int which, double* out, int
  * what[6]=factor flops what[7]=border (TRSM+SYRK) flops what[8]=arena bytes what[9]=max tail tile columns
  * what[10]=bytes of the head-to-head update position tables what[11]=sum of non-empty border columns what[12]=sum nnz(K lower)
  * what[13]=1 if solveCompressed takes its Ltsolve from the augmented factor (one backward sweep) while no pivot is perturbed
- * what[14]=1 multifrontal head ... what[24]=blocks analysed with the border split of the fronts (python/capi.py LeafBatch.info names all) */
+ * what[14]=1 multifrontal head ... what[24]=blocks analysed with the border split of the fronts; what[26]=right-hand sides of the packed
+ * blocked solves (max over the blocks of their non-empty border columns; Schur mode 2 with the sparse root), 0 where that path is
+ * not active (python/capi.py LeafBatch.info names all) */
 int pips_hip_batch_info(void* handle, int64_t* what, int n_what);
 int pips_hip_batch_sync(void* handle);
 /* per-phase device time in ms (HIP events on the handle's stream) of the last pips_hip_batch_factor
@@ -238,7 +240,9 @@ int pips_hip_kkt_create(void** handle, void* batch, int n0, int my0, int myl, in
  * 2-link structure (a linking row touches two blocks), where SC is sparse and S may be far beyond what S x S storage allows.
  * blk_cols_ptr / blk_cols: border column sets (ascending Schur column ids) of ALL n_blocks_global blocks of the problem -
  * required with n_ranks > 1 so that every rank reduces the same value array; NULL = the blocks of this batch.
- * The batch must be analyzed and use Schur mode 1 (set it explicitly for structured blocks). */
+ * The batch must be analyzed; either Schur mode works.  Mode 1 accumulates into the value array from the augmented factorisation;
+ * mode 2 forms it by blocked solves packed by block-local column (right-hand side q carries every block's q-th non-empty border
+ * column: max_b nb_b right-hand sides, pips_hip_batch_info what[26]) and, as with the dense root, leaves solveCompressed on path 0. */
 int pips_hip_kkt_create_sparse(void** handle, void* batch, int n0, int my0, int myl, int mzl, const int* A0_rowptr,
                                const int* A0_colidx, const double* A0_val, const int* F0_rowptr, const int* F0_colidx,
                                const double* F0_val, const int* G0_rowptr, const int* G0_colidx, const double* G0_val,
@@ -562,6 +566,12 @@ int pips_symbolic_probe_hubs(int n, int n_primal, const int* krow, const int* jc
 int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol,
                       int S, const int* const* bt_rowptr, const int* const* bt_colidx,
                       int deterministic, long long free_device_bytes, int64_t* what, int n_what);
+
+/* The tables of the packed blocked solves (Schur mode 2 with the sparse root), without a device; the code the engine builds its own
+ * with.  bt_rowptr[b]: the S + 1 row pointers of block b's border (NULL: no border).  nb[b] (nblk entries): the block's non-empty
+ * border columns; *nb_max their maximum = the right-hand sides of the packed solves; local_of_row[b] (S entries each): the local index
+ * of Schur column s in block b, ascending in s, -1 for an empty column. */
+int pips_schur_pack_probe(int nblk, int S, const int* const* bt_rowptr, int* nb, int* nb_max, int* const* local_of_row);
 
 /* ---- 6. input files ---------------------------------------------------------------------------------------------------
  * One block of a block-structured LP from a "jacobian" GDX file, the format gmspips_reader opens per block

@@ -715,6 +715,15 @@ struct EngineAnalysis {
    DevBuf<long long> d_flong;               // its rows longer than FULL_LONG_ROW
    DevBuf<int> d_sctab;                     // sparse Schur complement (set_sc_tables): position tables, BlkDesc::sctab_off
    DevBuf<int> d_schur_cols, d_schur_slot;
+   // Schur mode 2 into the sparse Schur complement (set_sc_tables; Engine::schur_by_packed_solves): the blocks' border column sets, per
+   // border row its local index (-1: empty) and the start of its row of the block's position table, and on the host what the lists of
+   // deterministic mode are built from
+   SchurPack pack;
+   int packed_rhs = 0;                  // max_b nb_b where the packed path is active, else 0
+   DevBuf<int> d_pk_la;
+   DevBuf<long long> d_pk_tabrow;
+   std::vector<int> h_pk_la, h_pk_tab;
+   std::vector<long long> h_pk_tabrow;
    // fronts on the rows of K only (BlockSym::mf_konly): records and lists of k_border_rows / k_border_tail
    DevBuf<int> d_kb_rec;
    DevBuf<long long> d_kb_off;          // per supernode (sorted id): offset of its record, -1 none
@@ -763,6 +772,7 @@ struct EngineAnalysis {
    GatherList g_tail, g_sc, gv_tail;
    GatherList g_sc_grp;                 // Schur targets of the head inside the group buffers
    GatherList g_btm_grp;                // border rows per (group, Schur column): Br^T z summed group-wise, then in the fixed tree
+   GatherList g_pk_grp;                 // packed blocked solves: contributions per (group, position of the value array) (k_border_tmult_chunk_packed_det)
    DevBuf<double> d_gvec, d_tvec;
    DevBuf<TileTask> d_det_tasks;
    DevBuf<double> d_gbuf;
@@ -940,6 +950,16 @@ struct Engine : EngineAnalysis, BatchLayout {
          PIPS_TRY(d_gvec.alloc((size_t)8 * S));
          PIPS_TRY(d_tvec.alloc((size_t)S));
          if ((rc = build_det_aug(grp))) return rc;
+      }
+      // packed blocked solves: per (group, position of the value array) its contributions (border row << 24 | local column); sorted by
+      // that word = by block within a target, the order k_border_tmult_chunk_packed_det adds them in
+      g_pk_grp = GatherList();
+      if (packed_rhs > 0) {
+         std::vector<SlotEntry> ent;
+         for (long long i = 0; i < bt_rows_total; ++i)
+            for (int q = 0; q <= h_pk_la[(size_t)i]; ++q)
+               ent.push_back({(long long)grp[h_bt_rowblk[(size_t)i]] * det_gstride() + h_pk_tab[(size_t)(h_pk_tabrow[(size_t)i] + q)], (i << 24) | q});
+         if ((rc = upload_gather(ent, g_pk_grp))) return rc;
       }
       if (!det_aug_ready) aug_sweeps_ok = false;   // (deterministic mode takes the sweeps of the augmented factor only through forward_augmented_det)
       return PIPS_OK;
@@ -1448,15 +1468,43 @@ struct Engine : EngineAnalysis, BatchLayout {
 
    // Sparse Schur complement: tab holds, block after block, the nb x nb table "position of entry (la, lb), la >= lb, of this
    // block's contribution inside the value array of SC's lower-triangular CSR"; factor(values, 0) then accumulates there.
+   // la / lb count the block's non-empty border columns (border_pack(): BlockSym::bmap is empty where the border stayed out of the
+   // symbolic analysis).  Schur mode 2: the blocked solves run packed by these local columns (schur_by_packed_solves); their per-row
+   // tables are built here, once.
+   const SchurPack& border_pack() {
+      if (pack.off.empty()) build_schur_pack(in, S, pack);
+      return pack;
+   }
    int set_sc_tables(const std::vector<int>& tab, const std::vector<long long>& off, long long sc_nnz) {
       if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_tables: analyze first");
-      if (schur_mode_eff != 1) PIPS_FAIL(PIPS_ERR_STATE, "a sparse Schur complement needs Schur mode 1 (set it before analyze)");
       HIP_TRY(hipSetDevice(device));
       int rc = d_sctab.upload(tab);
       if (rc) return rc;
       for (int b = 0; b < nblk; ++b) h_blks[b].sctab_off = off[b];
       HIP_TRY(hipMemcpy(d_blks, h_blks.data(), (size_t)nblk * sizeof(BlkDesc), hipMemcpyHostToDevice));
       sc_len = sc_nnz;
+      packed_rhs = 0;
+      if (schur_mode_eff == 2) {
+         const SchurPack& pk = border_pack();
+         if (pk.nb_max >= (1 << 24)) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_tables: %d border columns in one block exceed the packed solves' 2^24", pk.nb_max);
+         h_pk_la.clear(); h_pk_tabrow.clear();
+         std::vector<int> local(std::max(S, 1));
+         for (int b = 0; b < nblk; ++b) {
+            if (in[b].btrow.empty()) continue;   // (the rows of the global border CSR: S per block with a border, layout_border_csr)
+            const int nb_b = schur_pack_block(S, in[b].btrow.data(), local.data());
+            if (off[b] + (long long)nb_b * nb_b > (long long)tab.size())
+               PIPS_FAIL(PIPS_ERR_ARG, "set_sc_tables: the position table of block %d is shorter than its %d x %d border columns", b, nb_b, nb_b);
+            for (int s = 0; s < S; ++s) {
+               h_pk_la.push_back(local[s]);
+               h_pk_tabrow.push_back(local[s] >= 0 ? off[b] + (long long)local[s] * nb_b : 0);
+            }
+         }
+         if ((long long)h_pk_la.size() != bt_rows_total) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_tables: %zu border rows, the analysis holds %lld", h_pk_la.size(), bt_rows_total);
+         if ((rc = d_pk_la.upload(h_pk_la)) || (rc = d_pk_tabrow.upload(h_pk_tabrow))) return rc;
+         if (deterministic) h_pk_tab = tab;   // (set_det_groups builds the lists of k_border_tmult_chunk_packed_det from it)
+         else { std::vector<int>().swap(h_pk_la); std::vector<long long>().swap(h_pk_tabrow); }
+         packed_rhs = pk.nb_max;
+      }
       if (head_slots) {   // the Schur targets of the head moved into the CSR value array: record again
          g_levels.clear(); gv_levels.clear();
          g_tail = GatherList(); g_sc = GatherList(); gv_tail = GatherList();
@@ -1563,9 +1611,9 @@ struct Engine : EngineAnalysis, BatchLayout {
       factored = true;
       perturbed_cache = -1;
       if (SC && schur_mode_eff == 2 && !schur_cols.empty()) {
-         if (timer.on) timer.begin(stream, 5);
+         const int rec_schur = timer.begin_i(stream, 5);   // (stays open across the records of the solves inside: solve_once times its sweeps)
          rc = schur_by_solves(SC, ldSC);
-         if (timer.on) timer.end(stream);
+         timer.end_i(rec_schur, stream);
          if (rc) return rc;
       }
       if (SC && c.det_rounds && c.det_reduce_later) reduce_det_groups(c, SC, ldSC);   // one fixed-tree add, after every chunk
@@ -1594,6 +1642,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       int rc = ensure_multi_buffers();
       if (rc) return rc;
       const bool det = deterministic && d_gbuf;
+      if (packed_rhs > 0) return schur_by_packed_solves(SC, det);
       if (det && ldSC != S) PIPS_FAIL(PIPS_ERR_ARG, "deterministic mode, Schur mode 2: ldSC %d must equal S %d (the group buffers are S x S)", ldSC, S);
       const bool det_panel = det && det_panel_fits();
       if (det_panel && !d_mvslot) PIPS_TRY(d_mvslot.alloc((size_t)std::max<long long>(vslots_total, 1) * MQ));
@@ -1618,6 +1667,38 @@ struct Engine : EngineAnalysis, BatchLayout {
          hipLaunchKernelGGL(k_border_tmult_chunk, dim3(grid_for(bt_rows_total, 256, 1024), nr), dim3(256), 0, stream, d_bt_rowptr,
                             d_bt_colidx, d_bval, d_bt_rowsc, d_bt_xoff, d_schur_cols + c0, nr, d_mx_rhs, n_total, SC, ldSC,
                             bt_rows_total);
+      }
+      HIP_TRY(hipGetLastError());
+      return PIPS_OK;
+   }
+   // The same into the value array of the sparse Schur complement (set_sc_tables), the border columns packed block by block: chunks of 32
+   // LOCAL columns - right-hand side q holds every block's q-th non-empty border column, so packed_rhs = max_b nb_b right-hand sides
+   // instead of one per distinct Schur column (2-link borders: n0 plus two pairs' linking rows, whatever the number of blocks).  Same
+   // clear, same choice of sweeps as above; the three kernels address by local column (kernels.hip.h, k_border_tmult_chunk_packed)
+   int schur_by_packed_solves(double* values, bool det) {
+      int rc = PIPS_OK;
+      const bool det_panel = det && det_panel_fits();
+      if (det_panel && !d_mvslot) PIPS_TRY(d_mvslot.alloc((size_t)std::max<long long>(vslots_total, 1) * MQ));
+      const int bs = 32;
+      for (int q0 = 0; q0 < packed_rhs; q0 += bs) {
+         const int nr = std::min(bs, packed_rhs - q0);
+         HIP_TRY(hipMemsetAsync(d_mx_rhs, 0, (size_t)nr * n_total * sizeof(double), stream));
+         hipLaunchKernelGGL(k_border_rows_to_dense_packed, dim3(grid_for(bt_rows_total, 256)), dim3(256), 0, stream, d_bt_rowptr, d_bt_colidx,
+                            d_bval, d_bt_xoff, d_pk_la, q0, nr, d_mx_rhs, n_total, bt_rows_total);
+         if (det) {
+            if (det_panel) rc = solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw, 1);
+            else
+               for (int r = 0; r < nr && !rc; ++r) rc = solve_once(d_mx_rhs + (long long)r * n_total);
+            if (rc) return rc;
+            if (g_pk_grp.n_targets > 0)
+               hipLaunchKernelGGL(k_border_tmult_chunk_packed_det, dim3(grid_for(g_pk_grp.n_targets, 256)), dim3(256), 0, stream, g_pk_grp.n_targets,
+                                  g_pk_grp.d_tgt, g_pk_grp.d_off, g_pk_grp.d_slots, d_bt_rowptr, d_bt_colidx, d_bval, d_bt_xoff, q0, nr, d_mx_rhs,
+                                  n_total, d_gbuf);
+            continue;
+         }
+         if ((rc = use_multi(nr) ? solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw) : solve_once(d_mx_rhs, nr, n_total, d_mx_xw))) return rc;
+         hipLaunchKernelGGL(k_border_tmult_chunk_packed, dim3(grid_for(bt_rows_total, 256, 1024), nr), dim3(256), 0, stream, d_bt_rowptr,
+                            d_bt_colidx, d_bval, d_bt_xoff, d_pk_la, d_pk_tabrow, d_sctab, q0, nr, d_mx_rhs, n_total, values, bt_rows_total);
       }
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
@@ -3069,6 +3150,7 @@ int pips_hip_batch_info(void* handle, int64_t* what, int n_what) {
    }
    if (n_what > 24) { what[24] = 0; for (const BlockSym& s : e->sym) what[24] += s.mf_split ? 1 : 0; }   // blocks with the border split
    if (n_what > 25) { what[25] = 0; for (const BlockSym& s : e->sym) what[25] += (e->mf && s.mf_konly) ? 1 : 0; }   // ... whose fronts hold the rows of K only
+   if (n_what > 26) what[26] = e->packed_rhs;   // right-hand sides of the packed blocked solves (Schur mode 2 with the sparse root), else 0
    return PIPS_OK;
 }
 

@@ -1896,14 +1896,14 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
    if (sparse_root && p->n_ranks > 1)
       PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: the sparse root needs the border column sets of all blocks on every rank (pips_hip_kkt_create_sparse); "
                               "the harness passes only its own - use the dense root with several ranks");
-   if (sparse_root && (rc = pips_hip_batch_set_schur_mode(p->batch, 1))) return rc;
+   if (sparse_root && (rc = pips_hip_batch_set_schur_mode(p->batch, 1))) return rc;   // (the sparse root's default where PIPS_IPM_SCHUR_MODE is unset)
    // PIPS_IPM_SCHUR_MODE: how the leaves form their Schur contribution (pips_hip_batch_set_schur_mode: 0 auto, 1 augmented factorisation,
-   // 2 blocked solves - the reference's SC_COMPUTE_BLOCKWISE); unset: the batch's default
+   // 2 blocked solves - the reference's SC_COMPUTE_BLOCKWISE; with the sparse root packed by block-local column); unset: the batch's
+   // default, mode 1 with the sparse root
    if (const char* sm = getenv("PIPS_IPM_SCHUR_MODE")) {
       const int mode = atoi(sm);
       if (mode < 0 || mode > 2) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: PIPS_IPM_SCHUR_MODE=%s (0 auto, 1 augmented, 2 blocked solves)", sm);
-      if (sparse_root && mode == 2) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: the sparse root needs Schur mode 1, PIPS_IPM_SCHUR_MODE=2 asks for blocked solves");
-      if (!sparse_root && (rc = pips_hip_batch_set_schur_mode(p->batch, mode))) return rc;
+      if ((rc = pips_hip_batch_set_schur_mode(p->batch, mode))) return rc;
    }
    if ((rc = pips_hip_batch_analyze(p->batch, 16))) return rc;
    for (int i = 0; i < N; ++i)

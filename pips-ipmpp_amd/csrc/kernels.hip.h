@@ -3649,6 +3649,75 @@ __global__ __launch_bounds__(256) void k_border_tmult_chunk_det(long long n_targ
    }
 }
 
+// Blocked Schur path into the sparse root's value array: the border columns packed block by block.  Right-hand side q of the packed
+// solves carries, in every block, that block's q-th non-empty border column (local index q of the block's nb x nb position table,
+// sc_entry), so one interleaved sweep solves a different Schur column in every block and max_b nb_b right-hand sides do for all of
+// them.  Per border row i (Engine::set_sc_tables): la[i] = the row's local index in its block, -1 for an empty row; tabrow[i] = where
+// row la of its block's position table starts inside sctab.  A row with la < q has nothing in column q (lower triangle), and a block
+// with nb <= q has no such row: its table is never read past.
+__global__ void k_border_rows_to_dense_packed(const int* __restrict__ rowptr, const int* __restrict__ colidx,
+                                              const double* __restrict__ val, const long long* __restrict__ row_xoff,
+                                              const int* __restrict__ la, int q0, int nr, double* __restrict__ R, long long r_stride,
+                                              long long nrows) {
+   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nrows; i += (long long)gridDim.x * blockDim.x) {
+      const int r = la[i] - q0;
+      if (r < 0 || r >= nr) continue;
+      double* dst = R + r * r_stride + row_xoff[i];
+      for (int p = rowptr[i]; p < rowptr[i + 1]; ++p) dst[colidx[p]] = val[p];
+   }
+}
+
+// values[sctab[tabrow[i] + q]] -= Br_b^T(i, :) X_r restricted to block b, q = q0 + r <= la[i]
+// (addLeftBorderTimesDenseColsToResTranspSparse, DistributedLinearSystem.C:1050-1113)
+__global__ void k_border_tmult_chunk_packed(const int* __restrict__ rowptr, const int* __restrict__ colidx,
+                                            const double* __restrict__ val, const long long* __restrict__ row_xoff,
+                                            const int* __restrict__ la, const long long* __restrict__ tabrow,
+                                            const int* __restrict__ sctab, int q0, int nr, const double* __restrict__ X,
+                                            long long x_stride, double* __restrict__ values, long long nrows) {
+   const int r = blockIdx.y;
+   if (r >= nr) return;
+   const int q = q0 + r;
+   const double* x = X + r * x_stride;
+   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nrows; i += (long long)gridDim.x * blockDim.x) {
+      if (la[i] < q) continue;   // (an empty row has la = -1)
+      const long long xo = row_xoff[i];
+      double s = 0.0;
+      for (int p = rowptr[i]; p < rowptr[i + 1]; ++p) s += val[p] * x[xo + colidx[p]];
+      if (s != 0.0) atomic_add_f64(values + sctab[tabrow[i] + q], -s);
+   }
+}
+
+// deterministic mode: the same product without atomics.  Two blocks reach one position of the value array through different local
+// columns, possibly in different chunks, so a target cannot be summed in registers and stored once as k_border_tmult_chunk_det does.
+// Target t of Engine::g_pk_grp is g gstride + pos and lists the contributions to position pos from group g as (border row i << 24 | local
+// column q), ascending = in block order (a block reaches a position through one (la, q) only).  A thread owns a target and adds the
+// contributions of this chunk's columns [q0, q0 + nr) to gbuf[target] in list order, a plain read-modify-write on group buffers that
+// Engine::factor zeroed; the chunks are launches of one stream, so the order of all additions to a position is fixed at analyse time
+// and depends on block-local quantities only - not on the rank count (the groups hold the same blocks).
+__global__ __launch_bounds__(256) void k_border_tmult_chunk_packed_det(long long n_targets, const long long* __restrict__ tgt,
+                                                                      const long long* __restrict__ off, const long long* __restrict__ ent,
+                                                                      const int* __restrict__ rowptr, const int* __restrict__ colidx,
+                                                                      const double* __restrict__ val, const long long* __restrict__ row_xoff,
+                                                                      int q0, int nr, const double* __restrict__ X, long long x_stride,
+                                                                      double* __restrict__ gbuf) {
+   for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n_targets; t += (long long)gridDim.x * blockDim.x) {
+      double acc = 0.0;
+      bool any = false;
+      for (long long p = off[t]; p < off[t + 1]; ++p) {
+         const long long e = ent[p];
+         const int r = (int)(e & 0xffffff) - q0;
+         if (r < 0 || r >= nr) continue;
+         const long long i = e >> 24;
+         const double* x = X + r * x_stride + row_xoff[i];
+         double d = 0.0;
+         for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) d += val[k] * x[colidx[k]];
+         if (!any) { acc = gbuf[tgt[t]]; any = true; }
+         acc -= d;
+      }
+      if (any) gbuf[tgt[t]] = acc;
+   }
+}
+
 // dense helpers for the root system
 __global__ void k_copy_lower_to_padded(const double* __restrict__ src, int lds, int n, double* __restrict__ dst, int ldd,
                                        int npad, int rowmajor, const int* __restrict__ perm = nullptr) {

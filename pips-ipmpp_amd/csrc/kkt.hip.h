@@ -260,14 +260,17 @@ struct KktSystem {
       std::vector<std::pair<const int*, int>> cliques;
       if (blk_cols_ptr)
          for (int b = 0; b < n_blocks_global; ++b) cliques.emplace_back(blk_cols + blk_cols_ptr[b], blk_cols_ptr[b + 1] - blk_cols_ptr[b]);
-      for (int b = 0; b < e->nblk; ++b) cliques.emplace_back(e->sym[b].bmap.data(), (int)e->sym[b].bmap.size());
+      // (the blocks' non-empty border columns from the border's row pointers: BlockSym::bmap holds the same where the border took part in
+      //  the symbolic analysis and is empty in Schur mode 2 - pattern, position tables and the packed solves' tables rest on one rule)
+      const SchurPack& pk = e->border_pack();
+      for (int b = 0; b < e->nblk; ++b) cliques.emplace_back(pk.block_cols(b), pk.nb[b]);
       sc_lower_pattern(S, n0, rows, cliques, sc_rowptr, sc_colidx);
       // ---- per-block position tables for the leaf kernels
       std::vector<int> tab;
       std::vector<long long> off(e->nblk, 0);
       for (int b = 0; b < e->nblk; ++b) {
-         const std::vector<int>& bm = e->sym[b].bmap;
-         const int nb = (int)bm.size();
+         const int* bm = pk.block_cols(b);
+         const int nb = pk.nb[b];
          off[b] = (long long)tab.size();
          tab.resize(tab.size() + (size_t)nb * nb, 0);
          for (int la = 0; la < nb; ++la)

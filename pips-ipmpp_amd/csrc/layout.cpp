@@ -142,6 +142,27 @@ bool blocked_solves_cheaper(const std::vector<BlockSym>& sym, int S, const Analy
    return t_sol < t_aug;
 }
 
+int schur_pack_block(int S, const int* bt_rowptr, int* local_of_row) {
+   int nb = 0;
+   for (int s = 0; s < S; ++s) local_of_row[s] = (bt_rowptr && bt_rowptr[s + 1] > bt_rowptr[s]) ? nb++ : -1;
+   return nb;
+}
+
+void build_schur_pack(const std::vector<BlockInput>& in, int S, SchurPack& out) {
+   const int nblk = (int)in.size();
+   out = SchurPack();
+   out.nb.assign(nblk, 0);
+   out.off.assign(nblk + 1, 0);
+   std::vector<int> local(std::max(S, 1));
+   for (int b = 0; b < nblk; ++b) {
+      out.nb[b] = schur_pack_block(S, in[b].btrow.empty() ? nullptr : in[b].btrow.data(), local.data());
+      for (int s = 0; s < S; ++s)
+         if (local[s] >= 0) out.cols.push_back(s);
+      out.off[b + 1] = (long long)out.cols.size();
+      out.nb_max = std::max(out.nb_max, out.nb[b]);
+   }
+}
+
 int analyze_blocks(const std::vector<BlockInput>& in, int S, const AnalyzeOptions& opt, int n_threads, bool with_border, std::vector<BlockSym>& sym) {
    const int nblk = (int)in.size();
    sym.assign(nblk, BlockSym());
@@ -922,3 +943,15 @@ void BatchLayout::drop_uploaded() {
 }
 
 }  // namespace pips
+
+// ---- probe of the packed blocked solves' tables (CPU only): schur_pack_block as Engine::set_sc_tables calls it
+extern "C" int pips_schur_pack_probe(int nblk, int S, const int* const* bt_rowptr, int* nb, int* nb_max, int* const* local_of_row) {
+   if (nblk <= 0 || S < 0 || !bt_rowptr || !nb || !nb_max || !local_of_row) PIPS_FAIL(pips::PIPS_ERR_ARG, "pips_schur_pack_probe: bad arguments");
+   *nb_max = 0;
+   for (int b = 0; b < nblk; ++b) {
+      if (!local_of_row[b]) PIPS_FAIL(pips::PIPS_ERR_ARG, "pips_schur_pack_probe: local_of_row[%d] is NULL", b);
+      nb[b] = pips::schur_pack_block(S, bt_rowptr[b], local_of_row[b]);
+      *nb_max = std::max(*nb_max, nb[b]);
+   }
+   return pips::PIPS_OK;
+}

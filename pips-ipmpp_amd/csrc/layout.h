@@ -73,6 +73,21 @@ struct LayoutKnobs {
    int schur_mode_eff = 1;
 };
 
+// Every block's non-empty border columns from the border's row pointers alone - the column sets the sparse root's pattern, its position
+// tables and the packed blocked solves (Schur mode 2 with the sparse root: right-hand side q carries, in every block, that block's q-th
+// column) are built on.  Equal to BlockSym::bmap where the border took part in the symbolic analysis; filled in Schur mode 2 as well.
+struct SchurPack {
+   std::vector<int> nb;          // per block: non-empty border columns
+   std::vector<long long> off;   // nblk + 1 offsets into cols
+   std::vector<int> cols;        // the blocks' column sets (Schur column ids), ascending, block after block
+   int nb_max = 0;               // right-hand sides of the packed solves
+   const int* block_cols(int b) const { return cols.data() + off[b]; }
+};
+// one block: local_of_row[s] = position of Schur column s among the block's non-empty columns, -1 for an empty one (bt_rowptr == nullptr:
+// no border, all -1); returns their number
+int schur_pack_block(int S, const int* bt_rowptr, int* local_of_row);
+void build_schur_pack(const std::vector<BlockInput>& in, int S, SchurPack& out);
+
 // Everything Engine::analyze() computes on the host.  The engine keeps this record; the arrays under "uploaded, then dropped" are
 // cleared after their upload (drop_uploaded).
 struct BatchLayout {

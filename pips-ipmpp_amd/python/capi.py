@@ -74,7 +74,7 @@ SYMBOLS = [
     "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
-    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks",
+    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe",
 ]
 
 # problem scalers (pips_ipm_create_general_scaled; the order of the reference's ScalerType)
@@ -276,6 +276,21 @@ def symbolic_probe_hubs(K, hubs, n_primal=-1, min_size=48):
     return dict(nnzL=int(what[0]), n=int(what[1]), n_head=int(what[2]), m=int(what[3]), n_sn=int(what[4]), n_levels=int(what[5]),
                 flops_factor=int(what[6]), flops_border=int(what[7]), arena_bytes=int(what[8]), ntc=int(what[9]),
                 upd_bytes=int(what[10]), perm=perm, colcount=cc)
+
+
+def schur_pack_probe(Bts, S):
+    """Tables of the packed blocked solves (Schur mode 2 with the sparse root) for the borders Bts (CSR with S rows each, None: a block
+    without border), from the host code the engine uses: (nb per block, nb_max, local_of_row as an (nblk, S) array, -1 = empty)."""
+    nblk = len(Bts)
+    ip = C.POINTER(C.c_int)
+    nb = np.zeros(nblk, np.int32)
+    nb_max = C.c_int(0)
+    local = np.zeros((nblk, max(S, 1)), np.int32)
+    rps = [None if Bt is None else _i32(Bt.rowptr) for Bt in Bts]
+    rp = (ip * nblk)(*[ip() if r is None else r.ctypes.data_as(ip) for r in rps])
+    lo = (ip * nblk)(*[local[b].ctypes.data_as(ip) for b in range(nblk)])
+    _check(lib.pips_schur_pack_probe(C.c_int(nblk), C.c_int(S), rp, _ptr(nb), C.byref(nb_max), lo), "pips_schur_pack_probe")
+    return nb, int(nb_max.value), local[:, :S]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -561,11 +576,12 @@ class LeafBatch:
         return (out.T if w < 2 else out), (m, m_pad, nb, ldT)
 
     def info(self):
-        what = np.zeros(26, np.int64)
-        _check(lib.pips_hip_batch_info(self._h, _ptr(what), C.c_int(26)), "pips_hip_batch_info")
+        what = np.zeros(27, np.int64)
+        _check(lib.pips_hip_batch_info(self._h, _ptr(what), C.c_int(27)), "pips_hip_batch_info")
         keys = ["nnzL", "n", "n_head", "m", "n_sn", "n_levels", "flops_factor", "flops_border", "arena_bytes", "ntc", "upd_table_bytes", "nb", "nnzK",
                 "ltsolve_from_augmented_factor", "multifrontal_head", "max_front", "update_matrix_bytes", "fronts_in_device_memory", "nnzL_head", "head_row_indices",
-                "nnzL_border", "augmented_sweeps", "augmented_passes", "tail_border_entries", "blocks_with_border_split", "blocks_with_k_only_fronts"]
+                "nnzL_border", "augmented_sweeps", "augmented_passes", "tail_border_entries", "blocks_with_border_split", "blocks_with_k_only_fronts",
+                "packed_schur_rhs"]
         return {k: int(v) for k, v in zip(keys, what)}
 
     def sync(self):

@@ -37,7 +37,9 @@ def apply_options(opts, batch=None, ipm=None):
 
     batch (LeafBatch, before analyze):
       SC_COMPUTE_BLOCKWISE        true -> Schur mode 2 (blocked multi-RHS solves, the reference's K4-K6 loop); false -> mode 1
-                                  (partial factorisation of the augmented block - what PardisoSchurSolver does in the reference)
+                                  (partial factorisation of the augmented block - what PardisoSchurSolver does in the reference).
+                                  Holds with the sparse root too (KktSystem(..., sparse_root=True) on a mode-2 batch: the blocked
+                                  solves then run packed by block-local column)
       PARDISO_NITERATIVE_REFINS   >= 0 -> at most that many refinement steps per leaf solve (iparm[7])
       PARDISO_PIVOT_PERTURBATION  k > 0 -> pivots replaced at 1e-k relative (iparm[9])
     ipm (IpmSolver / GeneralIpmSolver): GONDZIO_MAX_CORRECTORS, OUTER_SOLVE, OUTER_BICG_MAX_ITER, OUTER_BICG_MAX_NORMR_DIVERGENCES,
