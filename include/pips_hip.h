@@ -263,6 +263,12 @@ int pips_hip_kkt_set_root_regularization(void* handle, double primal, double dua
  * device vector of mz0 entries) must be set before pips_hip_kkt_factorize */
 int pips_hip_kkt_set_root_inequalities(void* handle, int mz0, const int* C0_rowptr, const int* C0_colidx, const double* C0_val);
 int pips_hip_kkt_set_zdiag0_dev(void* handle, const double* zdiag0_dev);
+/* Q0, the Hessian of the first-stage variables (n0 x n0, lower-triangular CSR, diagonal included): constant lower-triangular entries
+ * added to the x0 block of the Schur complement at every factorize (sLinsysRootAug.C:234-261), after the reduction over the ranks and on
+ * every rank, like xdiag0.  Dense and sparse root alike (the sparse root's pattern holds the dense x0 block).  Entries given twice are added up.  A second call
+ * replaces the entries, Q0_rowptr == NULL removes them.  PIPS_ERR_ARG for an entry outside the lower triangle, PIPS_ERR_STATE if the sparse
+ * root's pattern has no place for one. */
+int pips_hip_kkt_set_root_hessian(void* handle, const int* Q0_rowptr, const int* Q0_colidx, const double* Q0_val);
 /* in place: b0 (replicated on every rank; [x0 | y0 | ylink | zlink], or [x0 | y0 | z0 | ylink | zlink] when mz0 > 0) and
  * the flat leaf vector of this rank's blocks */
 int pips_hip_kkt_solve_compressed(void* handle, double* b0_dev, double* b_leaf_dev);
@@ -403,8 +409,8 @@ int pips_hip_vec_dot_shifted(long long n, long long skip_root, const double* x_d
 
 /* ---------------------------------------------------------------------------------------------------------------
  * 4c. Host harness: Mehrotra predictor-corrector IPM with Gondzio correctors for the reference's full problem class
- *        min c^T x   s.t.  A x = b,  clow <= C x <= cupp,  xlow <= x <= xupp      (every bound optional per row / entry)
- *     with block-angular A and C, driving the fused KKT path (counterpart of PIPSIPMppSolver::solve / InteriorPointMethod /
+ *        min c^T x [+ 1/2 x^T Q x]   s.t.  A x = b,  clow <= C x <= cupp,  xlow <= x <= xupp      (every bound optional per row / entry)
+ *     with block-angular A and C (and a block-diagonal convex Hessian through pips_ipm_create_qp), driving the fused KKT path (counterpart of PIPSIPMppSolver::solve / InteriorPointMethod /
  *     LinearSystem::computeDiagonals, solve, solveXYZS, solveCompressedBiCGStab, system_mult / Residuals::evaluate /
  *     DistributedMatrix::mult).  One or several ranks.
  *     Input = the reader's per-block layout (GMSPIPSBlockData_t, Drivers/gams/gmspips/gmspipsio.h:5-58): block 0 is the root
@@ -518,6 +524,27 @@ int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_b
 int pips_ipm_get_scaling(void* handle, double* col, double* row_eq, double* row_ineq, double* info8);
 int pips_ipm_outer_solve(void* handle, const double* G_host, const double* L_host, const double* rhs_host, double tol, double* sol_host,
                          double* info6);
+/* Convex QPs: the reference's full problem class  min c^T x + 1/2 x^T Q x  over the same constraints, Q block-diagonal over the root
+ * and the blocks (the class PIPS-IPM++ inherits from OOQP).
+ * pips_ipm_create_general with Hessians: Q[i] belongs to blocks[i] (i = 0 the root), n_i x n_i, LOWER-triangular CSR as the reference's
+ * SparseSymmetricMatrix (isLower); Q == NULL or Q[i].rowptr == NULL: no Hessian for that block.  Several ranks: Q[0] identical on every rank.
+ * PIPS_ERR_ARG with a message for an entry above the diagonal, a column index out of range, Q[i].rows or Q[i].cols != n_i, and a
+ * negative diagonal entry.  The last is a cheap necessary test only: no test of positive semidefiniteness is made, CONVEXITY IS THE
+ * CALLER'S CONTRACT (an indefinite Q gives a KKT matrix of the wrong inertia, which the regularisation loop answers as it can).
+ * With Q == NULL (or no Q[i] present) the handle is the one pips_ipm_create_general builds and takes the LP path unchanged.
+ * With a Hessian: Q_i enters the leaf matrices and Q0 the x0 block of the Schur complement; rQ = c + Q x - A^T y - C^T z - gamma + phi;
+ * the operator of the outer solve (pips_ipm_outer_solve too) is [dd + Q  J^T; J diag(0, nOmegaInv)]; the data norm includes max |Q|;
+ * the primal and the dual part of the iterate take ONE step length min(alpha_p, alpha_d) (the trace reports both columns, equal).
+ * result7[0] and trace column 2 hold c^T x + 1/2 x^T Q x; result7[5] and trace column 3 hold the Lagrangian dual
+ * b^T y + clow^T lambda - cupp^T pi + xlow^T gamma - xupp^T phi - 1/2 x^T Q x, so that their difference is the reference's duality gap
+ * (Residuals.cpp:69-165) - the reference's own dual_objective field omits the quadratic term.
+ * Not offered: problem scaling together with a Hessian (there is no _scaled variant of this entry), the cross Hessian between x0 and
+ * x_i, and Hessians through the pips_ipm_create shorthand. */
+int pips_ipm_create_qp(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl,
+                       const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp,
+                       double dual_reg, int device, void* comm, int rank, int n_ranks);
+/* out = Q in over x = [x0 | own blocks] (Problem::hessian_multiplication; parity tests).  Zeros on a handle without Hessian. */
+int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host);
 void pips_ipm_destroy(void* handle);
 
 /* ---------------------------------------------------------------------------------------------------------------

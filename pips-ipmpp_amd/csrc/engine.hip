@@ -3956,6 +3956,14 @@ int pips_hip_kkt_set_root_inequalities(void* handle, int mz0, const int* C0_rowp
    return k->set_root_inequalities(mz0, C0_rowptr, C0_colidx, C0_val);
 }
 
+int pips_hip_kkt_set_root_hessian(void* handle, const int* Q0_rowptr, const int* Q0_colidx, const double* Q0_val) {
+   KktSystem* k = (KktSystem*)handle;
+   if (!k || (Q0_rowptr && k->n0 > 0 && Q0_rowptr[k->n0] > Q0_rowptr[0] && (!Q0_colidx || !Q0_val)))
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_set_root_hessian: bad arguments");
+   HIP_TRY(hipSetDevice(k->leaves->device));
+   return k->set_root_hessian(Q0_rowptr, Q0_colidx, Q0_val);
+}
+
 int pips_hip_kkt_set_root_pivoting(void* handle, int mode) {
    KktSystem* k = (KktSystem*)handle;
    if (!k || mode < 0 || mode > 1) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_set_root_pivoting: mode 0 (static order) or 1 (Bunch-Kaufman inside the diagonal tiles)");

@@ -1,7 +1,8 @@
 // Host harness: a Mehrotra predictor-corrector interior-point loop with Gondzio correctors driving the device KKT path end to
 // end, for the reference's full problem class
-//      min c^T x   s.t.  A x = b,   clow <= C x <= cupp (each side optional per row),   xlow <= x <= xupp (optional per entry)
-// with block-angular A and C (root rows, block rows, linking rows).  It is the build's counterpart of the reference callers
+//      min c^T x [+ 1/2 x^T Q x]   s.t.  A x = b,   clow <= C x <= cupp (each side optional per row),   xlow <= x <= xupp (optional per entry)
+// with block-angular A and C (root rows, block rows, linking rows) and, through pips_ipm_create_qp, a convex Hessian Q that is
+// block-diagonal over the root and the blocks.  It is the build's counterpart of the reference callers
 // that do not travel to the GPU box:
 //   PIPSIPMppSolver::solve            (InteriorPointMethod/PIPSIPMppSolver.cpp:29-83)   start point, loop, termination
 //   Solver::solve_linear_system       (InteriorPointMethod/Solver.cpp:19-31)            initial affine solve + shift
@@ -76,14 +77,15 @@ static inline int egrid(long long n) { return (int)std::max<long long>(1, std::m
 // the epilogue is added once by rank 0 and the rows are summed over the ranks afterwards (DistributedMatrix.C:224-326).
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int CSR_LONG_ROW = 512;
-enum SpmvMode : int { SP_RQ = 0, SP_RAC, SP_KX, SP_KYZ, SP_RES_X, SP_RES_YZ };
+enum SpmvMode : int { SP_RQ = 0, SP_RAC, SP_KX, SP_KYZ, SP_RES_X, SP_RES_YZ, SP_QX };
 
 struct SpmvArgs {
    int nrows;
    const int* rp; const int* ci; const double* v;   // CSR
    const double* in;                                 // multiplied vector
    double* out;
-   const double *e0, *e1, *e2, *e3;                  // epilogue operands, meaning per mode
+   const double *e0, *e1, *e2, *e3;                  // epilogue operands, meaning per mode; e3: the Hessian product Q x of a QP handle
+                                                     // (nullptr on an LP handle: a branch uniform over the launch)
    int split;                                        // SP_RAC: rows < split subtract e0[r], rows >= split subtract e1[r - split]
    int lin, r0e, r1b, r1e;
    const int* pred;                                  // run only if *pred != 0 (nullptr: always)
@@ -91,7 +93,14 @@ struct SpmvArgs {
 
 template <int MODE>
 __device__ __forceinline__ double spmv_epilogue(const SpmvArgs& a, int r, double s) {
+   if (MODE == SP_QX) return s;                                                               // Q x (the matrix is Q; rows x0 replicated)
    const bool rep = a.lin && (r < a.r0e || (r >= a.r1b && r < a.r1e));
+   // QP handle: Q x joins the non-linear part of the x rows, which on replicated rows only rank 0 contributes
+   if (a.e3 && (MODE == SP_RQ || MODE == SP_KX || MODE == SP_RES_X)) {
+      if (MODE == SP_RQ) return rep ? -s : a.e0[r] + a.e3[r] - s - a.e1[r] + a.e2[r];         // rQ = c + Q x - J^T[y;z] - gamma + phi
+      if (MODE == SP_KX) return rep ? s : a.e0[r] * a.e1[r] + a.e3[r] + s;                    // dd .* x + Q x + J^T[y;z]
+      return rep ? -s : a.e2[r] - (a.e0[r] * a.e1[r] + a.e3[r] + s);                          // rhs_x - (K z)_x
+   }
    switch (MODE) {
       case SP_RQ:     return rep ? -s : a.e0[r] - s - a.e1[r] + a.e2[r];                       // rQ = c - J^T[y;z] - gamma + phi
       case SP_RAC:    return rep ? s : s - (r < a.split ? a.e0[r] : a.e1[r - a.split]);        // [rA|rC] = J x - [b|s]
@@ -445,12 +454,15 @@ __global__ void k_shift_diag(const double* __restrict__ in, double reg, double* 
 
 // K_i diagonals of every leaf from the primal diagonal, the dual regularisation and nOmegaInv: code[p] >= 0 an x index,
 // -1 an equality row, <= -2 the inequality row -2 - code[p]
+// qdiag: the diagonal of the Hessian over x (nullptr: no Hessian) - the leaf diagonals are overwritten at every factorisation, so
+// the constant diagonal of Q_i is added here; its off-diagonal entries are constant values of K_i
 __global__ void k_leaf_diag(long long nleaf, const long long* __restrict__ code, const double* __restrict__ ddp,
-                            const double* __restrict__ nomega, double primal_reg, double dual_reg, double reg,
-                            double* __restrict__ leaf_diag) {
+                            const double* __restrict__ nomega, const double* __restrict__ qdiag, double primal_reg, double dual_reg,
+                            double reg, double* __restrict__ leaf_diag) {
    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < nleaf; p += (long long)gridDim.x * blockDim.x) {
       const long long c = code[p];
-      leaf_diag[p] = c >= 0 ? ddp[c] + primal_reg : (c == -1 ? -dual_reg : nomega[-2 - c] - reg);
+      if (c >= 0 && qdiag) leaf_diag[p] = ddp[c] + qdiag[c] + primal_reg;
+      else leaf_diag[p] = c >= 0 ? ddp[c] + primal_reg : (c == -1 ? -dual_reg : nomega[-2 - c] - reg);
    }
 }
 
@@ -753,6 +765,13 @@ struct Ipm {
    double *J_v = nullptr, *Jt_v = nullptr;
    int nJ_long = 0, nJt_long = 0;
    double* long_scratch = nullptr;   // LONG_PARTS partial sums per long row (k_spmv_long_part)
+   // Hessian of a QP handle (pips_ipm_create_qp): the full symmetric CSR (both triangles) over the flat x order with its own long-row
+   // list, its diagonal, and the product Q x the epilogues of the x rows read.  An LP handle holds none of this (has_q false).
+   bool has_q = false;
+   int *Q_rp = nullptr, *Q_ci = nullptr, *Q_long = nullptr;
+   double *Q_v = nullptr, *qdiag = nullptr, *qx = nullptr;
+   int nQ_long = 0;
+   long long Q_nnz = 0;
    long long J_nnz = 0, Jt_nnz = 0;
    // data
    double *c = nullptr, *bA = nullptr, *M = nullptr, *Bd = nullptr, *wG = nullptr, *wXYZ = nullptr, *wX = nullptr, *wY = nullptr;
@@ -886,9 +905,29 @@ struct Ipm {
       return PIPS_OK;
    }
 
+   // out = Q in (Problem::hessian_multiplication).  Several ranks: Q0 is replicated and every rank computes the same x0 rows - no
+   // reduction, so a predicate needs no staging either.  Sums in the fixed order of the block-angular products: no atomics.
+   int hess(const double* in, double* out, const int* pred = nullptr) {
+      SpmvArgs a;
+      a.nrows = nx;
+      a.rp = Q_rp; a.ci = Q_ci; a.v = Q_v;
+      a.in = in; a.out = out; a.e0 = a.e1 = a.e2 = a.e3 = nullptr; a.split = 0;
+      a.lin = 0; a.r0e = a.r1b = a.r1e = 0;
+      a.pred = pred;
+      if (nx > 0 && Q_nnz < 6LL * nx) hipLaunchKernelGGL((k_spmv<SP_QX, 4>), dim3(egrid(2LL * nx)), dim3(256), 0, stream, a);
+      else if (nx > 0) hipLaunchKernelGGL((k_spmv<SP_QX, 8>), dim3(egrid(4LL * nx)), dim3(256), 0, stream, a);
+      if (nQ_long > 0) {
+         hipLaunchKernelGGL(k_spmv_long_part, dim3(nQ_long, LONG_PARTS), dim3(256), 0, stream, a, Q_long, long_scratch);
+         hipLaunchKernelGGL(k_spmv_long_finish<SP_QX>, dim3((nQ_long + 255) / 256), dim3(256), 0, stream, a, Q_long, nQ_long, long_scratch);
+      }
+      HIP_TRYH(hipGetLastError());
+      return PIPS_OK;
+   }
+
    // ---- Residuals::evaluate -----------------------------------------------------------------------------------------------------
    int residuals(double* rnorm, double* pobj, double* dobj, double* mu_out) {
-      TRY((spmv<SP_RQ>(true, it.yz, rQ, c, it.L + 2 * mz, it.L + 2 * mz + nx, nullptr)));
+      if (has_q) TRY(hess(it.x, qx));
+      TRY((spmv<SP_RQ>(true, it.yz, rQ, c, it.L + 2 * mz, it.L + 2 * mz + nx, qx)));
       TRY((spmv<SP_RAC>(false, it.x, rAC, bA, it.s, nullptr, nullptr)));
       hipLaunchKernelGGL(k_bound_residuals, dim3(egrid(std::max(nx, mz))), dim3(256), 0, stream, lay, it.x, it.s, it.z, it.G, it.L, M, Bd, rz, rG);
       RedPack pk;
@@ -909,13 +948,19 @@ struct Ipm {
          pk.t[8] = term(R_ABSMAX, 2LL * nx, rG + 2LL * mz, nullptr, nullptr, nullptr, sc_col2);   // [rv | rw] * col
          pk.n_terms = 9;
       }
-      double o[9];
+      const int kq = pk.n_terms;
+      if (has_q) pk.t[pk.n_terms++] = term(R_DOT, nx, it.x, qx, nullptr, nullptr, wX);   // x^T Q x, root entries counted once
+      double o[10];
       TRY(reduce(pk, o));
       if (scaled) o[3] = std::max(o[3], o[8]);
       *rnorm = std::max(std::max(o[0], o[1]), std::max(o[2], o[3]));
       for (int k = 0; k < 4; ++k) last_rparts[k] = o[k];
       *pobj = o[4];
       *dobj = o[5] + o[6];
+      if (has_q) {   // c^T x + 1/2 x^T Q x, and the Lagrangian dual: their difference is the reference's duality gap (Residuals.cpp:69-165)
+         *pobj += 0.5 * o[kq];
+         *dobj -= 0.5 * o[kq];
+      }
       *mu_out = n_pairs > 0 ? o[7] / n_pairs : 0.0;
       cur_mu = *mu_out;
       return PIPS_OK;
@@ -958,7 +1003,7 @@ struct Ipm {
       double best_reg = reg;
       auto factor_with = [&](double r, int* pert) -> int {
          if (nleaf > 0)
-            hipLaunchKernelGGL(k_leaf_diag, dim3(egrid(nleaf)), dim3(256), 0, stream, nleaf, d_code, ddp, dyz + my, r, dual_reg + r, r, leaf_diag);
+            hipLaunchKernelGGL(k_leaf_diag, dim3(egrid(nleaf)), dim3(256), 0, stream, nleaf, d_code, ddp, dyz + my, (const double*)qdiag, r, dual_reg + r, r, leaf_diag);
          TRY(pips_hip_kkt_set_root_regularization(kkt, r, dual_reg + r));
          if (e_mz0 > 0) hipLaunchKernelGGL(k_shift_diag, dim3(egrid(e_mz0)), dim3(256), 0, stream, dyz + my, dual_reg + r, zd0, e_mz0);
          TRY(pips_hip_kkt_factorize(kkt, leaf_diag, ddp, e_mzl > 0 ? dyz + my + e_mz0 : nullptr));
@@ -1001,7 +1046,8 @@ struct Ipm {
       ++n_precond;
       return PIPS_OK;
    }
-   // out = K z with K = [dd J^T; J diag(0, nOmegaInv)]  (LinearSystem::system_mult on the unregularised system)
+   // out = K z with K = [dd + Q  J^T; J diag(0, nOmegaInv)]  (LinearSystem::system_mult on the unregularised system; Q: QP handles, through
+   // the product Q x - dd stays the pure barrier diagonal, so the diagonal of Q is counted once)
    // Free variables (no bound: dd_j = 0): optionally the proximal term of the preconditioner is part of the operator too, i.e. the
    // outer solve runs on the primal-regularised system (the reference's choice when OUTER_SOLVE_REFINE_ORIGINAL_SYSTEM is off,
    // LinearSystem.C:505-512 use_regularized_system) - a proximal-point step centred at the current iterate.  Off by default:
@@ -1025,12 +1071,14 @@ struct Ipm {
    bool reg_operator = false, reg_operator_always = false;
    int n_reg_operator = 0;
    int kmult(const double* z_, double* out, const int* pred = nullptr) {
-      TRY((spmv<SP_KX>(true, z_ + nx, out, dop(), z_, nullptr, nullptr, pred)));
+      if (has_q) TRY(hess(z_, qx, pred));
+      TRY((spmv<SP_KX>(true, z_ + nx, out, dop(), z_, nullptr, qx, pred)));
       TRY((spmv<SP_KYZ>(false, z_, out + nx, dyzop(), z_ + nx, nullptr, nullptr, pred)));
       return PIPS_OK;
    }
    int kresidual(const double* rhs_, const double* z_, double* r, const int* pred = nullptr) {   // r = rhs - K z
-      TRY((spmv<SP_RES_X>(true, z_ + nx, r, dop(), z_, rhs_, nullptr, pred)));
+      if (has_q) TRY(hess(z_, qx, pred));
+      TRY((spmv<SP_RES_X>(true, z_ + nx, r, dop(), z_, rhs_, qx, pred)));
       TRY((spmv<SP_RES_YZ>(false, z_, r + nx, dyzop(), z_ + nx, rhs_ + nx, nullptr, pred)));
       return PIPS_OK;
    }
@@ -1342,7 +1390,7 @@ struct Ipm {
       J_nnz = h.rp[my + mz]; Jt_nnz = h.trp[nx];
       la.push_back(0); lat.push_back(0);
       TRY(up(&J_long, la)); TRY(up(&Jt_long, lat));
-      TRY(alloc(&long_scratch, (long long)std::max<size_t>(std::max(la.size(), lat.size()), 1) * LONG_PARTS));
+      TRY(alloc(&long_scratch, (long long)std::max<size_t>(std::max(std::max(la.size(), lat.size()), (size_t)nQ_long + 1), 1) * LONG_PARTS));   // (nQ_long: the Hessian's long rows, known before J is uploaded)
       TRY(up(&J_rp, h.rp)); TRY(up(&J_ci, h.ci)); TRY(up(&J_v, h.v));
       TRY(up(&Jt_rp, h.trp)); TRY(up(&Jt_ci, h.tci)); TRY(up(&Jt_v, h.tv));
       return PIPS_OK;
@@ -1581,6 +1629,9 @@ struct Ipm {
          TRY(pips_hip_vec_axpy(ND, wd, co.D, st.D, stream));
          TRY(gondzio_loop(sigma, m, &ap, &ad));
          TRY(mehrotra_step_length(&ap, &ad));
+         // QP: one step length for both parts of the iterate - two lengths leave (ap - ad) Q dx in rQ at every step.  OOQP's rule; not the
+         // reference's PRIMAL variant, which runs a line search of its own
+         if (has_q) ap = ad = std::min(ap, ad);
          n_stall = (ap < 1e-10 && ad < 1e-10) ? n_stall + 1 : 0;
          { double* row = trace.data() + trace.size() - 7; row[4] = sigma; row[5] = ap; row[6] = ad; }
          TRY(pips_hip_vec_axpy(NP, ap, st.P, it.P, stream));
@@ -1744,8 +1795,42 @@ int prescale(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mz
    return PIPS_OK;
 }
 
-int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow, const double* dupp,
-          const double* idlow, const double* idupp, double dual_reg, int device) {
+// ---- Hessians (pips_ipm_create_qp) ---------------------------------------------------------------------------------------------
+// One block's Hessian as the caller gave it, checked and with sorted rows (duplicates added up): lower-triangular CSR like the
+// reference's SparseSymmetricMatrix.  A negative diagonal entry cannot belong to a positive semidefinite matrix: a cheap necessary test,
+// no full one - convexity is the caller's contract.
+struct LowerQ { bool have = false; std::vector<int> rp, ci; std::vector<double> v; };
+int check_hessian(int i, int n, const pips_csr_view& q, LowerQ& out) {
+   out.have = false;
+   if (!q.rowptr) return PIPS_OK;
+   if (q.rows != n || q.cols != n) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] is %d x %d but block %d has %d variables", i, q.rows, q.cols, i, n);
+   if (n > 0 && q.rowptr[n] > q.rowptr[0] && (!q.colidx || !q.val)) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] lacks colidx / val", i);
+   out.have = true;
+   out.rp.assign((size_t)n + 1, 0);
+   std::vector<std::pair<int, double>> row;
+   for (int r = 0; r < n; ++r) {
+      row.clear();
+      for (int q_ = q.rowptr[r]; q_ < q.rowptr[r + 1]; ++q_) {
+         const int c = q.colidx[q_];
+         if (c < 0 || c >= n) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] row %d has column index %d outside [0, %d)", i, r, c, n);
+         if (c > r) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] has entry (%d, %d) above the diagonal - lower-triangular storage expected", i, r, c);
+         row.push_back({c, q.val[q_]});
+      }
+      std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+      for (size_t k = 0; k < row.size(); ++k) {
+         if (!out.ci.empty() && (int)out.ci.size() > out.rp[r] && out.ci.back() == row[k].first) out.v.back() += row[k].second;
+         else { out.ci.push_back(row[k].first); out.v.push_back(row[k].second); }
+      }
+      out.rp[r + 1] = (int)out.ci.size();
+      if (out.rp[r + 1] > out.rp[r] && out.ci.back() == r && out.v.back() < 0.0)
+         PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] has the negative diagonal entry %g in row %d - not positive semidefinite", i, out.v.back(), r);
+   }
+   out.ci.push_back(0); out.v.push_back(0.0);   // never empty arrays
+   return PIPS_OK;
+}
+
+int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL, const double* dlow,
+          const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device) {
    const pips_ipm_block& root = blocks[0];
    const int N = n_blocks - 1;
    p->N = N; p->n0 = root.n; p->my0 = root.my; p->mz0 = root.mz; p->myl = myl; p->mzl = mzl; p->dual_reg = dual_reg;
@@ -1765,6 +1850,11 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
    p->ncp = 2LL * mz + 2LL * nx; p->nxyz = (long long)nx + my + mz;
    p->NP = nx + mz + p->ncp; p->ND = my + mz + p->ncp;
    p->lay = Lay{nx, my, mz, p->ncp};
+   std::vector<LowerQ> hq(n_blocks);
+   for (int i = 0; Q && i < n_blocks; ++i) {
+      if (int rcq = check_hessian(i, blocks[i].n, Q[i], hq[i])) return rcq;
+      p->has_q = p->has_q || hq[i].have;
+   }
    // Root inequality rows C0 x0 - s = ...: the reference eliminates them from the root system (-C0^T Omega^-1 C0 on the x0 block,
    // sLinsysRootAug.C:1276-1294) and leaves the rest to dsytrf's Bunch-Kaufman pivoting.  So does the harness now that the dense root
    // pivots (k_tile_diag_bk; pips_hip_kkt_set_root_inequalities switches it on): an active row has Omega^-1 ~ 1e14, the x0 block is
@@ -1820,11 +1910,14 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
       const int* Brp = present(B) ? B.rp : empty_rp_y.data();
       const int* Drp = present(D) ? D.rp : empty_rp_z.data();
       std::vector<int> Krp(nk + 1), dpos(nk);
-      rc = pips_kkt_leaf_assemble(nxi, myi, mzi, nullptr, nullptr, nullptr, Brp, B.ci, B.v, Drp, D.ci, D.v, Krp.data(), nullptr, nullptr, nullptr);
+      // Q_i: its off-diagonal entries are constant values of K_i; the diagonal is overwritten at every factorisation (k_leaf_diag adds qdiag)
+      const LowerQ& qi = hq[i];
+      const int* Qrp = qi.have ? qi.rp.data() : nullptr;
+      rc = pips_kkt_leaf_assemble(nxi, myi, mzi, Qrp, qi.ci.data(), qi.v.data(), Brp, B.ci, B.v, Drp, D.ci, D.v, Krp.data(), nullptr, nullptr, nullptr);
       if (rc) return rc;
       std::vector<int> Kci(Krp[nk]);
       kvals[i - 1].assign(Krp[nk], 0.0);
-      rc = pips_kkt_leaf_assemble(nxi, myi, mzi, nullptr, nullptr, nullptr, Brp, B.ci, B.v, Drp, D.ci, D.v, Krp.data(), Kci.data(), kvals[i - 1].data(), dpos.data());
+      rc = pips_kkt_leaf_assemble(nxi, myi, mzi, Qrp, qi.ci.data(), qi.v.data(), Brp, B.ci, B.v, Drp, D.ci, D.v, Krp.data(), Kci.data(), kvals[i - 1].data(), dpos.data());
       if (rc) return rc;
       std::vector<int> Brd(S + 1);
       auto P3 = [](const View& m) { return m; };
@@ -1874,6 +1967,8 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
       hBd[k] *= hM[k];   // matchesNonZeroPattern (Problem.cpp:69-79)
       dn = std::max(dn, std::fabs(hBd[k]));
    }
+   for (const LowerQ& q : hq)
+      for (double v : q.v) dn = std::max(dn, std::fabs(v));   // the data norm includes ||Q|| (Problem.cpp:81)
    for (double v : hc) dn = std::max(dn, std::fabs(v));
    for (double v : hb) dn = std::max(dn, std::fabs(v));
    p->dnorm = dn > 0 ? dn : 1.0;
@@ -1935,21 +2030,27 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
       rc = pips_hip_kkt_create(&p->kkt, p->batch, n0, my0, myl, e_mzl, rp(A0), A0.ci, A0.v, rp(F0), F0.ci, F0.v, rp(G0), G0.ci, G0.v, p->comm, p->rank,
                                p->n_ranks);
    if (rc) return rc;
+   // Q0 in the x0 block of the Schur complement (sLinsysRootAug.C:234-261), on either root kind; several ranks: every rank, after the reduction
+   if (hq[0].have && (rc = pips_hip_kkt_set_root_hessian(p->kkt, hq[0].rp.data(), hq[0].ci.data(), hq[0].v.data()))) return rc;
    // factorize() asks for every inertia right after the factorisation (the inertia loop): nothing would run beside a root on its own stream
    if ((rc = pips_hip_kkt_set_root_stream(p->kkt, 0))) return rc;
    HIP_TRYH(hipGetDevice(&p->device));
    if (!p->d_red && (rc = p->alloc(&p->d_red, 64 * (long long)p->n_ranks))) return rc;
    if (p->scaled) p->dnorm_orig = p->dnorm_orig > 0 ? p->dnorm_orig : 1.0;
    if (p->n_ranks > 1) {
-      const int ns = p->n_ranks + 1 + (p->scaled ? p->n_ranks : 0);   // scaled: the original data norm travels too
+      // scaled: the original data norm travels too.  Last slot: does any rank hold a Hessian?  The ranks must agree on it - it decides the
+      // number of terms in the fused reductions, which are collectives, and the step-length rule of the replicated iterate
+      const int ns = p->n_ranks + 2 + (p->scaled ? p->n_ranks : 0);
       std::vector<double> slots(ns, 0.0);
       slots[p->rank] = p->dnorm; slots[p->n_ranks] = pairs;
+      slots[ns - 1] = p->has_q ? 1.0 : 0.0;
       if (p->scaled) slots[p->n_ranks + 1 + p->rank] = p->dnorm_orig;
       if ((rc = p->reduce_host(slots.data(), ns))) return rc;
       for (int r = 0; r < p->n_ranks; ++r) p->dnorm = std::max(p->dnorm, slots[r]);
       if (p->scaled)
          for (int r = 0; r < p->n_ranks; ++r) p->dnorm_orig = std::max(p->dnorm_orig, slots[p->n_ranks + 1 + r]);
       pairs = slots[p->n_ranks];
+      p->has_q = slots[ns - 1] != 0.0;   // a rank whose own blocks have none then holds an empty Q, zero qdiag and qx: one path on all ranks
    }
    if (!p->scaled) p->dnorm_orig = p->dnorm;
    p->n_pairs = pairs;
@@ -1974,6 +2075,35 @@ int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, 
    }
    if (e_mz0 > 0) {
       if ((rc = pips_hip_kkt_set_root_inequalities(p->kkt, e_mz0, C0.rp, C0.ci, C0.v))) return rc;
+   }
+   if (p->has_q) {   // device copy of Q: both triangles over the flat x order, expanded once; its diagonal; the product vector
+      std::vector<std::vector<std::pair<int, double>>> qrows((size_t)nx);
+      std::vector<double> hqd((size_t)nx, 0.0);
+      for (int i = 0; i <= N; ++i) {
+         if (!hq[i].have) continue;
+         const int o = i == 0 ? 0 : xoff[i];
+         for (int r = 0; r < blocks[i].n; ++r)
+            for (int q = hq[i].rp[r]; q < hq[i].rp[r + 1]; ++q) {
+               const int c = hq[i].ci[q];
+               qrows[(size_t)o + r].push_back({o + c, hq[i].v[q]});
+               if (c != r) qrows[(size_t)o + c].push_back({o + r, hq[i].v[q]});
+               else hqd[(size_t)o + r] = hq[i].v[q];
+            }
+      }
+      std::vector<int> qrp((size_t)nx + 1, 0), qci, qlong;
+      std::vector<double> qv;
+      for (int r = 0; r < nx; ++r) {
+         std::sort(qrows[r].begin(), qrows[r].end());
+         for (auto& e : qrows[r]) { qci.push_back(e.first); qv.push_back(e.second); }
+         qrp[(size_t)r + 1] = (int)qci.size();
+         if (qrows[r].size() > (size_t)CSR_LONG_ROW) qlong.push_back(r);
+      }
+      p->Q_nnz = (long long)qci.size();
+      p->nQ_long = (int)qlong.size();
+      qci.push_back(0); qv.push_back(0.0); qlong.push_back(0);
+      if ((rc = p->up(&p->Q_rp, qrp)) || (rc = p->up(&p->Q_ci, qci)) || (rc = p->up(&p->Q_v, qv)) || (rc = p->up(&p->Q_long, qlong)) ||
+          (rc = p->up(&p->qdiag, hqd)) || (rc = p->alloc(&p->qx, nx)))
+         return rc;
    }
    if (!p->J_v && (rc = p->upload_J(hj))) return rc;   // a scaled handle holds J since prescale()
    if ((rc = p->up(&p->c, hc)) || (rc = p->up(&p->bA, hb)) || (rc = p->up(&p->M, hM)) || (rc = p->up(&p->Bd, hBd)) || (rc = p->up(&p->wG, hwG)) ||
@@ -2035,9 +2165,40 @@ int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_b
       if ((rc = prescale(p.get(), n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, device, scaler, sd))) return rc;
       if (p->scaled) { blocks = sd.blk.data(); bL = sd.bL; dlow = sd.dlow; dupp = sd.dupp; }
    }
-   rc = build(p.get(), n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device);
+   rc = build(p.get(), n_blocks, blocks, nullptr, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device);
    if (rc) return rc;
    *handle = p.release();
+   return PIPS_OK;
+}
+
+// The convex QP  min c^T x + 1/2 x^T Q x  over the same constraints, Q block-diagonal over the root and the blocks.  Without any
+// Hessian this is pips_ipm_create_general, call for call.  Problem scaling is not offered with a Hessian.
+int pips_ipm_create_qp(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL,
+                       const double* dlow, const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device, void* comm,
+                       int rank, int n_ranks) {
+   if (!handle || n_blocks < 2 || !blocks || myl < 0 || mzl < 0 || n_ranks < 1 || rank < 0 || rank >= n_ranks || (n_ranks > 1 && !comm) ||
+       (myl > 0 && !bL) || (mzl > 0 && (!dlow || !dupp || !idlow || !idupp)))
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: bad arguments");
+   auto p = std::make_unique<Ipm>();
+   p->comm = comm; p->rank = rank; p->n_ranks = n_ranks;
+   const int rc = build(p.get(), n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device);
+   if (rc) return rc;
+   *handle = p.release();
+   return PIPS_OK;
+}
+
+int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host) {
+   Ipm* p = (Ipm*)handle;
+   if (!p || !in_host || !out_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_hessian_mult: bad arguments");
+   if (!p->has_q) {
+      std::fill(out_host, out_host + p->nx, 0.0);
+      return PIPS_OK;
+   }
+   HIP_TRYH(hipSetDevice(p->device));
+   HIP_TRYH(hipMemcpy(p->w_dx, in_host, (size_t)p->nx * sizeof(double), hipMemcpyHostToDevice));
+   TRY(p->hess(p->w_dx, p->w_t));
+   HIP_TRYH(hipStreamSynchronize(p->stream));
+   HIP_TRYH(hipMemcpy(out_host, p->w_t, (size_t)p->nx * sizeof(double), hipMemcpyDeviceToHost));
    return PIPS_OK;
 }
 

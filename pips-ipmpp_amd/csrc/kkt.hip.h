@@ -99,6 +99,8 @@ struct KktSystem {
    DevBuf<double> d_SC, d_t, d_fin_val, d_c0_val, d_red, d_packed;
    DevBuf<long long> d_fin_idx;
    long long n_fin = 0;
+   std::vector<long long> fin_idx_rows;   // the table's entries from A0 / F0 / G0 (host copy: set_root_hessian appends to them)
+   std::vector<double> fin_val_rows;
    DevBuf<double> d_gall, d_gvec_all;   // deterministic mode over several ranks: all eight group slots (8 x S x S / 8 x S)
    int mz0 = 0;
    DevBuf<int> d_c0_rp, d_c0_ci;
@@ -213,9 +215,36 @@ struct KktSystem {
          for (int r = 0; r < b.nrows; ++r)
             for (int p = b.rowptr[r]; p < b.rowptr[r + 1]; ++p) { idx.push_back(pos(b.row0 + r, b.colidx[p])); val.push_back(b.val[p]); }
       }
+      fin_idx_rows = idx; fin_val_rows = val;
+      return upload_fin(idx, val);
+   }
+   int upload_fin(const std::vector<long long>& idx, const std::vector<double>& val) {
       n_fin = (long long)idx.size();
       if (int rc = d_fin_idx.upload(idx)) return rc;
       return d_fin_val.upload(val);
+   }
+   // Q0, the root block's Hessian (lower-triangular CSR, n0 x n0), as constant entries of the x0 block (sLinsysRootAug.C:234-261): they join
+   // the table finalize() applies at every factorisation - after the reduction over the ranks, on every rank, like xdiag0.  The sparse
+   // root's pattern holds the dense x0 block, so every entry has a place.  A second call replaces the first; nullptr removes the entries.
+   int set_root_hessian(const int* Q0_rowptr, const int* Q0_colidx, const double* Q0_val) {
+      std::vector<long long> idx = fin_idx_rows;
+      std::vector<double> val = fin_val_rows;
+      const long long ld = S;
+      std::vector<std::pair<long long, double>> q0;   // entries given twice are added up here: one addition per address in k_add_entries
+      for (int r = 0; Q0_rowptr && r < n0; ++r)
+         for (int p = Q0_rowptr[r]; p < Q0_rowptr[r + 1]; ++p) {
+            const int c = Q0_colidx[p];
+            if (c < 0 || c > r) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_set_root_hessian: entry (%d, %d) is not in the lower triangle of the x0 block", r, c);
+            const long long pos = sparse ? sc_pos(r, c) : (long long)r + (long long)c * ld;
+            if (pos < 0) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_set_root_hessian: entry (%d, %d) has no place in the sparse root's pattern", r, c);
+            q0.push_back({pos, Q0_val[p]});
+         }
+      std::stable_sort(q0.begin(), q0.end(), [](const std::pair<long long, double>& a, const std::pair<long long, double>& b) { return a.first < b.first; });
+      for (size_t k = 0; k < q0.size(); ++k) {
+         if (k > 0 && q0[k].first == q0[k - 1].first) val.back() += q0[k].second;
+         else { idx.push_back(q0[k].first); val.push_back(q0[k].second); }
+      }
+      return upload_fin(idx, val);
    }
    int init_dense_root(const RootRows (&rows)[3]) {
       Engine* e = leaves;

@@ -63,7 +63,7 @@ SYMBOLS = [
     "pips_hip_batch_inertia", "pips_hip_batch_tail_to_host", "pips_hip_batch_info", "pips_hip_batch_sync", "pips_hip_batch_set_timing",
     "pips_hip_batch_get_timing", "pips_hip_batch_destroy",
     "pips_hip_kkt_create", "pips_hip_kkt_create_sparse", "pips_hip_kkt_get_schur_sparse", "pips_hip_kkt_sparse_root_info", "pips_hip_kkt_factorize", "pips_hip_kkt_set_root_regularization", "pips_hip_kkt_solve_compressed", "pips_hip_kkt_get_schur",
-    "pips_hip_kkt_set_root_inequalities", "pips_hip_kkt_set_zdiag0_dev",
+    "pips_hip_kkt_set_root_inequalities", "pips_hip_kkt_set_zdiag0_dev", "pips_hip_kkt_set_root_hessian",
     "pips_hip_kkt_root_inertia", "pips_hip_kkt_get_timing", "pips_hip_kkt_last_ltsolve_from_factor", "pips_hip_kkt_last_solve_path", "pips_hip_kkt_set_solve_check", "pips_hip_kkt_solve_check_counts", "pips_hip_kkt_set_solve_graph", "pips_hip_kkt_set_root_stream", "pips_hip_kkt_solve_graph_stats", "pips_hip_kkt_set_root_pivoting", "pips_hip_kkt_destroy",
     "pips_hip_malloc", "pips_hip_free", "pips_hip_memcpy_h2d", "pips_hip_memcpy_d2h", "pips_hip_memset",
     "pips_hip_comm_unique_id", "pips_hip_comm_create", "pips_hip_comm_create_external", "pips_hip_comm_set_external_rsag", "pips_hip_comm_set_external_broadcast", "pips_hip_broadcast", "pips_hip_comm_has_broadcast", "pips_hip_allreduce_sum_rsag", "pips_hip_all_gather", "pips_hip_comm_size", "pips_hip_allreduce_sum", "pips_hip_comm_destroy",
@@ -71,7 +71,7 @@ SYMBOLS = [
     "pips_hip_vec_add_const", "pips_hip_vec_mul", "pips_hip_vec_div", "pips_hip_vec_add_product", "pips_hip_vec_add_quotient",
     "pips_hip_vec_divide_some", "pips_hip_vec_select_nonzeros", "pips_hip_vec_safe_invert", "pips_hip_vec_gondzio_projection", "pips_hip_vec_dot",
     "pips_hip_vec_one_norm", "pips_hip_vec_inf_norm", "pips_hip_vec_min", "pips_hip_vec_sumsq_scaled", "pips_hip_vec_stepbound",
-    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
+    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
     "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe",
@@ -746,6 +746,12 @@ class KktSystem:
         _check(lib.pips_hip_kkt_set_root_inequalities(self._h, C.c_int(C0.nrows), _ptr(C0.rowptr), _ptr(C0.colidx), _ptr(C0.val)),
                "pips_hip_kkt_set_root_inequalities")
 
+    def set_root_hessian(self, Q0):
+        """Q0 (Csr, n0 x n0, lower triangle with the diagonal): constant entries of the x0 block of the Schur complement in the
+        factorizations that follow (sLinsysRootAug.C:234-261); None removes them."""
+        _check(lib.pips_hip_kkt_set_root_hessian(self._h, *((None, None, None) if Q0 is None else (_ptr(Q0.rowptr), _ptr(Q0.colidx), _ptr(Q0.val)))),
+               "pips_hip_kkt_set_root_hessian")
+
     def set_zdiag0(self, zdiag0_dev):
         self._zdiag0 = zdiag0_dev   # keep alive: the library stores the pointer only
         _check(lib.pips_hip_kkt_set_zdiag0_dev(self._h, _ptr(zdiag0_dev)), "pips_hip_kkt_set_zdiag0_dev")
@@ -1075,11 +1081,18 @@ class GeneralIpmSolver(IpmSolver):
     and linking rows), fed with the reader's per-block dicts (fields of GMSPIPSBlockData_t as gdx.read_block / gdx_read_block
     return them): blocks[0] is the root.  Several ranks: blocks = [root] + this rank's blocks."""
 
-    def __init__(self, blocks, dual_reg=0.0, device=-1, comm=None, rank=0, n_ranks=1, scaler=None):
+    def __init__(self, blocks, dual_reg=0.0, device=-1, comm=None, rank=0, n_ranks=1, scaler=None, hessians=None):
         """scaler: None, "equilibrium", "geometric" or "geometric_equilibrium" (the reference's scale / scaleEqui, scaleGeo,
-        scaleGeoEqui); "curtis_reid" is reserved and raises, like any other name."""
+        scaleGeoEqui); "curtis_reid" is reserved and raises, like any other name.
+        hessians: None (an LP, created by pips_ipm_create_general), or a list as long as `blocks` whose entries are None or a
+        dict rows / cols / rowptr / colidx / val like the matrices of the block dicts (or a Csr): the LOWER triangle of the block's
+        convex Hessian (pips_ipm_create_qp; convexity is the caller's contract).  Not together with a scaler."""
         if scaler not in SCALERS:
             raise PipsHipError(f"unknown scaler {scaler!r}: one of None, 'equilibrium', 'geometric', 'geometric_equilibrium'")
+        if hessians is not None and scaler is not None:
+            raise PipsHipError("problem scaling together with Hessians is not supported")
+        if hessians is not None and len(hessians) != len(blocks):
+            raise PipsHipError(f"hessians has {len(hessians)} entries for {len(blocks)} blocks")
         keep = []
 
         def arr(a, dtype=np.float64):
@@ -1113,7 +1126,11 @@ class GeneralIpmSolver(IpmSolver):
         args = (C.byref(self._h), C.c_int(len(blocks)), cb, C.c_int(myl), C.c_int(mzl), C.c_void_p(arr(root["bL"])), C.c_void_p(arr(root["dlow"])),
                 C.c_void_p(arr(root["dupp"])), C.c_void_p(arr(root["idlow"])), C.c_void_p(arr(root["idupp"])), C.c_double(dual_reg), C.c_int(device),
                 comm._h if comm is not None else None, C.c_int(rank), C.c_int(n_ranks))
-        if scaler is None:
+        if hessians is not None:
+            cq = (_CsrView * len(blocks))(*[view(h) for h in hessians])
+            self._keep = (keep, cb, cq)
+            _check(lib.pips_ipm_create_qp(*args[:3], cq, *args[3:]), "pips_ipm_create_qp")
+        elif scaler is None:
             _check(lib.pips_ipm_create_general(*args), "pips_ipm_create_general")
         else:
             _check(lib.pips_ipm_create_general_scaled(*args, C.c_int(SCALERS[scaler])), "pips_ipm_create_general_scaled")
@@ -1137,8 +1154,17 @@ class GeneralIpmSolver(IpmSolver):
         _check(lib.pips_ipm_mult(self._h, C.c_int(1 if transposed else 0), _ptr(vec), _ptr(out)), "pips_ipm_mult")
         return out
 
+    def hessian_mult(self, vec):
+        """Q vec over x = [x0 | own blocks] (Problem::hessian_multiplication); zeros on a handle without Hessians."""
+        vec = _f64(vec)
+        if vec.shape[0] != self.nx:
+            raise ValueError("vec must have nx entries")
+        out = np.zeros(self.nx)
+        _check(lib.pips_ipm_hessian_mult(self._h, _ptr(vec), _ptr(out)), "pips_ipm_hessian_mult")
+        return out
+
     def outer_solve(self, G, L, rhs, tol=1e-10):
-        """Outer solve of [dd J^T; J diag(0, nOmegaInv)] sol = rhs with the diagonals of the pair vectors G = [t|u|v|w], L = [lambda|pi|gamma|phi]."""
+        """Outer solve of [dd (+ Q) J^T; J diag(0, nOmegaInv)] sol = rhs with the diagonals of the pair vectors G = [t|u|v|w], L = [lambda|pi|gamma|phi]."""
         G, L, rhs = _f64(G), _f64(L), _f64(rhs)
         sol, info = np.zeros(self.nx + self.ny + self.nzr), np.zeros(6)
         _check(lib.pips_ipm_outer_solve(self._h, _ptr(G), _ptr(L), _ptr(rhs), C.c_double(tol), _ptr(sol), _ptr(info)), "pips_ipm_outer_solve")
