@@ -858,7 +858,6 @@ struct Engine : EngineAnalysis, BatchLayout {
    // against 5.5 ms with FP64 atomics - not worth 16 bytes of device memory per contribution and the longer analysis; the switch that
    // selected it alone is gone).  Beyond HEAD_SLOTS_MAX contributions deterministic mode refuses.
    bool head_slots = false;
-   bool slot_solves = false;    // single-RHS forward substitution through slots outside deterministic mode too (measured: no gain)
    static constexpr long long HEAD_SLOTS_MAX = 400LL * 1000 * 1000;
    int last_multi_path = 0;      // how the last solve(nrhs) went: 0 one sweep per right-hand side, 1 interleaved panels, 2 interleaved panels with the slot / gather forward substitution
    std::vector<SlotEntry> sc_e_keep;
@@ -1642,28 +1641,24 @@ struct Engine : EngineAnalysis, BatchLayout {
       int rc = ensure_multi_buffers();
       if (rc) return rc;
       const bool det = deterministic && d_gbuf;
-      if (packed_rhs > 0) return schur_by_packed_solves(SC, det);
-      if (det && ldSC != S) PIPS_FAIL(PIPS_ERR_ARG, "deterministic mode, Schur mode 2: ldSC %d must equal S %d (the group buffers are S x S)", ldSC, S);
       const bool det_panel = det && det_panel_fits();
       if (det_panel && !d_mvslot) PIPS_TRY(d_mvslot.alloc((size_t)std::max<long long>(vslots_total, 1) * MQ));
+      if (packed_rhs > 0) return schur_by_packed_solves(SC, det, det_panel);
+      if (det && ldSC != S) PIPS_FAIL(PIPS_ERR_ARG, "deterministic mode, Schur mode 2: ldSC %d must equal S %d (the group buffers are S x S)", ldSC, S);
       const int bs = 32, ncols = (int)schur_cols.size();
       for (int c0 = 0; c0 < ncols; c0 += bs) {
          const int nr = std::min(bs, ncols - c0);
          HIP_TRY(hipMemsetAsync(d_mx_rhs, 0, (size_t)nr * n_total * sizeof(double), stream));
          hipLaunchKernelGGL(k_border_rows_to_dense, dim3(grid_for(bt_rows_total, 256)), dim3(256), 0, stream, d_bt_rowptr, d_bt_colidx,
                             d_bval, d_bt_rowsc, d_bt_xoff, d_schur_slot, c0, nr, d_mx_rhs, n_total, bt_rows_total);
+         if ((rc = solve_chunk(d_mx_rhs, nr, det, det_panel))) return rc;
          if (det) {
-            if (det_panel) rc = solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw, 1);
-            else
-               for (int r = 0; r < nr && !rc; ++r) rc = solve_once(d_mx_rhs + (long long)r * n_total);
-            if (rc) return rc;
             if (g_btm_grp.n_targets > 0)
                hipLaunchKernelGGL(k_border_tmult_chunk_det, dim3(grid_for(g_btm_grp.n_targets * 32, 256)), dim3(256), 0, stream, g_btm_grp.n_targets,
                                   g_btm_grp.d_tgt, g_btm_grp.d_off, g_btm_grp.d_slots, d_bt_rowptr, d_bt_colidx, d_bval, d_bt_xoff, d_schur_cols + c0, nr,
                                   d_mx_rhs, n_total, d_gbuf, det_gstride(), S, ldSC);
             continue;
          }
-         if ((rc = use_multi(nr) ? solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw) : solve_once(d_mx_rhs, nr, n_total, d_mx_xw))) return rc;
          hipLaunchKernelGGL(k_border_tmult_chunk, dim3(grid_for(bt_rows_total, 256, 1024), nr), dim3(256), 0, stream, d_bt_rowptr,
                             d_bt_colidx, d_bval, d_bt_rowsc, d_bt_xoff, d_schur_cols + c0, nr, d_mx_rhs, n_total, SC, ldSC,
                             bt_rows_total);
@@ -1675,33 +1670,39 @@ struct Engine : EngineAnalysis, BatchLayout {
    // LOCAL columns - right-hand side q holds every block's q-th non-empty border column, so packed_rhs = max_b nb_b right-hand sides
    // instead of one per distinct Schur column (2-link borders: n0 plus two pairs' linking rows, whatever the number of blocks).  Same
    // clear, same choice of sweeps as above; the three kernels address by local column (kernels.hip.h, k_border_tmult_chunk_packed)
-   int schur_by_packed_solves(double* values, bool det) {
+   int schur_by_packed_solves(double* values, bool det, bool det_panel) {
       int rc = PIPS_OK;
-      const bool det_panel = det && det_panel_fits();
-      if (det_panel && !d_mvslot) PIPS_TRY(d_mvslot.alloc((size_t)std::max<long long>(vslots_total, 1) * MQ));
       const int bs = 32;
       for (int q0 = 0; q0 < packed_rhs; q0 += bs) {
          const int nr = std::min(bs, packed_rhs - q0);
          HIP_TRY(hipMemsetAsync(d_mx_rhs, 0, (size_t)nr * n_total * sizeof(double), stream));
          hipLaunchKernelGGL(k_border_rows_to_dense_packed, dim3(grid_for(bt_rows_total, 256)), dim3(256), 0, stream, d_bt_rowptr, d_bt_colidx,
                             d_bval, d_bt_xoff, d_pk_la, q0, nr, d_mx_rhs, n_total, bt_rows_total);
+         if ((rc = solve_chunk(d_mx_rhs, nr, det, det_panel))) return rc;
          if (det) {
-            if (det_panel) rc = solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw, 1);
-            else
-               for (int r = 0; r < nr && !rc; ++r) rc = solve_once(d_mx_rhs + (long long)r * n_total);
-            if (rc) return rc;
             if (g_pk_grp.n_targets > 0)
                hipLaunchKernelGGL(k_border_tmult_chunk_packed_det, dim3(grid_for(g_pk_grp.n_targets, 256)), dim3(256), 0, stream, g_pk_grp.n_targets,
                                   g_pk_grp.d_tgt, g_pk_grp.d_off, g_pk_grp.d_slots, d_bt_rowptr, d_bt_colidx, d_bval, d_bt_xoff, q0, nr, d_mx_rhs,
                                   n_total, d_gbuf);
             continue;
          }
-         if ((rc = use_multi(nr) ? solve_once_multi(d_mx_rhs, nr, n_total, d_mx_xw) : solve_once(d_mx_rhs, nr, n_total, d_mx_xw))) return rc;
          hipLaunchKernelGGL(k_border_tmult_chunk_packed, dim3(grid_for(bt_rows_total, 256, 1024), nr), dim3(256), 0, stream, d_bt_rowptr,
                             d_bt_colidx, d_bval, d_bt_xoff, d_pk_la, d_pk_tabrow, d_sctab, q0, nr, d_mx_rhs, n_total, values, bt_rows_total);
       }
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
+   }
+   // nr <= 32 right-hand sides, contiguous at X, by the sweeps that suit them (work vectors: d_mx_xw).  det: the atomics-free sweeps - one
+   // interleaved panel with whole-panel slicing whatever the launch size (det_panel: d_mvslot holds its slots), else column by column.
+   // Otherwise the interleaved sweep from use_multi's threshold on, below it the per-right-hand-side sweeps
+   int solve_chunk(double* X, int nr, bool det, bool det_panel) {
+      if (det_panel) return solve_once_multi(X, nr, n_total, d_mx_xw, 1);
+      if (det) {
+         int rc = PIPS_OK;
+         for (int r = 0; r < nr && !rc; ++r) rc = solve_once(X + (long long)r * n_total);
+         return rc;
+      }
+      return use_multi(nr) ? solve_once_multi(X, nr, n_total, d_mx_xw) : solve_once(X, nr, n_total, d_mx_xw);
    }
    // deterministic blocked solves: the slots of one interleaved panel (MQ doubles per forward-substitution contribution of the head) within 4 GB, as
    // solve_multi's budget.  (A rank's contributions are a part of the one-rank total: where one rank takes the panels, every rank count does)
@@ -1709,8 +1710,70 @@ struct Engine : EngineAnalysis, BatchLayout {
 
    // workgroups per block of the vector norms: slices of about 16 K rows, the launch kept near the number resident at once
    int absmax_chunks() const { return (int)std::max<long long>(1, std::min<long long>(std::min<long long>(64, 2048 / std::max(nblk, 1) + 1), n_total / std::max(nblk, 1) / 16384 + 1)); }
+   // ---- the head levels of a solve sweep: one walk per direction, on nrhs work vectors at xw + r * xws (the callers keep their own
+   //      prologue, tail sweep and timer phases) ----
+   // Forward substitution.  sx says where a supernode's contributions go.  Mode 0: atomics on the work vector (the chain kernels, any nrhs).
+   // Mode 2, one right-hand side: without atomics - the contributions go to their slots (sx.val), every level first gathers what the lower
+   // levels left for its own columns, the tail rows are gathered before the dense sweep.  border: the border slots of the augmented factor
+   // are targets too (atomics, one right-hand side): the chain kernels take their own border rows, k_leaf_border those of the simple leaves.
+   // (The spine kernels know neither slots nor border rows: deterministic mode refuses spines, aug_sweeps_ok needs spine_total == 0.)
+   void head_forward(double* xw, int nrhs, long long xws, const ScatterCtx& sx, int border) {
+      const bool slots = sx.mode == 2;
+      for (size_t li = 0; li < levels.size(); ++li) {
+         const LevelRange& L = levels[li];
+         if (slots) gather(gv_levels[li], sx.val, xw);
+         if (L.simple_cnt > 0 && lf_rows > 0)   // the leaves' columns are final as they stand: every target row collects its sum
+            hipLaunchKernelGGL(k_leaf_fwd_gather, dim3((unsigned)((lf_rows + 255) / 256), nrhs), dim3(256), 0, stream, d_lf_rows, d_lf_ptr, d_lf_src,
+                               d_lf_val, xw, xws, (int)lf_rows);
+         else if (L.simple_cnt > 0)
+            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, nrhs), dim3(256), 0, stream, d_sns, L.simple_begin,
+                               L.simple_cnt, d_blks, d_rowidx, d_arena, xw, xws, 0, sx);
+         if (border && L.simple_cnt > 0 && n_lb > 0)
+            hipLaunchKernelGGL(k_leaf_border, dim3((n_lb + 255) / 256), dim3(256), 0, stream, d_lb_list, n_lb, d_sns, d_blks, d_rowidx, d_arena, xw, 0);
+         // small and large supernodes of one level are contiguous in d_sns
+         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
+         const int cnt = L.small_cnt + L.large_cnt;
+         if (cnt > 0 && slots)
+            hipLaunchKernelGGL(k_head_fwd, dim3(cnt, 1), dim3(64), 0, stream, d_sns, begin, d_blks, d_rowidx, d_arena, xw, 0LL, sx);
+         else if (cnt > 0)
+            hipLaunchKernelGGL(head_wcap <= 16 ? k_head_fwd_chain<16> : k_head_fwd_chain<HEAD_WMAX>, dim3(cnt, nrhs), dim3(64), 0, stream, d_sns, begin,
+                               d_blks, d_rowidx, d_arena, xw, xws, border);
+      }
+      if (slots) gather(gv_tail, sx.val, xw);
+      if (spine_total > 0)
+         hipLaunchKernelGGL(k_head_solve_spine, dim3(nblk, nrhs), dim3(64), 0, stream, d_spine, d_spine_off, d_sns, d_blks, d_rowidx,
+                            d_arena, xw, xws, 0);
+   }
+   // Backward substitution.  border: the border slots of the work vector hold the root solution and the border rows of the factor take part.
+   // dscale: D^-1 of the head columns inside the kernels (they read the diagonal's cache line anyway) - not with spines, whose kernel has no
+   // such argument.  The simple leaves: from their compact records (k_leaf_bwd: it stops at the border) where the layout has them, their
+   // border rows then by k_leaf_border; leaf_border_inline: instead k_head_solve_simple walks a leaf's rows, border included, in one sum.
+   void head_backward(double* xw, int nrhs, long long xws, int border, int dscale, bool leaf_border_inline = false) {
+      if (spine_total > 0)
+         hipLaunchKernelGGL(k_head_solve_spine, dim3(nblk, nrhs), dim3(64), 0, stream, d_spine, d_spine_off, d_sns, d_blks, d_rowidx,
+                            d_arena, xw, xws, 1, border);
+      const int inline_border = border && leaf_border_inline ? 1 : 0;
+      for (int l = (int)levels.size() - 1; l >= 0; --l) {
+         const LevelRange& L = levels[l];
+         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
+         const int cnt = L.small_cnt + L.large_cnt;
+         if (cnt > 0)
+            hipLaunchKernelGGL(head_wcap <= 16 ? k_head_bwd_chain<16> : k_head_bwd_chain<HEAD_WMAX>, dim3(cnt, nrhs), dim3(64), 0, stream, d_sns, begin,
+                               d_blks, d_rowidx, d_arena, xw, xws, border, dscale);
+         if (L.simple_cnt > 0 && d_leafdesc && !inline_border)
+            hipLaunchKernelGGL(k_leaf_bwd, dim3((L.simple_cnt + 255) / 256, nrhs), dim3(256), 0, stream, d_leafdesc, L.simple_cnt, d_rowidx, d_arena,
+                               xw, xws, dscale);
+         else if (L.simple_cnt > 0)
+            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, nrhs), dim3(256), 0, stream, d_sns, L.simple_begin,
+                               L.simple_cnt, d_blks, d_rowidx, d_arena, xw, xws, 1, sx_atomic(), inline_border, 0, dscale);
+         if (border && !inline_border && L.simple_cnt > 0 && n_lb > 0)
+            hipLaunchKernelGGL(k_leaf_border, dim3((n_lb + 255) / 256), dim3(256), 0, stream, d_lb_list, n_lb, d_sns, d_blks, d_rowidx, d_arena, xw, 1);
+      }
+   }
+
    // nrhs right-hand sides at x_dev + r * x_stride (flat over all blocks each); work vectors at xw + r * xw_total
    int solve_once(double* x_dev, int nrhs = 1, long long x_stride = 0, double* xw = nullptr) {
+      if (deterministic && nrhs != 1) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode solves one right-hand side at a time");
       if (!xw) xw = d_xw;
       const long long xws = nrhs > 1 ? xw_total : 0;
       const dim3 pg(64, nblk, nrhs);
@@ -1718,43 +1781,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       hipLaunchKernelGGL(k_permute_in, pg, dim3(256), 0, stream, d_blks, d_perm, d_perm_off, x_dev, x_stride, xw, xws);
       timer.end(stream);
       timer.begin(stream, 8);
-      if (deterministic && nrhs != 1) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode solves one right-hand side at a time");
-      if (head_slots && nrhs == 1 && (deterministic || slot_solves)) {
-         // forward substitution without atomics: the contributions go to their slots, every level first gathers what the lower
-         // levels left for its own columns, the tail rows are gathered before the dense sweep
-         const ScatterCtx sxv{2, nullptr, d_vslot_val, xw, nullptr};
-         for (size_t li = 0; li < levels.size(); ++li) {
-            const LevelRange& L = levels[li];
-            gather(gv_levels[li], d_vslot_val, xw);
-            if (L.simple_cnt > 0 && lf_rows > 0)
-               hipLaunchKernelGGL(k_leaf_fwd_gather, dim3((unsigned)((lf_rows + 255) / 256), 1), dim3(256), 0, stream, d_lf_rows, d_lf_ptr, d_lf_src,
-                                  d_lf_val, xw, 0LL, (int)lf_rows);
-            else if (L.simple_cnt > 0)
-               hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, 1), dim3(256), 0, stream, d_sns, L.simple_begin,
-                                  L.simple_cnt, d_blks, d_rowidx, d_arena, xw, 0LL, 0, sxv);
-            const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
-            const int cnt = L.small_cnt + L.large_cnt;
-            if (cnt > 0) hipLaunchKernelGGL(k_head_fwd, dim3(cnt, 1), dim3(64), 0, stream, d_sns, begin, d_blks, d_rowidx, d_arena, xw, 0LL, sxv);
-         }
-         gather(gv_tail, d_vslot_val, xw);
-      } else
-      for (const LevelRange& L : levels) {
-         if (L.simple_cnt > 0 && lf_rows > 0)   // the leaves' columns are final as they stand: every target row collects its sum
-            hipLaunchKernelGGL(k_leaf_fwd_gather, dim3((unsigned)((lf_rows + 255) / 256), nrhs), dim3(256), 0, stream, d_lf_rows, d_lf_ptr, d_lf_src,
-                               d_lf_val, xw, xws, (int)lf_rows);
-         else if (L.simple_cnt > 0)
-            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, nrhs), dim3(256), 0, stream, d_sns, L.simple_begin,
-                               L.simple_cnt, d_blks, d_rowidx, d_arena, xw, xws, 0);
-         // small and large supernodes of one level are contiguous in d_sns
-         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
-         const int cnt = L.small_cnt + L.large_cnt;
-         if (cnt > 0)
-            hipLaunchKernelGGL(head_wcap <= 16 ? k_head_fwd_chain<16> : k_head_fwd_chain<HEAD_WMAX>, dim3(cnt, nrhs), dim3(64), 0, stream, d_sns, begin,
-                               d_blks, d_rowidx, d_arena, xw, xws, 0);
-      }
-      if (spine_total > 0)
-         hipLaunchKernelGGL(k_head_solve_spine, dim3(nblk, nrhs), dim3(64), 0, stream, d_spine, d_spine_off, d_sns, d_blks, d_rowidx,
-                            d_arena, xw, xws, 0);
+      head_forward(xw, nrhs, xws, deterministic && head_slots ? ScatterCtx{2, nullptr, d_vslot_val, xw, nullptr} : sx_atomic(), 0);
       timer.end(stream);
       timer.begin(stream, 9);
       TailCtx c = ctx();
@@ -1763,7 +1790,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (rc) return rc;
       // D^-1 of the head columns: fused into the backward kernels of the common path (chain kernels + thread-per-leaf kernel: they
       // read the diagonal's cache line anyway; the separate pass reads 88 bytes of descriptor per supernode - 12.9 M of them on the
-      // configs[3] share); the other paths (spine kernels, deterministic mode, k_head_bwd) keep the pass
+      // configs[3] share); with spines (their kernel does not scale) the pass stays
       const bool fused_d = spine_total == 0;
       if (nsn_total > 0 && !fused_d)
          hipLaunchKernelGGL(k_head_dscale, dim3(grid_for(nsn_total, 256), nrhs), dim3(256), 0, stream, d_sns, nsn_total, d_blks,
@@ -1772,23 +1799,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (rc) return rc;
       timer.end(stream);
       timer.begin(stream, 10);
-      if (spine_total > 0)
-         hipLaunchKernelGGL(k_head_solve_spine, dim3(nblk, nrhs), dim3(64), 0, stream, d_spine, d_spine_off, d_sns, d_blks, d_rowidx,
-                            d_arena, xw, xws, 1);
-      for (int l = (int)levels.size() - 1; l >= 0; --l) {
-         const LevelRange& L = levels[l];
-         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
-         const int cnt = L.small_cnt + L.large_cnt;
-         if (cnt > 0)
-            hipLaunchKernelGGL(head_wcap <= 16 ? k_head_bwd_chain<16> : k_head_bwd_chain<HEAD_WMAX>, dim3(cnt, nrhs), dim3(64), 0, stream, d_sns, begin,
-                               d_blks, d_rowidx, d_arena, xw, xws, 0, fused_d ? 1 : 0);
-         if (L.simple_cnt > 0 && d_leafdesc)
-            hipLaunchKernelGGL(k_leaf_bwd, dim3((L.simple_cnt + 255) / 256, nrhs), dim3(256), 0, stream, d_leafdesc, L.simple_cnt, d_rowidx, d_arena,
-                               xw, xws, fused_d ? 1 : 0);
-         else if (L.simple_cnt > 0)
-            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, nrhs), dim3(256), 0, stream, d_sns, L.simple_begin,
-                               L.simple_cnt, d_blks, d_rowidx, d_arena, xw, xws, 1, sx_atomic(), 0, 0, fused_d ? 1 : 0);
-      }
+      head_backward(xw, nrhs, xws, 0, fused_d ? 1 : 0);
       timer.end(stream);
       timer.begin(stream, 7);
       hipLaunchKernelGGL(k_permute_out, pg, dim3(256), 0, stream, d_blks, d_perm, d_perm_off, x_dev, x_stride, xw, xws);
@@ -1801,9 +1812,18 @@ struct Engine : EngineAnalysis, BatchLayout {
    // and multiplies on the matrix pipe; the per-right-hand-side sweeps (grid.y = right-hand side) re-read L each time.  Round 2 measured
    // one config-2 block, 256 rhs: 11 ms separate / 43 ms interleaved - with a scalar multiply-add loop in the tile kernels; with the
    // matrix-pipe tiles and all panels in every launch the interleaved sweep wins from a few right-hand sides on.
+   // PIPS_HIP_MULTI, read at every call (tests change it between the solves of one process).  Not set: the rule above, and solve_once_multi
+   // slices its tail sweeps by the launch size.  0: never interleaved.  Any other value: from two right-hand sides on; 2 also takes whole
+   // panels whatever the size, 4 half panels
+   struct MultiKnob { int from; int slices; };   // fewest right-hand sides of an interleaved sweep (0 = never); forced slicing (0 = none)
+   static MultiKnob multi_knob() {
+      const char* f = getenv("PIPS_HIP_MULTI");
+      const int v = f ? atoi(f) : 1;
+      return MultiKnob{!f ? 8 : v != 0 ? 2 : 0, v == 2 ? 1 : v == 4 ? 2 : 0};
+   }
    bool use_multi(int nr) const {
-      if (const char* f = getenv("PIPS_HIP_MULTI")) return atoi(f) != 0 && nr >= 2;
-      return nr >= 8;
+      const int from = multi_knob().from;
+      return from > 0 && nr >= from;
    }
 
    // nr right-hand sides at X + q * x_stride in one interleaved sweep (kernels.hip.h "multi-vector solves"): panels of MQ, every launch
@@ -1855,9 +1875,9 @@ struct Engine : EngineAnalysis, BatchLayout {
       // of the launch must be resident for the slices to advance side by side (two per compute unit: the whole tile sits in registers), so the
       // finest slicing that keeps the launch within 512 workgroups is taken
       const long long wg = (long long)sweep.n_tasks * np;
-      const int forced = env_int("PIPS_HIP_MULTI", 1);   // (2: whole panels whatever the size, 4: half panels - tests)
+      const int forced = multi_knob().slices;   // (tests)
       // (pin_slices: a fixed slicing - the blocked Schur solves of deterministic mode, whose bits must not follow sweep.n_tasks, i.e. the blocks per rank)
-      const int sl = pin_slices ? pin_slices : forced == 2 ? 1 : forced == 4 ? 2 : wg * 4 <= 512 ? 4 : wg * 2 <= 512 ? 2 : 1;
+      const int sl = pin_slices ? pin_slices : forced ? forced : wg * 4 <= 512 ? 4 : wg * 2 <= 512 ? 2 : 1;
       auto tail_rows = [&](int backward) {
          const SweepArgs sa = sweep.args(0, stream);
          if (sl == 4 && !backward) hipLaunchKernelGGL(k_mtail_rows_fwd<2>, dim3(sweep.n_tasks, np * 4), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);
@@ -1947,11 +1967,7 @@ struct Engine : EngineAnalysis, BatchLayout {
                                         (size_t)n_total * sizeof(double), nr, hipMemcpyDeviceToDevice, stream));
                Xc = d_mx_xw;
             }
-            hipLaunchKernelGGL(k_full_spmv_sub, dim3(grid_for(n_total * 8, 256, 65536), nr), dim3(256), 0, stream, d_frowptr, d_fcol, d_fsrc, d_kval,
-                               Xc, d_mx_res, n_total, d_rowbase, n_total);
-            if (n_flong > 0)
-               hipLaunchKernelGGL(k_full_spmv_sub_long, dim3(n_flong, nr), dim3(256), 0, stream, d_flong, d_frowptr, d_fcol, d_fsrc, d_kval,
-                                  Xc, d_mx_res, d_rowbase, n_total);
+            if ((rc = launch_residual(Xc, n_total, nullptr, d_mx_res, nr))) return rc;
             int n_fix = nr;   // right-hand sides that take the correction solve: all of them, or (adaptive) those whose measure says so
             if (refine_tol > 0.0 && d_mmeasure) {
                // adaptive like the single right-hand side (solve()), per right-hand side like PARDISO: every column's worst block is measured,
@@ -1978,6 +1994,7 @@ struct Engine : EngineAnalysis, BatchLayout {
                   HIP_TRY(hipMemcpyAsync(d_midx, fix, (size_t)n_fix * sizeof(int), hipMemcpyHostToDevice, stream));
                }
             }
+            // (not solve_chunk: the choice follows the whole batch (multi), not n_fix, and a deterministic panel keeps the slicing of the first solve)
             rc = (multi && (n_fix > 1 || det_multi)) ? solve_once_multi(d_mx_res, n_fix, n_total, d_mx_xw) : solve_once(d_mx_res, n_fix, n_total, d_mx_xw);
             if (rc) return rc;
             if (n_fix < nr) hipLaunchKernelGGL(k_maxpy_idx, dim3(grid_for(n_total, 256, 1024), n_fix), dim3(256), 0, stream, X, x_stride, d_mx_res, n_total, 1.0, n_total, d_midx);
@@ -1986,6 +2003,48 @@ struct Engine : EngineAnalysis, BatchLayout {
          }
       }
       HIP_TRY(hipGetLastError());
+      return PIPS_OK;
+   }
+
+   // res = rhs - K x for nr vectors at distance stride (x and res alike) against the CSR values on the device.  rhs == nullptr: res holds the
+   // right-hand sides on entry.  Else (one vector) the copy of rhs is folded into the product - unless there are long rows, whose kernel
+   // subtracts from what res holds
+   int launch_residual(const double* x, long long stride, const double* rhs, double* res, int nr) {
+      if (rhs && n_flong > 0) {
+         HIP_TRY(hipMemcpyAsync(res, rhs, (size_t)n_total * sizeof(double), hipMemcpyDeviceToDevice, stream));
+         rhs = nullptr;
+      }
+      hipLaunchKernelGGL(k_full_spmv_sub, dim3(grid_for(n_total * 8, 256, 65536), nr), dim3(256), 0, stream, d_frowptr, d_fcol, d_fsrc, d_kval,
+                         x, res, n_total, d_rowbase, stride, rhs);
+      if (n_flong > 0)
+         hipLaunchKernelGGL(k_full_spmv_sub_long, dim3(n_flong, nr), dim3(256), 0, stream, d_flong, d_frowptr, d_fcol, d_fsrc, d_kval, x, res, d_rowbase, stride);
+      return PIPS_OK;
+   }
+   // The measure of the adaptive refinement from the per-block norms on the device (d_norms: ||r_b||inf, ||rhs_b||inf, ||x_b||inf): the worst
+   // block of ||r_b|| over the denominator of refine_mode - max|K_b| ||x_b|| + ||rhs_b|| (normwise backward error) or ||rhs_b||.  Ends the
+   // caller's timer phase behind the copy of the norms; one host wait
+   int worst_from_norms(double* worst_out) {
+      HIP_TRY(hipMemcpyAsync(h_norms, d_norms, (size_t)3 * nblk * sizeof(double), hipMemcpyDeviceToHost, stream));
+      timer.end(stream);
+      std::vector<BlkDesc> tmp;
+      const bool need_amax = refine_mode == 1 && h_amax.empty();   // (the blocks' largest entries: once per factorisation, with the same wait)
+      if (need_amax) {
+         tmp.resize(nblk);
+         HIP_TRY(hipMemcpyAsync(tmp.data(), d_blks, (size_t)nblk * sizeof(BlkDesc), hipMemcpyDeviceToHost, stream));
+      }
+      HIP_TRY(hipStreamSynchronize(stream));
+      if (need_amax) {
+         h_amax.resize(nblk);
+         for (int b = 0; b < nblk; ++b) h_amax[b] = tmp[b].repl_abs / (repl_rel > 0 ? repl_rel : 1.0);   // = max|K_b| (k_block_absmax)
+      }
+      double worst = 0.0;
+      for (int b = 0; b < nblk; ++b) {
+         const double den = refine_mode == 1 ? h_amax[b] * h_norms[2 * nblk + b] + h_norms[nblk + b] : h_norms[nblk + b];
+         // (a non-finite norm - Inf, or Inf / Inf = NaN - must win the comparison: never "converged" on a poisoned iterate)
+         if (den > 0.0) { const double q = h_norms[b] / den; if (!(q <= worst)) worst = q; }
+      }
+      *worst_out = worst;
+      last_refine_measure = worst;
       return PIPS_OK;
    }
 
@@ -2007,13 +2066,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (rc) return rc;
       for (int it = 0; it < refine_steps; ++it) {
          timer.begin(stream, 11);
-         // r = rhs - K x; without long rows the copy of rhs is folded into the product
-         if (n_flong > 0) HIP_TRY(hipMemcpyAsync(d_res, d_rhs, bytes, hipMemcpyDeviceToDevice, stream));
-         hipLaunchKernelGGL(k_full_spmv_sub, dim3(grid_for(n_total * 8, 256, 65536)), dim3(256), 0, stream, d_frowptr, d_fcol, d_fsrc, d_kval,
-                            x_dev, d_res, n_total, d_rowbase, 0LL, n_flong > 0 ? (const double*)nullptr : d_rhs);
-         if (n_flong > 0)
-            hipLaunchKernelGGL(k_full_spmv_sub_long, dim3(n_flong), dim3(256), 0, stream, d_flong, d_frowptr, d_fcol, d_fsrc, d_kval, x_dev,
-                               d_res, d_rowbase, 0LL);
+         if ((rc = launch_residual(x_dev, 0, d_rhs, d_res, 1))) return rc;
          if (refine_tol > 0.0) {
             HIP_TRY(hipMemsetAsync(d_norms, 0, (size_t)nblk * sizeof(double), stream));
             hipLaunchKernelGGL(k_vec_block_absmax, dim3(absmax_chunks(), nblk), dim3(256), 0, stream, d_res, d_blks, d_norms);
@@ -2021,23 +2074,8 @@ struct Engine : EngineAnalysis, BatchLayout {
                HIP_TRY(hipMemsetAsync(d_norms + 2 * nblk, 0, (size_t)nblk * sizeof(double), stream));
                hipLaunchKernelGGL(k_vec_block_absmax, dim3(absmax_chunks(), nblk), dim3(256), 0, stream, x_dev, d_blks, d_norms + 2 * nblk);
             }
-            HIP_TRY(hipMemcpyAsync(h_norms, d_norms, (size_t)3 * nblk * sizeof(double), hipMemcpyDeviceToHost, stream));
-            timer.end(stream);
-            if (refine_mode == 1 && h_amax.empty()) {
-               h_amax.resize(nblk);
-               std::vector<BlkDesc> tmp(nblk);
-               HIP_TRY(hipMemcpyAsync(tmp.data(), d_blks, (size_t)nblk * sizeof(BlkDesc), hipMemcpyDeviceToHost, stream));
-               HIP_TRY(hipStreamSynchronize(stream));
-               for (int b = 0; b < nblk; ++b) h_amax[b] = tmp[b].repl_abs / (repl_rel > 0 ? repl_rel : 1.0);   // = max|K_b| (k_block_absmax)
-            }
-            HIP_TRY(hipStreamSynchronize(stream));
-            double worst = 0.0;
-            for (int b = 0; b < nblk; ++b) {
-               const double den = refine_mode == 1 ? h_amax[b] * h_norms[2 * nblk + b] + h_norms[nblk + b] : h_norms[nblk + b];
-               // (a non-finite norm - Inf, or Inf / Inf = NaN - must win the comparison: never "converged" on a poisoned iterate)
-               if (den > 0.0) { const double q = h_norms[b] / den; if (!(q <= worst)) worst = q; }
-            }
-            last_refine_measure = worst;
+            double worst;
+            if ((rc = worst_from_norms(&worst))) return rc;
             if (worst <= refine_tol) break;
          } else
             timer.end(stream);
@@ -2054,35 +2092,13 @@ struct Engine : EngineAnalysis, BatchLayout {
    // refine_mode (normwise backward error, or ||rhs||inf) - one product with the CSR values, the norms, one small copy to the host.
    int residual_measure(const double* rhs_dev, const double* x_dev, double* worst_out) {
       if (refine_steps <= 0 || !d_res || !d_norms) PIPS_FAIL(PIPS_ERR_STATE, "residual_measure: refinement buffers missing");
-      const size_t bytes = (size_t)n_total * sizeof(double);
       timer.begin(stream, 11);
       HIP_TRY(hipMemsetAsync(d_norms, 0, (size_t)3 * nblk * sizeof(double), stream));
       hipLaunchKernelGGL(k_vec_block_absmax, dim3(absmax_chunks(), nblk), dim3(256), 0, stream, rhs_dev, d_blks, d_norms + nblk);
-      if (n_flong > 0) HIP_TRY(hipMemcpyAsync(d_res, rhs_dev, bytes, hipMemcpyDeviceToDevice, stream));
-      hipLaunchKernelGGL(k_full_spmv_sub, dim3(grid_for(n_total * 8, 256, 65536)), dim3(256), 0, stream, d_frowptr, d_fcol, d_fsrc, d_kval, x_dev, d_res, n_total,
-                         d_rowbase, 0LL, n_flong > 0 ? (const double*)nullptr : rhs_dev);
-      if (n_flong > 0)
-         hipLaunchKernelGGL(k_full_spmv_sub_long, dim3(n_flong), dim3(256), 0, stream, d_flong, d_frowptr, d_fcol, d_fsrc, d_kval, x_dev, d_res, d_rowbase, 0LL);
+      if (int rc = launch_residual(x_dev, 0, rhs_dev, d_res, 1)) return rc;
       hipLaunchKernelGGL(k_vec_block_absmax, dim3(absmax_chunks(), nblk), dim3(256), 0, stream, d_res, d_blks, d_norms);
       if (refine_mode == 1) hipLaunchKernelGGL(k_vec_block_absmax, dim3(absmax_chunks(), nblk), dim3(256), 0, stream, x_dev, d_blks, d_norms + 2 * nblk);
-      HIP_TRY(hipMemcpyAsync(h_norms, d_norms, (size_t)3 * nblk * sizeof(double), hipMemcpyDeviceToHost, stream));
-      timer.end(stream);
-      if (refine_mode == 1 && h_amax.empty()) {
-         h_amax.resize(nblk);
-         std::vector<BlkDesc> tmp(nblk);
-         HIP_TRY(hipMemcpyAsync(tmp.data(), d_blks, (size_t)nblk * sizeof(BlkDesc), hipMemcpyDeviceToHost, stream));
-         HIP_TRY(hipStreamSynchronize(stream));
-         for (int b = 0; b < nblk; ++b) h_amax[b] = tmp[b].repl_abs / (repl_rel > 0 ? repl_rel : 1.0);
-      }
-      HIP_TRY(hipStreamSynchronize(stream));
-      double worst = 0.0;
-      for (int b = 0; b < nblk; ++b) {
-         const double den = refine_mode == 1 ? h_amax[b] * h_norms[2 * nblk + b] + h_norms[nblk + b] : h_norms[nblk + b];
-         if (den > 0.0) { const double q = h_norms[b] / den; if (!(q <= worst)) worst = q; }
-      }
-      *worst_out = worst;
-      last_refine_measure = worst;
-      return PIPS_OK;
+      return worst_from_norms(worst_out);
    }
 
    // the measure of a solveCompressed by sweeps in one launch (k_measure_leaf_rows): x = the result, b = the leaf right-hand side as the
@@ -2095,27 +2111,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       hipLaunchKernelGGL(k_measure_leaf_rows, dim3(std::max(absmax_chunks(), (int)std::min<long long>(256, n_total / std::max(nblk, 1) / 2048 + 1)), nblk), dim3(256), 0, stream,
                          d_blks, d_frowptr, d_fcol, d_fsrc, d_kval, x_dev, b_dev, bt_rows_total > 0 ? d_br_rowptr : (const int*)nullptr, d_br_sc, d_br_src, d_bval, x0_dev,
                          d_norms, nblk);
-      HIP_TRY(hipMemcpyAsync(h_norms, d_norms, (size_t)3 * nblk * sizeof(double), hipMemcpyDeviceToHost, stream));
-      timer.end(stream);
-      std::vector<BlkDesc> tmp;
-      const bool need_amax = refine_mode == 1 && h_amax.empty();   // (the blocks' largest entries: once per factorisation, with the same wait)
-      if (need_amax) {
-         tmp.resize(nblk);
-         HIP_TRY(hipMemcpyAsync(tmp.data(), d_blks, (size_t)nblk * sizeof(BlkDesc), hipMemcpyDeviceToHost, stream));
-      }
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (need_amax) {
-         h_amax.resize(nblk);
-         for (int b = 0; b < nblk; ++b) h_amax[b] = tmp[b].repl_abs / (repl_rel > 0 ? repl_rel : 1.0);
-      }
-      double worst = 0.0;
-      for (int b = 0; b < nblk; ++b) {
-         const double den = refine_mode == 1 ? h_amax[b] * h_norms[2 * nblk + b] + h_norms[nblk + b] : h_norms[nblk + b];
-         if (den > 0.0) { const double q = h_norms[b] / den; if (!(q <= worst)) worst = q; }
-      }
-      *worst_out = worst;
-      last_refine_measure = worst;
-      return PIPS_OK;
+      return worst_from_norms(worst_out);
    }
 
    // The inertia counters travel to pinned host memory at the end of every factorisation (factor()); a query only waits for that
@@ -2173,21 +2169,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       hipLaunchKernelGGL(k_permute_in, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, b_dev, 0LL, d_xw, 0LL);
       timer.end(stream);
       timer.begin(stream, 8);
-      for (const LevelRange& L : levels) {
-         if (L.simple_cnt > 0 && lf_rows > 0)
-            hipLaunchKernelGGL(k_leaf_fwd_gather, dim3((unsigned)((lf_rows + 255) / 256), 1), dim3(256), 0, stream, d_lf_rows, d_lf_ptr, d_lf_src, d_lf_val, d_xw,
-                               0LL, (int)lf_rows);
-         else if (L.simple_cnt > 0)
-            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, 1), dim3(256), 0, stream, d_sns, L.simple_begin, L.simple_cnt, d_blks,
-                               d_rowidx, d_arena, d_xw, 0LL, 0);
-         if (L.simple_cnt > 0 && n_lb > 0)
-            hipLaunchKernelGGL(k_leaf_border, dim3((n_lb + 255) / 256), dim3(256), 0, stream, d_lb_list, n_lb, d_sns, d_blks, d_rowidx, d_arena, d_xw, 0);
-         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
-         const int cnt = L.small_cnt + L.large_cnt;
-         if (cnt > 0)
-            hipLaunchKernelGGL(head_wcap <= 16 ? k_head_fwd_chain<16> : k_head_fwd_chain<HEAD_WMAX>, dim3(cnt, 1), dim3(64), 0, stream, d_sns, begin, d_blks,
-                               d_rowidx, d_arena, d_xw, 0LL, 1);
-      }
+      head_forward(d_xw, 1, 0, sx_atomic(), 1);
       timer.end(stream);
       timer.begin(stream, 9);   // (one record of this phase per pass: the backward half books its tail sweep with the head's)
       TailCtx c = ctx();
@@ -2214,21 +2196,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       hipLaunchKernelGGL(k_permute_in, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, b_dev, 0LL, d_xw, 0LL);
       timer.end(stream);
       timer.begin(stream, 8);
-      const ScatterCtx sxv{2, nullptr, d_vslot_val, d_xw, nullptr};
-      for (size_t li = 0; li < levels.size(); ++li) {
-         const LevelRange& L = levels[li];
-         gather(gv_levels[li], d_vslot_val, d_xw);
-         if (L.simple_cnt > 0 && lf_rows > 0)
-            hipLaunchKernelGGL(k_leaf_fwd_gather, dim3((unsigned)((lf_rows + 255) / 256), 1), dim3(256), 0, stream, d_lf_rows, d_lf_ptr, d_lf_src, d_lf_val, d_xw,
-                               0LL, (int)lf_rows);
-         else if (L.simple_cnt > 0)
-            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, 1), dim3(256), 0, stream, d_sns, L.simple_begin, L.simple_cnt, d_blks,
-                               d_rowidx, d_arena, d_xw, 0LL, 0, sxv);
-         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
-         const int cnt = L.small_cnt + L.large_cnt;
-         if (cnt > 0) hipLaunchKernelGGL(k_head_fwd, dim3(cnt, 1), dim3(64), 0, stream, d_sns, begin, d_blks, d_rowidx, d_arena, d_xw, 0LL, sxv);
-      }
-      gather(gv_tail, d_vslot_val, d_xw);
+      head_forward(d_xw, 1, 0, ScatterCtx{2, nullptr, d_vslot_val, d_xw, nullptr}, 0);   // (the border slots: by the two kernels below, from the finished head part)
       hipLaunchKernelGGL(k_border_rowdot_det, dim3(grid_for(n_bg_ent, 256, 1 << 20)), dim3(256), 0, stream, n_bg_ent, d_bg_ent, d_arena, d_xw, d_bg_val);
       hipLaunchKernelGGL(k_border_gather_det, dim3((unsigned)((n_bg_targets + 3) / 4)), dim3(256), 0, stream, n_bg_targets, d_bg_ptr, d_bg_idx, d_bg_slot, d_bg_val, d_xw);
       timer.end(stream);
@@ -2255,21 +2223,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       c.timer = nullptr;
       int rc = tail_bwd(c, d_xw, 1, 0, 1);
       if (rc) return rc;
-      for (int l = (int)levels.size() - 1; l >= 0; --l) {
-         const LevelRange& L = levels[l];
-         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
-         const int cnt = L.small_cnt + L.large_cnt;
-         if (cnt > 0)
-            hipLaunchKernelGGL(head_wcap <= 16 ? k_head_bwd_chain<16> : k_head_bwd_chain<HEAD_WMAX>, dim3(cnt, 1), dim3(64), 0, stream, d_sns, begin, d_blks,
-                               d_rowidx, d_arena, d_xw, 0LL, 1, 1);
-         if (L.simple_cnt > 0 && d_leafdesc)
-            hipLaunchKernelGGL(k_leaf_bwd, dim3((L.simple_cnt + 255) / 256, 1), dim3(256), 0, stream, d_leafdesc, L.simple_cnt, d_rowidx, d_arena, d_xw, 0LL, 1);
-         else if (L.simple_cnt > 0)
-            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, 1), dim3(256), 0, stream, d_sns, L.simple_begin, L.simple_cnt, d_blks,
-                               d_rowidx, d_arena, d_xw, 0LL, 1, sx_atomic(), 0, 0, 1);
-         if (L.simple_cnt > 0 && n_lb > 0)
-            hipLaunchKernelGGL(k_leaf_border, dim3((n_lb + 255) / 256), dim3(256), 0, stream, d_lb_list, n_lb, d_sns, d_blks, d_rowidx, d_arena, d_xw, 1);
-      }
+      head_backward(d_xw, 1, 0, 1, 1);
       timer.end(stream);
       timer.begin(stream, 7);
       hipLaunchKernelGGL(k_permute_out, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, out_dev, 0LL, d_xw, 0LL);
@@ -2285,20 +2239,8 @@ struct Engine : EngineAnalysis, BatchLayout {
       TailCtx c = ctx();
       int rc = tail_bwd(c, d_xw, 1, 0, 1);
       if (rc) return rc;
-      const ScatterCtx none{0, nullptr, nullptr, nullptr, nullptr};
-      if (spine_total > 0)
-         hipLaunchKernelGGL(k_head_solve_spine, dim3(nblk, 1), dim3(64), 0, stream, d_spine, d_spine_off, d_sns, d_blks, d_rowidx, d_arena, d_xw, 0LL, 1, 1);
-      for (int l = (int)levels.size() - 1; l >= 0; --l) {
-         const LevelRange& L = levels[l];
-         const int begin = L.small_cnt > 0 ? L.small_begin : L.large_begin;
-         const int cnt = L.small_cnt + L.large_cnt;
-         if (cnt > 0)
-            hipLaunchKernelGGL(head_wcap <= 16 ? k_head_bwd_chain<16> : k_head_bwd_chain<HEAD_WMAX>, dim3(cnt, 1), dim3(64), 0, stream, d_sns, begin,
-                               d_blks, d_rowidx, d_arena, d_xw, 0LL, 1, 0);
-         if (L.simple_cnt > 0)
-            hipLaunchKernelGGL(k_head_solve_simple, dim3((L.simple_cnt + 255) / 256, 1), dim3(256), 0, stream, d_sns, L.simple_begin, L.simple_cnt,
-                               d_blks, d_rowidx, d_arena, d_xw, 0LL, 1, none, 1);
-      }
+      // no D^-1 (the right-hand side is zero); the leaves take their border rows in the sum of their other rows
+      head_backward(d_xw, 1, 0, 1, 0, true);
       hipLaunchKernelGGL(k_permute_out, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, out_dev, 0LL, d_xw, 0LL);
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
