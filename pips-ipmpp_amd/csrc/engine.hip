@@ -323,6 +323,14 @@ struct PhaseTimer {
    void end_i(int idx, hipStream_t s) {
       if (on && idx >= 0) (void)hipEventRecord(recs[idx].b, s);
    }
+   // a record over a lexical scope: begins where it is declared, ends where the scope is left, an error return included.  t may be null
+   struct Scope {
+      PhaseTimer* t; hipStream_t s; int idx;
+      Scope(PhaseTimer* t_, hipStream_t s_, int phase) : t(t_), s(s_), idx(t_ ? t_->begin_i(s_, phase) : -1) {}
+      ~Scope() { if (t) t->end_i(idx, s); }
+      Scope(const Scope&) = delete;
+      Scope& operator=(const Scope&) = delete;
+   };
    void collect() {
       for (int i = 0; i < NPHASE; ++i) { ms[i] = 0; cnt[i] = 0; }
       for (auto& r : recs) {
@@ -410,25 +418,27 @@ struct TailSingle {
    }
 };
 
+// Plain data, built per call and filled by name (Engine::ctx, DenseLdl::ctx): what only one of the two owners has keeps its default with the other
 struct TailCtx {
-   const BlkDesc* d_blks;
-   const TailPlan* plan;
-   double* d_arena;
-   double* d_dtail;
-   double* d_winv;
-   const signed char* d_psign;
-   const long long* d_psign_off;
-   const int* d_bmap;
-   int* d_inertia;
-   hipStream_t stream;
-   PhaseTimer* timer;
-   const double* d_pref;
+   const BlkDesc* d_blks = nullptr;
+   const TailPlan* plan = nullptr;
+   double* d_arena = nullptr;
+   double* d_uarena = nullptr;          // scaled copies U = L D of the tail rows (BlkDesc::U), B operand of the updates
+   double* d_dtail = nullptr;
+   double* d_winv = nullptr;
+   const signed char* d_psign = nullptr;
+   const long long* d_psign_off = nullptr;
+   int* d_inertia = nullptr;
+   const double* d_pref = nullptr;
+   hipStream_t stream = nullptr;
    hipStream_t side = nullptr;          // second stream for the lookahead of the right-looking root factorisation
    hipEvent_t ev_panel = nullptr;       // main -> side: panel j is final (trsm done)
    hipEvent_t ev_rest = nullptr;        // side -> main: trailing update of panel j is done
+   SweepRt* sweep = nullptr;            // single-launch solve sweeps
+   PhaseTimer* timer = nullptr;         // leaf batch: where the factorisation books its tail phases (Engine::factor_tail sets it, the solves do not)
+   const int* d_bmap = nullptr;         // leaf batch: compressed border ids of the blocks
    bool is_root = false;                // dense root: same update kernel under its own name (k_tile_gemm<3>)
    const int* d_sctab = nullptr;        // sparse Schur complement: per-block position tables (kernels.hip.h sc_entry)
-   double* d_uarena = nullptr;          // scaled copies U = L D of the tail rows (BlkDesc::U), B operand of the updates
    // Schur SYRK in row-panel groups (several ranks): group p holds the tile rows whose first Schur row lies in panel p; after
    // its launch ev_sc[p] is recorded and rows of panel p are final on this rank (Engine::set_sc_panels)
    const std::vector<TaskList>* sc_groups = nullptr;
@@ -450,7 +460,6 @@ struct TailCtx {
    long long sc_len = 0;                // sparse Schur complement: length of its value array (one group buffer)
    bool det_defer_reduce = false;       // several ranks: the group buffers are added over ALL ranks' groups in one fixed tree by the caller
    bool det_reduce_later = false;       // Schur mode 2: the blocked solves fill the group buffers after the tail; Engine::factor adds them then
-   SweepRt* sweep = nullptr;            // single-launch solve sweeps
    bool bunch_kaufman = false;          // diagonal tiles with 1 x 1 / 2 x 2 pivoting (k_tile_diag_bk) instead of the static pivot order
    int *d_pert_cnt = nullptr, *d_pert_list = nullptr;   // ... and where they record the indices no pivot was found for inside the tile
    const double* bk_orig = nullptr;                     // the matrix being factorised as the caller holds it (partner search), its layout, the order
@@ -474,59 +483,80 @@ static void reduce_det_groups(const TailCtx& c, double* SC, int ldSC) {
                          c.gstride, c.n_groups, c.first_slot);
 }
 
-static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
-   const TailPlan& p = *c.plan;
-   auto gemm_diag_tiles = [&](const TaskList& l, hipStream_t st) {
-      hipLaunchKernelGGL(k_tile_gemm<4>, dim3((l.cnt + 7) / 8 * 8), dim3(512), 0, st, p.d_tasks + l.off, l.cnt, c.d_blks, c.d_arena,
-                         c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
-   };
-   auto gemm0 = [&](const TaskList& l, hipStream_t st) {
-      // leaf tails: launches of two rounds of the chip or more draw their tiles from per-XCD counters with an eighth more workgroups than
-      // tiles (k_tile_gemm_bal); smaller ones one tile per workgroup.  (A persistent work-stealing variant, static shares, the root's bulk
-      // in chunks or as a persistent launch with fewer workgroups than the chip holds: measured, no gain - docs/HISTORY_r4.md.)
-      if (!c.is_root && c.d_ctr_pool && l.cnt >= GEMM_BAL_MIN_TASKS && *c.ctr_cursor < GEMM_CTR_SLOTS) {
-         int* ctr = c.d_ctr_pool + 8 * (*c.ctr_cursor)++;
-         const int wgs = ((l.cnt + 7) / 8 * 8) / 8 * 9;
-         hipLaunchKernelGGL(k_tile_gemm_bal<0>, dim3((wgs + 7) / 8 * 8), dim3(512), 0, st, p.d_tasks + l.off, l.cnt, c.d_blks, c.d_arena, c.d_dtail,
-                            c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena, ctr);
-         return;
+// The launch sites of the tile kernels (kernels.hip.h), one per kernel: list l of the task array `tasks` on stream st.  k_tile_gemm (MODE 0 / 3 / 4
+// updates, 1 / 5 trsm, 2 the Schur SYRK) deals its tasks to eight shares, one per XCD: a multiple of eight workgroups.  Only the SYRK takes SC, the
+// position tables of a sparse SC and, in deterministic rounds, the group buffers
+static inline int tile_grid(int n) { return (n + 7) / 8 * 8; }
+template <int MODE>
+static void launch_tile_gemm(const TailCtx& c, const TileTask* tasks, const TaskList& l, hipStream_t st, double* SC = nullptr, int ldSC = 0) {
+   const bool rounds = MODE == 2 && c.det_rounds;
+   hipLaunchKernelGGL(k_tile_gemm<MODE>, dim3(tile_grid(l.cnt)), dim3(512), 0, st, tasks + l.off, l.cnt, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, SC, ldSC,
+                      MODE == 2 ? c.d_sctab : nullptr, c.d_uarena, rounds ? c.d_gbuf : nullptr, rounds ? c.gstride : 0, rounds ? c.d_blk_group : nullptr);
+}
+// k_tile_gemm_bal (MODE 0 and 2): an eighth more workgroups than tasks, which they draw from the next eight-counter slot of the pool
+static bool tile_gemm_bal_ready(const TailCtx& c) { return c.d_ctr_pool && *c.ctr_cursor < GEMM_CTR_SLOTS; }
+template <int MODE>
+static void launch_tile_gemm_bal(const TailCtx& c, const TileTask* tasks, const TaskList& l, hipStream_t st, double* SC = nullptr, int ldSC = 0) {
+   const int wgs = tile_grid(l.cnt) / 8 * 9;
+   hipLaunchKernelGGL(k_tile_gemm_bal<MODE>, dim3(tile_grid(wgs)), dim3(512), 0, st, tasks + l.off, l.cnt, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, SC, ldSC,
+                      MODE == 2 ? c.d_sctab : nullptr, c.d_uarena, c.d_ctr_pool + 8 * (*c.ctr_cursor)++);
+}
+// the diagonal tiles of a column, one workgroup each: Bunch-Kaufman or the static pivot order
+static void launch_tile_diag(const TailCtx& c, const TileTask* tasks, const TaskList& l, hipStream_t st) {
+   if (c.bunch_kaufman)
+      hipLaunchKernelGGL(k_tile_diag_bk, dim3(l.cnt), dim3(256), 0, st, tasks + l.off, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_inertia, c.d_pert_cnt, c.d_pert_list,
+                         c.bk_orig, c.bk_orig_ld, c.bk_orig_rowmajor, c.d_bk_perm, c.bk_isolate);
+   else
+      hipLaunchKernelGGL(k_tile_diag, dim3(l.cnt), dim3(256), 0, st, tasks + l.off, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_psign, c.d_psign_off, c.d_inertia, c.d_pref);
+}
+// leaf tails: launches of two rounds of the chip or more draw their tiles from per-XCD counters with an eighth more workgroups than
+// tiles (k_tile_gemm_bal); smaller ones one tile per workgroup.  (A persistent work-stealing variant, static shares, the root's bulk
+// in chunks or as a persistent launch with fewer workgroups than the chip holds: measured, no gain - docs/HISTORY_r4.md.)
+static void launch_tile_update(const TailCtx& c, const TaskList& l, hipStream_t st) {
+   if (!c.is_root && l.cnt >= GEMM_BAL_MIN_TASKS && tile_gemm_bal_ready(c))
+      launch_tile_gemm_bal<0>(c, c.plan->d_tasks, l, st);
+   else if (c.is_root)
+      // The bulk update of the trailing matrix runs on the side stream beside the diagonal-tile chain of the next column.  Stream
+      // priorities only order the launches the command processor has not started yet: once a launch of thousands of workgroups is
+      // running, the single workgroup of k_tile_diag gets no slot until that launch drains (rocprofv3 trace at S = 16000: the diagonal
+      // kernel "takes" 270 - 1140 us beside the bulk and 70 us alone - it is waiting): the lookahead overlaps only the drain.
+      launch_tile_gemm<3>(c, c.plan->d_tasks, l, st);
+   else
+      launch_tile_gemm<0>(c, c.plan->d_tasks, l, st);
+}
+
+// PIPS_HIP_TAIL_TRACE: the per-task clocks of a k_tail_ldl launch into a file (tools/tail_trace.py); waits for the launch
+static int dump_tail_trace(const TailCtx& c, DevBuf<long long>& d_trace, size_t n_trace, const char* trace_file) {
+   const TailSingle& ts = *c.single;
+   std::vector<long long> h(n_trace);
+   std::vector<TileTask> ht((size_t)ts.n_tasks);
+   HIP_TRY(hipStreamSynchronize(c.stream));
+   HIP_TRY(hipMemcpy(h.data(), d_trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(ht.data(), ts.d_tasks, ht.size() * sizeof(TileTask), hipMemcpyDeviceToHost));
+   d_trace.reset();
+   if (FILE* f = fopen(trace_file, "w")) {   // ticket, list, kind, block, ti, tj, K range, the three clocks
+      for (int t = 0; t < ts.n_tasks; ++t) {
+         int x = 0;
+         while (x < 7 && t >= ts.args.xoff[x + 1]) ++x;
+         fprintf(f, "%d %d %d %d %d %d %d %lld %lld %lld\n", t, x, ht[t].blk >> 24, ht[t].blk & 0xffffff, ht[t].ti, ht[t].tj, ht[t].pad, h[3 * (size_t)t], h[3 * (size_t)t + 1],
+                 h[3 * (size_t)t + 2]);
       }
-      if (c.is_root)
-         // The bulk update of the trailing matrix runs on the side stream beside the diagonal-tile chain of the next column.  Stream
-         // priorities only order the launches the command processor has not started yet: once a launch of thousands of workgroups is
-         // running, the single workgroup of k_tile_diag gets no slot until that launch drains (rocprofv3 trace at S = 16000: the diagonal
-         // kernel "takes" 270 - 1140 us beside the bulk and 70 us alone - it is waiting): the lookahead overlaps only the drain.
-         hipLaunchKernelGGL(k_tile_gemm<3>, dim3((l.cnt + 7) / 8 * 8), dim3(512), 0, st, p.d_tasks + l.off, l.cnt, c.d_blks, c.d_arena,
-                            c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
-      else
-         hipLaunchKernelGGL(k_tile_gemm<0>, dim3((l.cnt + 7) / 8 * 8), dim3(512), 0, st, p.d_tasks + l.off, l.cnt, c.d_blks, c.d_arena,
-                            c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
-   };
-   // Lookahead bookkeeping (right-looking modes with a side stream): while the side stream applies a finished panel to
-   // the tile columns >= side_from, the main stream may only write columns left of that.
-   bool side_busy = false;
-   int side_from = 0;
-   auto main_writes = [&](int col) -> int {
-      if (side_busy && col >= side_from) {
-         HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_rest, 0));
-         side_busy = false;
-      }
-      return PIPS_OK;
-   };
-   // trsm of the leaf tails in the static pivot order: Winv is lower triangular, k_tile_gemm<5> skips the products with its zeros
-   // (PIPS_HIP_TRSM_DENSE=1: the dense product, for A/B runs and the test that compares the two bit for bit)
-   const bool trsm_tri = !c.bunch_kaufman && !c.is_root && env_int("PIPS_HIP_TRSM_DENSE", 0) == 0;
-   int rc;
-   if (c.single && c.single->n_tasks > 0) {
-      const TailSingle& ts = *c.single;
-      if (c.timer) c.timer->begin(c.stream, 2);
+      fclose(f);
+   }
+   return PIPS_OK;
+}
+
+// the leaf tails as one dependency-driven launch (tailkernel.hip.h): flags from their template, tickets cleared, k_tail_ldl
+static int tail_single_launch(const TailCtx& c) {
+   const TailSingle& ts = *c.single;
+   const char* trace_file = getenv("PIPS_HIP_TAIL_TRACE");   // diagnostics, read at every call
+   DevBuf<long long> d_trace;
+   const size_t n_trace = (size_t)3 * ts.n_tasks + 32 * (size_t)(c.plan->ntc_max + 1);
+   {
+      PhaseTimer::Scope phase(c.timer, c.stream, 2);
       HIP_TRY(hipMemcpyAsync(ts.d_flags, ts.d_flags_init, (size_t)ts.n_flags * sizeof(int), hipMemcpyDeviceToDevice, c.stream));
       HIP_TRY(hipMemsetAsync(ts.d_ctl, 0, 9 * sizeof(int), c.stream));   // (the tickets; the error word stays until it is read)
-      TailLdlArgs ta = ts.args;
-      ta.n_tasks = ts.n_tasks;
-      const char* trace_file = getenv("PIPS_HIP_TAIL_TRACE");   // diagnostics: per-task clocks of this launch into a file (tools/tail_trace.py)
-      DevBuf<long long> d_trace;
-      const size_t n_trace = (size_t)3 * ts.n_tasks + 32 * (size_t)(p.ntc_max + 1);
+      TailLdlArgs ta = ts.args; ta.n_tasks = ts.n_tasks;
       if (trace_file) {
          PIPS_TRY(d_trace.alloc(n_trace));
          HIP_TRY(hipMemsetAsync(d_trace, 0, n_trace * sizeof(long long), c.stream));
@@ -536,125 +566,107 @@ static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
       // compute unit of their own: one workgroup per unit there (a leaf handle's factorisation 6.9 -> 6.6 ms, level 1.5 1.03 -> 0.98 s per unit;
       // 8 blocks: 17.7 -> 17.9 ms, so only there)
       hipLaunchKernelGGL(k_tail_ldl, dim3(ts.n_blocks <= 2 ? 256 : 512), dim3(512), 0, c.stream, ta);
-      if (c.timer) c.timer->end(c.stream);
-      if (trace_file) {
-         std::vector<long long> h(n_trace);
-         std::vector<TileTask> ht((size_t)ts.n_tasks);
-         HIP_TRY(hipStreamSynchronize(c.stream));
-         HIP_TRY(hipMemcpy(h.data(), d_trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-         HIP_TRY(hipMemcpy(ht.data(), ts.d_tasks, ht.size() * sizeof(TileTask), hipMemcpyDeviceToHost));
-         d_trace.reset();
-         if (FILE* f = fopen(trace_file, "w")) {   // ticket, list, kind, block, ti, tj, K range, the three clocks
-            for (int t = 0; t < ts.n_tasks; ++t) {
-               int x = 0;
-               while (x < 7 && t >= ts.args.xoff[x + 1]) ++x;
-               fprintf(f, "%d %d %d %d %d %d %d %lld %lld %lld\n", t, x, ht[t].blk >> 24, ht[t].blk & 0xffffff, ht[t].ti, ht[t].tj, ht[t].pad, h[3 * (size_t)t], h[3 * (size_t)t + 1],
-                       h[3 * (size_t)t + 2]);
-            }
-            fclose(f);
-         }
-      }
    }
-   for (int j = 0; !c.single && j < p.ntc_max; ++j) {
-      if ((rc = main_writes(j))) return rc;
+   return trace_file ? dump_tail_trace(c, d_trace, n_trace, trace_file) : PIPS_OK;
+}
+
+// The launch-per-step factorisation of the tails, tile column by tile column: update, diagonal tiles, trsm; in the right-looking modes the
+// trailing update of every finished panel.  trsm_tri: k_tile_gemm<5> for the trsm (tail_factor)
+static int tail_columns(const TailCtx& c, bool trsm_tri) {
+   const TailPlan& p = *c.plan;
+   // Lookahead bookkeeping (right-looking modes with a side stream): while the side stream applies a finished panel to
+   // the tile columns >= side_from, the main stream may only write columns left of that.
+   bool side_busy = false; int side_from = 0;
+   auto main_writes = [&](int col) -> int {
+      if (side_busy && col >= side_from) {
+         HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_rest, 0));
+         side_busy = false;
+      }
+      return PIPS_OK;
+   };
+   for (int j = 0; j < p.ntc_max; ++j) {
+      PIPS_TRY(main_writes(j));
       const bool ahead = c.side && p.upd_diag[j].cnt > 0;   // left-looking batch: diagonal tiles first, factorised on the side stream
       if (ahead) {
          // side stream: update the diagonal tiles of column j (deep K, one workgroup per block) and factorise them, while
          // the main stream updates the rest of the column
          HIP_TRY(hipEventRecord(c.ev_panel, c.stream));
          HIP_TRY(hipStreamWaitEvent(c.side, c.ev_panel, 0));
-         gemm_diag_tiles(p.upd_diag[j], c.side);
-         if (c.bunch_kaufman)
-            hipLaunchKernelGGL(k_tile_diag_bk, dim3(p.diag[j].cnt), dim3(256), 0, c.side, p.d_tasks + p.diag[j].off, c.d_blks, c.d_arena, c.d_dtail,
-                               c.d_winv, c.d_inertia, c.d_pert_cnt, c.d_pert_list, c.bk_orig, c.bk_orig_ld, c.bk_orig_rowmajor, c.d_bk_perm, c.bk_isolate);
-         else
-         hipLaunchKernelGGL(k_tile_diag, dim3(p.diag[j].cnt), dim3(256), 0, c.side, p.d_tasks + p.diag[j].off,
-                            c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_psign, c.d_psign_off, c.d_inertia, c.d_pref);
+         launch_tile_gemm<4>(c, p.d_tasks, p.upd_diag[j], c.side);
+         launch_tile_diag(c, p.d_tasks, p.diag[j], c.side);
          HIP_TRY(hipEventRecord(c.ev_rest, c.side));
       } else if (p.upd_diag[j].cnt > 0) {
-         gemm_diag_tiles(p.upd_diag[j], c.stream);
+         launch_tile_gemm<4>(c, p.d_tasks, p.upd_diag[j], c.stream);
       }
-      if (p.upd[j].cnt > 0) {
-         if (c.timer) c.timer->begin(c.stream, 2);
-         gemm0(p.upd[j], c.stream);
-         if (c.timer) c.timer->end(c.stream);
-      }
+      if (p.upd[j].cnt > 0) { PhaseTimer::Scope phase(c.timer, c.stream, 2); launch_tile_update(c, p.upd[j], c.stream); }
       if (ahead) {
          HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_rest, 0));   // trsm needs Winv_j and d_j
       } else {
-         if (c.timer) c.timer->begin(c.stream, 3);
-         if (c.bunch_kaufman)
-            hipLaunchKernelGGL(k_tile_diag_bk, dim3(p.diag[j].cnt), dim3(256), 0, c.stream, p.d_tasks + p.diag[j].off, c.d_blks, c.d_arena, c.d_dtail,
-                               c.d_winv, c.d_inertia, c.d_pert_cnt, c.d_pert_list, c.bk_orig, c.bk_orig_ld, c.bk_orig_rowmajor, c.d_bk_perm, c.bk_isolate);
-         else
-         hipLaunchKernelGGL(k_tile_diag, dim3(p.diag[j].cnt), dim3(256), 0, c.stream, p.d_tasks + p.diag[j].off,
-                            c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_psign, c.d_psign_off, c.d_inertia, c.d_pref);
-         if (c.timer) c.timer->end(c.stream);
+         PhaseTimer::Scope phase(c.timer, c.stream, 3);
+         launch_tile_diag(c, p.d_tasks, p.diag[j], c.stream);
       }
       if (p.trsm[j].cnt > 0) {
-         if (c.timer) c.timer->begin(c.stream, 4);
-         if (trsm_tri)
-            hipLaunchKernelGGL(k_tile_gemm<5>, dim3((p.trsm[j].cnt + 7) / 8 * 8), dim3(512), 0, c.stream, p.d_tasks + p.trsm[j].off, p.trsm[j].cnt,
-                               c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
-         else
-            hipLaunchKernelGGL(k_tile_gemm<1>, dim3((p.trsm[j].cnt + 7) / 8 * 8), dim3(512), 0, c.stream, p.d_tasks + p.trsm[j].off, p.trsm[j].cnt,
-                               c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
-         if (c.timer) c.timer->end(c.stream);
-         // Bunch-Kaufman root that will be looked at (DenseLdl::check_pivots): multipliers beyond what a whole-column search allows?
-         if (c.bunch_kaufman && c.is_root && c.d_pert_cnt)
-            hipLaunchKernelGGL(k_bk_growth, dim3(TILE), dim3(256), 0, c.stream, c.d_blks, c.d_arena, j, 1e8, c.d_pert_cnt, c.d_pert_list);
+         PhaseTimer::Scope phase(c.timer, c.stream, 4);
+         if (trsm_tri) launch_tile_gemm<5>(c, p.d_tasks, p.trsm[j], c.stream);
+         else launch_tile_gemm<1>(c, p.d_tasks, p.trsm[j], c.stream);
       }
+      // Bunch-Kaufman root that will be looked at (DenseLdl::check_pivots): multipliers beyond what a whole-column search allows?
+      if (p.trsm[j].cnt > 0 && c.bunch_kaufman && c.is_root && c.d_pert_cnt)
+         hipLaunchKernelGGL(k_bk_growth, dim3(TILE), dim3(256), 0, c.stream, c.d_blks, c.d_arena, j, 1e8, c.d_pert_cnt, c.d_pert_list);
       // right-looking modes: trailing update with the panel that ends at column j.  With a side stream the bulk of it
       // (tile columns >= j+2) runs there, so that the main stream can finish column j+1 and go on with its diagonal tile
       // and trsm meanwhile (lookahead of one column).
       if (p.trail_next[j].cnt > 0 || p.trail[j].cnt > 0) {
-         if ((rc = main_writes(j + 1))) return rc;
+         PIPS_TRY(main_writes(j + 1));
          const bool split = c.side && p.trail[j].cnt > 0;
          if (split) {
             HIP_TRY(hipEventRecord(c.ev_panel, c.stream));   // panel final: its trsm is queued before this point
             HIP_TRY(hipStreamWaitEvent(c.side, c.ev_panel, 0));
-            gemm0(p.trail[j], c.side);                       // queued behind the bulk of the previous panel
+            launch_tile_update(c, p.trail[j], c.side);       // queued behind the bulk of the previous panel
             HIP_TRY(hipEventRecord(c.ev_rest, c.side));
             side_busy = true;
             side_from = j + 2;
          }
-         if (c.timer) c.timer->begin(c.stream, 2);
-         if (p.trail_next[j].cnt > 0) gemm0(p.trail_next[j], c.stream);
-         if (!split && p.trail[j].cnt > 0) gemm0(p.trail[j], c.stream);
-         if (c.timer) c.timer->end(c.stream);
+         PhaseTimer::Scope phase(c.timer, c.stream, 2);
+         if (p.trail_next[j].cnt > 0) launch_tile_update(c, p.trail_next[j], c.stream);
+         if (!split && p.trail[j].cnt > 0) launch_tile_update(c, p.trail[j], c.stream);
       }
    }
-   if ((rc = main_writes(1 << 30))) return rc;   // join the side stream
-   if (SC && c.det_rounds) {
-      if (c.timer) c.timer->begin(c.stream, 5);
+   return main_writes(1 << 30);   // join the side stream
+}
+
+// The tails' Schur contribution SC -= L_b D L_b^T over the border rows of every block (k_tile_gemm<2>), one of four ways: deterministic
+// rounds into the group buffers, row-panel groups with an event each, one balanced launch, one plain launch
+static int tail_schur(const TailCtx& c, double* SC, int ldSC) {
+   const TailPlan& p = *c.plan;
+   const bool rounds = c.det_rounds != nullptr, panels = !rounds && c.sc_groups && !c.d_sctab;
+   if (!SC || (!rounds && !panels && p.schur.cnt == 0)) return PIPS_OK;   // (no launch: no timer record either)
+   PhaseTimer::Scope phase(c.timer, c.stream, 5);
+   if (rounds) {
       for (const TaskList& l : *c.det_rounds)   // the group buffers were zeroed (and took the head's contributions) in Engine::factor
-         if (l.cnt > 0)
-            hipLaunchKernelGGL(k_tile_gemm<2>, dim3((l.cnt + 7) / 8 * 8), dim3(512), 0, c.stream, c.d_det_tasks + l.off, l.cnt, c.d_blks, c.d_arena,
-                               c.d_dtail, c.d_winv, c.d_bmap, SC, ldSC, c.d_sctab, c.d_uarena, c.d_gbuf, c.gstride, c.d_blk_group);
+         if (l.cnt > 0) launch_tile_gemm<2>(c, c.d_det_tasks, l, c.stream, SC, ldSC);
       if (!c.det_reduce_later) reduce_det_groups(c, SC, ldSC);
-      if (c.timer) c.timer->end(c.stream);
-   } else if (SC && c.sc_groups && !c.d_sctab) {
-      if (c.timer) c.timer->begin(c.stream, 5);
+   } else if (panels) {
       for (size_t g = 0; g < c.sc_groups->size(); ++g) {
          const TaskList& l = (*c.sc_groups)[g];
-         if (l.cnt > 0)
-            hipLaunchKernelGGL(k_tile_gemm<2>, dim3((l.cnt + 7) / 8 * 8), dim3(512), 0, c.stream, c.d_sc_tasks + l.off, l.cnt, c.d_blks, c.d_arena,
-                               c.d_dtail, c.d_winv, c.d_bmap, SC, ldSC, c.d_sctab, c.d_uarena);
-         HIP_TRY(hipEventRecord((*c.ev_sc)[g], c.stream));
+         if (l.cnt > 0) launch_tile_gemm<2>(c, c.d_sc_tasks, l, c.stream, SC, ldSC);
+         HIP_TRY(hipEventRecord((*c.ev_sc)[g], c.stream));   // (an empty group too: its panel is final)
       }
-      if (c.timer) c.timer->end(c.stream);
-   } else if (SC && p.schur.cnt > 0 && c.d_ctr_pool && !c.d_sctab && *c.ctr_cursor < GEMM_CTR_SLOTS) {
-      if (c.timer) c.timer->begin(c.stream, 5);
-      const int wgs = ((p.schur.cnt + 7) / 8 * 8) / 8 * 9;
-      hipLaunchKernelGGL(k_tile_gemm_bal<2>, dim3((wgs + 7) / 8 * 8), dim3(512), 0, c.stream, p.d_tasks + p.schur.off, p.schur.cnt, c.d_blks,
-                         c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, SC, ldSC, c.d_sctab, c.d_uarena, c.d_ctr_pool + 8 * (*c.ctr_cursor)++);
-      if (c.timer) c.timer->end(c.stream);
-   } else if (SC && p.schur.cnt > 0) {
-      if (c.timer) c.timer->begin(c.stream, 5);
-      hipLaunchKernelGGL(k_tile_gemm<2>, dim3((p.schur.cnt + 7) / 8 * 8), dim3(512), 0, c.stream, p.d_tasks + p.schur.off, p.schur.cnt, c.d_blks,
-                         c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, SC, ldSC, c.d_sctab, c.d_uarena);
-      if (c.timer) c.timer->end(c.stream);
-   }
+   } else if (tile_gemm_bal_ready(c) && !c.d_sctab)
+      launch_tile_gemm_bal<2>(c, p.d_tasks, p.schur, c.stream, SC, ldSC);
+   else
+      launch_tile_gemm<2>(c, p.d_tasks, p.schur, c.stream, SC, ldSC);
+   return PIPS_OK;
+}
+
+// Numeric factorisation of the dense tails (leaf batch: all blocks at once; dense root: one block) and, with SC, their Schur contribution
+static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
+   // trsm of the leaf tails in the static pivot order: Winv is lower triangular, k_tile_gemm<5> skips the products with its zeros
+   // (PIPS_HIP_TRSM_DENSE=1: the dense product, for A/B runs and the test that compares the two bit for bit)
+   const bool trsm_tri = !c.bunch_kaufman && !c.is_root && env_int("PIPS_HIP_TRSM_DENSE", 0) == 0;
+   if (!c.single) PIPS_TRY(tail_columns(c, trsm_tri));
+   else if (c.single->n_tasks > 0) PIPS_TRY(tail_single_launch(c));
+   PIPS_TRY(tail_schur(c, SC, ldSC));
    HIP_TRY(hipGetLastError());
    return PIPS_OK;
 }
@@ -1064,8 +1076,10 @@ struct Engine : EngineAnalysis, BatchLayout {
       return d_sc_tasks.upload(all);
    }
    TailCtx ctx() {
-      TailCtx c{d_blks, &plan, d_arena, d_dtail, d_winv, d_psign, d_psign_off, d_bmap, d_inertia, stream,
-                timer.on ? &timer : nullptr, d_pref, side, ev_diag_in, ev_diag_out, false, d_sctab, d_uarena};
+      TailCtx c;
+      c.d_blks = d_blks; c.plan = &plan; c.d_arena = d_arena; c.d_uarena = d_uarena; c.d_dtail = d_dtail; c.d_winv = d_winv;
+      c.d_psign = d_psign; c.d_psign_off = d_psign_off; c.d_inertia = d_inertia; c.d_pref = d_pref;
+      c.stream = stream; c.side = side; c.ev_panel = ev_diag_in; c.ev_rest = ev_diag_out; c.d_bmap = d_bmap; c.d_sctab = d_sctab;
       if (!sc_groups.empty()) { c.sc_groups = &sc_groups; c.d_sc_tasks = d_sc_tasks; c.ev_sc = &ev_sc; }
       c.d_ctr_pool = d_gemm_ctr; c.ctr_cursor = &gemm_ctr_cursor;
       if (deterministic && d_gbuf) {
@@ -1513,14 +1527,10 @@ struct Engine : EngineAnalysis, BatchLayout {
       return PIPS_OK;
    }
 
-   int factor(double* SC, int ldSC) {
-      if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "factor called before analyze");
-      HIP_TRY(hipSetDevice(device));
-      if (deterministic && SC && S > 0 && !d_gbuf && d_blk_group)
-         PIPS_TRY(d_gbuf.alloc((size_t)det_n_groups * det_gstride()));
-      timer.reset();
-      if (timer.on) timer.begin(stream, 6);
-      if (timer.on) timer.begin(stream, 0);
+   // ---- numeric factorisation: factor() calls the stages below in this order
+   // block maxima and thresholds, the arena cleared and filled with the values of K (and of the border), the reference magnitudes of the pivots
+   int factor_prologue() {
+      PhaseTimer::Scope phase(&timer, stream, 0);
       hipLaunchKernelGGL(k_block_absmax_init, dim3((nblk + 255) / 256), dim3(256), 0, stream, d_blks, nblk);
       hipLaunchKernelGGL(k_block_absmax, dim3(std::max(1, std::min(64, (int)(nnzK_total / nblk / 4096))), nblk), dim3(256), 0, stream, d_kval,
                          d_kptr, d_blks);
@@ -1529,11 +1539,9 @@ struct Engine : EngineAnalysis, BatchLayout {
       // of the border and comes with k_scatter; fronts: assembled in LDS, written out whole) - only the tails are cleared
       hipLaunchKernelGGL(k_arena_clear, dim3(256, nblk), dim3(256), 0, stream, d_blks, d_arena, mf ? 1 : 0);
       HIP_TRY(hipMemsetAsync(d_inertia, 0, (size_t)3 * nblk * sizeof(int), stream));
-      {
-         if (!d_gemm_ctr) PIPS_TRY(d_gemm_ctr.alloc((size_t)GEMM_CTR_SLOTS * 8));
-         HIP_TRY(hipMemsetAsync(d_gemm_ctr, 0, (size_t)GEMM_CTR_SLOTS * 8 * sizeof(int), stream));
-         gemm_ctr_cursor = 0;
-      }
+      if (!d_gemm_ctr) PIPS_TRY(d_gemm_ctr.alloc((size_t)GEMM_CTR_SLOTS * 8));
+      HIP_TRY(hipMemsetAsync(d_gemm_ctr, 0, (size_t)GEMM_CTR_SLOTS * 8 * sizeof(int), stream));
+      gemm_ctr_cursor = 0;
       if (nnzK_total > 0)
          hipLaunchKernelGGL(k_scatter, dim3(grid_for(nnzK_total, 256)), dim3(256), 0, stream, d_kdst, d_kval, d_arena, nnzK_total);
       if (nnzB_total > 0 && schur_mode_eff == 1)
@@ -1541,82 +1549,82 @@ struct Engine : EngineAnalysis, BatchLayout {
       hipLaunchKernelGGL(k_tail_pad_diag, dim3(nblk), dim3(128), 0, stream, d_blks, d_arena, nblk);
       hipLaunchKernelGGL(k_pref_rows, dim3(32, nblk), dim3(256), 0, stream, d_blks, d_kval, d_kdiag, d_res, d_nprimal, d_krowptr, d_kcolidx);   // (d_res: scratch of the solves)
       hipLaunchKernelGGL(k_pref_init, dim3(32, nblk), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, (const double*)d_res, d_pref);
-      if (timer.on) timer.end(stream);
-      // the whole-factor record (phase 6) was pushed first; close it at the end
-      const size_t total_rec = 0;
+      return PIPS_OK;
+   }
+   // the last update matrices of the fronts: into the tail and the Schur complement, front by front
+   void launch_root_assemble(double* SC, int ldSC) {
+      // about 2048 workgroups in the launch (what is resident at once): half of a block's chunks on the tail's columns, half on the border's
+      const int asm_half = std::max(1, std::min(32, 1024 / std::max(nblk, 1)));
+      if (deterministic && d_gbuf && SC && d_round_blk) {
+         for (size_t k = 0; k + 1 < round_off.size(); ++k) {
+            const int cnt = round_off[k + 1] - round_off[k];
+            if (cnt > 0)
+               hipLaunchKernelGGL(k_root_assemble, dim3(cnt, 2 * asm_half), dim3(256), 0, stream, d_round_blk + round_off[k], d_root_off, d_roots, d_sns, d_blks, d_rowidx,
+                                  d_bmap, d_arena, d_mfU, SC, ldSC, d_sctab, d_gbuf, det_gstride(), d_blk_group, asm_half, asm_half);
+         }
+      } else
+         hipLaunchKernelGGL(k_root_assemble, dim3(nblk, 2 * asm_half), dim3(256), 0, stream, (const int*)nullptr, d_root_off, d_roots, d_sns, d_blks, d_rowidx, d_bmap,
+                            d_arena, d_mfU, SC, ldSC, d_sctab, (double*)nullptr, 0LL, (const int*)nullptr, asm_half, asm_half);
+   }
+   // the head by levels, then what follows from its finished panels; one phase-1 record per level and per stage that runs
+   int factor_head(double* SC, int ldSC) {
       const ScatterCtx sx = head_slots ? ScatterCtx{2, nullptr, d_slot_val, d_arena, SC} : sx_atomic();
       for (size_t li = 0; li < levels.size(); ++li) {
-         if (timer.on) timer.begin(stream, 1);
+         PhaseTimer::Scope phase(&timer, stream, 1);
          if (head_slots) gather(g_levels[li], d_slot_val, d_arena);   // contributions of the lower levels, in fixed order
          launch_head_level(levels[li], SC, ldSC, sx);
-         if (mf) { const int frc = launch_fronts((int)li, SC, ldSC); if (frc) return frc; }
-         if (timer.on) timer.end(stream);
+         if (mf) PIPS_TRY(launch_fronts((int)li, SC, ldSC));
       }
       if (head_slots) {
-         if (timer.on) timer.begin(stream, 1);
+         PhaseTimer::Scope phase(&timer, stream, 1);
          gather(g_tail, d_slot_val, d_arena);
          if (SC && deterministic && d_gbuf) {
             HIP_TRY(hipMemsetAsync(d_gbuf, 0, (size_t)det_n_groups * det_gstride() * sizeof(double), stream));
             gather(g_sc_grp, d_slot_val, d_gbuf);
          } else if (SC) gather(g_sc, d_slot_val, SC);
-         if (timer.on) timer.end(stream);
       }
-      if (mf && n_roots > 0) {   // the last update matrices: into the tail and the Schur complement, front by front
-         if (timer.on) timer.begin(stream, 1);
-         // about 2048 workgroups in the launch (what is resident at once): half of a block's chunks on the tail's columns, half on the border's
-         const int asm_half = std::max(1, std::min(32, 1024 / std::max(nblk, 1)));
-         if (deterministic && d_gbuf && SC && d_round_blk) {
-            for (size_t k = 0; k + 1 < round_off.size(); ++k) {
-               const int cnt = round_off[k + 1] - round_off[k];
-               if (cnt > 0)
-                  hipLaunchKernelGGL(k_root_assemble, dim3(cnt, 2 * asm_half), dim3(256), 0, stream, d_round_blk + round_off[k], d_root_off, d_roots, d_sns, d_blks, d_rowidx,
-                                     d_bmap, d_arena, d_mfU, SC, ldSC, d_sctab, d_gbuf, det_gstride(), d_blk_group, asm_half, asm_half);
-            }
-         } else
-            hipLaunchKernelGGL(k_root_assemble, dim3(nblk, 2 * asm_half), dim3(256), 0, stream, (const int*)nullptr, d_root_off, d_roots, d_sns, d_blks, d_rowidx, d_bmap,
-                               d_arena, d_mfU, SC, ldSC, d_sctab, (double*)nullptr, 0LL, (const int*)nullptr, asm_half, asm_half);
-         if (timer.on) timer.end(stream);
-      }
+      if (mf && n_roots > 0) { PhaseTimer::Scope phase(&timer, stream, 1); launch_root_assemble(SC, ldSC); }
       if (mf && d_kb_list) {   // fronts on the rows of K only: their border rows now, level by level, from the finished panels; then the head's part
                                // of the dense tail's border rows.  (Forming level l on a second stream beside the fronts above it, which need
                                // nothing of it, was measured: no gain, 17.4 against 16.7 ms of head on the configs[3] share.)
-         if (timer.on) timer.begin(stream, 1);
+         PhaseTimer::Scope phase(&timer, stream, 1);
          for (size_t l = 0; l + 1 < kb_level_off.size(); ++l) launch_border_rows(l, stream);
          if (n_kb_tail > 0) hipLaunchKernelGGL(k_border_tail<16>, dim3(n_kb_tail), dim3(64), 0, stream, d_kb_tail, d_sns, d_blks, d_rowidx, d_arena);
-         if (timer.on) timer.end(stream);
       }
-      if (mf && n_bb > 0 && SC) {   // border split: the border x border part of every block's Schur contribution, from the finished panels
-         if (timer.on) timer.begin(stream, 1);
-         const int rc_bb = launch_border_schur(SC, ldSC);
-         if (rc_bb) return rc_bb;
-         if (timer.on) timer.end(stream);
-      }
+      // border split: the border x border part of every block's Schur contribution, from the finished panels
+      if (mf && n_bb > 0 && SC) { PhaseTimer::Scope phase(&timer, stream, 1); PIPS_TRY(launch_border_schur(SC, ldSC)); }
       if (spine_total > 0) {
-         if (timer.on) timer.begin(stream, 1);
+         PhaseTimer::Scope phase(&timer, stream, 1);
          hipLaunchKernelGGL((k_head_factor_spine<256, 32, 6144>), dim3(nblk), dim3(256), 0, stream, d_spine, d_spine_off, d_sns, d_blks,
                             d_rowidx, d_upd, d_psign, d_psign_off, d_bmap, d_arena, SC, ldSC, d_inertia, d_pref, d_sctab);
-         if (timer.on) timer.end(stream);
       }
-      if (mf && getenv("PIPS_HIP_MF_CLOCKS")) {
+      if (mf && getenv("PIPS_HIP_MF_CLOCKS")) {   // (read at every factorisation)
          if (!d_mfdbg) PIPS_TRY(d_mfdbg.alloc((size_t)std::max(nsn_total, 1) * 8));
-         else { int drc = dump_front_clocks(); if (drc) return drc; }
+         else PIPS_TRY(dump_front_clocks());
       }
       hipLaunchKernelGGL(k_pref_tail, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_arena, d_pref, 0);
       HIP_TRY(hipGetLastError());
+      return PIPS_OK;
+   }
+   // the tails, and with Schur mode 2 the leaves' Schur contribution by blocked solves
+   int factor_tail(double* SC, int ldSC) {
       TailCtx c = ctx();
+      c.timer = &timer;                           // (the tail's phase records belong to the factorisation: the solves leave it out)
       c.det_reduce_later = schur_mode_eff == 2;   // (deterministic mode 2: the group buffers are filled by schur_by_solves, below)
-      int rc = tail_factor(c, SC, ldSC);
-      if (rc) return rc;
+      PIPS_TRY(tail_factor(c, SC, ldSC));
       factored = true;
       perturbed_cache = -1;
       if (SC && schur_mode_eff == 2 && !schur_cols.empty()) {
          const int rec_schur = timer.begin_i(stream, 5);   // (stays open across the records of the solves inside: solve_once times its sweeps)
-         rc = schur_by_solves(SC, ldSC);
+         const int rc = schur_by_solves(SC, ldSC);
          timer.end_i(rec_schur, stream);
          if (rc) return rc;
       }
       if (SC && c.det_rounds && c.det_reduce_later) reduce_det_groups(c, SC, ldSC);   // one fixed-tree add, after every chunk
-      if (timer.on) (void)hipEventRecord(timer.recs[total_rec].b, stream);
+      return PIPS_OK;
+   }
+   // The inertia counters go to pinned host memory behind the factorisation (fetch_inertia waits for the event only)
+   int post_inertia() {
       h_amax.clear();
       if (!h_inertia_pin) {
          PIPS_TRY(h_inertia_pin.alloc((size_t)(3 * nblk + 1)));
@@ -1630,6 +1638,19 @@ struct Engine : EngineAnalysis, BatchLayout {
       inertia_in_flight = true;
       inertia_on_host = false;
       return PIPS_OK;
+   }
+   int factor(double* SC, int ldSC) {
+      if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "factor called before analyze");
+      HIP_TRY(hipSetDevice(device));
+      if (deterministic && SC && S > 0 && !d_gbuf && d_blk_group)
+         PIPS_TRY(d_gbuf.alloc((size_t)det_n_groups * det_gstride()));
+      timer.reset();
+      const int rec_total = timer.begin_i(stream, 6);   // the whole factorisation: stays open across the records of the stages
+      PIPS_TRY(factor_prologue());
+      PIPS_TRY(factor_head(SC, ldSC));
+      PIPS_TRY(factor_tail(SC, ldSC));
+      timer.end_i(rec_total, stream);
+      return post_inertia();
    }
 
    // SC -= sum_b Br_b^T K_b^-1 Br_b, chunk by chunk of 32 border columns: densify, solve (all blocks at once), multiply back.
@@ -1777,33 +1798,26 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (!xw) xw = d_xw;
       const long long xws = nrhs > 1 ? xw_total : 0;
       const dim3 pg(64, nblk, nrhs);
-      timer.begin(stream, 7);
-      hipLaunchKernelGGL(k_permute_in, pg, dim3(256), 0, stream, d_blks, d_perm, d_perm_off, x_dev, x_stride, xw, xws);
-      timer.end(stream);
-      timer.begin(stream, 8);
-      head_forward(xw, nrhs, xws, deterministic && head_slots ? ScatterCtx{2, nullptr, d_vslot_val, xw, nullptr} : sx_atomic(), 0);
-      timer.end(stream);
-      timer.begin(stream, 9);
-      TailCtx c = ctx();
-      c.timer = nullptr;   // (the tail's own phase records belong to the factorisation)
-      int rc = tail_fwd(c, xw, nrhs, xws);
-      if (rc) return rc;
+      { PhaseTimer::Scope phase(&timer, stream, 7); hipLaunchKernelGGL(k_permute_in, pg, dim3(256), 0, stream, d_blks, d_perm, d_perm_off, x_dev, x_stride, xw, xws); }
+      {
+         PhaseTimer::Scope phase(&timer, stream, 8);
+         head_forward(xw, nrhs, xws, deterministic && head_slots ? ScatterCtx{2, nullptr, d_vslot_val, xw, nullptr} : sx_atomic(), 0);
+      }
       // D^-1 of the head columns: fused into the backward kernels of the common path (chain kernels + thread-per-leaf kernel: they
       // read the diagonal's cache line anyway; the separate pass reads 88 bytes of descriptor per supernode - 12.9 M of them on the
       // configs[3] share); with spines (their kernel does not scale) the pass stays
       const bool fused_d = spine_total == 0;
-      if (nsn_total > 0 && !fused_d)
-         hipLaunchKernelGGL(k_head_dscale, dim3(grid_for(nsn_total, 256), nrhs), dim3(256), 0, stream, d_sns, nsn_total, d_blks,
-                            d_arena, xw, xws, 0);
-      rc = tail_bwd(c, xw, nrhs, xws);
-      if (rc) return rc;
-      timer.end(stream);
-      timer.begin(stream, 10);
-      head_backward(xw, nrhs, xws, 0, fused_d ? 1 : 0);
-      timer.end(stream);
-      timer.begin(stream, 7);
-      hipLaunchKernelGGL(k_permute_out, pg, dim3(256), 0, stream, d_blks, d_perm, d_perm_off, x_dev, x_stride, xw, xws);
-      timer.end(stream);
+      {
+         PhaseTimer::Scope phase(&timer, stream, 9);
+         const TailCtx c = ctx();
+         PIPS_TRY(tail_fwd(c, xw, nrhs, xws));
+         if (nsn_total > 0 && !fused_d)
+            hipLaunchKernelGGL(k_head_dscale, dim3(grid_for(nsn_total, 256), nrhs), dim3(256), 0, stream, d_sns, nsn_total, d_blks,
+                               d_arena, xw, xws, 0);
+         PIPS_TRY(tail_bwd(c, xw, nrhs, xws));
+      }
+      { PhaseTimer::Scope phase(&timer, stream, 10); head_backward(xw, nrhs, xws, 0, fused_d ? 1 : 0); }
+      { PhaseTimer::Scope phase(&timer, stream, 7); hipLaunchKernelGGL(k_permute_out, pg, dim3(256), 0, stream, d_blks, d_perm, d_perm_off, x_dev, x_stride, xw, xws); }
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
    }
@@ -2164,22 +2178,19 @@ struct Engine : EngineAnalysis, BatchLayout {
    int forward_augmented(const double* b_dev, double* red) {
       if (!factored) PIPS_FAIL(PIPS_ERR_STATE, "solve called before factor");
       HIP_TRY(hipSetDevice(device));
-      timer.begin(stream, 7);
-      hipLaunchKernelGGL(k_border_fill, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, (const double*)nullptr, d_xw, 0.0);
-      hipLaunchKernelGGL(k_permute_in, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, b_dev, 0LL, d_xw, 0LL);
-      timer.end(stream);
-      timer.begin(stream, 8);
-      head_forward(d_xw, 1, 0, sx_atomic(), 1);
-      timer.end(stream);
-      timer.begin(stream, 9);   // (one record of this phase per pass: the backward half books its tail sweep with the head's)
-      TailCtx c = ctx();
-      c.timer = nullptr;
-      int rc = tail_fwd(c, d_xw);
-      if (rc) return rc;
-      if (nb_pad_max > 0)
-         hipLaunchKernelGGL(k_tail_border_fwd, dim3(nb_pad_max / TILE, nblk), dim3(256), 0, stream, d_blks, d_arena, d_dtail, d_xw);
-      hipLaunchKernelGGL(k_border_collect, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, d_xw, red);
-      timer.end(stream);
+      {
+         PhaseTimer::Scope phase(&timer, stream, 7);
+         hipLaunchKernelGGL(k_border_fill, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, (const double*)nullptr, d_xw, 0.0);
+         hipLaunchKernelGGL(k_permute_in, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, b_dev, 0LL, d_xw, 0LL);
+      }
+      { PhaseTimer::Scope phase(&timer, stream, 8); head_forward(d_xw, 1, 0, sx_atomic(), 1); }
+      {
+         PhaseTimer::Scope phase(&timer, stream, 9);   // (one record of this phase per pass: the backward half books its tail sweep with the head's)
+         PIPS_TRY(tail_fwd(ctx(), d_xw));
+         if (nb_pad_max > 0)
+            hipLaunchKernelGGL(k_tail_border_fwd, dim3(nb_pad_max / TILE, nblk), dim3(256), 0, stream, d_blks, d_arena, d_dtail, d_xw);
+         hipLaunchKernelGGL(k_border_collect, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, d_xw, red);
+      }
       ++aug_passes;
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
@@ -2191,23 +2202,23 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (!factored) PIPS_FAIL(PIPS_ERR_STATE, "solve called before factor");
       if (!det_aug_ready || !head_slots) PIPS_FAIL(PIPS_ERR_STATE, "forward_augmented_det: not prepared");
       HIP_TRY(hipSetDevice(device));
-      timer.begin(stream, 7);
-      hipLaunchKernelGGL(k_border_fill, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, (const double*)nullptr, d_xw, 0.0);
-      hipLaunchKernelGGL(k_permute_in, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, b_dev, 0LL, d_xw, 0LL);
-      timer.end(stream);
-      timer.begin(stream, 8);
-      head_forward(d_xw, 1, 0, ScatterCtx{2, nullptr, d_vslot_val, d_xw, nullptr}, 0);   // (the border slots: by the two kernels below, from the finished head part)
-      hipLaunchKernelGGL(k_border_rowdot_det, dim3(grid_for(n_bg_ent, 256, 1 << 20)), dim3(256), 0, stream, n_bg_ent, d_bg_ent, d_arena, d_xw, d_bg_val);
-      hipLaunchKernelGGL(k_border_gather_det, dim3((unsigned)((n_bg_targets + 3) / 4)), dim3(256), 0, stream, n_bg_targets, d_bg_ptr, d_bg_idx, d_bg_slot, d_bg_val, d_xw);
-      timer.end(stream);
-      timer.begin(stream, 9);
-      TailCtx c = ctx();
-      c.timer = nullptr;
-      int rc = tail_fwd(c, d_xw);
-      if (rc) return rc;
-      if (nb_pad_max > 0)
-         hipLaunchKernelGGL(k_tail_border_fwd, dim3(nb_pad_max / TILE, nblk), dim3(256), 0, stream, d_blks, d_arena, d_dtail, d_xw);
-      timer.end(stream);
+      {
+         PhaseTimer::Scope phase(&timer, stream, 7);
+         hipLaunchKernelGGL(k_border_fill, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, (const double*)nullptr, d_xw, 0.0);
+         hipLaunchKernelGGL(k_permute_in, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, b_dev, 0LL, d_xw, 0LL);
+      }
+      {
+         PhaseTimer::Scope phase(&timer, stream, 8);
+         head_forward(d_xw, 1, 0, ScatterCtx{2, nullptr, d_vslot_val, d_xw, nullptr}, 0);   // (the border slots: by the two kernels below, from the finished head part)
+         hipLaunchKernelGGL(k_border_rowdot_det, dim3(grid_for(n_bg_ent, 256, 1 << 20)), dim3(256), 0, stream, n_bg_ent, d_bg_ent, d_arena, d_xw, d_bg_val);
+         hipLaunchKernelGGL(k_border_gather_det, dim3((unsigned)((n_bg_targets + 3) / 4)), dim3(256), 0, stream, n_bg_targets, d_bg_ptr, d_bg_idx, d_bg_slot, d_bg_val, d_xw);
+      }
+      {
+         PhaseTimer::Scope phase(&timer, stream, 9);
+         PIPS_TRY(tail_fwd(ctx(), d_xw));
+         if (nb_pad_max > 0)
+            hipLaunchKernelGGL(k_tail_border_fwd, dim3(nb_pad_max / TILE, nblk), dim3(256), 0, stream, d_blks, d_arena, d_dtail, d_xw);
+      }
       ++aug_passes;
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
@@ -2217,17 +2228,13 @@ struct Engine : EngineAnalysis, BatchLayout {
    int backward_augmented(const double* x0_dev, double* out_dev) {
       if (!factored) PIPS_FAIL(PIPS_ERR_STATE, "solve called before factor");
       HIP_TRY(hipSetDevice(device));
-      timer.begin(stream, 10);
-      hipLaunchKernelGGL(k_border_fill, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, x0_dev, d_xw, 1.0);
-      TailCtx c = ctx();
-      c.timer = nullptr;
-      int rc = tail_bwd(c, d_xw, 1, 0, 1);
-      if (rc) return rc;
-      head_backward(d_xw, 1, 0, 1, 1);
-      timer.end(stream);
-      timer.begin(stream, 7);
-      hipLaunchKernelGGL(k_permute_out, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, out_dev, 0LL, d_xw, 0LL);
-      timer.end(stream);
+      {
+         PhaseTimer::Scope phase(&timer, stream, 10);
+         hipLaunchKernelGGL(k_border_fill, dim3(8, nblk), dim3(256), 0, stream, d_blks, d_bmap, x0_dev, d_xw, 1.0);
+         PIPS_TRY(tail_bwd(ctx(), d_xw, 1, 0, 1));
+         head_backward(d_xw, 1, 0, 1, 1);
+      }
+      { PhaseTimer::Scope phase(&timer, stream, 7); hipLaunchKernelGGL(k_permute_out, dim3(64, nblk, 1), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, out_dev, 0LL, d_xw, 0LL); }
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
    }
@@ -2451,9 +2458,11 @@ struct DenseLdl {
       return PIPS_OK;
    }
    TailCtx ctx() {
-      TailCtx c{d_blks, &plan, d_R, d_dtail, d_winv, d_psign, d_psign_off, nullptr, d_inertia, stream, nullptr, d_pref, side, ev_panel, ev_rest, true, nullptr, d_U};
-      c.sweep = &sweep;
-      c.bunch_kaufman = pivoting == 1;
+      TailCtx c;
+      c.d_blks = d_blks; c.plan = &plan; c.d_arena = d_R; c.d_uarena = d_U; c.d_dtail = d_dtail; c.d_winv = d_winv;
+      c.d_psign = d_psign; c.d_psign_off = d_psign_off; c.d_inertia = d_inertia; c.d_pref = d_pref;
+      c.stream = stream; c.side = side; c.ev_panel = ev_panel; c.ev_rest = ev_rest;
+      c.is_root = true; c.sweep = &sweep; c.bunch_kaufman = pivoting == 1;
       if (pivoting == 1) {
          c.d_pert_cnt = d_pert_cnt; c.d_pert_list = d_pert_list;
          c.bk_orig = last_A; c.bk_orig_ld = last_lda; c.bk_orig_rowmajor = last_rowmajor; c.d_bk_perm = perm.empty() ? nullptr : d_perm;
@@ -2650,15 +2659,8 @@ struct DenseLdl {
          double* Up = Lp + rows * TILE;
          const size_t col0 = (size_t)(j + 1) * TILE + (size_t)j * TILE * npad;   // first entry below the diagonal tile of column j
          if (owner == dist_rank) {
-            if (c.bunch_kaufman)
-               hipLaunchKernelGGL(k_tile_diag_bk, dim3(1), dim3(256), 0, stream, d_dist_tasks + dist_diag[j].off, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_inertia,
-                                  c.d_pert_cnt, c.d_pert_list, c.bk_orig, c.bk_orig_ld, c.bk_orig_rowmajor, c.d_bk_perm, c.bk_isolate);
-            else
-               hipLaunchKernelGGL(k_tile_diag, dim3(1), dim3(256), 0, stream, d_dist_tasks + dist_diag[j].off, c.d_blks, c.d_arena, c.d_dtail, c.d_winv,
-                                  c.d_psign, c.d_psign_off, c.d_inertia, c.d_pref);
-            if (dist_trsm[j].cnt > 0)
-               hipLaunchKernelGGL(k_tile_gemm<1>, dim3((dist_trsm[j].cnt + 7) / 8 * 8), dim3(512), 0, stream, d_dist_tasks + dist_trsm[j].off, dist_trsm[j].cnt,
-                                  c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
+            launch_tile_diag(c, d_dist_tasks, dist_diag[j], stream);   // (one tile: the list holds the diagonal tile of column j)
+            if (dist_trsm[j].cnt > 0) launch_tile_gemm<1>(c, d_dist_tasks, dist_trsm[j], stream);
             // (the owner looks for multipliers a whole-column search would not allow, as on one rank: DenseLdl::check_pivots)
             if (c.bunch_kaufman && c.d_pert_cnt && dist_trsm[j].cnt > 0)
                hipLaunchKernelGGL(k_bk_growth, dim3(TILE), dim3(256), 0, stream, c.d_blks, c.d_arena, j, 1e8, c.d_pert_cnt, c.d_pert_list);
@@ -2691,13 +2693,9 @@ struct DenseLdl {
             HIP_TRY(hipEventRecord(ev_panel, stream));          // panel j is in d_R / d_U on this rank
             HIP_TRY(hipStreamWaitEvent(side, ev_panel, 0));
          }
-         if (dist_upd[j].cnt > 0)
-            hipLaunchKernelGGL(k_tile_gemm<3>, dim3((dist_upd[j].cnt + 7) / 8 * 8), dim3(512), 0, bulk, d_dist_tasks + dist_upd[j].off, dist_upd[j].cnt, c.d_blks,
-                               c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
+         if (dist_upd[j].cnt > 0) launch_tile_gemm<3>(c, d_dist_tasks, dist_upd[j], bulk);
          if (ahead) { HIP_TRY(hipEventRecord(ev_rest, side)); side_busy = true; }
-         if (dist_next[j].cnt > 0)
-            hipLaunchKernelGGL(k_tile_gemm<3>, dim3((dist_next[j].cnt + 7) / 8 * 8), dim3(512), 0, stream, d_dist_tasks + dist_next[j].off, dist_next[j].cnt, c.d_blks,
-                               c.d_arena, c.d_dtail, c.d_winv, c.d_bmap, (double*)nullptr, 0, (const int*)nullptr, c.d_uarena);
+         if (dist_next[j].cnt > 0) launch_tile_gemm<3>(c, d_dist_tasks, dist_next[j], stream);
       }
       if (side_busy) HIP_TRY(hipStreamWaitEvent(stream, ev_rest, 0));
       // every rank counted the pivots of its own diagonal tiles: the sum is the inertia
