@@ -594,6 +594,17 @@ int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* co
                       int S, const int* const* bt_rowptr, const int* const* bt_colidx,
                       int deterministic, long long free_device_bytes, int64_t* what, int n_what);
 
+/* The task plans of a leaf batch's launch-per-step tail factorisation, without a device (inputs as pips_layout_probe; force_n_head as
+ * pips_hip_batch_set_options, -1: the cost model): the column plan, and the same tasks regrouped by groups of four tile columns.
+ * col_tasks: rows of 6 ints in launch order - kind (0 update, 1 trsm), block, ti, tj, k0, k1 (the K range in tile columns; 0, 0 for a trsm).
+ * grp_tasks: rows of 9 ints in launch order - list (0 deep update, 1 / 2 the diagonal block's first and second deep step, 3 / 4 its updates
+ * and trsm of one column, 5 a strip of the panel launch), group, index (the tile column for 3 / 4, the strip's number inside its launch for 5),
+ * position inside the list or strip, block, ti, tj, k0, k1.  At most col_cap / grp_cap rows are written.
+ * counts (6 entries): rows of either kind there are, tile columns, groups, launches per factorisation of the column path and of the groups. */
+int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol,
+                         int S, const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head,
+                         int* col_tasks, long long col_cap, int* grp_tasks, long long grp_cap, int64_t* counts);
+
 /* The tables of the packed blocked solves (Schur mode 2 with the sparse root), without a device; the code the engine builds its own
  * with.  bt_rowptr[b]: the S + 1 row pointers of block b's border (NULL: no border).  nb[b] (nblk entries): the block's non-empty
  * border columns; *nb_max their maximum = the right-hand sides of the packed solves; local_of_row[b] (S entries each): the local index

@@ -104,6 +104,12 @@ struct TailPlan {
    // get no task, update depths start at the envelope (a banded tail costs band^2 per column instead of column^2)
    int build(const std::vector<BlkDesc>& blks, int panel = 0, bool lookahead = false, bool split_diag = false,
              const std::vector<const std::vector<int>*>* first = nullptr, bool diag_ahead = false, int pair2 = 1) {
+      lists(blks, panel, lookahead, split_diag, first, diag_ahead, pair2);
+      return d_tasks.upload(h_tasks);
+   }
+   // ... its host part: the lists and h_tasks, no device call (pips_tail_plan_probe)
+   void lists(const std::vector<BlkDesc>& blks, int panel, bool lookahead, bool split_diag, const std::vector<const std::vector<int>*>* first,
+              bool diag_ahead, int pair2) {
       std::vector<TileTask> all;
       ntc_max = 0;
       for (auto& b : blks) ntc_max = std::max(ntc_max, b.ntc);
@@ -214,8 +220,92 @@ struct TailPlan {
                for (int tj = 0; tj <= ti; ++tj) all.push_back({b, ti, tj, 0});
          }
       end(schur);
-      h_tasks = all;
-      return d_tasks.upload(all);
+      h_tasks = std::move(all);
+   }
+};
+
+// The update and trsm tasks of a left-looking column plan (TailPlan with diag_ahead and pair2 = P) regrouped by groups of P tile columns
+// (tail_panels): the same tasks, each exactly once, in lists of their own array.  With g the first column of a group and a task's launch
+// column j = its k1 (updates) or tile column (trsm), a task of a tile row >= g + P belongs to the main stream -
+//   deep[g / P]    the updates of launch column g (K left of the group), one launch;
+//   strips[g / P]  the rest per (block, tile row) in column order - trsm(ti, g), update(ti, g + 1; K = [g, g + 1)), trsm(ti, g + 1), ... - one
+//                  workgroup each of one k_tile_panel launch;
+// and a task of a tile row inside the group to the chain on the side stream that finishes the group's diagonal block beside the deep launch -
+//   pre[g / P]         the diagonal tile (g, g) with the columns g - P .. g - 2 (the column plan has it ride in the launch of column g - 1),
+//   block_deep[g / P]  the block's tiles with everything left of the group (for (g, g): its last step, with column g - 1),
+//   upd_in[j], trsm_in[j]  per column of the group the block's short updates before, and its trsm after, the diagonal tile of column j.
+// No list holds two tasks of one tile, and a tile meets its tasks in the column plan's order: the sums keep their order.
+struct PanelPlan {
+   int P = 0, n_groups = 0;
+   std::vector<TaskList> deep, pre, block_deep, strips;   // per group (strips: a range of h_strips / d_strips)
+   std::vector<TaskList> upd_in, trsm_in;                 // per tile column
+   std::vector<TileTask> h_tasks;
+   std::vector<TileStrip> h_strips;                       // (offsets into h_tasks)
+   DevBuf<TileTask> d_tasks;
+   DevBuf<TileStrip> d_strips;
+   void lists(const TailPlan& p, int P_) {
+      *this = PanelPlan();
+      P = P_;
+      n_groups = (p.ntc_max + P - 1) / P;
+      struct Group { std::vector<TileTask> deep, pre, block_deep; std::map<std::pair<int, int>, std::vector<TileTask>> strips; };
+      std::vector<Group> gs(n_groups);
+      std::vector<std::vector<TileTask>> ui(p.ntc_max), ti(p.ntc_max);
+      auto each = [&](const TaskList& l, auto&& f) {
+         for (long long q = l.off; q < l.off + l.cnt; ++q)
+            if (p.h_tasks[q].blk >= 0) f(p.h_tasks[q]);
+      };
+      auto update = [&](const TileTask& t) {
+         const int k1 = t.pad >> 16, g = k1 / P * P;
+         if (t.ti >= g + P) {
+            if (k1 == g) gs[g / P].deep.push_back(t);
+            else if (t.ti == t.tj) gs[t.tj / P].pre.push_back(t);
+            else gs[g / P].strips[{t.blk, t.ti}].push_back(t);
+         } else if (k1 == g)
+            gs[g / P].block_deep.push_back(t);
+         else
+            ui[k1].push_back(t);
+      };
+      for (int j = 0; j < p.ntc_max; ++j) {
+         each(p.upd_diag[j], update);
+         each(p.upd[j], update);
+         each(p.trsm[j], [&](const TileTask& t) {
+            const int g = j / P * P;
+            if (t.ti >= g + P) gs[g / P].strips[{t.blk, t.ti}].push_back(t);
+            else ti[j].push_back(t);
+         });
+      }
+      auto put = [&](TaskList& l, const std::vector<TileTask>& v) {
+         l.off = (long long)h_tasks.size(); l.cnt = (int)v.size();
+         h_tasks.insert(h_tasks.end(), v.begin(), v.end());
+      };
+      deep.assign(n_groups, {}); pre.assign(n_groups, {}); block_deep.assign(n_groups, {}); strips.assign(n_groups, {});
+      upd_in.assign(p.ntc_max, {}); trsm_in.assign(p.ntc_max, {});
+      // a strip's order: the update with columns < k1 before the trsm of column k1 and after that of column k1 - 1
+      auto step = [](const TileTask& t) { return t.pad ? 2 * (t.pad >> 16) : 2 * t.tj + 1; };
+      for (int i = 0; i < n_groups; ++i) {
+         put(deep[i], gs[i].deep);
+         put(pre[i], gs[i].pre);
+         put(block_deep[i], gs[i].block_deep);
+         strips[i].off = (long long)h_strips.size();
+         for (auto& kv : gs[i].strips) {   // (block, tile row) ascending: a block's strips side by side
+            std::vector<TileTask>& v = kv.second;
+            std::stable_sort(v.begin(), v.end(), [&](const TileTask& a, const TileTask& b) { return step(a) != step(b) ? step(a) < step(b) : a.tj < b.tj; });
+            h_strips.push_back({(int)h_tasks.size(), (int)v.size()});
+            h_tasks.insert(h_tasks.end(), v.begin(), v.end());
+         }
+         strips[i].cnt = (int)((long long)h_strips.size() - strips[i].off);
+         for (int j = i * P; j < std::min((i + 1) * P, p.ntc_max); ++j) {
+            put(upd_in[j], ui[j]);
+            put(trsm_in[j], ti[j]);
+         }
+      }
+   }
+   int build(const TailPlan& p, int P_) {
+      lists(p, P_);
+      if (h_tasks.empty()) h_tasks.push_back({-1, 0, 0, 0});
+      if (h_strips.empty()) h_strips.push_back({0, 0});
+      PIPS_TRY(d_tasks.upload(h_tasks));
+      return d_strips.upload(h_strips);
    }
 };
 
@@ -467,6 +557,7 @@ struct TailCtx {
    const int* d_bk_perm = nullptr;
    int bk_isolate = 0;
    const TailSingle* single = nullptr;   // the leaf tails as one dependency-driven launch (tailkernel.hip.h) instead of the column loop
+   const PanelPlan* panels = nullptr;    // the leaf tails group by group: diagonal block on the side stream, one panel launch below it (tail_panels)
 };
 constexpr int GEMM_CTR_SLOTS = 4096;
 constexpr int GEMM_BAL_MIN_TASKS = 1024;   // below two full rounds of the chip a static one-task-per-workgroup launch does as well
@@ -512,17 +603,18 @@ static void launch_tile_diag(const TailCtx& c, const TileTask* tasks, const Task
 // leaf tails: launches of two rounds of the chip or more draw their tiles from per-XCD counters with an eighth more workgroups than
 // tiles (k_tile_gemm_bal); smaller ones one tile per workgroup.  (A persistent work-stealing variant, static shares, the root's bulk
 // in chunks or as a persistent launch with fewer workgroups than the chip holds: measured, no gain - docs/HISTORY_r4.md.)
-static void launch_tile_update(const TailCtx& c, const TaskList& l, hipStream_t st) {
+static void launch_tile_update(const TailCtx& c, const TaskList& l, hipStream_t st, const TileTask* tasks = nullptr) {
+   if (!tasks) tasks = c.plan->d_tasks;
    if (!c.is_root && l.cnt >= GEMM_BAL_MIN_TASKS && tile_gemm_bal_ready(c))
-      launch_tile_gemm_bal<0>(c, c.plan->d_tasks, l, st);
+      launch_tile_gemm_bal<0>(c, tasks, l, st);
    else if (c.is_root)
       // The bulk update of the trailing matrix runs on the side stream beside the diagonal-tile chain of the next column.  Stream
       // priorities only order the launches the command processor has not started yet: once a launch of thousands of workgroups is
       // running, the single workgroup of k_tile_diag gets no slot until that launch drains (rocprofv3 trace at S = 16000: the diagonal
       // kernel "takes" 270 - 1140 us beside the bulk and 70 us alone - it is waiting): the lookahead overlaps only the drain.
-      launch_tile_gemm<3>(c, c.plan->d_tasks, l, st);
+      launch_tile_gemm<3>(c, tasks, l, st);
    else
-      launch_tile_gemm<0>(c, c.plan->d_tasks, l, st);
+      launch_tile_gemm<0>(c, tasks, l, st);
 }
 
 // PIPS_HIP_TAIL_TRACE: the per-task clocks of a k_tail_ldl launch into a file (tools/tail_trace.py); waits for the launch
@@ -635,6 +727,47 @@ static int tail_columns(const TailCtx& c, bool trsm_tri) {
    return main_writes(1 << 30);   // join the side stream
 }
 
+// The leaf tails group by group (PanelPlan; left-looking batches in the static pivot order with the triangular trsm): per group of P tile
+// columns the main stream has two launches, the deep update of the tile rows below the group's diagonal block and one k_tile_panel that
+// finishes those rows across the group; the block itself - its deep update, then per column short update, diagonal tile, trsm, the
+// column launches' kernels on short lists - is a chain on the side stream beside the deep launch, from the panel launch of the group
+// before (ev_panel) to this group's (ev_rest).  The panel launch is booked with the updates (phase 2), the trsm inside it included; a
+// chain on the side stream is not booked (it ends under the deep launch: DESIGN.md 4.2).
+static int tail_panels(const TailCtx& c) {
+   const TailPlan& p = *c.plan;
+   const PanelPlan& g = *c.panels;
+   const int n_tasks = (int)g.h_tasks.size();
+   for (int i = 0; i < g.n_groups; ++i) {
+      // a group without a deep launch (the first) has nothing to hide its chain behind: it runs on the main stream, booked as the column
+      // launches book their steps
+      const bool beside = g.deep[i].cnt > 0;
+      const hipStream_t st = beside ? c.side : c.stream;
+      PhaseTimer* const tm = beside ? nullptr : c.timer;
+      if (beside) {
+         HIP_TRY(hipEventRecord(c.ev_panel, c.stream));
+         HIP_TRY(hipStreamWaitEvent(c.side, c.ev_panel, 0));
+      }
+      if (g.pre[i].cnt > 0) { PhaseTimer::Scope phase(tm, st, 2); launch_tile_gemm<4>(c, g.d_tasks, g.pre[i], st); }
+      if (g.block_deep[i].cnt > 0) { PhaseTimer::Scope phase(tm, st, 2); launch_tile_gemm<4>(c, g.d_tasks, g.block_deep[i], st); }
+      for (int j = i * g.P; j < std::min((i + 1) * g.P, p.ntc_max); ++j) {
+         if (g.upd_in[j].cnt > 0) { PhaseTimer::Scope phase(tm, st, 2); launch_tile_gemm<4>(c, g.d_tasks, g.upd_in[j], st); }
+         { PhaseTimer::Scope phase(tm, st, 3); launch_tile_diag(c, p.d_tasks, p.diag[j], st); }
+         if (g.trsm_in[j].cnt > 0) { PhaseTimer::Scope phase(tm, st, 4); launch_tile_gemm<5>(c, g.d_tasks, g.trsm_in[j], st); }
+      }
+      if (beside) {
+         HIP_TRY(hipEventRecord(c.ev_rest, c.side));
+         { PhaseTimer::Scope phase(c.timer, c.stream, 2); launch_tile_update(c, g.deep[i], c.stream, g.d_tasks); }
+         HIP_TRY(hipStreamWaitEvent(c.stream, c.ev_rest, 0));
+      }
+      if (g.strips[i].cnt > 0) {
+         PhaseTimer::Scope phase(c.timer, c.stream, 2);
+         hipLaunchKernelGGL(k_tile_panel, dim3(tile_grid(g.strips[i].cnt)), dim3(512), 0, c.stream, g.d_strips + g.strips[i].off, g.strips[i].cnt, g.d_tasks, n_tasks,
+                            c.d_blks, c.d_arena, c.d_dtail, c.d_winv, c.d_uarena);
+      }
+   }
+   return PIPS_OK;
+}
+
 // The tails' Schur contribution SC -= L_b D L_b^T over the border rows of every block (k_tile_gemm<2>), one of four ways: deterministic
 // rounds into the group buffers, row-panel groups with an event each, one balanced launch, one plain launch
 static int tail_schur(const TailCtx& c, double* SC, int ldSC) {
@@ -664,7 +797,9 @@ static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
    // trsm of the leaf tails in the static pivot order: Winv is lower triangular, k_tile_gemm<5> skips the products with its zeros
    // (PIPS_HIP_TRSM_DENSE=1: the dense product, for A/B runs and the test that compares the two bit for bit)
    const bool trsm_tri = !c.bunch_kaufman && !c.is_root && env_int("PIPS_HIP_TRSM_DENSE", 0) == 0;
-   if (!c.single) PIPS_TRY(tail_columns(c, trsm_tri));
+   // ... and group by group, unless PIPS_HIP_TAIL_PANEL=0 (or the dense trsm) asks for the column launches
+   if (!c.single && c.panels && c.side && trsm_tri && env_int("PIPS_HIP_TAIL_PANEL", 1) != 0) PIPS_TRY(tail_panels(c));
+   else if (!c.single) PIPS_TRY(tail_columns(c, trsm_tri));
    else if (c.single->n_tasks > 0) PIPS_TRY(tail_single_launch(c));
    PIPS_TRY(tail_schur(c, SC, ldSC));
    HIP_TRY(hipGetLastError());
@@ -754,6 +889,7 @@ struct EngineAnalysis {
    DevBuf<long long> d_mfdbg;           // PIPS_HIP_MF_CLOCKS: phase stamps of every front (8 per supernode), dumped after the factorisation
    DevBuf<int> d_spine, d_spine_off;
    TailPlan plan;
+   PanelPlan panels;                    // ... regrouped by groups of tile columns (tail_panels; not for the single-launch tails)
    SweepRt sweep;
    TailSingle tsingle;                  // the tails as one dependency-driven launch (tailkernel.hip.h)
    DevBuf<double> d_uarena;             // U = L D copies of the tails (see k_tile_gemm)
@@ -1092,7 +1228,8 @@ struct Engine : EngineAnalysis, BatchLayout {
          tsingle.args.blks = d_blks; tsingle.args.arena = d_arena; tsingle.args.uarena = d_uarena; tsingle.args.winv = d_winv; tsingle.args.dtail = d_dtail;
          tsingle.args.pref = d_pref; tsingle.args.psign = d_psign; tsingle.args.psign_off = d_psign_off; tsingle.args.inertia = d_inertia;
          c.single = &tsingle;
-      }
+      } else if (panels.n_groups > 0)
+         c.panels = &panels;
       return c;
    }
 
@@ -1130,7 +1267,8 @@ struct Engine : EngineAnalysis, BatchLayout {
          if ((rc = tsingle.build(plan, h_blks, stream))) return rc;
          tsingle.args.poll_limit = knobs.tail_poll_limit;
          tsingle.args.diag_blocked = knobs.tail_diag_blocked;
-      }
+      } else if ((rc = panels.build(plan, pair2)))
+         return rc;
       drop_uploaded();
       if (!side) {
          // highest priority: the few workgroups of the diagonal chain must not queue behind the thousands of the column update
@@ -4077,13 +4215,12 @@ int pips_symbolic_probe_hubs(int n, int n_primal, const int* krow, const int* jc
 }
 
 // ---- layout probe (CPU only): symbolic analysis and host layout of a batch as Engine::analyze forms them, and the layout's invariants
-int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
-                      const int* const* bt_rowptr, const int* const* bt_colidx, int deterministic, long long free_device_bytes,
-                      int64_t* what, int n_what) {
-   if (nblk <= 0 || !n || !krow || !kcol || S < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_layout_probe: bad arguments");
-   std::vector<BlockInput> in(nblk);
+static int probe_inputs(const char* who, int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
+                        const int* const* bt_rowptr, const int* const* bt_colidx, std::vector<BlockInput>& in) {
+   if (nblk <= 0 || !n || !krow || !kcol || S < 0) PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments", who);
+   in.assign(nblk, BlockInput());
    for (int b = 0; b < nblk; ++b) {
-      if (n[b] <= 0 || !krow[b] || !kcol[b]) PIPS_FAIL(PIPS_ERR_ARG, "pips_layout_probe: block %d is empty", b);
+      if (n[b] <= 0 || !krow[b] || !kcol[b]) PIPS_FAIL(PIPS_ERR_ARG, "%s: block %d is empty", who, b);
       in[b].n = n[b];
       in[b].n_primal = n_primal ? n_primal[b] : -1;
       in[b].krow.assign(krow[b], krow[b] + n[b] + 1);
@@ -4094,6 +4231,14 @@ int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* co
          in[b].btval.assign(in[b].btcol.size(), 0.0);
       }
    }
+   return PIPS_OK;
+}
+
+int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
+                      const int* const* bt_rowptr, const int* const* bt_colidx, int deterministic, long long free_device_bytes,
+                      int64_t* what, int n_what) {
+   std::vector<BlockInput> in;
+   PIPS_TRY(probe_inputs("pips_layout_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
    AnalyzeOptions opt;
    AnalyzeKnobs knobs;
    read_layout_knobs(nullptr, opt, knobs);
@@ -4111,6 +4256,72 @@ int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* co
                     lay.slots_total, lay.vslots_total, lay.n_total, lay.mf, lay.schur_mode_eff, lay.bb_doubles, lay.mfU_total, lay.spine_total};
    for (const MfLaunch& m : lay.mf_launches) if (m.cls >= 6) v[7] += m.cnt;
    for (int i = 0; what && i < n_what && i < 21; ++i) what[i] = v[i];
+   return PIPS_OK;
+}
+
+// ---- tail plan probe (CPU only): the task plans of a leaf batch's launch-per-step tail factorisation as Engine::analyze forms them - the
+// column plan (TailPlan) and its regrouping by groups of tile columns (PanelPlan) - as rows of integers (include/pips_hip.h)
+int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
+                         const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head, int* col_tasks, long long col_cap,
+                         int* grp_tasks, long long grp_cap, int64_t* counts) {
+   std::vector<BlockInput> in;
+   PIPS_TRY(probe_inputs("pips_tail_plan_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
+   if (!counts || col_cap < 0 || grp_cap < 0 || (col_cap > 0 && !col_tasks) || (grp_cap > 0 && !grp_tasks))
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_tail_plan_probe: bad arguments");
+   AnalyzeOptions opt;
+   AnalyzeKnobs knobs;
+   read_layout_knobs(nullptr, opt, knobs);
+   opt.force_n_head = force_n_head;
+   knobs.free_device_bytes = 0;
+   std::vector<BlockSym> sym;
+   BatchLayout lay;
+   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+   PIPS_TRY(analyze_symbolic(in, S, n_threads, opt, knobs, sym));
+   PIPS_TRY(build_batch_layout(in, sym, S, knobs, lay));
+   TailPlan plan;
+   plan.lists(lay.h_blks, 0, false, true, &lay.tile_first, true, 4);
+   PanelPlan pp;
+   pp.lists(plan, 4);
+   long long nc = 0, ng = 0, launches_col = 0, launches_grp = 0;
+   auto col = [&](const TaskList& l, int kind) {
+      launches_col += l.cnt > 0;
+      for (long long q = l.off; q < l.off + l.cnt; ++q, ++nc) {
+         const TileTask& t = plan.h_tasks[q];
+         if (nc < col_cap) { int* r = col_tasks + 6 * nc; r[0] = kind; r[1] = t.blk; r[2] = t.ti; r[3] = t.tj; r[4] = t.pad & 0xffff; r[5] = t.pad >> 16; }
+      }
+   };
+   auto grp = [&](long long off, int cnt, int list, int group, int index) {
+      for (int q = 0; q < cnt; ++q, ++ng) {
+         const TileTask& t = pp.h_tasks[off + q];
+         if (ng < grp_cap) {
+            int* r = grp_tasks + 9 * ng;
+            r[0] = list; r[1] = group; r[2] = index; r[3] = q; r[4] = t.blk; r[5] = t.ti; r[6] = t.tj; r[7] = t.pad & 0xffff; r[8] = t.pad >> 16;
+         }
+      }
+   };
+   auto grp_list = [&](const TaskList& l, int list, int group, int index) { launches_grp += l.cnt > 0; grp(l.off, l.cnt, list, group, index); };
+   for (int j = 0; j < plan.ntc_max; ++j) {
+      col(plan.upd_diag[j], 0);
+      col(plan.upd[j], 0);
+      launches_col += plan.diag[j].cnt > 0;
+      col(plan.trsm[j], 1);
+   }
+   for (int i = 0; i < pp.n_groups; ++i) {
+      grp_list(pp.deep[i], 0, i, 0);
+      grp_list(pp.pre[i], 1, i, 0);
+      grp_list(pp.block_deep[i], 2, i, 0);
+      for (int j = i * pp.P; j < std::min((i + 1) * pp.P, plan.ntc_max); ++j) {
+         grp_list(pp.upd_in[j], 3, i, j);
+         launches_grp += plan.diag[j].cnt > 0;
+         grp_list(pp.trsm_in[j], 4, i, j);
+      }
+      launches_grp += pp.strips[i].cnt > 0;
+      for (int q = 0; q < pp.strips[i].cnt; ++q) {
+         const TileStrip& st = pp.h_strips[pp.strips[i].off + q];
+         grp(st.off, st.cnt, 5, i, q);
+      }
+   }
+   counts[0] = nc; counts[1] = ng; counts[2] = plan.ntc_max; counts[3] = pp.n_groups; counts[4] = launches_col; counts[5] = launches_grp;
    return PIPS_OK;
 }
 

@@ -1738,6 +1738,37 @@ __global__ __launch_bounds__(512, 4) void k_tile_gemm_bal(const TileTask* __rest
    tile_gemm_body<MODE>(tix, sh, tasks, n_tasks, blks, arena, dtail, winv, bmap, SC, ldSC, sctab, uarena);
 }
 
+// A group of tile columns below its diagonal block in one launch (engine.hip tail_panels): one workgroup per (block, tile row) strip
+// runs the strip's tasks back to back - trsm (pad == 0) and update (pad = K range != 0) bodies as the column launches run them, in
+// column order.  What a body reads may be what the body before it stored (the A panel of an update is the L the strip's trsm wrote,
+// the trsm's A tile the C the update wrote; the B panels are rows of the diagonal block, never the strip's own): between two bodies every wave retires
+// its stores, releases and acquires at workgroup scope and meets the others at a barrier.  The waves of a workgroup share their
+// compute unit's vector L1, through which plain loads and the LDS-DMA alike read, so that scope is enough; no other workgroup of
+// the launch touches the strip's tile row, and the B operands of the diagonal block were final before the launch.  The barrier also
+// hands the LDS buffers over.  Strips are dealt to the XCDs as k_tile_gemm deals tasks: a block's strips share a slice and an L2.
+__global__ __launch_bounds__(512, 4) void k_tile_panel(const TileStrip* __restrict__ strips, int n_strips, const TileTask* __restrict__ tasks,
+                                                      int n_tasks, const BlkDesc* __restrict__ blks, double* __restrict__ arena,
+                                                      const double* __restrict__ dtail, const double* __restrict__ winv,
+                                                      double* __restrict__ uarena) {
+   __shared__ GemmShared sh;
+   const int per = (n_strips + 7) >> 3;
+   const int six = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+   if (six >= n_strips) return;
+   const TileStrip s = strips[six];
+   for (int t = s.off; t < s.off + s.cnt; ++t) {
+      if (t > s.off) {
+         dma_wait();
+         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+         __syncthreads();
+         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      }
+      if (__builtin_amdgcn_readfirstlane(tasks[t].pad) == 0)
+         tile_gemm_body<5>(t, sh, tasks, n_tasks, blks, arena, dtail, winv, nullptr, nullptr, 0, nullptr, uarena);
+      else
+         tile_gemm_body<0>(t, sh, tasks, n_tasks, blks, arena, dtail, winv, nullptr, nullptr, 0, nullptr, uarena);
+   }
+}
+
 // deterministic mode: SC += ((g0 + g1) + (g2 + g3)) + ((g4 + g5) + (g6 + g7)) over the (at most eight) group buffers, lower triangle.
 // The order is a function of the global block partition only, so one rank with eight groups and two ranks with four groups each
 // followed by the two-operand sum of the all-reduce give the same bits.  (Not so for 4 or 8 ranks: there the all-reduce associates

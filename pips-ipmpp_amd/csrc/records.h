@@ -51,6 +51,7 @@ struct BlkDesc {
 };
 
 struct TileTask { int blk, ti, tj, pad; };
+struct TileStrip { int off, cnt; };   // k_tile_panel: the tasks [off, off + cnt) of one tile row, in the order they run
 
 constexpr int HEAD_WMAX = 32;   // widest head supernode (solve kernels)
 constexpr int SIMPLE_RMAX = 16;
