@@ -605,6 +605,28 @@ int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int*
                          int S, const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head,
                          int* col_tasks, long long col_cap, int* grp_tasks, long long grp_cap, int64_t* counts);
 
+/* The host layout pass of an IPM handle's creation, without a device (csrc/ipmlayout.cpp; tests): the functions pips_ipm_create_qp runs
+ * before it touches the device.  Inputs as pips_ipm_create_qp without device and comm; eliminate_z0: whether the root inequality rows are
+ * eliminated from the root system (what PIPS_IPM_ROOT_INEQ_ELIMINATE / PIPS_IPM_SPARSE_ROOT decide at creation); col (nx) and
+ * row ([row_eq | row_ineq], my + mz): both NULL, or scaling factors the data is scaled with first, as pips_ipm_create_general_scaled
+ * scales it with its scaler's.
+ * dims (PIPS_IPML_DIMS): N n0 my0 mz0 myl mzl ry rzr nx my mz ncp nxyz NP ND nleaf e_mz0 e_mzl S has_q.  scalars: this rank's
+ * complementarity pairs and data norm.  Arrays by size-then-fill: with out == NULL sizes[k] receives the entry count of array k; with
+ * out given, sizes must hold those counts and out[k] receives array k (out[k] may be NULL where sizes[k] is 0).  The arrays
+ * (i: int, l: long long, d: double; pads of "never empty" arrays are not counted):
+ *   0-3   xoff yoff zoff (i, N + 2) koff (l, N + 2)
+ *   4-11  J rowptr colidx (i) val (d), J^T rowptr colidx (i) val (d), long rows of J, of J^T (i)
+ *   12-20 c b M Bd wG wGs wXYZ (d) pack code (l)
+ *   21-26 per leaf, back to back: K rowptr colidx (i) constant values (d), border rowptr (S + 1 each) colidx (i) val (d)
+ *   27-38 rowptr colidx (i) val (d) of A0, F0, C0 and of G0 (eliminate_z0 == 0: [C0; G0]); an absent matrix has size 0
+ *   39-42 per block: Hessian present (i, 0/1); of the present ones, back to back: rowptr (n + 1 each) colidx (i) val (d), lower triangle, sorted
+ *   43-47 the flat Hessian (both triangles over x): rowptr colidx (i) val diagonal (d) long rows (i); all empty without a Hessian */
+enum { PIPS_IPML_DIMS = 20, PIPS_IPML_SLOTS = 48 };
+int pips_ipm_layout_probe(int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL,
+                          const double* dlow, const double* dupp, const double* idlow, const double* idupp, int rank, int n_ranks,
+                          int eliminate_z0, const double* col, const double* row, long long* dims, double* scalars, long long* sizes,
+                          void* const* out);
+
 /* The tables of the packed blocked solves (Schur mode 2 with the sparse root), without a device; the code the engine builds its own
  * with.  bt_rowptr[b]: the S + 1 row pointers of block b's border (NULL: no border).  nb[b] (nblk entries): the block's non-empty
  * border columns; *nb_max their maximum = the right-hand sides of the packed solves; local_of_row[b] (S entries each): the local index

@@ -34,13 +34,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "devmem.h"
+#include "ipmlayout.h"
 #include "pips_hip.h"
 
 extern "C" {
@@ -76,7 +76,6 @@ static inline int egrid(long long n) { return (int)std::max<long long>(1, std::m
 // one - on replicated output rows (ranges rep0 = [0, r0e), rep1 = [r1b, r1e)) only the linear term is produced, the rest of
 // the epilogue is added once by rank 0 and the rows are summed over the ranks afterwards (DistributedMatrix.C:224-326).
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr int CSR_LONG_ROW = 512;
 enum SpmvMode : int { SP_RQ = 0, SP_RAC, SP_KX, SP_KYZ, SP_RES_X, SP_RES_YZ, SP_QX };
 
 struct SpmvArgs {
@@ -1381,16 +1380,11 @@ struct Ipm {
    }
 
    // J, J^T and their long-row lists to the device
-   template <class H>
-   int upload_J(const H& h) {
-      std::vector<int> la, lat;
-      for (int r = 0; r < my + mz; ++r) if (h.rp[r + 1] - h.rp[r] > CSR_LONG_ROW) la.push_back(r);
-      for (int r = 0; r < nx; ++r) if (h.trp[r + 1] - h.trp[r] > CSR_LONG_ROW) lat.push_back(r);
-      nJ_long = (int)la.size(); nJt_long = (int)lat.size();
+   int upload_J(const HostCsr& h) {
+      nJ_long = h.n_long; nJt_long = h.n_tlong;
       J_nnz = h.rp[my + mz]; Jt_nnz = h.trp[nx];
-      la.push_back(0); lat.push_back(0);
-      TRY(up(&J_long, la)); TRY(up(&Jt_long, lat));
-      TRY(alloc(&long_scratch, (long long)std::max<size_t>(std::max(std::max(la.size(), lat.size()), (size_t)nQ_long + 1), 1) * LONG_PARTS));   // (nQ_long: the Hessian's long rows, known before J is uploaded)
+      TRY(up(&J_long, h.long_rows)); TRY(up(&Jt_long, h.long_trows));
+      TRY(alloc(&long_scratch, (long long)std::max<size_t>(std::max(std::max(h.long_rows.size(), h.long_trows.size()), (size_t)nQ_long + 1), 1) * LONG_PARTS));   // (nQ_long: the Hessian's long rows, known before J is uploaded)
       TRY(up(&J_rp, h.rp)); TRY(up(&J_ci, h.ci)); TRY(up(&J_v, h.v));
       TRY(up(&Jt_rp, h.trp)); TRY(up(&Jt_ci, h.tci)); TRY(up(&Jt_v, h.tv));
       return PIPS_OK;
@@ -1643,6 +1637,50 @@ struct Ipm {
          for (int i = 0; i < 7; ++i) result[i] = last[i];
       return PIPS_OK;
    }
+
+   // ---- creation: what the host layout pass (ipmlayout.cpp) computed, to the handle and the device -------------
+   void set_dims(const IpmLayout& L) {
+      N = L.N; n0 = L.n0; my0 = L.my0; mz0 = L.mz0; myl = L.myl; mzl = L.mzl; ry = L.ry; rzr = L.rzr;
+      nx = L.nx; my = L.my; mz = L.mz; e_mz0 = L.e_mz0; e_mzl = L.e_mzl; S = L.S;
+      ncp = L.ncp; nxyz = L.nxyz; NP = L.NP; ND = L.ND; nleaf = L.nleaf;
+      lay = Lay{nx, my, mz, ncp};
+   }
+   int upload(const IpmLayout& L) {
+      npack = (long long)L.pack.size();
+      TRY(up(&d_pack, L.pack)); TRY(up(&d_code, L.code));
+      if (has_q) {   // device copy of Q, its diagonal, the product vector
+         Q_nnz = L.Q_nnz; nQ_long = L.nQ_long;
+         TRY(up(&Q_rp, L.Q_rp)); TRY(up(&Q_ci, L.Q_ci)); TRY(up(&Q_v, L.Q_v)); TRY(up(&Q_long, L.Q_long)); TRY(up(&qdiag, L.qdiag));
+         TRY(alloc(&qx, nx));
+      }
+      if (!J_v) TRY(upload_J(L.J));   // a scaled handle holds J since prescale()
+      TRY(up(&c, L.c)); TRY(up(&bA, L.b)); TRY(up(&M, L.M)); TRY(up(&Bd, L.Bd)); TRY(up(&wG, L.wG)); TRY(up(&wGs, L.wGs)); TRY(up(&wXYZ, L.wXYZ));
+      wX = wXYZ;
+      wY = wXYZ + nx;
+      return PIPS_OK;
+   }
+   int alloc_state() {
+      double* bases[4];
+      for (auto& b : bases) TRY(alloc(&b, NP + ND));
+      it.bind(bases[0], nx, my, mz, ncp); st.bind(bases[1], nx, my, mz, ncp);
+      co.bind(bases[2], nx, my, mz, ncp); best.bind(bases[3], nx, my, mz, ncp);
+      const long long nyz = (long long)my + mz;
+      TRY(alloc(&rQ, nx)); TRY(alloc(&rAC, nyz)); TRY(alloc(&rz, mz)); TRY(alloc(&rG, ncp)); TRY(alloc(&rL, ncp)); TRY(alloc(&rs, mz));
+      TRY(alloc(&dd, nx)); TRY(alloc(&ddp, nx)); TRY(alloc(&dop_r, nx)); TRY(alloc(&dyz_r, nyz)); TRY(alloc(&dyz, nyz)); TRY(alloc(&leaf_diag, nleaf));
+      double** zs[] = {&rhs, &sol, &w_r, &w_r0, &w_best, &w_v, &w_t, &w_p, &w_dx, &w_tmp};
+      for (auto d : zs) TRY(alloc(d, nxyz));
+      TRY(alloc(&b0, (long long)S + e_mz0 + nleaf));   // [b0 | leaves] in one array (one gather / scatter)
+      bl = b0 + S + e_mz0;
+      TRY(alloc(&d_partial, (long long)RED_MAX * RED_GRID)); TRY(alloc(&d_out, 2 * RED_MAX)); TRY(alloc(&d_bst, B_SLOTS));
+      TRY(h_out.alloc(2 * RED_MAX));
+      TRY(h_bst.alloc(B_SLOTS));
+      TRY(d_pred.alloc_zero(P_COUNT));
+      if (e_mz0 > 0) {   // nOmegaInv of the eliminated root rows, regularised
+         TRY(alloc(&zd0, e_mz0));
+         TRY(pips_hip_kkt_set_zdiag0_dev(kkt, zd0));
+      }
+      return PIPS_OK;
+   }
 };
 
 }  // namespace pips
@@ -1654,484 +1692,139 @@ using namespace pips;
 // ------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct View { int rows = 0, cols = 0; const int* rp = nullptr; const int* ci = nullptr; const double* v = nullptr; };
-View view(const pips_csr_view& m) { return View{m.rows, m.cols, m.rowptr, m.colidx, m.val}; }
-bool present(const View& m) { return m.rp != nullptr && m.rows > 0; }
-
-struct HostCsr { std::vector<int> rp, ci, trp, tci; std::vector<double> v, tv; };
-// J = [A; C] and J^T from the rows (sorted in place)
-void rows_to_csr(std::vector<std::vector<std::pair<int, double>>>& rows, int nx, HostCsr& h) {
-   h.rp.assign(rows.size() + 1, 0);
-   h.trp.assign((size_t)nx + 1, 0);
-   for (size_t r = 0; r < rows.size(); ++r) {
-      std::sort(rows[r].begin(), rows[r].end());
-      h.rp[r + 1] = h.rp[r] + (int)rows[r].size();
-      for (auto& e : rows[r]) ++h.trp[e.first + 1];
-   }
-   const int nnz = h.rp[rows.size()];
-   h.ci.resize(nnz); h.tci.resize(nnz); h.v.resize(nnz); h.tv.resize(nnz);
-   for (int j = 0; j < nx; ++j) h.trp[j + 1] += h.trp[j];
-   std::vector<int> fill(h.trp.begin(), h.trp.end() - 1);
-   for (size_t r = 0; r < rows.size(); ++r) {
-      int q = h.rp[r];
-      for (auto& e : rows[r]) {
-         h.ci[q] = e.first; h.v[q] = e.second; ++q;
-         const int t = fill[e.first]++;
-         h.tci[t] = (int)r; h.tv[t] = e.second;
-      }
-   }
-}
-
-// ---- scaling before assembly (pips_ipm_create_general_scaled) -----------------------------------------------------------------
-// The data as the harness reads it, scaled by the factors (Scaler::applyScaling): matrices (a col_j) row_i, c col, b / clow / cupp
-// row, xlow / xupp / col.  Host copies of O(nnz): the existing assembly reads them.
-struct ScaledData {
-   std::vector<pips_ipm_block> blk;
-   std::deque<std::vector<double>> keep;
-   const double *bL = nullptr, *dlow = nullptr, *dupp = nullptr;
+// the switches creation reads from the environment, parsed once
+struct IpmKnobs {
+   bool sparse_root = false;      // PIPS_IPM_SPARSE_ROOT
+   bool eliminate_z0 = true;      // PIPS_IPM_ROOT_INEQ_ELIMINATE; unset: on the dense root only (ipm_dims, ipmlayout.cpp)
+   const char* schur_mode = nullptr;   // PIPS_IPM_SCHUR_MODE as given; unset: the batch's default, mode 1 with the sparse root
 };
-void make_scaled(const Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow,
-                 const double* dupp, ScaledData& sd) {
-   const int N = n_blocks - 1, n0 = blocks[0].n, my0 = blocks[0].my, mz0 = blocks[0].mz;
-   const double* col = p->h_col.data();
-   const double* re = p->h_row.data();
-   const double* ri = re + p->my;
-   sd.blk.assign(blocks, blocks + n_blocks);
-   auto mat = [&](pips_csr_view& m, const double* rf, int c0) {   // rf: factors of the matrix' rows, c0: its first column in x
-      if (!m.rowptr || m.rows <= 0) return;
-      sd.keep.emplace_back((size_t)m.rowptr[m.rows], 0.0);
-      std::vector<double>& v = sd.keep.back();
-      for (int r = 0; r < m.rows; ++r)
-         for (int q = m.rowptr[r]; q < m.rowptr[r + 1]; ++q) v[q] = (m.val[q] * col[c0 + m.colidx[q]]) * rf[r];
-      m.val = v.data();
-   };
-   auto vec = [&](const double*& x, int n, const double* f, bool div) {
-      if (!x || n <= 0) return;
-      sd.keep.emplace_back(x, x + n);
-      std::vector<double>& v = sd.keep.back();
-      for (int k = 0; k < n; ++k) v[k] = div ? v[k] / f[k] : v[k] * f[k];
-      x = v.data();
-   };
-   int xo = n0, yo = my0 + myl, zo = mz0 + mzl;
-   for (int i = 0; i <= N; ++i) {
-      pips_ipm_block& b = sd.blk[i];
-      const int xi = i == 0 ? 0 : xo, yi = i == 0 ? 0 : yo, zi = i == 0 ? 0 : zo;
-      mat(b.A, re + yi, 0);
-      mat(b.C, ri + zi, 0);
-      if (i > 0) { mat(b.B, re + yi, xi); mat(b.D, ri + zi, xi); }
-      mat(b.BL, re + my0, xi);
-      mat(b.DL, ri + mz0, xi);
-      vec(b.c, b.n, col + xi, false); vec(b.xlow, b.n, col + xi, true); vec(b.xupp, b.n, col + xi, true);
-      vec(b.b, b.my, re + yi, false); vec(b.clow, b.mz, ri + zi, false); vec(b.cupp, b.mz, ri + zi, false);
-      if (i > 0) { xo += b.n; yo += b.my; zo += b.mz; }
-   }
-   sd.bL = bL; sd.dlow = dlow; sd.dupp = dupp;
-   vec(sd.bL, myl, re + my0, false); vec(sd.dlow, mzl, ri + mz0, false); vec(sd.dupp, mzl, ri + mz0, false);
+IpmKnobs read_ipm_knobs() {
+   IpmKnobs k;
+   const char* e;
+   k.sparse_root = (e = getenv("PIPS_IPM_SPARSE_ROOT")) && atoi(e) != 0;
+   k.eliminate_z0 = (e = getenv("PIPS_IPM_ROOT_INEQ_ELIMINATE")) ? atoi(e) != 0 : !k.sparse_root;
+   k.schur_mode = getenv("PIPS_IPM_SCHUR_MODE");
+   return k;
 }
-// this rank's part of the data norm as build() forms it (every matrix entry, c, b, the bounds under their indicators)
-double data_norm(int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow, const double* dupp,
-                 const double* idlow, const double* idupp) {
-   double dn = 0.0;
-   auto m = [&](const pips_csr_view& a) {
-      if (a.rowptr && a.rows > 0) for (int q = a.rowptr[0]; q < a.rowptr[a.rows]; ++q) dn = std::max(dn, std::fabs(a.val[q]));
-   };
-   auto v = [&](const double* x, const double* ind, int n) {
-      if (x) for (int k = 0; k < n; ++k) dn = std::max(dn, std::fabs(ind ? x[k] * ind[k] : x[k]));
-   };
-   for (int i = 0; i < n_blocks; ++i) {
-      const pips_ipm_block& b = blocks[i];
-      m(b.A); m(b.C); m(b.BL); m(b.DL);
-      if (i > 0) { m(b.B); m(b.D); }
-      v(b.c, nullptr, b.n); v(b.b, nullptr, b.my);
-      v(b.xlow, b.ixlow, b.n); v(b.xupp, b.ixupp, b.n); v(b.clow, b.iclow, b.mz); v(b.cupp, b.icupp, b.mz);
-   }
-   v(bL, nullptr, myl); v(dlow, idlow, mzl); v(dupp, idupp, mzl);
-   return dn;
-}
-// J of the original data to the device, the scaler on it (J, J^T scaled in place), and the scaled host copies for build()
-int prescale(Ipm* p, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL, const double* dlow, const double* dupp,
-             const double* idlow, const double* idupp, int device, int scaler, ScaledData& sd) {
+
+// J of the original data to the device, the scaler on it (J, J^T scaled in place), and the scaled host copies for build().  The device
+// keeps that J: the scaled host data's own J differs from it in rounding and is never formed.
+int prescale(Ipm* p, const IpmInput& in, const IpmKnobs& knobs, int device, int scaler, ScaledData& sd) {
    if (device >= 0) HIP_TRYH(hipSetDevice(device));
-   const int N = n_blocks - 1;
-   const pips_ipm_block& root = blocks[0];
-   p->N = N; p->n0 = root.n; p->my0 = root.my; p->mz0 = root.mz; p->myl = myl; p->mzl = mzl;
-   p->ry = root.my + myl; p->rzr = root.mz + mzl;
-   std::vector<int> xoff(N + 2, 0), yoff(N + 2, 0), zoff(N + 2, 0);
-   xoff[1] = root.n; yoff[1] = p->ry; zoff[1] = p->rzr;
-   for (int i = 1; i <= N; ++i) {
-      if (blocks[i].n < 0 || blocks[i].my < 0 || blocks[i].mz < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: negative block dimension");
-      xoff[i + 1] = xoff[i] + blocks[i].n; yoff[i + 1] = yoff[i] + blocks[i].my; zoff[i + 1] = zoff[i] + blocks[i].mz;
-   }
-   p->nx = xoff[N + 1]; p->my = yoff[N + 1]; p->mz = zoff[N + 1];
-   const int my = p->my, my0 = root.my, mz0 = root.mz;
-   std::vector<std::vector<std::pair<int, double>>> rows((size_t)p->my + p->mz);
-   auto add = [&](const pips_csr_view& m, int row0, int col0) {
-      if (!m.rowptr || m.rows <= 0) return;
-      for (int r = 0; r < m.rows; ++r)
-         for (int q = m.rowptr[r]; q < m.rowptr[r + 1]; ++q) rows[(size_t)row0 + r].push_back({col0 + m.colidx[q], m.val[q]});
-   };
-   if (p->rank == 0) { add(root.A, 0, 0); add(root.BL, my0, 0); add(root.C, my, 0); add(root.DL, my + mz0, 0); }
-   for (int i = 1; i <= N; ++i) {
-      const pips_ipm_block& b = blocks[i];
-      add(b.A, yoff[i], 0); add(b.B, yoff[i], xoff[i]); add(b.C, my + zoff[i], 0); add(b.D, my + zoff[i], xoff[i]);
-      add(b.BL, my0, xoff[i]); add(b.DL, my + mz0, xoff[i]);
-   }
-   {
-      HostCsr h;
-      rows_to_csr(rows, p->nx, h);
-      rows = {};
-      TRY(p->upload_J(h));
-   }
+   IpmLayout L;
+   TRY(ipm_dims(in, knobs.eliminate_z0, L));
+   p->set_dims(L);
+   ipm_rows_J(in, p->rank, L);
+   TRY(p->upload_J(L.J));
+   L.J = HostCsr{};
    TRY(p->sc_alloc());
    TRY(p->alloc(&p->d_red, 64 * (long long)p->n_ranks));
    TRY(p->run_scaler(scaler));
-   p->dnorm_orig = data_norm(n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp);
-   if (p->scaled) make_scaled(p, n_blocks, blocks, myl, mzl, bL, dlow, dupp, sd);
+   p->dnorm_orig = ipm_data_norm(in, {});
+   if (p->scaled) make_scaled(in, L, p->h_col.data(), p->h_row.data(), sd);
    std::vector<double> ri2(2 * (size_t)p->mz), col2(2 * (size_t)p->nx);
-   for (int k = 0; k < p->mz; ++k) ri2[k] = ri2[(size_t)p->mz + k] = p->h_row[(size_t)my + k];
+   for (int k = 0; k < p->mz; ++k) ri2[k] = ri2[(size_t)p->mz + k] = p->h_row[(size_t)p->my + k];
    for (int k = 0; k < p->nx; ++k) col2[k] = col2[(size_t)p->nx + k] = p->h_col[k];
    TRY(p->up(&p->sc_ri2, ri2));
    TRY(p->up(&p->sc_col2, col2));
    return PIPS_OK;
 }
 
-// ---- Hessians (pips_ipm_create_qp) ---------------------------------------------------------------------------------------------
-// One block's Hessian as the caller gave it, checked and with sorted rows (duplicates added up): lower-triangular CSR like the
-// reference's SparseSymmetricMatrix.  A negative diagonal entry cannot belong to a positive semidefinite matrix: a cheap necessary test,
-// no full one - convexity is the caller's contract.
-struct LowerQ { bool have = false; std::vector<int> rp, ci; std::vector<double> v; };
-int check_hessian(int i, int n, const pips_csr_view& q, LowerQ& out) {
-   out.have = false;
-   if (!q.rowptr) return PIPS_OK;
-   if (q.rows != n || q.cols != n) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] is %d x %d but block %d has %d variables", i, q.rows, q.cols, i, n);
-   if (n > 0 && q.rowptr[n] > q.rowptr[0] && (!q.colidx || !q.val)) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] lacks colidx / val", i);
-   out.have = true;
-   out.rp.assign((size_t)n + 1, 0);
-   std::vector<std::pair<int, double>> row;
-   for (int r = 0; r < n; ++r) {
-      row.clear();
-      for (int q_ = q.rowptr[r]; q_ < q.rowptr[r + 1]; ++q_) {
-         const int c = q.colidx[q_];
-         if (c < 0 || c >= n) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] row %d has column index %d outside [0, %d)", i, r, c, n);
-         if (c > r) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] has entry (%d, %d) above the diagonal - lower-triangular storage expected", i, r, c);
-         row.push_back({c, q.val[q_]});
-      }
-      std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
-      for (size_t k = 0; k < row.size(); ++k) {
-         if (!out.ci.empty() && (int)out.ci.size() > out.rp[r] && out.ci.back() == row[k].first) out.v.back() += row[k].second;
-         else { out.ci.push_back(row[k].first); out.v.push_back(row[k].second); }
-      }
-      out.rp[r + 1] = (int)out.ci.size();
-      if (out.rp[r + 1] > out.rp[r] && out.ci.back() == r && out.v.back() < 0.0)
-         PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: Q[%d] has the negative diagonal entry %g in row %d - not positive semidefinite", i, out.v.back(), r);
+// the leaf batch: blocks, Schur mode, analysis, constant values.  Each leaf's pattern is dropped once the batch has copied it.
+int make_batch(Ipm* p, IpmLayout& L, const IpmKnobs& knobs, int device) {
+   TRY(pips_hip_batch_create(&p->batch, L.N, L.S, device, nullptr));
+   for (int i = 0; i < L.N; ++i) {
+      LeafSystem& s = L.leaf[i];
+      TRY(pips_hip_batch_set_block(p->batch, i, (int)(L.koff[i + 2] - L.koff[i + 1]), L.xoff[i + 2] - L.xoff[i + 1], s.Krp.data(), s.Kci.data(),
+                                   s.Brd.data(), s.Bci.data(), s.Bv.data()));
+      std::vector<double> kvals = std::move(s.kvals);
+      s = LeafSystem{};
+      s.kvals = std::move(kvals);
    }
-   out.ci.push_back(0); out.v.push_back(0.0);   // never empty arrays
+   if (knobs.sparse_root && p->n_ranks > 1)
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: the sparse root needs the border column sets of all blocks on every rank (pips_hip_kkt_create_sparse); "
+                              "the harness passes only its own - use the dense root with several ranks");
+   if (knobs.sparse_root) TRY(pips_hip_batch_set_schur_mode(p->batch, 1));   // (the sparse root's default where PIPS_IPM_SCHUR_MODE is unset)
+   // PIPS_IPM_SCHUR_MODE: how the leaves form their Schur contribution (pips_hip_batch_set_schur_mode: 0 auto, 1 augmented factorisation,
+   // 2 blocked solves - the reference's SC_COMPUTE_BLOCKWISE; with the sparse root packed by block-local column)
+   if (knobs.schur_mode) {
+      const int mode = atoi(knobs.schur_mode);
+      if (mode < 0 || mode > 2) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: PIPS_IPM_SCHUR_MODE=%s (0 auto, 1 augmented, 2 blocked solves)", knobs.schur_mode);
+      TRY(pips_hip_batch_set_schur_mode(p->batch, mode));
+   }
+   TRY(pips_hip_batch_analyze(p->batch, 16));
+   for (int i = 0; i < L.N; ++i) TRY(pips_hip_batch_set_values(p->batch, i, L.leaf[i].kvals.data()));
+   return pips_hip_batch_set_refinement_backward_error(p->batch, 2, 1e-15);   // PARDISO iparm[7]=2 semantics
+}
+
+// the KKT system of either root kind, with the root's Hessian, stream and eliminated inequality rows
+int make_kkt(Ipm* p, const IpmLayout& L, const IpmKnobs& knobs) {
+   auto rp = [](const View& m) { return present(m) ? m.rp : nullptr; };
+   const View &A0 = L.A0, &F0 = L.F0, &G0 = L.G0;
+   if (knobs.sparse_root)
+      TRY(pips_hip_kkt_create_sparse(&p->kkt, p->batch, L.n0, L.my0, L.myl, L.e_mzl, rp(A0), A0.ci, A0.v, rp(F0), F0.ci, F0.v, rp(G0), G0.ci, G0.v, 0,
+                                     nullptr, nullptr, p->comm, p->rank, p->n_ranks));
+   else
+      TRY(pips_hip_kkt_create(&p->kkt, p->batch, L.n0, L.my0, L.myl, L.e_mzl, rp(A0), A0.ci, A0.v, rp(F0), F0.ci, F0.v, rp(G0), G0.ci, G0.v, p->comm,
+                              p->rank, p->n_ranks));
+   // Q0 in the x0 block of the Schur complement (sLinsysRootAug.C:234-261), on either root kind; several ranks: every rank, after the reduction
+   if (L.hq[0].have) TRY(pips_hip_kkt_set_root_hessian(p->kkt, L.hq[0].rp.data(), L.hq[0].ci.data(), L.hq[0].v.data()));
+   // factorize() asks for every inertia right after the factorisation (the inertia loop): nothing would run beside a root on its own stream
+   TRY(pips_hip_kkt_set_root_stream(p->kkt, 0));
+   if (L.e_mz0 > 0) TRY(pips_hip_kkt_set_root_inequalities(p->kkt, L.e_mz0, L.C0.rp, L.C0.ci, L.C0.v));
    return PIPS_OK;
 }
 
-int build(Ipm* p, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL, const double* dlow,
-          const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device) {
-   const pips_ipm_block& root = blocks[0];
-   const int N = n_blocks - 1;
-   p->N = N; p->n0 = root.n; p->my0 = root.my; p->mz0 = root.mz; p->myl = myl; p->mzl = mzl; p->dual_reg = dual_reg;
-   const int n0 = p->n0, my0 = p->my0, mz0 = p->mz0;
-   p->ry = my0 + myl; p->rzr = mz0 + mzl;
-   std::vector<int> xoff(N + 2, 0), yoff(N + 2, 0), zoff(N + 2, 0);
-   std::vector<long long> koff(N + 2, 0);
-   xoff[1] = n0; yoff[1] = p->ry; zoff[1] = p->rzr;
-   for (int i = 1; i <= N; ++i) {
-      const pips_ipm_block& b = blocks[i];
-      if (b.n < 0 || b.my < 0 || b.mz < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: negative block dimension");
-      xoff[i + 1] = xoff[i] + b.n; yoff[i + 1] = yoff[i] + b.my; zoff[i + 1] = zoff[i] + b.mz;
-      koff[i + 1] = koff[i] + b.n + b.my + b.mz;
-   }
-   p->nx = xoff[N + 1]; p->my = yoff[N + 1]; p->mz = zoff[N + 1]; p->nleaf = koff[N + 1];
-   const int nx = p->nx, my = p->my, mz = p->mz;
-   p->ncp = 2LL * mz + 2LL * nx; p->nxyz = (long long)nx + my + mz;
-   p->NP = nx + mz + p->ncp; p->ND = my + mz + p->ncp;
-   p->lay = Lay{nx, my, mz, p->ncp};
-   std::vector<LowerQ> hq(n_blocks);
-   for (int i = 0; Q && i < n_blocks; ++i) {
-      if (int rcq = check_hessian(i, blocks[i].n, Q[i], hq[i])) return rcq;
-      p->has_q = p->has_q || hq[i].have;
-   }
-   // Root inequality rows C0 x0 - s = ...: the reference eliminates them from the root system (-C0^T Omega^-1 C0 on the x0 block,
-   // sLinsysRootAug.C:1276-1294) and leaves the rest to dsytrf's Bunch-Kaufman pivoting.  So does the harness now that the dense root
-   // pivots (k_tile_diag_bk; pips_hip_kkt_set_root_inequalities switches it on): an active row has Omega^-1 ~ 1e14, the x0 block is
-   // then a huge low-rank matrix plus an O(1) rest and a static pivot order reports the cancelled pivots as perturbed at every
-   // regularisation (round 2: 2 % of the seeded general LPs ended with status 3 that way, which is why the rows were then kept in
-   // the root system as rows of the linking-inequality kind - diagonal nOmegaInv, no cancellation).  That formulation remains for the
-   // sparse root, whose factorisation is the leaf engine's (static order), and under PIPS_IPM_ROOT_INEQ_ELIMINATE=0.
-   const bool sparse_root_req = getenv("PIPS_IPM_SPARSE_ROOT") && atoi(getenv("PIPS_IPM_SPARSE_ROOT")) != 0;
-   const bool eliminate_z0 = getenv("PIPS_IPM_ROOT_INEQ_ELIMINATE") ? atoi(getenv("PIPS_IPM_ROOT_INEQ_ELIMINATE")) != 0 : !sparse_root_req;
-   p->e_mz0 = eliminate_z0 ? mz0 : 0;
-   p->e_mzl = eliminate_z0 ? mzl : mz0 + mzl;
-   const int e_mz0 = p->e_mz0, e_mzl = p->e_mzl;
-   const int S = n0 + my0 + myl + e_mzl;
-   p->S = S;
-   int rc = pips_hip_batch_create(&p->batch, N, S, device, nullptr);
-   if (rc) return rc;
-   // ---- rows of J = [A; C]: y rows [y0 | ylink | blocks], z rows [z0 | zlink | blocks]
-   std::vector<std::vector<std::pair<int, double>>> rows((size_t)my + mz);
-   double dn = 0.0;
-   auto add_rows = [&](const View& m, int row0, int col0) {
-      if (!present(m)) return;
-      for (int r = 0; r < m.rows; ++r)
-         for (int q = m.rp[r]; q < m.rp[r + 1]; ++q) {
-            rows[(size_t)row0 + r].push_back({col0 + m.ci[q], m.v[q]});
-            dn = std::max(dn, std::fabs(m.v[q]));
-         }
-   };
-   auto norm_only = [&](const View& m) {
-      if (!present(m)) return;
-      for (int q = m.rp[0]; q < m.rp[m.rows]; ++q) dn = std::max(dn, std::fabs(m.v[q]));
-   };
-   // root matrices enter the local J on rank 0 only: replicated rows are summed over the ranks
-   if (p->rank == 0) {
-      add_rows(view(root.A), 0, 0);                 // A0
-      add_rows(view(root.BL), my0, 0);              // F0
-      add_rows(view(root.C), my, 0);                // C0
-      add_rows(view(root.DL), my + mz0, 0);         // G0
-   } else { norm_only(view(root.A)); norm_only(view(root.BL)); norm_only(view(root.C)); norm_only(view(root.DL)); }
-   std::vector<std::vector<double>> kvals(N);
-   for (int i = 1; i <= N; ++i) {
-      const pips_ipm_block& b = blocks[i];
-      const View A = view(b.A), B = view(b.B), Cm = view(b.C), D = view(b.D), BL = view(b.BL), DL = view(b.DL);
-      if (b.my > 0 && !present(B)) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: block %d has equality rows but no B matrix", i);
-      add_rows(A, yoff[i], 0);
-      add_rows(B, yoff[i], xoff[i]);
-      add_rows(Cm, my + zoff[i], 0);
-      add_rows(D, my + zoff[i], xoff[i]);
-      add_rows(BL, my0, xoff[i]);
-      add_rows(DL, my + mz0, xoff[i]);
-      // K_i pattern / values and border for the engine
-      const int nxi = b.n, myi = b.my, mzi = b.mz, nk = nxi + myi + mzi;
-      std::vector<int> empty_rp_y(myi + 1, 0), empty_rp_z(mzi + 1, 0);
-      const int* Brp = present(B) ? B.rp : empty_rp_y.data();
-      const int* Drp = present(D) ? D.rp : empty_rp_z.data();
-      std::vector<int> Krp(nk + 1), dpos(nk);
-      // Q_i: its off-diagonal entries are constant values of K_i; the diagonal is overwritten at every factorisation (k_leaf_diag adds qdiag)
-      const LowerQ& qi = hq[i];
-      const int* Qrp = qi.have ? qi.rp.data() : nullptr;
-      rc = pips_kkt_leaf_assemble(nxi, myi, mzi, Qrp, qi.ci.data(), qi.v.data(), Brp, B.ci, B.v, Drp, D.ci, D.v, Krp.data(), nullptr, nullptr, nullptr);
-      if (rc) return rc;
-      std::vector<int> Kci(Krp[nk]);
-      kvals[i - 1].assign(Krp[nk], 0.0);
-      rc = pips_kkt_leaf_assemble(nxi, myi, mzi, Qrp, qi.ci.data(), qi.v.data(), Brp, B.ci, B.v, Drp, D.ci, D.v, Krp.data(), Kci.data(), kvals[i - 1].data(), dpos.data());
-      if (rc) return rc;
-      std::vector<int> Brd(S + 1);
-      auto P3 = [](const View& m) { return m; };
-      const View a_ = P3(A), c_ = P3(Cm), f_ = P3(BL);
-      View g_ = P3(DL);
-      std::vector<int> g_rp;
-      if (e_mzl != mzl && present(g_)) {   // root inequality rows ride among the linking inequalities: no leaf part
-         g_rp.assign((size_t)e_mzl + 1, 0);
-         for (int r = 0; r <= mzl; ++r) g_rp[(size_t)(e_mzl - mzl) + r] = g_.rp[r] - g_.rp[0];
-         g_.ci += g_.rp[0]; g_.v += g_.rp[0];
-         g_.rp = g_rp.data();
-         g_.rows = e_mzl;
-      }
-      rc = pips_border_assemble(nxi, myi, mzi, n0, my0, myl, e_mzl, nullptr, nullptr, nullptr, present(a_) ? a_.rp : nullptr, a_.ci, a_.v,
-                                present(c_) ? c_.rp : nullptr, c_.ci, c_.v, present(f_) ? f_.rp : nullptr, f_.ci, f_.v,
-                                present(g_) ? g_.rp : nullptr, g_.ci, g_.v, Brd.data(), nullptr, nullptr);
-      if (rc) return rc;
-      std::vector<int> Bci(Brd[S]);
-      std::vector<double> Bv(Brd[S]);
-      rc = pips_border_assemble(nxi, myi, mzi, n0, my0, myl, e_mzl, nullptr, nullptr, nullptr, present(a_) ? a_.rp : nullptr, a_.ci, a_.v,
-                                present(c_) ? c_.rp : nullptr, c_.ci, c_.v, present(f_) ? f_.rp : nullptr, f_.ci, f_.v,
-                                present(g_) ? g_.rp : nullptr, g_.ci, g_.v, Brd.data(), Bci.data(), Bv.data());
-      if (rc) return rc;
-      rc = pips_hip_batch_set_block(p->batch, i - 1, nk, nxi, Krp.data(), Kci.data(), Brd.data(), Bci.data(), Bv.data());
-      if (rc) return rc;
-   }
-   // ---- vectors in the flat layout
-   std::vector<double> hc(nx, 0.0), hb(my, 0.0), hM(p->ncp, 0.0), hBd(p->ncp, 0.0);
-   auto put = [&](const double* src, int n, double* dst) { if (src) for (int k = 0; k < n; ++k) dst[k] = src[k]; };
-   const long long oT = 0, oU = mz, oV = 2LL * mz, oW = 2LL * mz + nx;
-   for (int i = 0; i <= N; ++i) {
-      const pips_ipm_block& b = blocks[i];
-      const int x0_ = i == 0 ? 0 : xoff[i], y0_ = i == 0 ? 0 : yoff[i], z0_ = i == 0 ? 0 : zoff[i];
-      if (b.n > 0 && (!b.c || !b.ixlow || !b.ixupp || !b.xlow || !b.xupp)) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: block %d lacks c / bounds", i);
-      put(b.c, b.n, hc.data() + x0_);
-      put(b.b, b.my, hb.data() + y0_);
-      put(b.ixlow, b.n, hM.data() + oV + x0_); put(b.ixupp, b.n, hM.data() + oW + x0_);
-      put(b.xlow, b.n, hBd.data() + oV + x0_); put(b.xupp, b.n, hBd.data() + oW + x0_);
-      put(b.iclow, b.mz, hM.data() + oT + z0_); put(b.icupp, b.mz, hM.data() + oU + z0_);
-      put(b.clow, b.mz, hBd.data() + oT + z0_); put(b.cupp, b.mz, hBd.data() + oU + z0_);
-   }
-   put(bL, myl, hb.data() + my0);
-   put(idlow, mzl, hM.data() + oT + mz0); put(idupp, mzl, hM.data() + oU + mz0);
-   put(dlow, mzl, hBd.data() + oT + mz0); put(dupp, mzl, hBd.data() + oU + mz0);
-   for (long long k = 0; k < p->ncp; ++k) {
-      if (hM[k] != 0.0 && hM[k] != 1.0) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: bound indicators must be 0 or 1");
-      hBd[k] *= hM[k];   // matchesNonZeroPattern (Problem.cpp:69-79)
-      dn = std::max(dn, std::fabs(hBd[k]));
-   }
-   for (const LowerQ& q : hq)
-      for (double v : q.v) dn = std::max(dn, std::fabs(v));   // the data norm includes ||Q|| (Problem.cpp:81)
-   for (double v : hc) dn = std::max(dn, std::fabs(v));
-   for (double v : hb) dn = std::max(dn, std::fabs(v));
-   p->dnorm = dn > 0 ? dn : 1.0;
-   // weights that count replicated root entries once (iAmSpecial, DistributedVector.C:1293-1303)
-   const double wroot = p->rank == 0 ? 1.0 : 0.0;
-   std::vector<double> hwG(p->ncp, 1.0), hwGs(p->ncp, 1.0), hwXYZ(p->nxyz, 1.0);
-   for (int k = 0; k < p->rzr; ++k) hwG[oT + k] = hwG[oU + k] = wroot;
-   for (int k = 0; k < n0; ++k) hwG[oV + k] = hwG[oW + k] = wroot;
-   for (long long k = 0; k < p->ncp; ++k) hwGs[k] = hwG[k] * ((k >= oU && k < oV) || k >= oW ? -1.0 : 1.0);
-   for (int k = 0; k < n0; ++k) hwXYZ[k] = wroot;
-   for (int k = 0; k < p->ry; ++k) hwXYZ[(size_t)nx + k] = wroot;
-   for (int k = 0; k < p->rzr; ++k) hwXYZ[(size_t)nx + my + k] = wroot;
-   double pairs = 0.0;
-   for (long long k = 0; k < p->ncp; ++k) pairs += hwG[k] * hM[k];
-   // ---- CSR of J and J^T
-   HostCsr hj;
-   rows_to_csr(rows, nx, hj);
-   // ---- engine: analyze, values, root system
-   const bool sparse_root = getenv("PIPS_IPM_SPARSE_ROOT") && atoi(getenv("PIPS_IPM_SPARSE_ROOT")) != 0;
-   if (sparse_root && p->n_ranks > 1)
-      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: the sparse root needs the border column sets of all blocks on every rank (pips_hip_kkt_create_sparse); "
-                              "the harness passes only its own - use the dense root with several ranks");
-   if (sparse_root && (rc = pips_hip_batch_set_schur_mode(p->batch, 1))) return rc;   // (the sparse root's default where PIPS_IPM_SCHUR_MODE is unset)
-   // PIPS_IPM_SCHUR_MODE: how the leaves form their Schur contribution (pips_hip_batch_set_schur_mode: 0 auto, 1 augmented factorisation,
-   // 2 blocked solves - the reference's SC_COMPUTE_BLOCKWISE; with the sparse root packed by block-local column); unset: the batch's
-   // default, mode 1 with the sparse root
-   if (const char* sm = getenv("PIPS_IPM_SCHUR_MODE")) {
-      const int mode = atoi(sm);
-      if (mode < 0 || mode > 2) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create: PIPS_IPM_SCHUR_MODE=%s (0 auto, 1 augmented, 2 blocked solves)", sm);
-      if ((rc = pips_hip_batch_set_schur_mode(p->batch, mode))) return rc;
-   }
-   if ((rc = pips_hip_batch_analyze(p->batch, 16))) return rc;
-   for (int i = 0; i < N; ++i)
-      if ((rc = pips_hip_batch_set_values(p->batch, i, kvals[i].data()))) return rc;
-   if ((rc = pips_hip_batch_set_refinement_backward_error(p->batch, 2, 1e-15))) return rc;   // PARDISO iparm[7]=2 semantics
-   const View A0 = view(root.A), F0 = view(root.BL), C0 = view(root.C);
-   View G0 = view(root.DL);
-   std::vector<int> g0_rp, g0_ci;
-   std::vector<double> g0_v;
-   if (e_mzl != mzl) {   // G0' = [C0; G0]
-      g0_rp.assign(1, 0);
-      const View G0in = G0;
-      for (const View* m : {&C0, &G0in}) {
-         const int nr = m == &C0 ? mz0 : mzl;
-         for (int r = 0; r < nr; ++r) {
-            if (present(*m))
-               for (int q = m->rp[r]; q < m->rp[r + 1]; ++q) { g0_ci.push_back(m->ci[q]); g0_v.push_back(m->v[q]); }
-            g0_rp.push_back((int)g0_ci.size());
-         }
-      }
-      g0_ci.push_back(0); g0_v.push_back(0.0);   // never empty arrays
-      G0.rows = e_mzl; G0.cols = n0; G0.rp = g0_rp.data(); G0.ci = g0_ci.data(); G0.v = g0_v.data();
-   }
-   auto rp = [](const View& m) { return present(m) ? m.rp : nullptr; };
-   if (sparse_root)
-      rc = pips_hip_kkt_create_sparse(&p->kkt, p->batch, n0, my0, myl, e_mzl, rp(A0), A0.ci, A0.v, rp(F0), F0.ci, F0.v, rp(G0), G0.ci, G0.v, 0, nullptr,
-                                      nullptr, p->comm, p->rank, p->n_ranks);
-   else
-      rc = pips_hip_kkt_create(&p->kkt, p->batch, n0, my0, myl, e_mzl, rp(A0), A0.ci, A0.v, rp(F0), F0.ci, F0.v, rp(G0), G0.ci, G0.v, p->comm, p->rank,
-                               p->n_ranks);
-   if (rc) return rc;
-   // Q0 in the x0 block of the Schur complement (sLinsysRootAug.C:234-261), on either root kind; several ranks: every rank, after the reduction
-   if (hq[0].have && (rc = pips_hip_kkt_set_root_hessian(p->kkt, hq[0].rp.data(), hq[0].ci.data(), hq[0].v.data()))) return rc;
-   // factorize() asks for every inertia right after the factorisation (the inertia loop): nothing would run beside a root on its own stream
-   if ((rc = pips_hip_kkt_set_root_stream(p->kkt, 0))) return rc;
+// data norms, pair count and the has-Q flag over the ranks
+int exchange(Ipm* p, const IpmLayout& L) {
    HIP_TRYH(hipGetDevice(&p->device));
-   if (!p->d_red && (rc = p->alloc(&p->d_red, 64 * (long long)p->n_ranks))) return rc;
+   if (!p->d_red) TRY(p->alloc(&p->d_red, 64 * (long long)p->n_ranks));
+   p->dnorm = L.norm > 0 ? L.norm : 1.0;
+   p->n_pairs = L.pairs;
    if (p->scaled) p->dnorm_orig = p->dnorm_orig > 0 ? p->dnorm_orig : 1.0;
    if (p->n_ranks > 1) {
       // scaled: the original data norm travels too.  Last slot: does any rank hold a Hessian?  The ranks must agree on it - it decides the
       // number of terms in the fused reductions, which are collectives, and the step-length rule of the replicated iterate
       const int ns = p->n_ranks + 2 + (p->scaled ? p->n_ranks : 0);
       std::vector<double> slots(ns, 0.0);
-      slots[p->rank] = p->dnorm; slots[p->n_ranks] = pairs;
+      slots[p->rank] = p->dnorm; slots[p->n_ranks] = L.pairs;
       slots[ns - 1] = p->has_q ? 1.0 : 0.0;
       if (p->scaled) slots[p->n_ranks + 1 + p->rank] = p->dnorm_orig;
-      if ((rc = p->reduce_host(slots.data(), ns))) return rc;
+      TRY(p->reduce_host(slots.data(), ns));
       for (int r = 0; r < p->n_ranks; ++r) p->dnorm = std::max(p->dnorm, slots[r]);
       if (p->scaled)
          for (int r = 0; r < p->n_ranks; ++r) p->dnorm_orig = std::max(p->dnorm_orig, slots[p->n_ranks + 1 + r]);
-      pairs = slots[p->n_ranks];
+      p->n_pairs = slots[p->n_ranks];
       p->has_q = slots[ns - 1] != 0.0;   // a rank whose own blocks have none then holds an empty Q, zero qdiag and qx: one path on all ranks
    }
    if (!p->scaled) p->dnorm_orig = p->dnorm;
-   p->n_pairs = pairs;
-   // ---- maps: KKT right-hand sides <- [x|y|z], leaf diagonal codes
-   {
-      std::vector<long long> pack;
-      pack.reserve((size_t)S + e_mz0 + p->nleaf);
-      for (int k = 0; k < n0; ++k) pack.push_back(k);
-      for (int k = 0; k < my0; ++k) pack.push_back((long long)nx + k);
-      for (int k = 0; k < e_mz0; ++k) pack.push_back((long long)nx + my + k);
-      for (int k = 0; k < myl; ++k) pack.push_back((long long)nx + my0 + k);
-      for (int k = 0; k < e_mzl; ++k) pack.push_back((long long)nx + my + e_mz0 + k);   // [z0 | zlink] is contiguous in the harness' z order
-      std::vector<long long> code;
-      code.reserve(p->nleaf);
-      for (int i = 1; i <= N; ++i) {
-         for (int k = xoff[i]; k < xoff[i + 1]; ++k) { pack.push_back(k); code.push_back(k); }
-         for (int k = yoff[i]; k < yoff[i + 1]; ++k) { pack.push_back((long long)nx + k); code.push_back(-1); }
-         for (int k = zoff[i]; k < zoff[i + 1]; ++k) { pack.push_back((long long)nx + my + k); code.push_back(-2 - (long long)k); }
-      }
-      p->npack = (long long)pack.size();
-      if ((rc = p->up(&p->d_pack, pack)) || (rc = p->up(&p->d_code, code))) return rc;
-   }
-   if (e_mz0 > 0) {
-      if ((rc = pips_hip_kkt_set_root_inequalities(p->kkt, e_mz0, C0.rp, C0.ci, C0.v))) return rc;
-   }
-   if (p->has_q) {   // device copy of Q: both triangles over the flat x order, expanded once; its diagonal; the product vector
-      std::vector<std::vector<std::pair<int, double>>> qrows((size_t)nx);
-      std::vector<double> hqd((size_t)nx, 0.0);
-      for (int i = 0; i <= N; ++i) {
-         if (!hq[i].have) continue;
-         const int o = i == 0 ? 0 : xoff[i];
-         for (int r = 0; r < blocks[i].n; ++r)
-            for (int q = hq[i].rp[r]; q < hq[i].rp[r + 1]; ++q) {
-               const int c = hq[i].ci[q];
-               qrows[(size_t)o + r].push_back({o + c, hq[i].v[q]});
-               if (c != r) qrows[(size_t)o + c].push_back({o + r, hq[i].v[q]});
-               else hqd[(size_t)o + r] = hq[i].v[q];
-            }
-      }
-      std::vector<int> qrp((size_t)nx + 1, 0), qci, qlong;
-      std::vector<double> qv;
-      for (int r = 0; r < nx; ++r) {
-         std::sort(qrows[r].begin(), qrows[r].end());
-         for (auto& e : qrows[r]) { qci.push_back(e.first); qv.push_back(e.second); }
-         qrp[(size_t)r + 1] = (int)qci.size();
-         if (qrows[r].size() > (size_t)CSR_LONG_ROW) qlong.push_back(r);
-      }
-      p->Q_nnz = (long long)qci.size();
-      p->nQ_long = (int)qlong.size();
-      qci.push_back(0); qv.push_back(0.0); qlong.push_back(0);
-      if ((rc = p->up(&p->Q_rp, qrp)) || (rc = p->up(&p->Q_ci, qci)) || (rc = p->up(&p->Q_v, qv)) || (rc = p->up(&p->Q_long, qlong)) ||
-          (rc = p->up(&p->qdiag, hqd)) || (rc = p->alloc(&p->qx, nx)))
-         return rc;
-   }
-   if (!p->J_v && (rc = p->upload_J(hj))) return rc;   // a scaled handle holds J since prescale()
-   if ((rc = p->up(&p->c, hc)) || (rc = p->up(&p->bA, hb)) || (rc = p->up(&p->M, hM)) || (rc = p->up(&p->Bd, hBd)) || (rc = p->up(&p->wG, hwG)) ||
-       (rc = p->up(&p->wGs, hwGs)) || (rc = p->up(&p->wXYZ, hwXYZ)))
-      return rc;
-   p->wX = p->wXYZ;
-   p->wY = p->wXYZ + nx;
-   // ---- state
-   double* bases[4];
-   for (auto& b : bases)
-      if ((rc = p->alloc(&b, p->NP + p->ND))) return rc;
-   p->it.bind(bases[0], nx, my, mz, p->ncp); p->st.bind(bases[1], nx, my, mz, p->ncp);
-   p->co.bind(bases[2], nx, my, mz, p->ncp); p->best.bind(bases[3], nx, my, mz, p->ncp);
-   if ((rc = p->alloc(&p->rQ, nx)) || (rc = p->alloc(&p->rAC, (long long)my + mz)) || (rc = p->alloc(&p->rz, mz)) || (rc = p->alloc(&p->rG, p->ncp)) ||
-       (rc = p->alloc(&p->rL, p->ncp)) || (rc = p->alloc(&p->rs, mz)) || (rc = p->alloc(&p->dd, nx)) || (rc = p->alloc(&p->ddp, nx)) || (rc = p->alloc(&p->dop_r, nx)) || (rc = p->alloc(&p->dyz_r, (long long)my + mz)) ||
-       (rc = p->alloc(&p->dyz, (long long)my + mz)) || (rc = p->alloc(&p->leaf_diag, p->nleaf)))
-      return rc;
-   double** zs[] = {&p->rhs, &p->sol, &p->w_r, &p->w_r0, &p->w_best, &p->w_v, &p->w_t, &p->w_p, &p->w_dx, &p->w_tmp};
-   for (auto d : zs)
-      if ((rc = p->alloc(d, p->nxyz))) return rc;
-   if ((rc = p->alloc(&p->b0, (long long)S + e_mz0 + p->nleaf))) return rc;   // [b0 | leaves] in one array (one gather / scatter)
-   p->bl = p->b0 + S + e_mz0;
-   if ((rc = p->alloc(&p->d_partial, (long long)RED_MAX * RED_GRID)) || (rc = p->alloc(&p->d_out, 2 * RED_MAX)) || (rc = p->alloc(&p->d_bst, B_SLOTS)))
-      return rc;
-   TRY(p->h_out.alloc(2 * RED_MAX));
-   TRY(p->h_bst.alloc(B_SLOTS));
-   TRY(p->d_pred.alloc_zero(P_COUNT));
-   if (e_mz0 > 0 && ((rc = p->alloc(&p->zd0, e_mz0)) || (rc = pips_hip_kkt_set_zdiag0_dev(p->kkt, p->zd0)))) return rc;   // nOmegaInv of the root rows, regularised
+   return PIPS_OK;
+}
+
+int build(Ipm* p, const IpmInput& in, const IpmKnobs& knobs, int device) {
+   IpmLayout L;
+   TRY(ipm_layout(in, p->rank, knobs.eliminate_z0, !p->J_v, L));   // (a scaled handle holds J since prescale())
+   p->set_dims(L);
+   p->has_q = L.has_q;
+   TRY(make_batch(p, L, knobs, device));
+   TRY(make_kkt(p, L, knobs));
+   TRY(exchange(p, L));
+   if (p->has_q && !L.has_q) ipm_flat_hessian(in, L);
+   TRY(p->upload(L));
+   return p->alloc_state();
+}
+
+// who: the entry point the "bad arguments" message names
+int create(void** handle, const IpmInput& in, double dual_reg, int device, void* comm, int rank, int n_ranks, int scaler, const char* who) {
+   if (!handle || (n_ranks > 1 && !comm)) PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments", who);
+   TRY(check_ipm_input(in, rank, n_ranks, who));
+   auto p = std::make_unique<Ipm>();
+   p->comm = comm; p->rank = rank; p->n_ranks = n_ranks; p->dual_reg = dual_reg;
+   const IpmKnobs knobs = read_ipm_knobs();
+   ScaledData sd;
+   if (scaler != PIPS_SCALER_NONE) TRY(prescale(p.get(), in, knobs, device, scaler, sd));
+   TRY(build(p.get(), p->scaled ? sd.in : in, knobs, device));
+   *handle = p.release();
    return PIPS_OK;
 }
 
@@ -2154,21 +1847,8 @@ int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_b
    if (scaler < PIPS_SCALER_NONE || scaler > PIPS_SCALER_CURTIS_REID)
       PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general_scaled: scaler %d is not supported (0 none, 1 equilibrium, 2 geometric mean, "
                               "3 geometric mean + equilibrium)", scaler);
-   if (!handle || n_blocks < 2 || !blocks || myl < 0 || mzl < 0 || n_ranks < 1 || rank < 0 || rank >= n_ranks || (n_ranks > 1 && !comm) ||
-       (myl > 0 && !bL) || (mzl > 0 && (!dlow || !dupp || !idlow || !idupp)))
-      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general: bad arguments");
-   auto p = std::make_unique<Ipm>();
-   p->comm = comm; p->rank = rank; p->n_ranks = n_ranks;
-   int rc;
-   ScaledData sd;
-   if (scaler != PIPS_SCALER_NONE) {
-      if ((rc = prescale(p.get(), n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, device, scaler, sd))) return rc;
-      if (p->scaled) { blocks = sd.blk.data(); bL = sd.bL; dlow = sd.dlow; dupp = sd.dupp; }
-   }
-   rc = build(p.get(), n_blocks, blocks, nullptr, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device);
-   if (rc) return rc;
-   *handle = p.release();
-   return PIPS_OK;
+   const IpmInput in{n_blocks, blocks, nullptr, myl, mzl, bL, dlow, dupp, idlow, idupp};
+   return create(handle, in, dual_reg, device, comm, rank, n_ranks, scaler, "pips_ipm_create_general");
 }
 
 // The convex QP  min c^T x + 1/2 x^T Q x  over the same constraints, Q block-diagonal over the root and the blocks.  Without any
@@ -2176,15 +1856,8 @@ int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_b
 int pips_ipm_create_qp(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL,
                        const double* dlow, const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device, void* comm,
                        int rank, int n_ranks) {
-   if (!handle || n_blocks < 2 || !blocks || myl < 0 || mzl < 0 || n_ranks < 1 || rank < 0 || rank >= n_ranks || (n_ranks > 1 && !comm) ||
-       (myl > 0 && !bL) || (mzl > 0 && (!dlow || !dupp || !idlow || !idupp)))
-      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp: bad arguments");
-   auto p = std::make_unique<Ipm>();
-   p->comm = comm; p->rank = rank; p->n_ranks = n_ranks;
-   const int rc = build(p.get(), n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device);
-   if (rc) return rc;
-   *handle = p.release();
-   return PIPS_OK;
+   const IpmInput in{n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp};
+   return create(handle, in, dual_reg, device, comm, rank, n_ranks, PIPS_SCALER_NONE, "pips_ipm_create_qp");
 }
 
 int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host) {

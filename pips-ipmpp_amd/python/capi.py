@@ -54,7 +54,7 @@ SYMBOLS = [
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
     "pips_hip_ldl_inertia_batch",
     "pips_hip_dense_ldl_create", "pips_hip_dense_ldl_factor", "pips_hip_dense_ldl_factor_dev", "pips_hip_dense_ldl_solve",
-    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
+    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_ipm_layout_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
     "pips_hip_batch_create", "pips_hip_batch_set_block", "pips_hip_batch_set_options", "pips_hip_batch_set_schur_mode", "pips_hip_batch_set_deterministic", "pips_hip_batch_get_schur_mode", "pips_hip_batch_add_regularization", "pips_hip_batch_set_refinement",
     "pips_hip_batch_last_refinement_steps", "pips_hip_batch_set_refinement_backward_error",
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
@@ -1076,6 +1076,39 @@ class _IpmBlock(C.Structure):
                [(k, C.c_void_p) for k in ("c", "xlow", "xupp", "ixlow", "ixupp", "b", "clow", "cupp", "iclow", "icupp")]
 
 
+def _ipm_input(blocks, hessians):
+    """The reader's block dicts (and Hessians) as the C structs of the creation entry points: (what must stay alive, blocks, Q or None,
+    [myl, mzl, bL, dlow, dupp, idlow, idupp])."""
+    keep = []
+
+    def arr(a, dtype=np.float64):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        keep.append(a)
+        return a.ctypes.data_as(C.c_void_p).value if a.size else None
+
+    def view(m):
+        if m is None:
+            return _CsrView(0, 0, None, None, None)
+        if isinstance(m, Csr):
+            m = dict(rows=m.nrows, cols=m.ncols, rowptr=m.rowptr, colidx=m.colidx, val=m.val)
+        rp = np.ascontiguousarray(m["rowptr"], dtype=np.int32)
+        keep.append(rp)
+        return _CsrView(int(m["rows"]), int(m["cols"]), rp.ctypes.data_as(C.c_void_p).value, arr(m["colidx"], np.int32), arr(m["val"]))
+
+    root = blocks[0]
+    cb = (_IpmBlock * len(blocks))()
+    for k, b in enumerate(blocks):
+        n = int(b["n0"] if k == 0 else b["ni"])
+        cb[k].n, cb[k].my, cb[k].mz = n, int(b["mA"]), int(b["mC"])
+        cb[k].A, cb[k].C, cb[k].BL, cb[k].DL = view(b["A"]), view(b["C"]), view(b["BL"]), view(b["DL"])
+        cb[k].B, cb[k].D = (view(None), view(None)) if k == 0 else (view(b["B"]), view(b["D"]))
+        for f in ("c", "xlow", "xupp", "ixlow", "ixupp", "b", "clow", "cupp", "iclow", "icupp"):
+            setattr(cb[k], f, arr(b[f]))
+    cq = (_CsrView * len(blocks))(*[view(h) for h in hessians]) if hessians is not None else None
+    tail = [C.c_int(int(root["mBL"])), C.c_int(int(root["mDL"]))] + [C.c_void_p(arr(root[f])) for f in ("bL", "dlow", "dupp", "idlow", "idupp")]
+    return keep, cb, cq, tail
+
+
 class GeneralIpmSolver(IpmSolver):
     """The device IPM on the reference's full problem class (bounds of either side on variables and rows, inequality rows, root
     and linking rows), fed with the reader's per-block dicts (fields of GMSPIPSBlockData_t as gdx.read_block / gdx_read_block
@@ -1093,42 +1126,14 @@ class GeneralIpmSolver(IpmSolver):
             raise PipsHipError("problem scaling together with Hessians is not supported")
         if hessians is not None and len(hessians) != len(blocks):
             raise PipsHipError(f"hessians has {len(hessians)} entries for {len(blocks)} blocks")
-        keep = []
-
-        def arr(a, dtype=np.float64):
-            a = np.ascontiguousarray(a, dtype=dtype)
-            keep.append(a)
-            return a.ctypes.data_as(C.c_void_p).value if a.size else None
-
-        def view(m):
-            if m is None:
-                return _CsrView(0, 0, None, None, None)
-            if isinstance(m, Csr):
-                m = dict(rows=m.nrows, cols=m.ncols, rowptr=m.rowptr, colidx=m.colidx, val=m.val)
-            rp = np.ascontiguousarray(m["rowptr"], dtype=np.int32)
-            keep.append(rp)
-            return _CsrView(int(m["rows"]), int(m["cols"]), rp.ctypes.data_as(C.c_void_p).value, arr(m["colidx"], np.int32), arr(m["val"]))
-
-        root = blocks[0]
-        myl, mzl = int(root["mBL"]), int(root["mDL"])
-        cb = (_IpmBlock * len(blocks))()
-        for k, b in enumerate(blocks):
-            n = int(b["n0"] if k == 0 else b["ni"])
-            cb[k].n, cb[k].my, cb[k].mz = n, int(b["mA"]), int(b["mC"])
-            cb[k].A, cb[k].C, cb[k].BL, cb[k].DL = view(b["A"]), view(b["C"]), view(b["BL"]), view(b["DL"])
-            cb[k].B, cb[k].D = (view(None), view(None)) if k == 0 else (view(b["B"]), view(b["D"]))
-            for f in ("c", "xlow", "xupp", "ixlow", "ixupp", "b", "clow", "cupp", "iclow", "icupp"):
-                setattr(cb[k], f, arr(b[f]))
+        keep, cb, cq, tail = _ipm_input(blocks, hessians)
         self.n_blocks = len(blocks)
-        self._keep = (keep, cb)
+        self._keep = (keep, cb, cq)
         self._comm = comm
         self._h = C.c_void_p()
-        args = (C.byref(self._h), C.c_int(len(blocks)), cb, C.c_int(myl), C.c_int(mzl), C.c_void_p(arr(root["bL"])), C.c_void_p(arr(root["dlow"])),
-                C.c_void_p(arr(root["dupp"])), C.c_void_p(arr(root["idlow"])), C.c_void_p(arr(root["idupp"])), C.c_double(dual_reg), C.c_int(device),
+        args = (C.byref(self._h), C.c_int(len(blocks)), cb, *tail, C.c_double(dual_reg), C.c_int(device),
                 comm._h if comm is not None else None, C.c_int(rank), C.c_int(n_ranks))
         if hessians is not None:
-            cq = (_CsrView * len(blocks))(*[view(h) for h in hessians])
-            self._keep = (keep, cb, cq)
             _check(lib.pips_ipm_create_qp(*args[:3], cq, *args[3:]), "pips_ipm_create_qp")
         elif scaler is None:
             _check(lib.pips_ipm_create_general(*args), "pips_ipm_create_general")
@@ -1184,6 +1189,37 @@ class GeneralIpmSolver(IpmSolver):
         return dict(col=col, row_eq=req, row_ineq=rin, applied=bool(info[0]), row_ratio_before=info[1], col_ratio_before=info[2],
                     row_ratio_after=info[3], col_ratio_after=info[4], geometric_passes=int(info[5]), geometric_kept=bool(info[6]),
                     host_waits=int(info[7]))
+
+
+IPM_LAYOUT_DIMS = ("N", "n0", "my0", "mz0", "myl", "mzl", "ry", "rzr", "nx", "my", "mz", "ncp", "nxyz", "NP", "ND", "nleaf", "e_mz0", "e_mzl", "S", "has_q")
+# the arrays of pips_ipm_layout_probe in slot order, with their element types (include/pips_hip.h)
+IPM_LAYOUT_ARRAYS = (
+    [(k, np.int32) for k in ("xoff", "yoff", "zoff")] + [("koff", np.int64)] +
+    [("J_rp", np.int32), ("J_ci", np.int32), ("J_v", np.float64), ("Jt_rp", np.int32), ("Jt_ci", np.int32), ("Jt_v", np.float64),
+     ("J_long", np.int32), ("Jt_long", np.int32)] +
+    [(k, np.float64) for k in ("c", "b", "M", "Bd", "wG", "wGs", "wXYZ")] + [("pack", np.int64), ("code", np.int64)] +
+    [("Krp", np.int32), ("Kci", np.int32), ("kvals", np.float64), ("Brd", np.int32), ("Bci", np.int32), ("Bv", np.float64)] +
+    [(m + s, t) for m in ("A0", "F0", "C0", "G0") for s, t in (("_rp", np.int32), ("_ci", np.int32), ("_v", np.float64))] +
+    [("hq_have", np.int32), ("hq_rp", np.int32), ("hq_ci", np.int32), ("hq_v", np.float64)] +
+    [("Q_rp", np.int32), ("Q_ci", np.int32), ("Q_v", np.float64), ("qdiag", np.float64), ("Q_long", np.int32)])
+
+
+def ipm_layout_probe(blocks, hessians=None, rank=0, n_ranks=1, eliminate_z0=True, col=None, row=None):
+    """The host layout pass of an IPM handle's creation, without a device (pips_ipm_layout_probe): a dict of the dimensions
+    (IPM_LAYOUT_DIMS), `pairs`, `norm` and the arrays (IPM_LAYOUT_ARRAYS; per-leaf and per-block arrays back to back).  blocks /
+    hessians as GeneralIpmSolver takes them; col, row = [row_eq | row_ineq]: factors the data is scaled with first."""
+    keep, cb, cq, tail = _ipm_input(blocks, hessians)
+    col, row = (None, None) if col is None else (_f64(col), _f64(row))
+    dims, scal, sizes = (C.c_longlong * len(IPM_LAYOUT_DIMS))(), (C.c_double * 2)(), (C.c_longlong * len(IPM_LAYOUT_ARRAYS))()
+    head = (C.c_int(len(blocks)), cb, cq, *tail, C.c_int(rank), C.c_int(n_ranks), C.c_int(1 if eliminate_z0 else 0), _ptr(col), _ptr(row), dims, scal, sizes)
+    _check(lib.pips_ipm_layout_probe(*head, None), "pips_ipm_layout_probe")
+    arrays = [np.zeros(int(sizes[k]), dtype=t) for k, (_, t) in enumerate(IPM_LAYOUT_ARRAYS)]
+    out = (C.c_void_p * len(arrays))(*[a.ctypes.data_as(C.c_void_p).value if a.size else None for a in arrays])
+    _check(lib.pips_ipm_layout_probe(*head, out), "pips_ipm_layout_probe")
+    res = {k: int(dims[i]) for i, k in enumerate(IPM_LAYOUT_DIMS)}
+    res.update(pairs=float(scal[0]), norm=float(scal[1]))
+    res.update({k: a for (k, _), a in zip(IPM_LAYOUT_ARRAYS, arrays)})
+    return res
 
 
 def gdx_read_block(path, num_blocks, act_block, offset=1):
