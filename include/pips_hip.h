@@ -131,6 +131,10 @@ int pips_hip_dense_ldl_factor_dev(void* handle, const double* A_dev, int lda);
 int pips_hip_dense_ldl_solve(void* handle, int nrhs, double* rhs_inout_host, int ld);
 int pips_hip_dense_ldl_solve_dev(void* handle, double* rhs_inout_dev);
 int pips_hip_dense_ldl_inertia(void* handle, int* pos, int* neg, int* zero);
+/* diagnostics (read-only; tests assert which path ran): what[0]=1 if the last factorisation was the single launch, what[1]=tile columns
+ * of 128, what[2]=ranks the factorisation is distributed over, what[3]=pivoting mode, what[4]=how often Bunch-Kaufman pivoting had to
+ * factorise again under a new order since the handle was created */
+int pips_hip_dense_ldl_info(void* handle, int64_t* what, int n_what);
 void pips_hip_dense_ldl_destroy(void* handle);
 
 /* ---------------------------------------------------------------------------------------------------------------

@@ -29,10 +29,17 @@ _SO = os.path.join(_HERE, "liboracle.so")
 
 
 def build():
-    """gcc -O2 oracle_ldl.c -> liboracle.so (idempotent)."""
+    """gcc -O2 oracle_ldl.c -> liboracle.so (idempotent).  The library appears under its name complete or not at all: the ranks a test
+    spawns may all find it out of date at once, and one that loads it while another's gcc is still writing it reads a truncated file."""
     src = os.path.join(_HERE, "oracle_ldl.c")
     if not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
-        subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-o", _SO, src, "-lm"])
+        tmp = os.path.join(_HERE, f"liboracle.{os.getpid()}.tmp.so")
+        try:
+            subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-o", tmp, src, "-lm"])
+            os.replace(tmp, _SO)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
     return _SO
 
 

@@ -2478,6 +2478,7 @@ struct DenseLdl {
    // (a 454-register diagonal kernel) and the root distributed over ranks keep the launch-per-step driver (tail_factor / factor_distributed);
    // PIPS_HIP_ROOT_LAUNCHES=1 keeps it everywhere (the tests run both).
    bool single_launch = !getenv("PIPS_HIP_ROOT_LAUNCHES");
+   bool last_single = false;       // which driver the last factorisation took (pips_hip_dense_ldl_info)
    DevBuf<double> d_C;             // the accumulating tiles (scratch): L goes to d_R, U to d_U, each written once per launch
    DevBuf<TileTask> d_rtasks;
    int n_rtasks = 0, n_rbulk = 0;
@@ -2866,6 +2867,7 @@ struct DenseLdl {
          HIP_TRY(hipMemsetAsync(d_pert_cnt, 0, sizeof(int), stream));
       }
       const bool single = single_launch && pivoting == 0 && dist_P <= 1;
+      last_single = single;
       if (single) { const int rcs = ensure_single_launch(); if (rcs) return rcs; }
       double* d_work = single ? d_C : d_R;   // where the matrix is accumulated: a scratch copy (single launch) or in place
       hipLaunchKernelGGL(k_copy_lower_to_padded, dim3(grid_for((long long)npad * npad, 256)), dim3(256), 0, stream, A_dev,
@@ -3873,6 +3875,14 @@ int pips_hip_dense_ldl_inertia(void* handle, int* pos, int* neg, int* zero) {
    if (pos) *pos = d->h_inertia[0];
    if (neg) *neg = d->h_inertia[1];
    if (zero) *zero = d->h_inertia[2];
+   return PIPS_OK;
+}
+
+int pips_hip_dense_ldl_info(void* handle, int64_t* what, int n_what) {
+   DenseLdl* d = (DenseLdl*)handle;
+   if (!d || !what || n_what < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_info: bad arguments");
+   const int64_t v[5] = {d->factored && d->last_single ? 1 : 0, d->npad / TILE, d->dist_P, d->pivoting, d->bk_refactorizations};
+   for (int i = 0; i < n_what && i < 5; ++i) what[i] = v[i];
    return PIPS_OK;
 }
 

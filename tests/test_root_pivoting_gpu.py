@@ -1,6 +1,7 @@
 """Dense root with Bunch-Kaufman pivoting inside the diagonal tiles (k_tile_diag_bk) against LAPACK dsytrf / dsytrs, the routine
 behind the reference's DeSymIndefSolver (DeSymIndefSolver.C:56-168): solutions, inertia (2 x 2 blocks counted as :135-160 does:
-one positive and one negative eigenvalue), zero perturbed pivots - on matrices a static pivot order cannot take."""
+one positive and one negative eigenvalue), zero perturbed pivots - on matrices a static pivot order cannot take.
+Accuracy is judged against a long-double reference by a measured margin in tests/test_dense_root_judged_gpu.py."""
 import numpy as np
 import pytest
 import scipy.linalg as sla

@@ -1,6 +1,7 @@
 """The dense root with the static pivot order as ONE dependency-driven launch (csrc/rootkernel.hip.h, csrc/rootplan.cpp) against LAPACK
 dsytrf / dsytrs - the routine DeSymIndefSolver hands the Schur complement to (DeSymIndefSolver.C:56-129) - and against the
-launch-per-step factorisation it replaces (PIPS_HIP_ROOT_LAUNCHES=1)."""
+launch-per-step factorisation it replaces (PIPS_HIP_ROOT_LAUNCHES=1).
+Accuracy is judged against a long-double reference by a measured margin in tests/test_dense_root_judged_gpu.py."""
 import numpy as np
 import pytest
 import scipy.linalg as sla

@@ -354,3 +354,228 @@ def schur_reference(key, finalized=False):
     if (key, finalized) not in _schur_cache:
         _schur_cache[(key, finalized)] = SchurReference(_schur_cache[("problem", key)], finalized)
     return _schur_cache[(key, finalized)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the dense root's solves judged against a long-double reference (tests/test_dense_root_reference_cpu.py, tests/test_dense_root_judged_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------------
+DENSE_ROOT_FAMILIES = {"flat": 0.0, "spread": 2.0}      # the spread of the diagonals in decades: cond about 20, and 1e2 .. 1e3
+DENSE_ROOT_TILE = 128
+
+
+def dense_root_matrix(n, n_primal, seed, spread):
+    """[[H, A^T], [A, -G]] with H = diag(10 ** U(-spread, spread)) + R R^T / r (R n_primal x r standard normal, r = max(1, n_primal // 8)),
+    G = diag(10 ** U(-spread, spread)) and A (n - n_primal) x n_primal standard normal, kept where a uniform draw is below 0.3: quasi-definite,
+    inertia (n_primal, n - n_primal, 0) in the given order."""
+    rng = np.random.default_rng(seed)
+    m, r = n - n_primal, max(1, n_primal // 8)
+    dH = 10.0 ** rng.uniform(-spread, spread, n_primal)
+    R = rng.standard_normal((n_primal, r))
+    H = np.diag(dH) + R @ R.T / r
+    G = np.diag(10.0 ** rng.uniform(-spread, spread, m))
+    A = rng.standard_normal((m, n_primal))
+    A = A * (rng.random((m, n_primal)) < 0.3)
+    return np.block([[H, A.T], [A, -G]])
+
+
+def dense_root_zero_diagonal(n, seed):
+    """N + N^T with its diagonal zeroed (tests/test_root_pivoting_gpu.py): no 1 x 1 pivot exists at the start of any tile"""
+    N = np.random.default_rng(seed).standard_normal((n, n))
+    M = N + N.T
+    np.fill_diagonal(M, 0.0)
+    return M
+
+
+def dense_root_rhs(n, seed):
+    """the right-hand sides, one per row: three standard-normal ones, e_0 and e_{n-1}"""
+    B = np.zeros((5, n))
+    B[:3] = np.random.default_rng(seed).standard_normal((3, n))
+    B[3, 0] = 1.0
+    B[4, n - 1] = 1.0
+    return B
+
+
+def dense_root_with_garbage_above(M, seed):
+    """M's lower triangle under a strict upper triangle of other finite numbers (standard normal, its own seed): what the device is handed,
+    "lower triangle authoritative" being the contract"""
+    n = M.shape[0]
+    return np.tril(M) + np.triu(np.random.default_rng(seed).standard_normal((n, n)), 1)
+
+
+def dense_root_symmetric_from_lower(A):
+    return np.tril(A) + np.tril(A, -1).T
+
+
+def dense_root_ldl_static(S, skip_update_of=None):
+    """Unblocked right-looking LDL^T of the symmetric S in the given order, plain FP64: (L unit lower, d).  skip_update_of = k: the rank-one
+    update of pivot k is left out (a mutant of tests/test_dense_root_reference_cpu.py)."""
+    A = np.array(S, dtype=np.float64)
+    n = A.shape[0]
+    d = np.empty(n)
+    for k in range(n):
+        d[k] = A[k, k]
+        u = A[k + 1:, k].copy()
+        l = u / d[k]
+        if k != skip_update_of:
+            A[k + 1:, k + 1:] -= np.outer(l, u)
+        A[k + 1:, k] = l
+    L = np.tril(A, -1)
+    np.fill_diagonal(L, 1.0)
+    return L, d
+
+
+def dense_root_ldl_solve(L, d, B):
+    """L D L^T x = b for every row b of B by column substitution, plain FP64"""
+    X = np.array(np.atleast_2d(B), dtype=np.float64).T.copy()        # (n, nrhs)
+    n = X.shape[0]
+    for k in range(n - 1):
+        X[k + 1:] -= np.outer(L[k + 1:, k], X[k])
+    X /= d[:, None]
+    for k in range(n - 1, 0, -1):
+        X[:k] -= np.outer(L[k, :k], X[k])
+    return np.ascontiguousarray(X.T)
+
+
+class DenseRootReference:
+    """One symmetric M (its lower triangle counts) and right-hand sides (one per row of B): X_star from LAPACK dsytrf / dsytrs and refinement
+    steps on a long-double x (the residual formed in long double - exactly from the third step on, see _residual_rounded_once - and the correction
+    added in long double) until a correction is below 2^-58 max|x|, rounded to FP64 once; X_lapack, LAPACK's unrefined dsytrs solution - x_ref0 of
+    Bunch-Kaufman pivoting (mode 1); static=True: the unblocked FP64 LDL^T in the given order (L, d) and its solution X_static - x_ref0 of the
+    static order (mode 0).  The predicate is UnrefinedReference's, per right-hand side.  Computed once, read-only."""
+    MAX_STEPS = 5
+
+    def __init__(self, M, B, n_primal=None, static=True):
+        import scipy.linalg as sla
+        self.M = dense_root_symmetric_from_lower(np.asarray(M, dtype=np.float64))
+        self.n, self.n_primal = self.M.shape[0], n_primal
+        self.B = np.ascontiguousarray(np.atleast_2d(B), dtype=np.float64)
+        self._M_ld = self.M.astype(np.longdouble)
+        self.norm_M = float(np.abs(self.M).sum(axis=1).max())
+        ldu, ipiv, info = sla.lapack.dsytrf(np.tril(self.M), lower=1)
+        assert info == 0
+        X0, info = sla.lapack.dsytrs(ldu, ipiv, self.B.T.copy(), lower=1)
+        assert info == 0
+        self.X_lapack = np.ascontiguousarray(X0.T)
+        X = self.X_lapack.astype(np.longdouble)
+        self.refinement_steps, self.converged = 0, False
+        while self.refinement_steps < self.MAX_STEPS and not self.converged:
+            # two steps with the residual accumulated in long double settle all but the worst conditioned case; what they leave takes it exact
+            Rres = (self.B.astype(np.longdouble) - X @ self._M_ld).astype(np.float64) if self.refinement_steps < 2 else self._residual_rounded_once(X)
+            dX, info = sla.lapack.dsytrs(ldu, ipiv, Rres.T.copy(), lower=1)
+            assert info == 0
+            X = X + dX.T.astype(np.longdouble)
+            self.refinement_steps += 1
+            self.converged = bool(np.all(np.abs(dX.T).max(axis=1) <= 2.0 ** -58 * np.abs(X).max(axis=1).astype(np.float64)))
+        self.X_star = X.astype(np.float64)
+        self.xs_norm = np.abs(self.X_star).max(axis=1)
+        self.L = self.d = self.X_static = None
+        x_ref0 = {1: self.X_lapack}
+        if static:
+            self.L, self.d = dense_root_ldl_static(self.M)
+            self.X_static = dense_root_ldl_solve(self.L, self.d, self.B)
+            x_ref0[0] = self.X_static
+        self.eta_ref = {mode: self.backward_errors(x) for mode, x in x_ref0.items()}
+        self.fwd_ref = {mode: np.abs(x - self.X_star).max(axis=1) for mode, x in x_ref0.items()}
+        for a in [self.M, self.B, self.X_lapack, self.X_star, self.xs_norm, self.L, self.d, self.X_static] + list(self.eta_ref.values()) + list(self.fwd_ref.values()):
+            if a is not None:
+                a.setflags(write=False)
+
+    def _residual_rounded_once(self, X):
+        """B - X M of a long-double X, every entry the exact sum rounded to FP64 once.  A residual accumulated in plain long double carries
+        an error of some 2^-64 ||M|| ||x||, and the correction solved from it stalls at cond(M) 2^-64 max|x|: 2^-56 on the all-primal case of
+        the spread family, above the 2^-58 the refinement has to reach.  So the long-double x is split into two doubles, every product
+        into its rounded value and its exact error (Dekker), and each row is summed with math.fsum."""
+        import math
+        hi = X.astype(np.float64)
+        lo = (X - hi.astype(np.longdouble)).astype(np.float64)           # (exact: 64 bits fit into 53 + 53)
+
+        def split(a):
+            c = 134217729.0 * a                                           # 2^27 + 1 (Veltkamp)
+            h = c - (c - a)
+            return h, a - h
+
+        Mh, Ml = split(self.M)
+        out = np.empty(self.B.shape)
+        for i in range(self.B.shape[0]):
+            terms = [self.B[i][None, :]]
+            for x in (hi[i], lo[i]):
+                xh, xl = split(x)
+                P = x[:, None] * self.M                                   # P[j, k] = x_j M[j, k]: column k sums to (x M)_k
+                E = ((xh[:, None] * Mh - P) + xh[:, None] * Ml + xl[:, None] * Mh) + xl[:, None] * Ml
+                terms += [-P, -E]
+            out[i] = [math.fsum(col) for col in np.concatenate(terms, axis=0).T.tolist()]
+        return out
+
+    def backward_errors(self, X):
+        """eta(x) = ||b - M x||inf / (||M||inf ||x||inf + ||b||inf) per right-hand side, the residual formed in long double; anything
+        non-finite has eta = inf"""
+        X = np.atleast_2d(X)
+        with np.errstate(all="ignore"):
+            Rres = self.B.astype(np.longdouble) - X.astype(np.longdouble) @ self._M_ld
+            num = np.abs(Rres).max(axis=1).astype(np.float64)
+            den = self.norm_M * np.abs(X).max(axis=1) + np.abs(self.B).max(axis=1)
+            eta = np.where(num == 0.0, 0.0, num / np.where(den > 0.0, den, 1.0))
+        return np.where(np.isfinite(eta), eta, np.inf)
+
+    def ratios(self, X, mode=0):
+        """(forward, backward) per right-hand side: max|x - x*| / max(max|x_ref0 - x*|, 2^-53 max|x*|) and eta(x) / max(eta(x_ref0), 2^-53)
+        - what the margin M bounds.  mode: the pivoting mode, it selects x_ref0."""
+        X = np.atleast_2d(X)
+        with np.errstate(all="ignore"):
+            err = np.abs(X - self.X_star).max(axis=1)
+            den = np.maximum(self.fwd_ref[mode], UNIT_ROUNDOFF * self.xs_norm)
+            fwd = np.where(err == 0.0, 0.0, err / np.where(den > 0.0, den, 1.0))
+        fwd = np.where(np.isfinite(fwd), fwd, np.inf)
+        return fwd, self.backward_errors(X) / np.maximum(self.eta_ref[mode], UNIT_ROUNDOFF)
+
+    def accepts(self, X, M, mode=0):
+        """the predicate, per right-hand side: forward and backward"""
+        assert M <= UNREFINED_M_CAP
+        fwd, bwd = self.ratios(X, mode)
+        return (fwd <= M) & (bwd <= M)
+
+
+# the cases (n, n_primal, family): the smallest that still select each piece - 128-wide tiles, 32-wide sub-blocks of the blocked diagonal tile,
+# K ranges the plan cuts only from three or four tile columns on.  n_primal = (2 n) // 3, at n = 257 also all dual, the sign boundary on the tile
+# edge, one past it, all primal.
+DENSE_ROOT_SIZES = (1, 31, 32, 33, 127, 128, 129, 257, 385, 513)
+DENSE_ROOT_CASES = [(n, (2 * n) // 3, "flat") for n in DENSE_ROOT_SIZES] + [(n, (2 * n) // 3, "spread") for n in DENSE_ROOT_SIZES if n >= 129] + \
+                   [(257, n_primal, fam) for fam in DENSE_ROOT_FAMILIES for n_primal in (0, 128, 129, 257)]
+DENSE_ROOT_ZERO_DIAGONAL_SIZES = (128, 300)
+
+
+def dense_root_case_id(case):
+    return f"n{case[0]}-p{case[1]}-{case[2]}"
+
+
+def dense_root_case_matrix(case):
+    n, n_primal, family = case
+    if family == "zero_diagonal":
+        return dense_root_zero_diagonal(n, 10 * n + 3), 10 * n + 3
+    seed = 10 * n + {"flat": 1, "spread": 2}[family] + 7000 * (n_primal + 1 if n_primal != (2 * n) // 3 else 0)
+    return dense_root_matrix(n, n_primal, seed, DENSE_ROOT_FAMILIES[family]), seed
+
+
+def dense_root_case_inputs(case):
+    """(M, B, seed of the strict upper triangle the device is handed) of a case"""
+    M, seed = dense_root_case_matrix(case)
+    return M, dense_root_rhs(case[0], seed + 500000), seed + 900000
+
+
+_dense_root_cache = {}
+
+
+def dense_root_reference(case):
+    """The shared DenseRootReference of a case (n, n_primal, family) of DENSE_ROOT_CASES, or (n, None, "zero_diagonal"); .garbage_seed: the seed
+    of the strict upper triangle the device is handed"""
+    if case not in _dense_root_cache:
+        M, B, garbage_seed = dense_root_case_inputs(case)
+        ref = DenseRootReference(M, B, case[1], static=case[2] != "zero_diagonal")
+        ref.garbage_seed = garbage_seed
+        if case[2] == "zero_diagonal":
+            ev = np.linalg.eigvalsh(ref.M)
+            ref.inertia = (int((ev > 0).sum()), int((ev < 0).sum()), 0)
+        else:
+            ref.inertia = (case[1], case[0] - case[1], 0)
+        _dense_root_cache[case] = ref
+    return _dense_root_cache[case]
