@@ -405,6 +405,13 @@ class HipLdlSolver:
         _check(lib.pips_hip_ldl_inertia(self._h, C.byref(p), C.byref(n), C.byref(z)), "pips_hip_ldl_inertia")
         return p.value, n.value, z.value
 
+    def get_perm(self):
+        """perm[k] = the row of K that is eliminated k-th (after analyze() or the first matrixChanged()); symbolic_probe(..., want_perm=True)
+        of the same K and hint returns the same order without a device"""
+        perm = np.zeros(self.n, np.int32)
+        _check(lib.pips_hip_ldl_get_perm(self._h, _ptr(perm)), "pips_hip_ldl_get_perm")
+        return perm
+
     def info(self):
         what = np.zeros(8, np.int64)
         _check(lib.pips_hip_ldl_info(self._h, _ptr(what), C.c_int(8)), "pips_hip_ldl_info")

@@ -10,7 +10,7 @@ import scipy.sparse as sp
 
 import pips_ipmpp_amd as pa
 from oracle import oracle as orc
-from tests.util import hip_lower_as_rowmajor
+from tests.util import PIVOT_THR_REL, PivotRuleReference, hip_lower_as_rowmajor
 
 pytestmark = pytest.mark.gpu
 
@@ -146,8 +146,13 @@ def test_inertia_contract_drives_regularisation_loop():
     bt.analyze(1)
     bt.set_values(0, K.val)
     bt.factor()
-    pos, neg, zero = bt.inertia(0)
-    assert (pos, neg, zero) != (nx, my, 0) and zero >= 1
+    # the first triple is the reference's: the long-double LDL^T in the device's order under the device's rule rejects the later of the two equal
+    # rows and nothing else, with a margin of 64 either way on every decision (tests/util.py: PivotRuleReference)
+    probe = pa.symbolic_probe(K, nx, want_perm=True)
+    ref = PivotRuleReference(sp.csr_matrix((K.val.copy(), K.colidx, K.rowptr), shape=(nx + my, nx + my)), nx, probe["perm"], probe["n_head"])
+    assert ref.triple == (nx, my - 1, 1) and set(ref.rejected_rows) < {nx, nx + my - 1}
+    assert ref.ratio[ref.accepted].min() >= 64 * PIVOT_THR_REL and ref.ratio[~ref.accepted].max() <= PIVOT_THR_REL / 64
+    assert bt.inertia(0) == ref.triple
     # Friedlander-Orban style: increase the dual regularisation until the inertia is (nx, my, 0)
     reg, tries = 1e-8, 0
     while bt.inertia(0) != (nx, my, 0) and tries < 12:

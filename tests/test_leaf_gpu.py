@@ -7,6 +7,7 @@ import pips_ipmpp_amd as pa
 from oracle import oracle as orc
 from tests.util import Problem, hip_lower_as_rowmajor
 from tests.util import TimeCoupledProblem as _TimeCoupledProblem
+from tests.util import pivot_primals_before_their_duals as _primals_before_their_duals
 
 pytestmark = pytest.mark.gpu
 
@@ -119,7 +120,8 @@ def test_leaf_many_rhs_on_the_matrix_pipe(scheme, nrhs, monkeypatch):
 
 def test_leaf_many_rhs_refine_only_where_needed():
     """solve(nrhs) with the adapters' refinement (at most two steps, backward error 1e-15: iparm[7] = 2, PardisoProjectSolver.C:72): a chunk whose
-    first solve is accurate takes no correction solve; a pivot rule that perturbs (threshold far above the small dual pivots) leaves factors
+    first solve is accurate takes no correction solve; values that always perturb (three free primal variables: zero diagonal, their entries in
+    W kept, every dual neighbour eliminated later - the pivots are exact zeros and the rule replaces them) leave factors of a perturbed matrix that
     the measure rejects - the steps are taken and bring the chunk to the accuracy of the refined single solve."""
     n_i = 1200
     prob = Problem(7, 1, n_i, n_i // 2, 4, 4, 6.0 / n_i)
@@ -136,11 +138,13 @@ def test_leaf_many_rhs_refine_only_where_needed():
         xr = lu.solve(R[k])
         assert np.linalg.norm(X[k] - xr) / np.linalg.norm(xr) < 1e-9
     s.close()
-    s = pa.HipLdlSolver(K, n_primal=prob.n_i, refine_steps=2, refine_tol=1e-15, backward_error=True)
-    s.set_pivot_rule(1e-3, 1e-3)                 # pivots below 1e-3 max|K| are replaced: the factors are those of a perturbed matrix
+    free = _primals_before_their_duals(prob.blocks[0]["W"].to_scipy(), K, prob.n_i, 3)
+    val = K.val.copy()
+    val[prob.blocks[0]["dpos"][free]] = 0.0
+    Kfree = pa.Csr(K.nrows, K.ncols, K.rowptr, K.colidx, val)
+    s = pa.HipLdlSolver(Kfree, n_primal=prob.n_i, refine_steps=2, refine_tol=1e-15, backward_error=True)
     s.matrixChanged()
-    if s.get_inertia()[2] == 0:
-        pytest.skip("no pivot of this block falls under the threshold")
+    assert s.get_inertia() == (prob.n_i - 3, prob.my_i, 3)      # the three zero pivots are replaced: the factors are those of a perturbed matrix
     X = R.copy()
     s.solve(X)
     assert s.info()["last_refinement_steps"] >= 1

@@ -579,3 +579,488 @@ def dense_root_reference(case):
             ref.inertia = (case[1], case[0] - case[1], 0)
         _dense_root_cache[case] = ref
     return _dense_root_cache[case]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the static pivot rule when it rejects a pivot (tests/test_pivot_rule_reference_cpu.py, tests/test_pivot_rule_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------------
+PIVOT_THR_REL, PIVOT_REPL_REL = 1e-13, 1e-8         # the library's defaults (engine.hip: thr_rel, repl_rel)
+PIVOT_MUTANTS = ("replacement_sign_flipped", "repl_abs_where_pref_positive", "repl_rel_where_pref_zero", "magnitude_test_with_hint",
+                 "perturbed_counted_negative", "tail_pref_not_refreshed", "dual_pref_without_sum", "updates_with_rejected_pivot")
+
+
+class PivotRule:
+    """The rule of fix_pivot (csrc/kernels.hip.h) as data: thr_rel, repl_rel and at most one mutation out of PIVOT_MUTANTS - what the CPU module
+    runs through PivotRuleReference to show that the cases tell a wrong rule from the right one."""
+
+    def __init__(self, thr_rel=PIVOT_THR_REL, repl_rel=PIVOT_REPL_REL, mutant=None):
+        assert mutant is None or mutant in PIVOT_MUTANTS
+        self.thr_rel, self.repl_rel, self.mutant = thr_rel, repl_rel, mutant
+
+    def sign(self, hint, d):
+        """the hint's sign, the pivot's own where there is none (fix_pivot: s)"""
+        return float(hint) if hint != 0 else (-1.0 if d < 0 else 1.0)
+
+    def decide(self, d, hint, pref, repl_abs):
+        """(accepted, d'): accepted iff s d > thr_rel pref, else d' = s (pref > 0 ? repl_rel pref : repl_abs)"""
+        s = self.sign(hint, d)
+        sd = abs(d) if (self.mutant == "magnitude_test_with_hint" and hint != 0) else s * d
+        if sd > self.thr_rel * pref:
+            return True, d
+        use_rel = pref > 0.0
+        if self.mutant == "repl_abs_where_pref_positive":
+            use_rel = False
+        if self.mutant == "repl_rel_where_pref_zero":
+            use_rel = True
+        repl = self.repl_rel * pref if use_rel else repl_abs          # (FP64 products, as on the device)
+        return False, (-s if self.mutant == "replacement_sign_flipped" else s) * repl
+
+
+def pivot_leaf_pref(K, n_primal, rule=None):
+    """pref per row of a leaf K (lower CSR, scipy) in the caller's order, FP64, summed in the order of k_pref_rows (csrc/kernels.hip.h): primal
+    rows |a_kk|, dual rows |a_kk| + sum_j K_kj^2 / |K_jj| over the primal neighbours with a non-zero diagonal (OracleLdl._pivot_reference);
+    without a hint |a_kk| for every row.  And repl_abs = repl_rel max|K| (k_block_absmax_finish: 1 in place of a maximum of 0)."""
+    rule = rule or PivotRule()
+    diag = np.abs(K.diagonal())
+    pref = diag.copy()
+    if n_primal >= 0 and rule.mutant != "dual_pref_without_sum":
+        for i in range(n_primal, K.shape[0]):
+            v = pref[i]
+            for q in range(K.indptr[i], K.indptr[i + 1]):
+                j = K.indices[q]
+                if j < n_primal and diag[j] > 0.0:
+                    v += K.data[q] * K.data[q] / diag[j]
+            pref[i] = v
+    amax = float(np.abs(K.data).max()) if K.nnz else 0.0
+    return pref, rule.repl_rel * (amax if amax > 0.0 else 1.0)
+
+
+class PivotRuleReference:
+    """Dense right-looking LDL^T of P K P^T in long double under the device's static pivot rule, restated from csrc/kernels.hip.h (fix_pivot,
+    k_pref_rows, k_pref_init, k_pref_tail, k_block_absmax_finish) and csrc/engine.hip (factor_prologue, factor_head; the dense root's
+    factor_enqueue):
+      leaf: pref as pivot_leaf_pref in the order perm; when the head (the first n_head positions) is eliminated the last m positions take
+            pref = max(pref, |diagonal as it then stands|); repl_abs = repl_rel max|K|;
+      root: perm = identity, n_head = 0, pref = |diagonal| (overwritten), repl_abs = repl_rel max|diagonal|.
+    A pivot k replaced by d'_k makes the factors those of K' = K + (d'_k - d_k) e_k e_k^T exactly, d_k the pivot as it stood.
+    K_lower: scipy CSR, lower triangle, the caller's numbering; hint: n_primal, or -1 for none; perm[k] = the row eliminated k-th.
+    Yields per position: stood (the pivot as it stood), accepted, ratio (s d / pref, inf where pref = 0 and s d > 0, 0 where both are 0),
+    dprime, pref; triple (positive, negative, perturbed); Kp_lower (K' as lower CSR of the same pattern) and Kp_dense; solve(B) with its own
+    factors in its own precision (for a mutant: what a device with that defect would return).
+    variant: "right" - right-looking, divisions, dtype long double (the reference) or float64; "left_reverse" - FP64, every pivot and column
+    summed from the last eliminated contribution to the first and multiplied by the rounded reciprocal of the pivot (the plain restatement of
+    the decision margins)."""
+
+    def __init__(self, K_lower, hint, perm, n_head, kind="leaf", rule=None, dtype=np.longdouble, variant="right"):
+        self.rule = rule = rule or PivotRule()
+        K_lower = sp.csr_matrix(K_lower)
+        K_lower.sort_indices()
+        self.K_lower, self.hint, self.kind = K_lower, hint, kind
+        n = self.n = K_lower.shape[0]
+        self.perm = perm = np.arange(n) if perm is None else np.asarray(perm, dtype=np.int64)
+        self.n_head = n_head
+        Kd = K_lower.toarray()
+        Kd = np.tril(Kd) + np.tril(Kd, -1).T
+        hints = np.zeros(n, np.int64) if hint < 0 else np.where(perm < hint, 1, -1)
+        if kind == "leaf":
+            pref_rows, self.repl_abs = pivot_leaf_pref(K_lower, hint, rule)
+            pref = pref_rows[perm].copy()
+            refresh = None if rule.mutant == "tail_pref_not_refreshed" else "max"
+        else:
+            assert n_head == 0
+            dmax = float(np.abs(np.diag(Kd)).max())
+            self.repl_abs = rule.repl_rel * (dmax if dmax > 0.0 else 1.0)
+            pref = np.zeros(n)
+            refresh = "overwrite"
+        A0 = Kd[np.ix_(perm, perm)]
+        self.exact_entry = np.diag(A0).copy()
+        run = self._left_reverse if variant == "left_reverse" else self._right
+        self.L, self.stood, self.dprime, self.accepted, self.pref = run(A0, hints, pref, refresh, np.float64 if variant == "left_reverse" else dtype)
+        s = np.array([rule.sign(h, d) for h, d in zip(hints, self.stood)])
+        sd = (s * self.stood).astype(np.float64)
+        with np.errstate(all="ignore"):
+            self.ratio = np.where(self.pref > 0.0, sd / np.where(self.pref > 0.0, self.pref, 1.0), np.where(sd > 0.0, np.inf, np.where(sd < 0.0, -np.inf, 0.0)))
+        acc = self.accepted
+        pos, neg, pert = int((acc & (self.dprime > 0)).sum()), int((acc & ~(self.dprime > 0)).sum()), int((~acc).sum())
+        self.triple = (pos, neg + pert, 0) if rule.mutant == "perturbed_counted_negative" else (pos, neg, pert)
+        self.rejected_positions = np.nonzero(~acc)[0]
+        self.rejected_rows = perm[self.rejected_positions]
+        # K': the diagonal entries of the rejected rows move by d' - d: exactly d' where d is the entry itself, else formed in long double
+        newdiag = K_lower.diagonal().astype(np.longdouble)
+        for k in self.rejected_positions:
+            if self.stood[k] == newdiag[perm[k]]:
+                newdiag[perm[k]] = self.dprime[k]
+            else:
+                newdiag[perm[k]] += np.longdouble(self.dprime[k]) - np.longdouble(self.stood[k])
+        Kp = K_lower.copy().tolil()
+        Kp.setdiag(newdiag.astype(np.float64))
+        self.Kp_lower = Kp.tocsr()
+        self.Kp_lower.sort_indices()
+        self.Kp_dense = np.tril(self.Kp_lower.toarray()) + np.tril(self.Kp_lower.toarray(), -1).T
+
+    def _decide_all(self, k, d, hints, pref):
+        return self.rule.decide(float(d), int(hints[k]), float(pref[k]), self.repl_abs)
+
+    def _right(self, A0, hints, pref, refresh, dtype):
+        n, mutant = self.n, self.rule.mutant
+        A = A0.astype(dtype)
+        stood, dprime, accepted = np.zeros(n, dtype), np.zeros(n), np.zeros(n, bool)
+        with np.errstate(all="ignore"):
+            for k in range(n):
+                if k == self.n_head and refresh is not None:
+                    dg = np.abs(np.diag(A)[k:]).astype(np.float64)
+                    pref[k:] = dg if refresh == "overwrite" else np.maximum(pref[k:], dg)
+                stood[k] = A[k, k]
+                accepted[k], dprime[k] = self._decide_all(k, stood[k], hints, pref)
+                dp = stood[k] if accepted[k] else dtype(dprime[k])
+                u = A[k + 1:, k].copy()
+                idx = np.nonzero(u)[0]
+                if idx.size:
+                    ui = u[idx]
+                    l = ui / dp
+                    lu = ui / stood[k] if mutant == "updates_with_rejected_pivot" else l
+                    ii = k + 1 + idx
+                    A[np.ix_(ii, ii)] -= np.outer(lu, ui)
+                    A[ii, k] = l
+        L = np.tril(A, -1)
+        return L, stood, dprime, accepted, pref
+
+    def _left_reverse(self, A0, hints, pref, refresh, dtype):
+        n = self.n
+        A0 = A0.astype(np.float64)
+        L = np.zeros((n, n))
+        dfin, rd = np.zeros(n), np.zeros(n)
+        stood, dprime, accepted = np.zeros(n), np.zeros(n), np.zeros(n, bool)
+
+        def column(k, upto):
+            """A0[k:, k] minus the contributions of the columns upto-1 .. 0 that reach row k, the last one first"""
+            c = A0[k:, k].copy()
+            for j in np.nonzero(L[k, :upto])[0][::-1]:
+                c -= L[k:, j] * (L[k, j] * dfin[j])
+            return c
+
+        for k in range(n):
+            if k == self.n_head and refresh is not None:
+                dg = np.abs(np.array([column(i, k)[0] for i in range(k, n)]))
+                pref[k:] = dg if refresh == "overwrite" else np.maximum(pref[k:], dg)
+            c = column(k, k)
+            stood[k] = c[0]
+            accepted[k], dprime[k] = self._decide_all(k, stood[k], hints, pref)
+            dfin[k] = stood[k] if accepted[k] else dprime[k]
+            with np.errstate(all="ignore"):
+                rd[k] = 1.0 / dfin[k]
+            L[k + 1:, k] = c[1:] * rd[k]
+        return L, stood, dprime, accepted, pref
+
+    def solve(self, B):
+        """L D' L^T (P x) = P b per row b of B by column substitution with this factorisation's own L and stored pivots, in its own precision,
+        rounded to FP64 at the end"""
+        dt = self.L.dtype
+        X = np.atleast_2d(B).astype(dt)[:, self.perm].T.copy()
+        dfin = np.where(self.accepted, self.stood, self.dprime.astype(dt))
+        with np.errstate(all="ignore"):
+            for k in range(self.n - 1):
+                idx = np.nonzero(self.L[k + 1:, k])[0] + k + 1
+                if idx.size:
+                    X[idx] -= np.outer(self.L[idx, k], X[k])
+            X /= dfin[:, None]
+            for k in range(self.n - 1, 0, -1):
+                idx = np.nonzero(self.L[k, :k])[0]
+                if idx.size:
+                    X[idx] -= np.outer(self.L[k, idx], X[k])
+        out = np.empty((X.shape[1], self.n))
+        out[:, self.perm] = X.T.astype(np.float64)
+        return out
+
+
+class _OneLeafMatrix:
+    """what UnrefinedReference asks of a Problem, for one lower-CSR matrix (K' of a PivotRuleReference)"""
+
+    def __init__(self, K_lower, n_primal):
+        self.K_lower, self.n_i, self.my_i = K_lower, max(n_primal, 0), K_lower.shape[0] - max(n_primal, 0)
+        self.hint = n_primal
+
+    @property
+    def n_leaf(self):
+        return self.K_lower.shape[0]
+
+    def K_full(self, b):
+        return (self.K_lower + sp.tril(self.K_lower, -1).T).tocsc()
+
+    def oracle_leaf(self, b, **kw):
+        s = orc.OracleLdl(self.K_lower.copy(), n_primal=self.hint, **kw)
+        s.matrixChanged()
+        return s
+
+
+PIVOT_CUTS = {"model": -1, "all_head": None, "all_tail": 0}      # force_n_head (None: the leaf's dimension)
+PIVOT_LEAF_SHAPE = (400, 200)
+PIVOT_SMALL_SHAPE = (170, 85)
+PIVOT_WANTED_TILE_COLUMNS = (0, 31, 32, 127)
+_ALL_CUTS = ("model", "all_head", "all_tail")
+# (case, (n_i, my_i), kind of W, block of the generator, cuts).  400 / 200 random W: the model cuts head 344 (singletons: k_head_factor_simple) + tail 256;
+# 400 / 200 time-coupled (banded W): fronts; 170 / 85: no tail from the model.  The last three rows are the blocks of the three-block batch two_blocks.
+PIVOT_LEAF_TABLE = [(name, PIVOT_LEAF_SHAPE, kind, 0, _ALL_CUTS) for kind in ("random", "time_coupled")
+                    for name in ("dead_primal", "dead_dual", "free_primal", "wrong_sign_primal", "wrong_sign_primal_unhinted")] + \
+                   [("duplicate_rows", PIVOT_LEAF_SHAPE, "random", 0, _ALL_CUTS), ("duplicate_rows_wrong_sign", PIVOT_LEAF_SHAPE, "random", 0, ("model",)),
+                    ("dead_primal", PIVOT_SMALL_SHAPE, "random", 0, ("model",)), ("clean", PIVOT_SMALL_SHAPE, "random", 1, ("model",)),
+                    ("duplicate_rows", PIVOT_SMALL_SHAPE, "random", 2, ("model",))]
+PIVOT_TWO_BLOCKS = PIVOT_LEAF_TABLE[-3:]
+
+
+class PivotLeafCase:
+    """One leaf block of the case table: K (pa.Csr, lower), its diagonal positions, n_i, my_i, the hint it is factorised with (n_i or -1),
+    whether its solves are judged, and the rows (caller's numbering) the construction means to have rejected."""
+
+    def __init__(self, name, K, dpos, n_i, my_i, hint, solve_judged, meant_rows, decoupled=False):
+        self.name, self.K, self.dpos, self.n_i, self.my_i, self.hint = name, K, dpos, n_i, my_i, hint
+        self.solve_judged, self.meant_rows, self.decoupled = solve_judged, np.sort(np.asarray(meant_rows, dtype=np.int64)), decoupled
+        self.n = n_i + my_i
+        K.val.setflags(write=False)
+
+    def K_scipy(self):
+        return sp.csr_matrix((self.K.val.copy(), self.K.colidx, self.K.rowptr), shape=(self.n, self.n))
+
+    def probe(self, cut):
+        f = PIVOT_CUTS[cut]
+        return pa.symbolic_probe(self.K, self.hint, force_n_head=self.n if f is None else f, want_perm=True)
+
+
+def _pivot_base_block(shape, kind, block=0):
+    n_i, my_i = shape
+    prob = TimeCoupledProblem(5, 3, n_i, my_i, 0, 0, 6) if kind == "time_coupled" else Problem(41, 3, n_i, my_i, 0, 0, 8.0 / n_i, diag_lo=-2.0, diag_hi=2.0)
+    blk = prob.blocks[block]
+    return blk["W"].to_scipy().tocsr(), blk["diag"].copy()
+
+
+def _pivot_assemble(W, diag, n_i):
+    W = sp.csr_matrix(W)
+    W.sort_indices()
+    Wp = pa.Csr(W.shape[0], n_i, W.indptr, W.indices, W.data)
+    K, dpos = pa.kkt_leaf_assemble(n_i, Wp)
+    K.val[dpos] = diag
+    return K, dpos
+
+
+def _pivot_positions(K, hint, n):
+    """position in the elimination order of every row, at each of the three cuts"""
+    out = {}
+    for cut, f in PIVOT_CUTS.items():
+        pr = pa.symbolic_probe(K, hint, force_n_head=n if f is None else f, want_perm=True)
+        pos = np.empty(n, np.int64)
+        pos[pr["perm"]] = np.arange(n)
+        out[cut] = (pos, pr["n_head"], pr["m"])
+    return out
+
+
+def pivot_primals_before_their_duals(W, K, n_i, count):
+    """primal variables with entries in W whose dual neighbours are all eliminated later at every cut; spread over head and tail of the model's cut
+    (the first two of the head, then the tail's, then the head's)"""
+    n = n_i + W.shape[0]
+    Wc = sp.csc_matrix(W)
+    posn = _pivot_positions(K, n_i, n)
+    good = [j for j in range(n_i) if Wc.indptr[j + 1] > Wc.indptr[j] and
+            all(pos[n_i + r] > pos[j] for pos, _, _ in posn.values() for r in Wc.indices[Wc.indptr[j]:Wc.indptr[j + 1]])]
+    pos, n_head, _ = posn["model"]
+    head = [j for j in good if pos[j] < n_head]
+    tail = [j for j in good if pos[j] >= n_head]
+    picked = (head[:2] + tail[:1] + head[2:] + tail[1:])[:count]
+    assert len(picked) == count
+    return picked
+
+
+def pivot_leaf_case(name, shape=PIVOT_LEAF_SHAPE, kind="random", cut="model", block=0):
+    """The leaf cases of the table (see tests/test_pivot_rule_gpu.py).  duplicate_rows depends on the cut: the pairs that are given equal values are
+    those whose later row lands on the wanted positions of that cut's elimination order."""
+    key = ("leaf_case", name, shape, kind, cut if name.startswith("duplicate_rows") else None, block)
+    if key in _pivot_cache:
+        return _pivot_cache[key]
+    n_i, my_i = shape
+    W, diag = _pivot_base_block(shape, kind, block)
+    n = n_i + my_i
+    if name in ("dead_primal", "dead_dual", "free_primal", "wrong_sign_primal", "wrong_sign_primal_unhinted", "clean"):
+        K, dpos = _pivot_assemble(W, diag, n_i)
+        rows = pivot_primals_before_their_duals(W, K, n_i, 3)
+        if name == "dead_dual":             # zero diagonal and a row of W of stored zeros: the primal neighbours eliminated earlier contribute exact zeros,
+            duals = [0, my_i // 2, my_i - 1]     # the pivot stands as the entry; expected negative, so d' = -repl_abs
+            Wc = sp.csr_matrix(W)
+            for r in duals:
+                Wc.data[Wc.indptr[r]:Wc.indptr[r + 1]] = 0.0
+            W = Wc
+            rows = [n_i + r for r in duals]
+            diag[rows] = 0.0
+        elif name == "dead_primal":           # zero diagonal, and every entry of W in these columns a stored zero: decoupled
+            Wc = sp.csr_matrix(W)
+            Wc.data = np.where(np.isin(Wc.indices, rows), 0.0, Wc.data)        # (the pattern stays: the probe's order is the case's)
+            W = Wc
+            diag[rows] = 0.0
+        elif name == "free_primal":
+            diag[rows] = 0.0
+        elif name.startswith("wrong_sign_primal"):
+            rows = rows[:1]
+            diag[rows] = -2.0 ** -3
+        else:
+            rows = []
+        hint = -1 if name.endswith("unhinted") else n_i
+        K, dpos = _pivot_assemble(W, diag, n_i)
+        case = PivotLeafCase(name, K, dpos, n_i, my_i, hint, name not in ("wrong_sign_primal_unhinted",), [] if name.endswith("unhinted") else rows,
+                             decoupled=name in ("dead_primal", "dead_dual"))
+    else:
+        assert name in ("duplicate_rows", "duplicate_rows_wrong_sign")
+        hint = n_i
+        W = sp.csr_matrix(W)
+        W.sort_indices()
+        assert np.all(np.diff(W.indptr) == np.diff(W.indptr)[0])           # (the generator gives every row the same number of entries)
+        per = int(np.diff(W.indptr)[0])
+        # groups of up to five consecutive rows share the pattern of their first row, values stay different (five and this offset: the later
+        # rows of the groups then reach every wanted in-tile column at the model's cut and with all of K in the tail - asserted by the CPU module)
+        G, shift = 5, 4
+        first = np.array([max(0, (r + shift) - (r + shift) % G - shift) for r in range(my_i)])
+        idx = W.indices.reshape(my_i, per)[first].copy()
+        W = sp.csr_matrix((W.data.copy(), idx.ravel(), W.indptr.copy()), shape=W.shape)
+        diag[n_i:] = 0.0
+        K, dpos = _pivot_assemble(W, diag, n_i)
+        f = PIVOT_CUTS[cut]
+        pr = pa.symbolic_probe(K, hint, force_n_head=n if f is None else f, want_perm=True)
+        perm, n_head, m = pr["perm"], pr["n_head"], pr["m"]
+        pos = np.empty(n, np.int64)
+        pos[perm] = np.arange(n)
+
+        def earlier_mate(r):
+            mates = [q for q in np.nonzero(first == first[r])[0] if q != r and pos[n_i + q] < pos[n_i + r]]
+            return min(mates, key=lambda q: pos[n_i + q]) if mates else None
+
+        wanted = []          # positions in the elimination order
+        dual_head = [k for k in range(n_head) if perm[k] >= n_i and earlier_mate(perm[k] - n_i) is not None]
+        if dual_head:        # inside the head: three, spread
+            wanted += [dual_head[len(dual_head) // 4], dual_head[len(dual_head) // 2], dual_head[-1]]
+        for col in PIVOT_WANTED_TILE_COLUMNS:      # in the tail: the first position at each wanted in-tile column that a later row of a pair can take
+            ts = [t for t in range(col, m, DENSE_ROOT_TILE) if perm[n_head + t] >= n_i and earlier_mate(perm[n_head + t] - n_i) is not None]
+            if ts:
+                wanted.append(n_head + ts[0])
+        if m > 128 and perm[n_head + 128] >= n_i and earlier_mate(perm[n_head + 128] - n_i) is not None:
+            wanted.append(n_head + 128)            # column 128: the second tile's first
+        wanted = sorted(set(wanted))
+        data = W.data.reshape(my_i, per).copy()
+        rng = np.random.default_rng(7)
+        for k in wanted:
+            r = perm[k] - n_i
+            q = earlier_mate(r)
+            if not np.array_equal(data[q], data[r]):
+                vals = rng.choice([1.0, -1.0, 0.5, -0.5], per)
+                for t in np.nonzero(first == first[r])[0]:
+                    if np.array_equal(data[t], data[q]) and t != q:       # (a row already equal to q stays equal)
+                        data[t] = vals
+                data[q] = vals
+                data[r] = vals
+            diag[idx[r]] = 2.0 ** rng.integers(-2, 3, per)
+        meant = list(perm[wanted])
+        if name == "duplicate_rows_wrong_sign":
+            # a primal neighbour of the last wanted tail row that lies in the head gets the diagonal -2^-3: replaced by +repl_rel 2^-3, its update
+            # of some -1e8 makes the diagonal after the head, not the sum of k_pref_rows, the reference magnitude of that row's pivot
+            assert cut == "model" and wanted and wanted[-1] >= n_head > 0
+            j = [c for c in idx[perm[wanted[-1]] - n_i] if pos[c] < n_head][0]
+            diag[j] = -2.0 ** -3
+            meant.append(j)
+        W = sp.csr_matrix((data.ravel(), idx.ravel(), W.indptr.copy()), shape=W.shape)
+        K2, dpos = _pivot_assemble(W, diag, n_i)
+        assert np.array_equal(K2.colidx, K.colidx)
+        case = PivotLeafCase(name, K2, dpos, n_i, my_i, hint, False, meant)
+        case.wanted_positions, case.cut = np.asarray(wanted), cut
+    _pivot_cache[key] = case
+    return case
+
+
+_pivot_cache = {}
+
+
+def pivot_leaf_reference(case, cut, rule=None, variant="right"):
+    """The shared PivotRuleReference of a leaf case at a cut (the right rule: cached)"""
+    key = ("leaf_ref", case.name, (case.n_i, case.my_i), id(case), cut, variant)
+    if rule is None and key in _pivot_cache:
+        return _pivot_cache[key]
+    pr = case.probe(cut)
+    ref = PivotRuleReference(case.K_scipy(), case.hint, pr["perm"], pr["n_head"], "leaf", rule, variant=variant)
+    ref.probe = pr
+    if rule is None:
+        _pivot_cache[key] = ref
+    return ref
+
+
+def pivot_rhs(n, rejected_rows, seed=3):
+    """one Gaussian right-hand side and one unit vector on a rejected row (the first), one per row"""
+    B = np.zeros((2, n))
+    B[0] = np.random.default_rng(seed).standard_normal(n)
+    B[1, rejected_rows[0] if len(rejected_rows) else 0] = 1.0
+    return B
+
+
+def pivot_leaf_judge(case, cut):
+    """UnrefinedReference on K' of the case at the cut, right-hand sides of pivot_rhs: the existing predicate with K' in place of K"""
+    key = ("leaf_judge", id(case), cut)
+    if key not in _pivot_cache:
+        ref = pivot_leaf_reference(case, cut)
+        j = UnrefinedReference(_OneLeafMatrix(ref.Kp_lower, case.hint), 0, pivot_rhs(case.n, ref.rejected_rows))
+        j.rule_ref = ref
+        _pivot_cache[key] = j
+    return _pivot_cache[key]
+
+
+# ---- dense root
+PIVOT_ROOT_SIZES = (129, 300, 513)
+PIVOT_ROOT_DEAD = (0, 31, 32, 96, 127, 128)
+PIVOT_ROOT_WRONG_SIGN = ((129, 32), (300, 0), (300, 32), (300, 128), (513, 128))      # (n, p): p a primal row (n_primal = 2 n // 3)
+
+
+def pivot_root_quasi_definite(n, n_primal, seed):
+    """[H A^T; A -G], H and G diagonally dominant with diagonals near 2 n (tests/test_root_single_launch_gpu.py: quasi_definite, no spread)"""
+    rng = np.random.default_rng(seed)
+    M = rng.standard_normal((n, n)) * 0.5
+    M = M + M.T
+    d = np.full(n, float(n))
+    d[n_primal:] *= -1
+    M[np.arange(n), np.arange(n)] = d
+    M[:n_primal, :n_primal] += np.diag(np.abs(M[:n_primal, :n_primal]).sum(axis=1))
+    M[n_primal:, n_primal:] -= np.diag(np.abs(M[n_primal:, n_primal:]).sum(axis=1))
+    return M
+
+
+def pivot_root_case(kind, n, p=None):
+    """("dead", n): rows and columns PIVOT_ROOT_DEAD (those below n) zeroed; ("wrong_sign", n, p): M_pp = -2^-3, M[p, :p] = 0 and
+    M[p+1:n_primal, p] = 0 - row p couples to dual rows only and its pivot stands as the entry.  Returns (M, n_primal, rows meant to be rejected)."""
+    n_primal = (2 * n) // 3
+    M = pivot_root_quasi_definite(n, n_primal, 50 + n)
+    if kind == "dead":
+        rows = [i for i in PIVOT_ROOT_DEAD if i < n]
+        for i in rows:
+            M[i, :] = 0.0
+            M[:, i] = 0.0
+    else:
+        assert p < n_primal
+        M[p, :p] = 0.0
+        M[:p, p] = 0.0
+        M[p + 1:n_primal, p] = 0.0
+        M[p, p + 1:n_primal] = 0.0
+        M[p, p] = -2.0 ** -3
+        rows = [p]
+    M.setflags(write=False)
+    return M, n_primal, np.asarray(rows)
+
+
+PIVOT_ROOT_CASES = [("dead", n, None) for n in PIVOT_ROOT_SIZES] + [("wrong_sign", n, p) for n, p in PIVOT_ROOT_WRONG_SIGN]
+
+
+def pivot_root_reference(case, rule=None, variant="right"):
+    """(PivotRuleReference of the case, DenseRootReference of its K' with the right-hand sides of pivot_rhs) - the latter for the right rule only"""
+    key = ("root_ref", case, variant)
+    if rule is None and key in _pivot_cache:
+        return _pivot_cache[key]
+    M, n_primal, rows = pivot_root_case(*case)
+    ref = PivotRuleReference(sp.csr_matrix(np.tril(M)), n_primal, None, 0, "root", rule, variant=variant)
+    ref.M, ref.n_primal, ref.meant_rows = M, n_primal, rows
+    judge = None
+    if rule is None and variant == "right":
+        judge = DenseRootReference(ref.Kp_dense, pivot_rhs(M.shape[0], rows), n_primal, static=True)
+    if rule is None:
+        _pivot_cache[key] = (ref, judge)
+    return ref, judge
