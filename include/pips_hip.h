@@ -609,6 +609,24 @@ int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int*
                          int S, const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head,
                          int* col_tasks, long long col_cap, int* grp_tasks, long long grp_cap, int64_t* counts);
 
+/* The host plans of deterministic mode, without a device (csrc/detplan.cpp; tests): the layout of a deterministic analysis (inputs as
+ * pips_layout_probe with deterministic set), then the planners the engine runs for this rank of n_ranks that need no recording of the
+ * head's scatters, and the Schur SYRK's row panels for n_panels.  out receives 16 sections of integers back to back, at most cap
+ * of them (cap 0: sizes only); a gather list is written as its number of targets T, its T targets, T + 1 offsets and its slots:
+ *   0 block -> group          1 per block: tile columns, nb, nb_pad, root fronts, border-split batches, entries of bmap
+ *   2 rounds of the Schur SYRK, rows (round, block, ti, tj)      3 / 4 rounds of k_root_assemble / k_border_schur_add, rows (round, block)
+ *   5 gather list of Br^T z per (group, Schur column)     6 / 7 gather lists of the border products: rows per Schur column, entries per leaf row
+ *   8 - 12 forward sweep of the augmented factor: gather list of the border slots per (group, Schur column); entries, rows (offset of the
+ *     factors, first column in the work vector, stride, width); per target: entry pointers (targets + 1), entry indices, slot
+ *   13 first Schur row of every panel (panels + 1; empty: one panel)    14 the panels' tasks, rows (group, block, ti, tj)    15 bmap, block after block
+ * counts (32 entries): [0] groups, [1] first group slot, [2] group slots of this rank, [3] all eight slots are added on every rank,
+ * [4] the augmented sweep's lists are built, [5] / [6] sweeps of the augmented factor: the plan's answer / the layout's, [7] multifrontal
+ * head, [8] border-split batches, [9] root fronts, [10] Schur mode taken, [11] panel groups, [12] / [13] targets / entries of the augmented
+ * sweep, [14] border rows of all head supernodes, [15] integers in all sections, [16 + k] integers of section k. */
+int pips_det_plan_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol,
+                        int S, const int* const* bt_rowptr, const int* const* bt_colidx, int rank, int n_ranks, int n_panels,
+                        long long* out, long long cap, int64_t* counts);
+
 /* The host layout pass of an IPM handle's creation, without a device (csrc/ipmlayout.cpp; tests): the functions pips_ipm_create_qp runs
  * before it touches the device.  Inputs as pips_ipm_create_qp without device and comm; eliminate_z0: whether the root inequality rows are
  * eliminated from the root system (what PIPS_IPM_ROOT_INEQ_ELIMINATE / PIPS_IPM_SPARSE_ROOT decide at creation); col (nx) and

@@ -159,7 +159,7 @@ int pips_hip_allreduce_sum_rsag(void* comm, double* buf_dev, size_t n, void* str
 /* In-place all-gather of n_parts (= number of ranks) equal parts: rank r's part lies at buf_dev + r * chunk on entry, all n_parts * chunk
  * doubles are every rank's on return.  RCCL: ncclAllGather; a host-supplied communicator: its all-gather callback (pips_hip_comm_set_external_rsag), or - it has none -
  * the all-reduce, for which the OTHER ranks' parts must be zero on entry (exact either way; the all-reduce moves n_ranks times the bytes).
- * Used by deterministic mode over several ranks: every rank's group buffers to every rank (Engine::det_global). */
+ * Used by deterministic mode over several ranks: every rank's group buffers to every rank (DetGroupPlan::global). */
 int pips_hip_all_gather(void* comm, double* buf_dev, size_t chunk, int n_parts, void* stream) {
    Comm* c = (Comm*)comm;
    if (!c || !buf_dev || n_parts < 1) PIPS_FAIL(pips::PIPS_ERR_ARG, "pips_hip_all_gather: bad arguments");

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "devmem.h"
 #include "layout.h"
+#include "detplan.h"
 #include "kernels.hip.h"
 #include "rootkernel.hip.h"
 #include "tailkernel.hip.h"
@@ -83,8 +84,6 @@ static inline int grid_for(long long n, int block, int cap = 4096) {
 // ---------------------------------------------------------------------------------------------------------------
 // tiled dense LDL^T driver shared by the leaf tails and the dense root
 // ---------------------------------------------------------------------------------------------------------------
-struct TaskList { long long off = 0; int cnt = 0; };
-
 struct TailPlan {
    int ntc_max = 0;
    std::vector<TaskList> upd, upd_diag, diag, trsm, fwd, bwd, trail, trail_next;
@@ -538,7 +537,7 @@ struct TailCtx {
    // start of a factorisation; every such launch takes the next slot
    int* d_ctr_pool = nullptr;
    int* ctr_cursor = nullptr;
-   // deterministic Schur accumulation (Engine::set_det_groups): the blocks are cut into at most eight contiguous groups with a
+   // deterministic Schur accumulation (DetGroupPlan, detplan.h): the blocks are cut into at most eight contiguous groups with a
    // buffer each; round k of the SYRK handles the k-th block of every group, so a launch never has two workgroups on the same
    // entry of a buffer and the blocks of a group arrive in their order; k_reduce_groups then adds the buffers in a fixed tree
    const std::vector<TaskList>* det_rounds = nullptr;
@@ -861,6 +860,7 @@ struct EngineAnalysis {
    DevBuf<int> d_frowptr, d_fcol, d_fsrc;   // full row structure of K for the refinement residual
    DevBuf<long long> d_flong;               // its rows longer than FULL_LONG_ROW
    DevBuf<int> d_sctab;                     // sparse Schur complement (set_sc_tables): position tables, BlkDesc::sctab_off
+   long long sc_len = 0;                    // ... and the length of its value array (one group buffer of deterministic mode); 0: dense, S x S
    DevBuf<int> d_schur_cols, d_schur_slot;
    // Schur mode 2 into the sparse Schur complement (set_sc_tables; Engine::schur_by_packed_solves): the blocks' border column sets, per
    // border row its local index (-1: empty) and the start of its row of the block's position table, and on the host what the lists of
@@ -869,8 +869,8 @@ struct EngineAnalysis {
    int packed_rhs = 0;                  // max_b nb_b where the packed path is active, else 0
    DevBuf<int> d_pk_la;
    DevBuf<long long> d_pk_tabrow;
-   std::vector<int> h_pk_la, h_pk_tab;
-   std::vector<long long> h_pk_tabrow;
+   PackRows h_pk_rows;
+   std::vector<int> h_pk_tab;
    // fronts on the rows of K only (BlockSym::mf_konly): records and lists of k_border_rows / k_border_tail
    DevBuf<int> d_kb_rec;
    DevBuf<long long> d_kb_off;          // per supernode (sorted id): offset of its record, -1 none
@@ -884,7 +884,7 @@ struct EngineAnalysis {
    DevBuf<int> d_bb_off, d_bb_pos;      // batches of block b: [d_bb_off[b], d_bb_off[b + 1]); compressed border ids of the staged rows
    DevBuf<double> d_bb_out;             // deterministic mode: the blocks' border x border triangles before they join their groups
    DevBuf<int> d_bb_round_blk;          // deterministic mode: the blocks of round k of k_border_schur
-   DevBuf<int> d_round_blk;             // deterministic mode: the blocks of round k at [round_off[k], round_off[k + 1])
+   DevBuf<int> d_round_blk;             // deterministic mode: the blocks of round k of k_root_assemble (DetGroupPlan::round_off)
    DevBuf<int> d_mfint;                 // front records (common.h)
    DevBuf<long long> d_mfdbg;           // PIPS_HIP_MF_CLOCKS: phase stamps of every front (8 per supernode), dumped after the factorisation
    DevBuf<int> d_spine, d_spine_off;
@@ -908,12 +908,21 @@ struct EngineAnalysis {
    DevBuf<int> d_br_rowptr, d_br_sc, d_br_src;   // the border by leaf row (k_border_mult_rows)
    DevBuf<int> d_krowptr, d_kcolidx, d_bt_rowptr, d_bt_colidx, d_bt_rowsc;
    DevBuf<signed char> d_psign;
-   // ---- deterministic mode (see Engine): slots, gather lists, group buffers
+   // ---- deterministic mode (see Engine): slots, gather lists, group buffers.  What the lists hold is planned on the host (detplan.h)
    struct GatherList {
       long long n_targets = 0, n_slots = 0;
       DevBuf<long long> d_tgt, d_off, d_slots;
+      int upload(const HostGather& h) {
+         *this = GatherList();
+         n_targets = (long long)h.tgt.size(); n_slots = (long long)h.slots.size();
+         if (h.tgt.empty()) return PIPS_OK;
+         int rc;
+         if ((rc = d_tgt.upload(h.tgt)) || (rc = d_off.upload(h.off)) || (rc = d_slots.upload(h.slots))) return rc;
+         return PIPS_OK;
+      }
    };
-   struct SlotEntry { long long target, slot; };
+   DetGroupPlan det;                    // groups, rounds and the sweep of the augmented factor: what the launches read of the plan
+   ScKept sc_kept;                      // the Schur targets of the head as recorded (build_deterministic), for DetGroupPlan::sc_grp
    DevBuf<double> d_slot_val, d_vslot_val;
    DevBuf<double> d_mvslot;             // several right-hand sides: the forward substitution's slots for one panel of MQ (solve_multi)
    std::vector<GatherList> g_levels, gv_levels;   // targets inside the head, per level (factorisation / forward substitution)
@@ -932,15 +941,12 @@ struct EngineAnalysis {
    DevBuf<long long> d_bg_ptr, d_bg_slot;
    DevBuf<int> d_bg_idx;
    DevBuf<double> d_bg_val;
-   long long n_bg_targets = 0, n_bg_ent = 0;
    GatherList g_bslot_grp;
-   bool det_aug_ready = false;
    DevBuf<double> d_bt_tmp;
    DevBuf<int> d_gemm_ctr;              // counter slots of the persistent update kernel
    // ---- Schur SYRK in row-panel groups, so that a multi-rank root can reduce panel p while the leaves still compute p + 1 ..
-   std::vector<TaskList> sc_groups;
-   std::vector<int> sc_row_begin;       // panel p = Schur rows [sc_row_begin[p], sc_row_begin[p + 1])
-   std::vector<hipEvent_t> ev_sc;       // (destroyed by Engine::release / set_sc_panels)
+   ScPanelPlan scp;                     // the groups and the panels' first rows (its tasks are dropped once uploaded)
+   std::vector<hipEvent_t> ev_sc;       // one per group (destroyed by Engine::release / set_sc_panels)
    DevBuf<TileTask> d_sc_tasks;
    // ---- multi-RHS solve (Engine::ensure_multi_buffers) and the host-pointer solves of a leaf handle
    DevBuf<double> d_mx_xw, d_mx_rhs, d_mx_res;
@@ -975,8 +981,6 @@ struct Engine : EngineAnalysis, BatchLayout {
    std::vector<BlockSym> sym;
    int schur_mode = 0;        // requested: 0 auto, 1 augmented partial factorisation, 2 blocked solves (reference K4-K6)
    int sn_width = 0;           // > 0: supernode width cap of this engine instead of the tuned default (the sparse root: a single block, every level is latency)
-   std::vector<int> bb_round_off;
-   std::vector<int> round_off;
    PhaseTimer timer;
    std::vector<int> h_inertia;
    std::vector<double> h_amax;   // max|K_b| of the current factorisation (backward-error refinement criterion)
@@ -1008,220 +1012,74 @@ struct Engine : EngineAnalysis, BatchLayout {
    bool head_slots = false;
    static constexpr long long HEAD_SLOTS_MAX = 400LL * 1000 * 1000;
    int last_multi_path = 0;      // how the last solve(nrhs) went: 0 one sweep per right-hand side, 1 interleaved panels, 2 interleaved panels with the slot / gather forward substitution
-   std::vector<SlotEntry> sc_e_keep;
-   std::vector<int> sc_blk_keep;
-   std::vector<TaskList> det_rounds;
-   int det_n_groups = 0, det_first_slot = 0;
-   // Several ranks whose count divides eight: every rank's group buffers travel to every rank (an all-reduce in which the others hold
-   // zeros at these slots: exact) and ALL eight slots are added in the one fixed tree of k_reduce_groups on every rank - the sums
-   // associate the same way for 1, 2, 4 and 8 ranks (pips_hip_kkt_factorize / the deterministic Lsolve), at eight times the bytes of
-   // the plain reduction of the Schur complement
-   bool det_global = false;
-   int det_slots = 8;                 // group slots of this rank among the global eight (8 / n_ranks where that divides)
    bool defer_group_reduce = false;   // set by pips_hip_kkt_factorize around its factor() call: it adds the groups of ALL ranks in one tree itself;
                                       // a direct pips_hip_batch_factor on the same batch reduces its own groups as on one rank
    // length of one group buffer: S x S (dense Schur complement) or the value array of the sparse one (set_sc_tables)
-   long long sc_len = 0;
    long long det_gstride() const { return sc_len > 0 ? sc_len : (long long)S * S; }
-   // groups for the deterministic Schur accumulation: the global problem has eight group slots; this rank (rank of n_ranks, blocks
-   // sharded contiguously and evenly) fills 8 / n_ranks of them (all eight when n_ranks does not divide 8).  What holds across rank
-   // counts: 1 and 2 ranks give equal bits; 4 and 8 ranks are reproducible run to run only - the all-reduce, not the fixed tree,
-   // associates the ranks' partial sums
+   // The groups of the deterministic Schur accumulation for this rank of n_ranks (build_det_group_plan), uploaded.  (The group buffers
+   // themselves are allocated by the first factorisation that has a Schur complement to fill: a system with the sparse root never needs
+   // the n_groups x S x S doubles of the dense layout this is first called with.)
    int set_det_groups(int rank, int n_ranks) {
       if (!analyzed || !deterministic) return PIPS_OK;
-      const int slots = (n_ranks >= 1 && n_ranks <= 8 && 8 % n_ranks == 0) ? 8 / n_ranks : 8;
-      det_first_slot = slots == 8 ? 0 : rank * slots;
-      det_global = n_ranks > 1 && slots < 8;
-      det_slots = slots;
-      const int gs = std::max(1, (nblk + slots - 1) / slots);     // blocks per group
-      det_n_groups = (nblk + gs - 1) / gs;
-      std::vector<int> grp(std::max(nblk, 1), 0);
-      for (int b = 0; b < nblk; ++b) grp[b] = b / gs;
-      std::vector<std::vector<TileTask>> rounds(gs);
-      for (int b = 0; b < nblk; ++b) {
-         if (h_blks[b].ntc <= 0 || h_blks[b].nb <= 0) continue;
-         const int nt = h_blks[b].nb_pad / TILE;
-         for (int ti = 0; ti < nt; ++ti)
-            for (int tj = 0; tj <= ti; ++tj) rounds[b % gs].push_back({b, ti, tj, 0});
+      PackedTables packed;
+      if (packed_rhs > 0) { packed.rows = &h_pk_rows; packed.tab = &h_pk_tab; }
+      det = build_det_group_plan(*this, sym, S, rank, n_ranks, det_gstride(), sc_kept, packed);
+      aug_sweeps_ok = det.aug_sweeps_ok;
+      d_gbuf.reset(); d_gvec.reset(); d_tvec.reset();
+      d_bg_ent.reset(); d_bg_ptr.reset(); d_bg_idx.reset(); d_bg_val.reset(); d_bg_slot.reset();
+      if (mf) {
+         PIPS_TRY(d_round_blk.upload(det.round_blk));
+         PIPS_TRY(d_bb_round_blk.upload(det.bb_round_blk));
       }
-      if (mf) {   // root fronts of round k = those of the k-th block of every group: one block per group and launch
-         std::vector<int> rb;
-         round_off.assign(1, 0);
-         for (int k = 0; k < gs; ++k) {
-            for (int b = k; b < nblk; b += gs)
-               if (h_root_off[b + 1] > h_root_off[b]) rb.push_back(b);
-            round_off.push_back((int)rb.size());
-         }
-         if (rb.empty()) rb.push_back(0);
-         int rcb = d_round_blk.upload(rb);
-         if (rcb) return rcb;
-         // ... and the same rounds over the blocks whose border x border part k_border_schur forms
-         std::vector<int> bbr;
-         bb_round_off.assign(1, 0);
-         for (int k = 0; k < gs; ++k) {
-            for (int b = k; b < nblk; b += gs)
-               if (n_bb > 0 && h_bb_off[b + 1] > h_bb_off[b]) bbr.push_back(b);
-            bb_round_off.push_back((int)bbr.size());
-         }
-         if (bbr.empty()) bbr.push_back(0);
-         if ((rcb = d_bb_round_blk.upload(bbr))) return rcb;
-      }
-      det_rounds.clear();
-      std::vector<TileTask> all;
-      for (int k = 0; k < gs; ++k) {
-         TaskList l;
-         l.off = (long long)all.size(); l.cnt = (int)rounds[k].size();
-         all.insert(all.end(), rounds[k].begin(), rounds[k].end());
-         det_rounds.push_back(l);
-      }
-      if (all.empty()) all.push_back({-1, 0, 0, 0});
-      d_det_tasks.reset(); d_gbuf.reset(); d_blk_group.reset();
-      int rc;
-      if ((rc = d_det_tasks.upload(all)) || (rc = d_blk_group.upload(grp))) return rc;
-      // (the group buffers themselves are allocated by the first factorisation that has a Schur complement to fill: a system with the
-      //  sparse root never needs the det_n_groups x S x S doubles of the dense layout this is first called with)
-      {  // the head's own Schur contributions join their block's group buffer
-         g_sc_grp = GatherList();
-         std::vector<SlotEntry> ent(sc_e_keep.size());
-         for (size_t i = 0; i < sc_e_keep.size(); ++i) ent[i] = {(long long)grp[sc_blk_keep[i]] * det_gstride() + sc_e_keep[i].target, sc_e_keep[i].slot};
-         if ((rc = upload_gather(ent, g_sc_grp))) return rc;
-      }
-      // Br^T z in the same group order: rows of group g go to slot g of an 8 x S scratch matrix
-      g_btm_grp = GatherList();
-      d_gvec.reset(); d_tvec.reset();
+      PIPS_TRY(d_det_tasks.upload(det.tasks));
+      PIPS_TRY(d_blk_group.upload(det.grp));
+      PIPS_TRY(g_sc_grp.upload(det.sc_grp));
+      PIPS_TRY(g_btm_grp.upload(det.btm_grp));
       if (S > 0) {
-         std::vector<SlotEntry> ent;
-         for (long long i = 0; i < bt_rows_total; ++i)
-            if (h_bt_rownnz[(size_t)i] > 0) ent.push_back({(long long)grp[h_bt_rowblk[(size_t)i]] * S + h_bt_rowsc[(size_t)i], i});
-         if ((rc = upload_gather(ent, g_btm_grp))) return rc;
          PIPS_TRY(d_gvec.alloc((size_t)8 * S));
          PIPS_TRY(d_tvec.alloc((size_t)S));
-         if ((rc = build_det_aug(grp))) return rc;
       }
-      // packed blocked solves: per (group, position of the value array) its contributions (border row << 24 | local column); sorted by
-      // that word = by block within a target, the order k_border_tmult_chunk_packed_det adds them in
-      g_pk_grp = GatherList();
-      if (packed_rhs > 0) {
-         std::vector<SlotEntry> ent;
-         for (long long i = 0; i < bt_rows_total; ++i)
-            for (int q = 0; q <= h_pk_la[(size_t)i]; ++q)
-               ent.push_back({(long long)grp[h_bt_rowblk[(size_t)i]] * det_gstride() + h_pk_tab[(size_t)(h_pk_tabrow[(size_t)i] + q)], (i << 24) | q});
-         if ((rc = upload_gather(ent, g_pk_grp))) return rc;
+      if (det.aug.ready) {   // forward_augmented_det
+         PIPS_TRY(d_bg_ent.upload(det.aug.ent));
+         PIPS_TRY(d_bg_ptr.upload(det.aug.ptr));
+         PIPS_TRY(d_bg_idx.upload(det.aug.idx));
+         PIPS_TRY(d_bg_slot.upload(det.aug.slot));
       }
-      if (!det_aug_ready) aug_sweeps_ok = false;   // (deterministic mode takes the sweeps of the augmented factor only through forward_augmented_det)
-      return PIPS_OK;
-   }
-   // Deterministic forward sweep of the augmented factor (forward_augmented_det).  Per (block, border id): the head supernodes that hold that
-   // border row, in the order of the supernode array - entry = where its w factors L_b(a, 0 .. w-1) lie (the border-row arena of a front
-   // under the border split, else the panel) and the first of its w columns in the work vector.  And the gather of the blocks' border slots
-   // into the group slots of d_gvec.
-   int build_det_aug(const std::vector<int>& grp) {
-      det_aug_ready = false;
-      d_bg_ent.reset(); d_bg_ptr.reset(); d_bg_idx.reset(); d_bg_val.reset(); d_bg_slot.reset();
-      n_bg_targets = n_bg_ent = 0;
-      g_bslot_grp = GatherList();
-      if (!aug_sweeps_ok || h_sns.empty()) return PIPS_OK;
-      std::vector<long long> tbase(nblk + 1, 0);
-      for (int b = 0; b < nblk; ++b) tbase[b + 1] = tbase[b] + h_blks[b].nb;
-      const long long nt = tbase[nblk];
-      if (nt == 0) return PIPS_OK;
-      std::vector<long long> cnt((size_t)nt + 1, 0);
-      auto for_rows = [&](auto&& fn) {
-         for (size_t i = 0; i < h_sns.size(); ++i) {
-            const SnDesc& sn = h_sns[i];
-            if (sn.rb >= sn.r) continue;
-            const BlockSym& bs = sym[sn.blk];
-            const int loc = bs.sn_of_col[(size_t)sn.c0];
-            const int* rows = bs.rowidx.data() + bs.sn[loc].rows;
-            for (int a = sn.rb; a < sn.r; ++a) fn(sn, tbase[sn.blk] + (rows[a] - bs.n), a);
-         }
-      };
-      for_rows([&](const SnDesc&, long long t, int) { ++cnt[(size_t)t + 1]; });
-      for (long long t = 0; t < nt; ++t) cnt[(size_t)t + 1] += cnt[(size_t)t];
-      // entries in the order of the supernode array (a supernode's border rows side by side: the threads of k_border_rowdot_det read them
-      // coalesced); per target the indices of its entries, ascending
-      const long long n_ent = cnt[(size_t)nt];
-      if (n_ent >= (1LL << 31) || xw_total >= (1LL << 32)) return PIPS_OK;   // (index widths of the lists; the refined path stays)
-      std::vector<BgEntry> ent((size_t)n_ent);
-      std::vector<int> idx((size_t)n_ent);
-      std::vector<long long> fill(cnt.begin(), cnt.end() - 1);
-      bool ok = true;
-      long long e_next = 0;
-      for_rows([&](const SnDesc& sn, long long t, int a) {
-         BgEntry e;
-         const bool in_panel = sn.ld >= sn.w + sn.r;
-         const int stride = in_panel ? sn.ld : ((sn.r - sn.rb + 3) & ~3);
-         if (!in_panel && sn.bb < 0) ok = false;
-         if (stride > 65535 || sn.w > 65535) ok = false;
-         e.off = in_panel ? sn.panel + sn.w + a : sn.bb + (a - sn.rb);
-         e.y = (unsigned)(h_blks[sn.blk].xw_off + sn.c0); e.stride = (unsigned short)stride; e.w = (unsigned short)sn.w;
-         idx[(size_t)fill[(size_t)t]++] = (int)e_next;
-         ent[(size_t)e_next++] = e;
-      });
-      if (!ok) return PIPS_OK;   // (a layout this sweep does not read: the refined path stays)
-      std::vector<long long> slot((size_t)nt);
-      std::vector<SlotEntry> col;
-      for (int b = 0; b < nblk; ++b)
-         for (int g = 0; g < h_blks[b].nb; ++g) {
-            slot[(size_t)(tbase[b] + g)] = h_blks[b].xw_off + h_blks[b].n_head + h_blks[b].m_pad + g;
-            col.push_back({(long long)grp[b] * S + sym[b].bmap[(size_t)g], slot[(size_t)(tbase[b] + g)]});
-         }
-      int rc;
-      if ((rc = d_bg_ent.upload(ent)) || (rc = d_bg_ptr.upload(cnt)) || (rc = d_bg_idx.upload(idx)) ||
-          (rc = d_bg_slot.upload(slot)) || (rc = upload_gather(col, g_bslot_grp)))
-         return rc;
-      PIPS_TRY(d_bg_val.alloc((size_t)std::max<long long>(n_ent, 1)));
-      n_bg_ent = n_ent;
-      n_bg_targets = nt;
-      det_aug_ready = true;
+      PIPS_TRY(g_bslot_grp.upload(det.aug.bslot_grp));
+      if (det.aug.ready) PIPS_TRY(d_bg_val.alloc((size_t)std::max<long long>(det.aug.n_ent, 1)));
+      PIPS_TRY(g_pk_grp.upload(det.pk_grp));
+      det.drop_uploaded();
       return PIPS_OK;
    }
    int gemm_ctr_cursor = 0;
+   // the Schur SYRK in row-panel groups (sc_panel_plan), one event per group
    int set_sc_panels(int n_panels) {
       if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_panels: analyze first");
       for (auto ev : ev_sc) (void)hipEventDestroy(ev);
-      ev_sc.clear(); sc_groups.clear(); sc_row_begin.clear();
+      ev_sc.clear();
       d_sc_tasks.reset();
-      n_panels = std::min(n_panels, std::max(1, S / (2 * TILE)));
-      if (n_panels <= 1 || schur_mode_eff != 1) return PIPS_OK;
-      for (int q = 0; q <= n_panels; ++q) sc_row_begin.push_back(q == n_panels ? S : (int)((long long)S * q / n_panels) / TILE * TILE);
-      std::vector<std::vector<TileTask>> g(n_panels);
-      for (int b = 0; b < nblk; ++b) {
-         if (h_blks[b].ntc <= 0 || h_blks[b].nb <= 0) continue;
-         const int nt = h_blks[b].nb_pad / TILE;
-         for (int ti = 0; ti < nt; ++ti) {
-            // a tile row belongs to the panel of its FIRST Schur row: every tile row that touches panel q then sits in a group <= q
-            // (compressed border ids ascend like the Schur ids), so panel q is final once group q has run
-            const int first = sym[b].bmap[std::min(ti * TILE, h_blks[b].nb - 1)];
-            int q = (int)(std::upper_bound(sc_row_begin.begin(), sc_row_begin.end(), first) - sc_row_begin.begin()) - 1;
-            q = std::max(0, std::min(q, n_panels - 1));
-            for (int tj = 0; tj <= ti; ++tj) g[q].push_back({b, ti, tj, 0});
-         }
-      }
-      std::vector<TileTask> all;
-      for (int q = 0; q < n_panels; ++q) {
-         TaskList l;
-         l.off = (long long)all.size(); l.cnt = (int)g[q].size();
-         all.insert(all.end(), g[q].begin(), g[q].end());
-         sc_groups.push_back(l);
+      scp = sc_panel_plan(*this, sym, S, n_panels);
+      if (scp.groups.empty()) return PIPS_OK;
+      for (size_t q = 0; q < scp.groups.size(); ++q) {
          hipEvent_t ev;
          HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
          ev_sc.push_back(ev);
       }
-      if (all.empty()) all.push_back({-1, 0, 0, 0});
-      return d_sc_tasks.upload(all);
+      PIPS_TRY(d_sc_tasks.upload(scp.tasks));
+      std::vector<TileTask>().swap(scp.tasks);
+      return PIPS_OK;
    }
    TailCtx ctx() {
       TailCtx c;
       c.d_blks = d_blks; c.plan = &plan; c.d_arena = d_arena; c.d_uarena = d_uarena; c.d_dtail = d_dtail; c.d_winv = d_winv;
       c.d_psign = d_psign; c.d_psign_off = d_psign_off; c.d_inertia = d_inertia; c.d_pref = d_pref;
       c.stream = stream; c.side = side; c.ev_panel = ev_diag_in; c.ev_rest = ev_diag_out; c.d_bmap = d_bmap; c.d_sctab = d_sctab;
-      if (!sc_groups.empty()) { c.sc_groups = &sc_groups; c.d_sc_tasks = d_sc_tasks; c.ev_sc = &ev_sc; }
+      if (!scp.groups.empty()) { c.sc_groups = &scp.groups; c.d_sc_tasks = d_sc_tasks; c.ev_sc = &ev_sc; }
       c.d_ctr_pool = d_gemm_ctr; c.ctr_cursor = &gemm_ctr_cursor;
       if (deterministic && d_gbuf) {
-         c.det_rounds = &det_rounds; c.d_det_tasks = d_det_tasks; c.d_gbuf = d_gbuf; c.gstride = det_gstride(); c.sc_len = sc_len; c.d_blk_group = d_blk_group;
-         c.n_groups = det_n_groups; c.first_slot = det_first_slot;
-         c.det_defer_reduce = det_global && defer_group_reduce;   // (only the kkt paths finish the reduction themselves)
+         c.det_rounds = &det.rounds; c.d_det_tasks = d_det_tasks; c.d_gbuf = d_gbuf; c.gstride = det_gstride(); c.sc_len = sc_len; c.d_blk_group = d_blk_group;
+         c.n_groups = det.n_groups; c.first_slot = det.first_slot;
+         c.det_defer_reduce = det.global && defer_group_reduce;   // (only the kkt paths finish the reduction themselves)
       }
       c.sweep = &sweep;
       if (tail_single) {
@@ -1320,13 +1178,9 @@ struct Engine : EngineAnalysis, BatchLayout {
       PIPS_TRY(d_fsrc.upload(h_fsrc));
       PIPS_TRY(d_flong.upload(h_flong));
       if (deterministic && bt_rows_total > 0) {   // gather lists of the border products (see k_border_rowdot)
-         std::vector<SlotEntry> by_sc, by_entry;
-         for (long long i = 0; i < bt_rows_total; ++i) {
-            if (h_bt_rowptr[i + 1] > h_bt_rowptr[i]) by_sc.push_back({(long long)h_bt_rowsc[i], i});
-            for (int q = h_bt_rowptr[i]; q < h_bt_rowptr[i + 1]; ++q) by_entry.push_back({h_bt_xoff[i] + h_bt_colidx[q], (long long)q});
-         }
-         PIPS_TRY(upload_gather(by_sc, g_btm));
-         PIPS_TRY(upload_gather(by_entry, g_bm));
+         const BorderGathers bg = border_product_gathers(*this);
+         PIPS_TRY(g_btm.upload(bg.btm));
+         PIPS_TRY(g_bm.upload(bg.bm));
          PIPS_TRY(d_bt_tmp.alloc((size_t)std::max<long long>(std::max(bt_rows_total, nnzB_total), 1)));
       }
       PIPS_TRY(d_schur_cols.upload(schur_cols));
@@ -1444,10 +1298,10 @@ struct Engine : EngineAnalysis, BatchLayout {
          if (!d_bb_out) PIPS_TRY(d_bb_out.alloc((size_t)std::max(nblk, 1) * tri));
          rc = small ? go(k_border_schur<BLK, 3>, nblk, (const int*)nullptr, (double*)nullptr, 0LL, (const int*)nullptr, 1, 1, d_bb_out, tri)
                     : go(k_border_schur<BLK, 6>, nblk, (const int*)nullptr, (double*)nullptr, 0LL, (const int*)nullptr, 1, 1, d_bb_out, tri);
-         for (size_t k = 0; k + 1 < bb_round_off.size() && !rc; ++k) {
-            const int cnt = bb_round_off[k + 1] - bb_round_off[k];
+         for (size_t k = 0; k + 1 < det.bb_round_off.size() && !rc; ++k) {
+            const int cnt = det.bb_round_off[k + 1] - det.bb_round_off[k];
             if (cnt > 0)
-               hipLaunchKernelGGL(k_border_schur_add, dim3(cnt, 8), dim3(256), 0, stream, d_bb_round_blk + bb_round_off[k], d_blks, d_bmap, d_bb_out, tri, ldSC, d_sctab,
+               hipLaunchKernelGGL(k_border_schur_add, dim3(cnt, 8), dim3(256), 0, stream, d_bb_round_blk + det.bb_round_off[k], d_blks, d_bmap, d_bb_out, tri, ldSC, d_sctab,
                                   d_gbuf, det_gstride(), d_blk_group);
          }
       } else
@@ -1507,21 +1361,6 @@ struct Engine : EngineAnalysis, BatchLayout {
          hipLaunchKernelGGL(k_gather_slots, dim3(grid_for(g.n_targets, 256)), dim3(256), 0, stream, g.n_targets, g.d_tgt, g.d_off, g.d_slots, vals, target);
    }
 
-   // the recorded contributions (target, slot) are sorted, then turned into the CSR "target -> its slots"
-   int upload_gather(std::vector<SlotEntry>& e, GatherList& g) {
-      std::sort(e.begin(), e.end(), [](const SlotEntry& a, const SlotEntry& b) { return a.target != b.target ? a.target < b.target : a.slot < b.slot; });
-      std::vector<long long> tgt, off, sl(e.size());
-      for (size_t i = 0; i < e.size(); ++i) {
-         if (i == 0 || e[i].target != e[i - 1].target) { tgt.push_back(e[i].target); off.push_back((long long)i); }
-         sl[i] = e[i].slot;
-      }
-      off.push_back((long long)e.size());
-      g.n_targets = (long long)tgt.size(); g.n_slots = (long long)e.size();
-      if (tgt.empty()) return PIPS_OK;
-      int rc;
-      if ((rc = g.d_tgt.upload(tgt)) || (rc = g.d_off.upload(off)) || (rc = g.d_slots.upload(sl))) return rc;
-      return PIPS_OK;
-   }
    int build_deterministic(int n_threads) {
       if (spine_total > 0) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode: spine kernels must be off");
       const int nlev = (int)levels.size();
@@ -1543,37 +1382,15 @@ struct Engine : EngineAnalysis, BatchLayout {
          d_rec.reset();
          PIPS_TRY(d_slot_val.alloc((size_t)slots_total));
       }
-      // classify: Schur complement / tail of block b / head panel of a supernode at level l (targets of different blocks are disjoint)
-      std::vector<std::vector<SlotEntry>> per_level(nlev);
-      std::vector<SlotEntry> tail_e, sc_e;
-      sc_blk_keep.clear();
-      std::vector<std::vector<std::pair<long long, int>>> panel_level(nblk);   // (panel offset inside the block arena, level), ascending
-      for (int b = 0; b < nblk; ++b) {
-         for (const HeadSupernode& hs : sym[b].sn) panel_level[b].push_back({hs.panel, hs.level});
-         std::sort(panel_level[b].begin(), panel_level[b].end());
+      {  // the slots by target: head panels level by level, tails, Schur complement (detplan.h)
+         FactorSlotPlan fp;
+         if ((rc = classify_factor_slots(rec, SCATTER_SC_FLAG, *this, sym, fp))) return rc;
+         std::vector<long long>().swap(rec);
+         for (int l = 0; l < nlev; ++l) PIPS_TRY(g_levels[l].upload(fp.levels[l]));
+         PIPS_TRY(g_tail.upload(fp.tail));
+         PIPS_TRY(g_sc.upload(fp.sc));
+         sc_kept = std::move(fp.kept);
       }
-      for (int i = 0; i < nsn_total; ++i) {
-         const SnDesc& sn = h_sns[i];
-         if (mf && !(sn.mf < 0 && sn.n_useg == 0)) continue;   // multifrontal head: only the leaves without a front above them own slots
-         const long long cnt = (long long)sn.r * (sn.r + 1) / 2;
-         const BlkDesc& bd = h_blks[sn.blk];
-         for (long long q = 0; q < cnt; ++q) {
-            const long long t = rec[(size_t)(sn.slot + q)];
-            if (t < 0) continue;
-            if (t & SCATTER_SC_FLAG) { sc_e.push_back({t & ~SCATTER_SC_FLAG, sn.slot + q}); sc_blk_keep.push_back(sn.blk); continue; }
-            if (t >= bd.T) { tail_e.push_back({t, sn.slot + q}); continue; }
-            const long long rel = t - bd.arena_off;
-            auto& pl = panel_level[sn.blk];
-            auto it = std::upper_bound(pl.begin(), pl.end(), std::make_pair(rel, INT32_MAX));
-            if (it == pl.begin()) PIPS_FAIL(PIPS_ERR_STATE, "deterministic mode: a recorded target lies outside every head panel");
-            per_level[std::prev(it)->second].push_back({t, sn.slot + q});
-         }
-      }
-      std::vector<long long>().swap(rec);
-      for (int l = 0; l < nlev; ++l)
-         if ((rc = upload_gather(per_level[l], g_levels[l]))) return rc;
-      sc_e_keep = sc_e;   // (unsorted, parallel to sc_blk_keep) for the group-wise variant of deterministic mode
-      if ((rc = upload_gather(tail_e, g_tail)) || (rc = upload_gather(sc_e, g_sc))) return rc;
       // ---- forward-substitution scatter: same recording, targets are entries of the permuted work vector
       if (vslots_total > 0) {
          DevBuf<long long> d_rec;
@@ -1595,23 +1412,10 @@ struct Engine : EngineAnalysis, BatchLayout {
          HIP_TRY(hipMemcpy(vrec.data(), d_rec, (size_t)vslots_total * sizeof(long long), hipMemcpyDeviceToHost));
          d_rec.reset();
          PIPS_TRY(d_vslot_val.alloc((size_t)vslots_total));
-         std::vector<std::vector<SlotEntry>> v_level(nlev);
-         std::vector<SlotEntry> v_tail;
-         for (int i = 0; i < nsn_total; ++i) {
-            const SnDesc& sn = h_sns[i];
-            const BlkDesc& bd = h_blks[sn.blk];
-            for (int a = 0; a < sn.r; ++a) {
-               const long long t = vrec[(size_t)(sn.vslot + a)];
-               if (t < 0) continue;
-               const long long col = t - bd.xw_off;
-               if (col >= bd.n_head) { v_tail.push_back({t, sn.vslot + a}); continue; }
-               const int loc = sym[sn.blk].sn_of_col[(size_t)col];
-               v_level[sym[sn.blk].sn[loc].level].push_back({t, sn.vslot + a});
-            }
-         }
-         for (int l = 0; l < nlev; ++l)
-            if ((rc = upload_gather(v_level[l], gv_levels[l]))) return rc;
-         if ((rc = upload_gather(v_tail, gv_tail))) return rc;
+         SolveSlotPlan vp;
+         classify_solve_slots(vrec, *this, sym, vp);
+         for (int l = 0; l < nlev; ++l) PIPS_TRY(gv_levels[l].upload(vp.levels[l]));
+         PIPS_TRY(gv_tail.upload(vp.tail));
       }
       (void)n_threads;
       return PIPS_OK;
@@ -1638,22 +1442,13 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (schur_mode_eff == 2) {
          const SchurPack& pk = border_pack();
          if (pk.nb_max >= (1 << 24)) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_tables: %d border columns in one block exceed the packed solves' 2^24", pk.nb_max);
-         h_pk_la.clear(); h_pk_tabrow.clear();
-         std::vector<int> local(std::max(S, 1));
-         for (int b = 0; b < nblk; ++b) {
-            if (in[b].btrow.empty()) continue;   // (the rows of the global border CSR: S per block with a border, layout_border_csr)
-            const int nb_b = schur_pack_block(S, in[b].btrow.data(), local.data());
-            if (off[b] + (long long)nb_b * nb_b > (long long)tab.size())
-               PIPS_FAIL(PIPS_ERR_ARG, "set_sc_tables: the position table of block %d is shorter than its %d x %d border columns", b, nb_b, nb_b);
-            for (int s = 0; s < S; ++s) {
-               h_pk_la.push_back(local[s]);
-               h_pk_tabrow.push_back(local[s] >= 0 ? off[b] + (long long)local[s] * nb_b : 0);
-            }
-         }
-         if ((long long)h_pk_la.size() != bt_rows_total) PIPS_FAIL(PIPS_ERR_STATE, "set_sc_tables: %zu border rows, the analysis holds %lld", h_pk_la.size(), bt_rows_total);
-         if ((rc = d_pk_la.upload(h_pk_la)) || (rc = d_pk_tabrow.upload(h_pk_tabrow))) return rc;
-         if (deterministic) h_pk_tab = tab;   // (set_det_groups builds the lists of k_border_tmult_chunk_packed_det from it)
-         else { std::vector<int>().swap(h_pk_la); std::vector<long long>().swap(h_pk_tabrow); }
+         if ((rc = schur_pack_rows(in, S, off, (long long)tab.size(), h_pk_rows))) return rc;
+         if ((long long)h_pk_rows.la.size() != bt_rows_total)
+            PIPS_FAIL(PIPS_ERR_STATE, "set_sc_tables: %zu border rows, the analysis holds %lld", h_pk_rows.la.size(), bt_rows_total);
+         PIPS_TRY(d_pk_la.upload(h_pk_rows.la));
+         PIPS_TRY(d_pk_tabrow.upload(h_pk_rows.tabrow));
+         if (deterministic) h_pk_tab = tab;   // (build_det_group_plan builds the lists of k_border_tmult_chunk_packed_det from them)
+         else h_pk_rows = PackRows();
          packed_rhs = pk.nb_max;
       }
       if (head_slots) {   // the Schur targets of the head moved into the CSR value array: record again
@@ -1694,10 +1489,10 @@ struct Engine : EngineAnalysis, BatchLayout {
       // about 2048 workgroups in the launch (what is resident at once): half of a block's chunks on the tail's columns, half on the border's
       const int asm_half = std::max(1, std::min(32, 1024 / std::max(nblk, 1)));
       if (deterministic && d_gbuf && SC && d_round_blk) {
-         for (size_t k = 0; k + 1 < round_off.size(); ++k) {
-            const int cnt = round_off[k + 1] - round_off[k];
+         for (size_t k = 0; k + 1 < det.round_off.size(); ++k) {
+            const int cnt = det.round_off[k + 1] - det.round_off[k];
             if (cnt > 0)
-               hipLaunchKernelGGL(k_root_assemble, dim3(cnt, 2 * asm_half), dim3(256), 0, stream, d_round_blk + round_off[k], d_root_off, d_roots, d_sns, d_blks, d_rowidx,
+               hipLaunchKernelGGL(k_root_assemble, dim3(cnt, 2 * asm_half), dim3(256), 0, stream, d_round_blk + det.round_off[k], d_root_off, d_roots, d_sns, d_blks, d_rowidx,
                                   d_bmap, d_arena, d_mfU, SC, ldSC, d_sctab, d_gbuf, det_gstride(), d_blk_group, asm_half, asm_half);
          }
       } else
@@ -1717,7 +1512,7 @@ struct Engine : EngineAnalysis, BatchLayout {
          PhaseTimer::Scope phase(&timer, stream, 1);
          gather(g_tail, d_slot_val, d_arena);
          if (SC && deterministic && d_gbuf) {
-            HIP_TRY(hipMemsetAsync(d_gbuf, 0, (size_t)det_n_groups * det_gstride() * sizeof(double), stream));
+            HIP_TRY(hipMemsetAsync(d_gbuf, 0, (size_t)det.n_groups * det_gstride() * sizeof(double), stream));
             gather(g_sc_grp, d_slot_val, d_gbuf);
          } else if (SC) gather(g_sc, d_slot_val, SC);
       }
@@ -1781,7 +1576,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (!analyzed) PIPS_FAIL(PIPS_ERR_STATE, "factor called before analyze");
       HIP_TRY(hipSetDevice(device));
       if (deterministic && SC && S > 0 && !d_gbuf && d_blk_group)
-         PIPS_TRY(d_gbuf.alloc((size_t)det_n_groups * det_gstride()));
+         PIPS_TRY(d_gbuf.alloc((size_t)det.n_groups * det_gstride()));
       timer.reset();
       const int rec_total = timer.begin_i(stream, 6);   // the whole factorisation: stays open across the records of the stages
       PIPS_TRY(factor_prologue());
@@ -2338,7 +2133,7 @@ struct Engine : EngineAnalysis, BatchLayout {
    // writer per row).  The border slots stay in the work vector: the caller gathers them group-wise (g_bslot_grp) like Br^T z.
    int forward_augmented_det(const double* b_dev) {
       if (!factored) PIPS_FAIL(PIPS_ERR_STATE, "solve called before factor");
-      if (!det_aug_ready || !head_slots) PIPS_FAIL(PIPS_ERR_STATE, "forward_augmented_det: not prepared");
+      if (!det.aug.ready || !head_slots) PIPS_FAIL(PIPS_ERR_STATE, "forward_augmented_det: not prepared");
       HIP_TRY(hipSetDevice(device));
       {
          PhaseTimer::Scope phase(&timer, stream, 7);
@@ -2348,8 +2143,8 @@ struct Engine : EngineAnalysis, BatchLayout {
       {
          PhaseTimer::Scope phase(&timer, stream, 8);
          head_forward(d_xw, 1, 0, ScatterCtx{2, nullptr, d_vslot_val, d_xw, nullptr}, 0);   // (the border slots: by the two kernels below, from the finished head part)
-         hipLaunchKernelGGL(k_border_rowdot_det, dim3(grid_for(n_bg_ent, 256, 1 << 20)), dim3(256), 0, stream, n_bg_ent, d_bg_ent, d_arena, d_xw, d_bg_val);
-         hipLaunchKernelGGL(k_border_gather_det, dim3((unsigned)((n_bg_targets + 3) / 4)), dim3(256), 0, stream, n_bg_targets, d_bg_ptr, d_bg_idx, d_bg_slot, d_bg_val, d_xw);
+         hipLaunchKernelGGL(k_border_rowdot_det, dim3(grid_for(det.aug.n_ent, 256, 1 << 20)), dim3(256), 0, stream, det.aug.n_ent, d_bg_ent, d_arena, d_xw, d_bg_val);
+         hipLaunchKernelGGL(k_border_gather_det, dim3((unsigned)((det.aug.n_targets + 3) / 4)), dim3(256), 0, stream, det.aug.n_targets, d_bg_ptr, d_bg_idx, d_bg_slot, d_bg_val, d_xw);
       }
       {
          PhaseTimer::Scope phase(&timer, stream, 9);
@@ -4332,6 +4127,82 @@ int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int*
       }
    }
    counts[0] = nc; counts[1] = ng; counts[2] = plan.ntc_max; counts[3] = pp.n_groups; counts[4] = launches_col; counts[5] = launches_grp;
+   return PIPS_OK;
+}
+
+// ---- plan probe of deterministic mode (CPU only): the layout of a deterministic analysis, then the planners of detplan.h that need no
+// recording, as Engine::upload_layout / set_det_groups / set_sc_panels call them - sections of integers (include/pips_hip.h)
+int pips_det_plan_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
+                        const int* const* bt_rowptr, const int* const* bt_colidx, int rank, int n_ranks, int n_panels, long long* out,
+                        long long cap, int64_t* counts) {
+   std::vector<BlockInput> in;
+   PIPS_TRY(probe_inputs("pips_det_plan_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
+   if (!counts || cap < 0 || (cap > 0 && !out) || n_ranks < 1 || rank < 0 || rank >= n_ranks) PIPS_FAIL(PIPS_ERR_ARG, "pips_det_plan_probe: bad arguments");
+   AnalyzeOptions opt;
+   AnalyzeKnobs knobs;
+   read_layout_knobs(nullptr, opt, knobs);
+   knobs.deterministic = true; opt.mf_konly = false;   // (as pips_layout_probe with deterministic set)
+   knobs.free_device_bytes = 0;
+   std::vector<BlockSym> sym;
+   BatchLayout lay;
+   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+   PIPS_TRY(analyze_symbolic(in, S, n_threads, opt, knobs, sym));
+   PIPS_TRY(build_batch_layout(in, sym, S, knobs, lay));
+   const BorderGathers bg = lay.bt_rows_total > 0 ? border_product_gathers(lay) : BorderGathers();
+   const DetGroupPlan p = build_det_group_plan(lay, sym, S, rank, n_ranks, (long long)S * S, ScKept(), PackedTables());
+   const ScPanelPlan sp = sc_panel_plan(lay, sym, S, n_panels);
+   long long at = 0;
+   int section = 0;
+   auto put = [&](long long v) { if (at < cap) out[at] = v; ++at; };
+   auto end = [&](long long& from) { counts[16 + section++] = at - from; from = at; };
+   auto gather = [&](const HostGather& g) {
+      put((long long)g.tgt.size());
+      for (long long v : g.tgt) put(v);
+      for (long long v : g.off) put(v);
+      for (long long v : g.slots) put(v);
+   };
+   long long from = 0, aug_rows = 0;
+   for (const SnDesc& sn : lay.h_sns) aug_rows += sn.r - sn.rb;
+   for (int b = 0; b < nblk; ++b) put(p.grp[b]);
+   end(from);
+   for (int b = 0; b < nblk; ++b) {
+      const BlkDesc& d = lay.h_blks[b];
+      put(d.ntc); put(d.nb); put(d.nb_pad); put(lay.mf ? lay.h_root_off[b + 1] - lay.h_root_off[b] : 0);
+      put(lay.n_bb > 0 ? lay.h_bb_off[b + 1] - lay.h_bb_off[b] : 0); put((long long)sym[b].bmap.size());
+   }
+   end(from);
+   for (size_t k = 0; k < p.rounds.size(); ++k)
+      for (long long q = p.rounds[k].off; q < p.rounds[k].off + p.rounds[k].cnt; ++q) { put((long long)k); put(p.tasks[q].blk); put(p.tasks[q].ti); put(p.tasks[q].tj); }
+   end(from);
+   for (size_t k = 0; k + 1 < p.round_off.size(); ++k)
+      for (int q = p.round_off[k]; q < p.round_off[k + 1]; ++q) { put((long long)k); put(p.round_blk[q]); }
+   end(from);
+   for (size_t k = 0; k + 1 < p.bb_round_off.size(); ++k)
+      for (int q = p.bb_round_off[k]; q < p.bb_round_off[k + 1]; ++q) { put((long long)k); put(p.bb_round_blk[q]); }
+   end(from);
+   gather(p.btm_grp); end(from);
+   gather(bg.btm); end(from);
+   gather(bg.bm); end(from);
+   gather(p.aug.bslot_grp); end(from);
+   for (const BgEntry& e : p.aug.ent) { put(e.off); put(e.y); put(e.stride); put(e.w); }
+   end(from);
+   for (long long v : p.aug.ptr) put(v);
+   end(from);
+   for (int v : p.aug.idx) put(v);
+   end(from);
+   for (long long v : p.aug.slot) put(v);
+   end(from);
+   for (int v : sp.row_begin) put(v);
+   end(from);
+   for (size_t g = 0; g < sp.groups.size(); ++g)
+      for (long long q = sp.groups[g].off; q < sp.groups[g].off + sp.groups[g].cnt; ++q) { put((long long)g); put(sp.tasks[q].blk); put(sp.tasks[q].ti); put(sp.tasks[q].tj); }
+   end(from);
+   for (int b = 0; b < nblk; ++b)
+      for (int v : sym[b].bmap) put(v);
+   end(from);
+   const int64_t head[16] = {p.n_groups, p.first_slot, p.slots, p.global, p.aug.ready, p.aug_sweeps_ok, lay.aug_sweeps_ok, lay.mf, lay.n_bb, lay.n_roots,
+                             lay.schur_mode_eff, (int64_t)sp.groups.size(), p.aug.n_targets, p.aug.n_ent, aug_rows, at};
+   std::copy(head, head + 16, counts);
    return PIPS_OK;
 }
 

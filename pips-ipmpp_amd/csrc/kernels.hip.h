@@ -3683,7 +3683,7 @@ __global__ __launch_bounds__(256) void k_border_tmult_chunk_det(long long n_targ
 // Blocked Schur path into the sparse root's value array: the border columns packed block by block.  Right-hand side q of the packed
 // solves carries, in every block, that block's q-th non-empty border column (local index q of the block's nb x nb position table,
 // sc_entry), so one interleaved sweep solves a different Schur column in every block and max_b nb_b right-hand sides do for all of
-// them.  Per border row i (Engine::set_sc_tables): la[i] = the row's local index in its block, -1 for an empty row; tabrow[i] = where
+// them.  Per border row i (schur_pack_rows, layout.h): la[i] = the row's local index in its block, -1 for an empty row; tabrow[i] = where
 // row la of its block's position table starts inside sctab.  A row with la < q has nothing in column q (lower triangle), and a block
 // with nb <= q has no such row: its table is never read past.
 __global__ void k_border_rows_to_dense_packed(const int* __restrict__ rowptr, const int* __restrict__ colidx,

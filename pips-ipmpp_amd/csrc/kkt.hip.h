@@ -378,15 +378,15 @@ struct KktSystem {
       return PIPS_OK;
    }
    // deterministic mode over several ranks: every rank's group buffers to every rank, then ALL eight slots in the one fixed tree (the
-   // leaf engine left its groups unreduced, Engine::det_global) - equal bits for 1, 2, 4 and 8 ranks
+   // leaf engine left its groups unreduced, DetGroupPlan::global) - equal bits for 1, 2, 4 and 8 ranks
    int reduce_groups(const ScView& sc) {
       Engine* e = leaves;
       const size_t gs = sc.count;
       if (!d_gall) PIPS_TRY(d_gall.alloc(8 * gs));
       HIP_TRY(hipMemsetAsync(d_gall, 0, 8 * gs * sizeof(double), e->stream));
-      HIP_TRY(hipMemcpyAsync(d_gall + (size_t)e->det_first_slot * gs, e->d_gbuf, (size_t)e->det_n_groups * gs * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+      HIP_TRY(hipMemcpyAsync(d_gall + (size_t)e->det.first_slot * gs, e->d_gbuf, (size_t)e->det.n_groups * gs * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
       // every rank's slots to every rank: 1 x the bytes (the all-reduce of zeros it replaces moved 8 x the bytes)
-      if (int rc = pips_hip_all_gather(comm, d_gall, (size_t)e->det_slots * gs, 8 / e->det_slots, e->stream)) return rc;
+      if (int rc = pips_hip_all_gather(comm, d_gall, (size_t)e->det.slots * gs, 8 / e->det.slots, e->stream)) return rc;
       // the dense array column by column, the value array as one vector
       const dim3 grid = sc.rowptr ? dim3((unsigned)std::max<size_t>(1, std::min<size_t>(1024, (gs + 255) / 256)), 1) : dim3(std::max(1, std::min(64, (S + 255) / 256)), S);
       hipLaunchKernelGGL(k_reduce_groups, grid, dim3(256), 0, e->stream, sc.val, sc.ld, sc.rowptr ? (int)gs : S, d_gall, (long long)gs, 8, 0);
@@ -399,14 +399,14 @@ struct KktSystem {
       if (sc.rowptr) return pips_hip_allreduce_sum(comm, sc.val, sc.count, e->stream);
       int rc;
       const size_t np = (size_t)S * (S + 1) / 2;
-      const size_t n_groups = std::max<size_t>(e->sc_groups.size(), 1);
+      const size_t n_groups = std::max<size_t>(e->scp.groups.size(), 1);
       const size_t P = (size_t)std::max(1, pips_hip_comm_size(comm));
       const size_t cap = np + (n_groups + 1) * P;   // reduce-scatter pads every piece to a multiple of the rank count
       PIPS_TRY(d_packed.reserve(cap));
       auto reduce_piece = [&](double* buf, size_t cnt, hipStream_t st) -> int {
          return use_rsag ? pips_hip_allreduce_sum_rsag(comm, buf, cnt, st) : pips_hip_allreduce_sum(comm, buf, cnt, st);
       };
-      if (e->sc_groups.empty()) {
+      if (e->scp.groups.empty()) {
          const dim3 pg(std::max(1, std::min(64, (S + 255) / 256)), S);
          hipLaunchKernelGGL(k_pack_lower, pg, dim3(256), 0, e->stream, sc.val, S, S, d_packed, 0);
          if ((rc = reduce_piece(d_packed, np, e->stream))) return rc;
@@ -422,8 +422,8 @@ struct KktSystem {
          HIP_TRY(hipEventCreateWithFlags(&ev_reduced, hipEventDisableTiming));
       }
       size_t off = 0;
-      for (size_t q = 0; q < e->sc_groups.size(); ++q) {
-         const int R0 = e->sc_row_begin[q], R1 = e->sc_row_begin[q + 1];
+      for (size_t q = 0; q < e->scp.groups.size(); ++q) {
+         const int R0 = e->scp.row_begin[q], R1 = e->scp.row_begin[q + 1];
          if (R1 <= R0) continue;
          const size_t h = (size_t)(R1 - R0);
          const size_t cnt = (size_t)R0 * h + h * (h + 1) / 2;
@@ -523,7 +523,7 @@ struct KktSystem {
       timer.begin(e->stream, 1);
       // PIPS_HIP_FORCE_REDUCE exercises the reduction path with a one-rank communicator (tests).
       const bool reduce = n_ranks > 1 || force_reduce;
-      e->defer_group_reduce = reduce && e->deterministic && e->det_global;
+      e->defer_group_reduce = reduce && e->deterministic && e->det.global;
       rc = e->factor(sc.val, sc.ld);                                                    // children factor2 + assembleLocalKKT
       e->defer_group_reduce = false;
       if (rc) return rc;
@@ -531,7 +531,7 @@ struct KktSystem {
       const int rec_reduce = timer.begin_i(e->stream, 2);   // what the main stream waits for the reduction: its exposed part
       if (reduce) {
          if (!comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_factorize: n_ranks > 1 needs a communicator");
-         if ((rc = e->deterministic && e->det_global && e->d_gbuf ? reduce_groups(sc) : reduce_sum(sc))) return rc;
+         if ((rc = e->deterministic && e->det.global && e->d_gbuf ? reduce_groups(sc) : reduce_sum(sc))) return rc;
       }
       timer.end_i(rec_reduce, e->stream);
       timer.begin(e->stream, 3);
@@ -621,14 +621,14 @@ struct KktSystem {
          e->gather(e->g_btm_grp, e->d_bt_tmp, e->d_gvec);
       }
       const dim3 grid(std::max(1, std::min(64, (S + 255) / 256)), 1);
-      if (e->det_global && n_ranks > 1) {   // all eight group slots on every rank, one tree (see reduce_groups)
+      if (e->det.global && n_ranks > 1) {   // all eight group slots on every rank, one tree (see reduce_groups)
          if (!d_gvec_all) PIPS_TRY(d_gvec_all.alloc((size_t)8 * S));
          HIP_TRY(hipMemsetAsync(d_gvec_all, 0, (size_t)8 * S * sizeof(double), e->stream));
-         HIP_TRY(hipMemcpyAsync(d_gvec_all + (size_t)e->det_first_slot * S, e->d_gvec, (size_t)e->det_n_groups * S * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
-         if ((rc = pips_hip_all_gather(comm, d_gvec_all, (size_t)e->det_slots * S, 8 / e->det_slots, e->stream))) return rc;
+         HIP_TRY(hipMemcpyAsync(d_gvec_all + (size_t)e->det.first_slot * S, e->d_gvec, (size_t)e->det.n_groups * S * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+         if ((rc = pips_hip_all_gather(comm, d_gvec_all, (size_t)e->det.slots * S, 8 / e->det.slots, e->stream))) return rc;
          hipLaunchKernelGGL(k_reduce_groups, grid, dim3(256), 0, e->stream, e->d_tvec, S, S, d_gvec_all, (long long)S, 8, 0);
       } else {
-         hipLaunchKernelGGL(k_reduce_groups, grid, dim3(256), 0, e->stream, e->d_tvec, S, S, e->d_gvec, (long long)S, e->det_n_groups, e->det_first_slot);
+         hipLaunchKernelGGL(k_reduce_groups, grid, dim3(256), 0, e->stream, e->d_tvec, S, S, e->d_gvec, (long long)S, e->det.n_groups, e->det.first_slot);
          if ((n_ranks > 1 || force_reduce) && (rc = pips_hip_allreduce_sum(comm, e->d_tvec, (size_t)S, e->stream))) return rc;
       }
       hipLaunchKernelGGL(k_axpy, dim3(grid_for(S, 256)), dim3(256), 0, e->stream, c.red, e->d_tvec, 1.0, (long long)S);

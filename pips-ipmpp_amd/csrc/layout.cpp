@@ -163,6 +163,22 @@ void build_schur_pack(const std::vector<BlockInput>& in, int S, SchurPack& out) 
    }
 }
 
+int schur_pack_rows(const std::vector<BlockInput>& in, int S, const std::vector<long long>& off, long long tab_size, PackRows& out) {
+   out = PackRows();
+   std::vector<int> local(std::max(S, 1));
+   for (int b = 0; b < (int)in.size(); ++b) {
+      if (in[b].btrow.empty()) continue;   // (the rows of the global border CSR: S per block with a border, layout_border_csr)
+      const int nb_b = schur_pack_block(S, in[b].btrow.data(), local.data());
+      if (off[b] + (long long)nb_b * nb_b > tab_size)
+         PIPS_FAIL(PIPS_ERR_ARG, "set_sc_tables: the position table of block %d is shorter than its %d x %d border columns", b, nb_b, nb_b);
+      for (int s = 0; s < S; ++s) {
+         out.la.push_back(local[s]);
+         out.tabrow.push_back(local[s] >= 0 ? off[b] + (long long)local[s] * nb_b : 0);
+      }
+   }
+   return PIPS_OK;
+}
+
 int analyze_blocks(const std::vector<BlockInput>& in, int S, const AnalyzeOptions& opt, int n_threads, bool with_border, std::vector<BlockSym>& sym) {
    const int nblk = (int)in.size();
    sym.assign(nblk, BlockSym());
@@ -733,7 +749,7 @@ void layout_sweep_decisions(const std::vector<BlockSym>& sym, const LayoutKnobs&
    // Both halves of solveCompressed from the augmented factor (forward_augmented / backward_augmented): one forward and one backward
    // sweep that also read the border rows, instead of two full solves (two sweeps each, a residual check each, two border
    // products) - pays as long as the border rows are not several times what a sweep reads anyway
-   // (deterministic mode: forward_augmented_det, if set_det_groups can build its lists)
+   // (deterministic mode: forward_augmented_det, if build_det_group_plan can build its lists - DetGroupPlan::aug_sweeps_ok)
    const bool aug_paths = o.schur_mode_eff == 1 && o.nnzB_total > 0 && (sweep_enabled || ntc_max == 0) && o.spine_total == 0;
    o.aug_sweeps_ok = aug_paths && border_entries <= 3.0 * fwd_entries;
    if (knobs.aug_sweeps >= 0) o.aug_sweeps_ok = knobs.aug_sweeps != 0 && aug_paths;
@@ -944,7 +960,7 @@ void BatchLayout::drop_uploaded() {
 
 }  // namespace pips
 
-// ---- probe of the packed blocked solves' tables (CPU only): schur_pack_block as Engine::set_sc_tables calls it
+// ---- probe of the packed blocked solves' tables (CPU only): schur_pack_block as schur_pack_rows (Engine::set_sc_tables) calls it
 extern "C" int pips_schur_pack_probe(int nblk, int S, const int* const* bt_rowptr, int* nb, int* nb_max, int* const* local_of_row) {
    if (nblk <= 0 || S < 0 || !bt_rowptr || !nb || !nb_max || !local_of_row) PIPS_FAIL(pips::PIPS_ERR_ARG, "pips_schur_pack_probe: bad arguments");
    *nb_max = 0;

@@ -87,6 +87,14 @@ struct SchurPack {
 // no border, all -1); returns their number
 int schur_pack_block(int S, const int* bt_rowptr, int* local_of_row);
 void build_schur_pack(const std::vector<BlockInput>& in, int S, SchurPack& out);
+// The per-row tables of the packed blocked solves, per row of the global border CSR (S rows per block with a border): la = the row's
+// local index in its block, -1 for an empty row; tabrow = where its row of the block's nb x nb position table starts (off[b]: the
+// block's table inside the tab_size entries of all tables; PIPS_ERR_ARG where a table would end behind them)
+struct PackRows {
+   std::vector<int> la;
+   std::vector<long long> tabrow;
+};
+int schur_pack_rows(const std::vector<BlockInput>& in, int S, const std::vector<long long>& off, long long tab_size, PackRows& out);
 
 // Everything Engine::analyze() computes on the host.  The engine keeps this record; the arrays under "uploaded, then dropped" are
 // cleared after their upload (drop_uploaded).

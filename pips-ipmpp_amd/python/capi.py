@@ -74,7 +74,7 @@ SYMBOLS = [
     "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
-    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe",
+    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe", "pips_det_plan_probe",
 ]
 
 # problem scalers (pips_ipm_create_general_scaled; the order of the reference's ScalerType)
@@ -291,6 +291,47 @@ def schur_pack_probe(Bts, S):
     lo = (ip * nblk)(*[local[b].ctypes.data_as(ip) for b in range(nblk)])
     _check(lib.pips_schur_pack_probe(C.c_int(nblk), C.c_int(S), rp, _ptr(nb), C.byref(nb_max), lo), "pips_schur_pack_probe")
     return nb, int(nb_max.value), local[:, :S]
+
+
+def det_plan_probe(blocks, S, rank=0, n_ranks=1, n_panels=1):
+    """The host plans of deterministic mode for the blocks (K lower CSR, n_primal, border CSR with S rows or None) this rank of
+    n_ranks holds, without a device (pips_det_plan_probe): a dict of the scalars and of the 16 sections as int64 arrays (rows where
+    the header says rows; a gather list as a dict of tgt, off, slots)."""
+    nblk = len(blocks)
+    ip = C.POINTER(C.c_int)
+    keep = []
+
+    def arr(seq):
+        a = (ip * nblk)()
+        for i, v in enumerate(seq):
+            if v is not None:
+                keep.append(_i32(v))
+                a[i] = keep[-1].ctypes.data_as(ip)
+        return a
+
+    n = _i32([K.nrows for K, _, _ in blocks])
+    npr = _i32([p for _, p, _ in blocks])
+    head = (C.c_int(nblk), _ptr(n), _ptr(npr), arr(K.rowptr for K, _, _ in blocks), arr(K.colidx for K, _, _ in blocks), C.c_int(S),
+            arr(None if B is None else B.rowptr for _, _, B in blocks), arr(None if B is None else B.colidx for _, _, B in blocks),
+            C.c_int(rank), C.c_int(n_ranks), C.c_int(n_panels))
+    counts = np.zeros(32, np.int64)
+    _check(lib.pips_det_plan_probe(*head, None, C.c_longlong(0), _ptr(counts)), "pips_det_plan_probe")
+    out = np.zeros(int(counts[15]), np.int64)
+    _check(lib.pips_det_plan_probe(*head, _ptr(out), C.c_longlong(len(out)), _ptr(counts)), "pips_det_plan_probe")
+    sec = np.split(out, np.cumsum(counts[16:31]))
+
+    def gather(a):
+        t = int(a[0])
+        return dict(tgt=a[1:1 + t], off=a[1 + t:2 + 2 * t], slots=a[2 + 2 * t:])
+
+    names = ("n_groups", "first_slot", "slots", "global", "aug_ready", "aug_sweeps_ok", "layout_aug_sweeps_ok", "mf", "n_bb", "n_roots",
+             "schur_mode", "panel_groups", "aug_targets", "aug_entries", "head_border_rows")
+    res = {k: int(v) for k, v in zip(names, counts)}
+    res.update(grp=sec[0], blocks=sec[1].reshape(-1, 6), syrk_rounds=sec[2].reshape(-1, 4), root_rounds=sec[3].reshape(-1, 2),
+               bb_rounds=sec[4].reshape(-1, 2), g_btm_grp=gather(sec[5]), g_btm=gather(sec[6]), g_bm=gather(sec[7]),
+               g_bslot_grp=gather(sec[8]), aug_ent=sec[9].reshape(-1, 4), aug_ptr=sec[10], aug_idx=sec[11], aug_slot=sec[12],
+               panel_row_begin=sec[13], panel_tasks=sec[14].reshape(-1, 4), bmap=sec[15])
+    return res
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -132,7 +132,7 @@ def _worker(rank, world, port, out, kind):
                                         ("sparse_dissected", 8)])
 def test_bit_identical_between_one_and_several_ranks(tmp_path, kind, world, monkeypatch):
     """2, 4 and 8 processes sharing the GPU: every rank's group buffers reach every rank and all eight group slots are added in one fixed
-    tree (Engine::det_global), so the sums associate as on one rank - equal bits, not just reproducible ones."""
+    tree (DetGroupPlan::global), so the sums associate as on one rank - equal bits, not just reproducible ones."""
     if kind.startswith("sparse"):
         monkeypatch.setenv("PIPS_HIP_SPARSE_ROOT_BAND", _ROOT_ORDER[kind])   # (inherited by the spawned ranks)
     port = 29500 + (os.getpid() % 2000) + {"random": 41, "banded": 43}.get(kind, 47) + 3 * world
