@@ -1064,3 +1064,315 @@ def pivot_root_reference(case, rule=None, variant="right"):
     if rule is None:
         _pivot_cache[key] = (ref, judge)
     return ref, judge
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# solveCompressed judged against a long-double arrowhead reference (tests/test_solve_compressed_reference_cpu.py,
+# tests/test_solve_compressed_judged_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------------
+SOLVE_COMPRESSED_MUTANTS = ("float32_leaves", "block_term_left_out", "border_row_dropped", "root_rhs_entry_off", "x0_entries_swapped", "z0_without_C0_x0")
+
+
+class ArrowheadSystem:
+    """What ArrowheadReference asks of a Problem, TimeCoupledProblem, TwoLinkProblem or GeneralProblem (told apart by its dims): the dimensions, the
+    leaf matrices (lower CSR; diag_scale: with their diagonals times that factor, rounded once, as KktSystem.factorize is handed them), the borders
+    Br_i^T (S x n_leaf, rows in the reduced order [x0 | y0 | ylink | zlink]) and the constant root parts.  The caller's root vector is
+    [x0 | y0 | z0 | ylink | zlink] (S + mz0 entries); red maps the reduced order into it."""
+
+    def __init__(self, prob, diag_scale=1.0):
+        self.prob, self.diag_scale = prob, float(diag_scale)
+        if hasattr(prob, "dims"):
+            self.N, nx, my, mz, self.n0, self.my0, self.mz0, self.myl, self.mzl = prob.dims
+            self.n_primal, self.n_leaf = nx, nx + my + mz
+            self.root_parts = dict(A0=prob.A0.to_scipy(), F0=prob.F0.to_scipy(), G0=prob.G0.to_scipy(), z_diag_link=prob.z_diag_link)
+            self.C0, self.z_diag0 = sp.csr_matrix(prob.C0.to_scipy()), np.asarray(prob.z_diag0, dtype=np.float64)
+        else:
+            self.N, self.n0, self.my0, self.mz0, self.myl, self.mzl = prob.N, prob.n0, 0, 0, prob.myl, 0
+            self.n_primal, self.n_leaf = prob.n_i, prob.n_leaf
+            self.root_parts = dict(F0=prob.F0.to_scipy())
+            self.C0, self.z_diag0 = sp.csr_matrix((0, self.n0)), np.zeros(0)
+        self.S = self.n0 + self.my0 + self.myl + self.mzl
+        self.S_full = self.S + self.mz0
+        head = self.n0 + self.my0
+        self.red = np.concatenate([np.arange(head), np.arange(head + self.mz0, self.S_full)])
+        self.z0_rows = np.arange(head, head + self.mz0)
+        self.x_diag0 = np.asarray(prob.x_diag0, dtype=np.float64)
+
+    def K_lower(self, b):
+        K = self.prob.blocks[b]["K"]
+        Kl = sp.csr_matrix((K.val.copy(), K.colidx, K.rowptr), shape=(K.nrows, K.ncols))
+        if self.diag_scale != 1.0:
+            Kl = sp.csr_matrix(sp.tril(Kl, -1) + sp.diags(self.diag_scale * Kl.diagonal()))
+        Kl.sort_indices()
+        return Kl
+
+    def Bt(self, b):
+        Bt = sp.csr_matrix(self.prob.blocks[b]["Bt"].to_scipy())
+        Bt.sort_indices()
+        return Bt
+
+    def oracle_leaf(self, b, **kw):
+        s = orc.OracleLdl(self.K_lower(b), n_primal=self.n_primal, **kw)
+        s.matrixChanged()
+        return s
+
+    def finalize(self, SC, with_C0):
+        """finalizeKKTdense on SC (S x S, row-major, lower); with_C0 = False: without the eliminated z0 rows' - C0^T diag(z_diag0)^-1 C0"""
+        kw = dict(self.root_parts)
+        if with_C0 and self.mz0:
+            kw.update(C0=self.C0, z_diag=self.z_diag0)
+        return orc.finalize_kkt_dense(SC, self.n0, self.my0, self.myl, self.mzl, self.x_diag0, **kw)
+
+    def root_matrix(self):
+        """K_0 on the caller's root vector (S + mz0, dense, symmetric): finalizeKKTdense of zeros, and with mz0 > 0 the z0 rows [C0 0 diag(z_diag0) 0 0]
+        (z_diag0 = -Omega^-1 is negative as it is handed over: C0 x0 + diag(z_diag0) z0 = b_z0 is the row solveReducedLinkCons eliminates)"""
+        K0 = np.tril(self.finalize(np.zeros((self.S, self.S)), with_C0=False))
+        K0 = K0 + np.tril(K0, -1).T
+        R = np.zeros((self.S_full, self.S_full))
+        R[np.ix_(self.red, self.red)] = K0
+        if self.mz0:
+            C0 = self.C0.toarray()
+            R[np.ix_(self.z0_rows, np.arange(self.n0))] = C0
+            R[np.ix_(np.arange(self.n0), self.z0_rows)] = C0.T
+            R[self.z0_rows, self.z0_rows] = self.z_diag0
+        return R
+
+
+def solve_compressed_fp64(sysm, leaves, Bts, root, b0, bl, mutant=None, block=None):
+    """oracle.solve_compressed restated on copies of one right-hand side (b0: S + mz0, bl: N n_leaf), plain FP64, the same operations in the same
+    order - mutant = None gives its bits - with one defect out of SOLVE_COMPRESSED_MUTANTS, in block `block` (default N // 2) where it has one:
+      float32_leaves       every leaf solution rounded to float32 at the end
+      block_term_left_out  the root right-hand side without that block's Br^T z
+      border_row_dropped   the same term without the block's last non-empty border row
+      root_rhs_entry_off   the largest entry of the root right-hand side (as the root solver is handed it) times 1 + 1e-11
+      x0_entries_swapped   the Ltsolve reads x0 with its first and last entry swapped
+      z0_without_C0_x0     z0 = b_z0 / z_diag0, the C0 x0 term left out (mz0 > 0)"""
+    assert mutant is None or mutant in SOLVE_COMPRESSED_MUTANTS
+    n0, my0, mz0, red = sysm.n0, sysm.my0, sysm.mz0, sysm.red
+    block = sysm.N // 2 if block is None else block
+    b0 = np.array(b0, dtype=np.float64)
+    bs = [np.array(v, dtype=np.float64) for v in np.asarray(bl).reshape(sysm.N, -1)]
+    for i, (bi, sol, Bt) in enumerate(zip(bs, leaves, Bts)):
+        sol.solve(bi)
+        if mutant == "block_term_left_out" and i == block:
+            continue
+        t = Bt @ bi
+        if mutant == "border_row_dropped" and i == block:
+            t[np.nonzero(np.diff(Bt.indptr) > 0)[0][-1]] = 0.0
+        b0[red] -= t
+    rhs = b0[red].copy()
+    if mz0:
+        b3 = b0[n0 + my0:n0 + my0 + mz0] / sysm.z_diag0
+        rhs[:n0] -= sysm.C0.T @ b3
+    if mutant == "root_rhs_entry_off":
+        rhs[np.argmax(np.abs(rhs))] *= 1.0 + 1e-11
+    root.solve(rhs)
+    b0[red] = rhs
+    if mz0:
+        x3 = b0[n0 + my0:n0 + my0 + mz0] - (0.0 if mutant == "z0_without_C0_x0" else sysm.C0 @ rhs[:n0])
+        b0[n0 + my0:n0 + my0 + mz0] = x3 / sysm.z_diag0
+    x0 = b0[red]
+    if mutant == "x0_entries_swapped":
+        x0[[0, -1]] = x0[[-1, 0]]
+    for bi, sol, Bt in zip(bs, leaves, Bts):
+        t = Bt.T @ x0
+        sol.solve(t)
+        bi -= t
+    xl = np.concatenate(bs)
+    return b0, (xl.astype(np.float32).astype(np.float64) if mutant == "float32_leaves" else xl)
+
+
+class ArrowheadReference:
+    """The whole system solveCompressed solves, A = [[diag(K_i), Br_i], [Br_i^T, K_0]] as one CSR on [x_1 .. x_N | x0 y0 z0 ylink zlink], and a set of
+    right-hand sides (row k of B0 and BL):
+      X_star  scipy's splu on A, then refinement steps on a long-double x (residual in long double, correction added in long double) until a
+              correction is below 2^-58 max|x|, rounded to FP64 once;
+      X_ref0  the plain FP64 algorithm of the same kind: oracle.solve_compressed over unrefined oracle leaves and LAPACK's dsytrf / dsytrs on the
+              oracle's own FP64 Schur complement (unrefined solves of the border columns, finalizeKKTdense);
+    and per right-hand side the ratios of three measures of a solution to the same measure of X_ref0, at least 2^-53 of its scale:
+      backward      eta = ||b - A x||inf / (||A||inf ||x||inf + ||b||inf) over the whole system
+      root_rows     the same quotient over the root rows alone: ||r_0||inf / (||A_0||inf ||x||inf + ||b_0||inf), A_0 the root rows of A
+      forward_root  max|x - x*| over the root part, scale max|x*| there;  forward_leaf: the same over the leaf part.
+    A solution of the all-zero right-hand side that is not exactly zero, and anything non-finite, has every ratio inf.  Computed once, read-only."""
+    MAX_STEPS = 8
+
+    def __init__(self, sysm, B0, BL):
+        import scipy.sparse.linalg as spl
+        self.sys = sysm
+        N, nl, Sf = sysm.N, sysm.n_leaf, sysm.S_full
+        self.n_leaves = N * nl
+        self.B0 = np.ascontiguousarray(np.atleast_2d(B0), dtype=np.float64)
+        self.BL = np.ascontiguousarray(np.atleast_2d(BL), dtype=np.float64)
+        assert self.B0.shape[1] == Sf and self.BL.shape[1] == self.n_leaves and self.B0.shape[0] == self.BL.shape[0]
+        self.Bts = [sysm.Bt(b) for b in range(N)]
+        E = sp.csr_matrix((np.ones(sysm.S), (sysm.red, np.arange(sysm.S))), shape=(Sf, sysm.S))
+        Btf = [sp.csr_matrix(E @ Bt) for Bt in self.Bts]
+        Kl = [sysm.K_lower(b) for b in range(N)]
+        A = sp.bmat([[sp.block_diag([K + sp.tril(K, -1).T for K in Kl]), sp.vstack([B.T for B in Btf])],
+                     [sp.hstack(Btf), sp.csr_matrix(sysm.root_matrix())]], format="csr")
+        A.sum_duplicates()
+        A.sort_indices()
+        assert A.shape == (self.n_leaves + Sf,) * 2 and np.all(np.diff(A.indptr) > 0) and abs(A - A.T).max() == 0.0
+        self.A = A
+        self._indptr, self._indices, self._data = A.indptr[:-1].copy(), A.indices.copy(), A.data.astype(np.longdouble)
+        rowsum = np.asarray(abs(A).sum(axis=1)).ravel()
+        self.norm_A, self.norm_A_root = float(rowsum.max()), float(rowsum[self.n_leaves:].max())
+        self.B = np.hstack([self.BL, self.B0])
+        # x*
+        lu = spl.splu(A.tocsc())
+        X = lu.solve(self.B.T.copy()).T.astype(np.longdouble)
+        self.refinement_steps, self.converged = 0, False
+        while self.refinement_steps < self.MAX_STEPS and not self.converged:
+            dX = lu.solve(self._residual(X).astype(np.float64).T.copy()).T
+            X = X + dX.astype(np.longdouble)
+            self.refinement_steps += 1
+            self.converged = bool(np.all(np.abs(dX).max(axis=1) <= 2.0 ** -58 * np.abs(X).max(axis=1).astype(np.float64)))
+        self.X_star = X.astype(np.float64)
+        # x_ref0
+        self.leaves0 = [sysm.oracle_leaf(b, refine_steps=0) for b in range(N)]
+        self.leaf_inertia = [s.get_inertia() for s in self.leaves0]
+        SC = np.zeros((sysm.S, sysm.S))
+        for s, Bt in zip(self.leaves0, self.Bts):
+            orc.add_term_to_schur_compl_blocked(SC, s, Bt)
+        self.SC_ref0 = np.tril(sysm.finalize(SC, with_C0=True))
+        self.root0 = orc.DenseRootSolver(sysm.S)
+        self.root0.matrixChanged(self.SC_ref0)
+        self.root_inertia = self.root0.get_inertia()
+        self.X_ref0 = np.empty_like(self.B)
+        for k in range(self.B.shape[0]):
+            b0, bs = self.B0[k].copy(), [v.copy() for v in self.BL[k].reshape(N, -1)]
+            orc.solve_compressed(b0, bs, self.leaves0, self.Bts, self.root0, sysm.n0, sysm.my0, sysm.mz0, sysm.myl, sysm.mzl, C0=sysm.C0, z_diag_reg=sysm.z_diag0)
+            self.X_ref0[k] = np.concatenate(bs + [b0])
+        self.is_zero_rhs = ~self.B.any(axis=1)
+        self.measures_ref0 = self.measures(self.X_ref0[:, self.n_leaves:], self.X_ref0[:, :self.n_leaves])
+        nl_ = self.n_leaves
+        self.scales = dict(backward=np.ones(len(self.B)), root_rows=np.ones(len(self.B)), forward_root=np.abs(self.X_star[:, nl_:]).max(axis=1),
+                           forward_leaf=np.abs(self.X_star[:, :nl_]).max(axis=1))
+        for a in [self.B0, self.BL, self.B, self.X_star, self.X_ref0, self.SC_ref0] + list(self.measures_ref0.values()) + list(self.scales.values()):
+            a.setflags(write=False)
+
+    def mutant(self, k, which, block=None):
+        """(x0, xl) of right-hand side k by X_ref0's algorithm with one defect (solve_compressed_fp64)"""
+        return solve_compressed_fp64(self.sys, self.leaves0, self.Bts, self.root0, self.B0[k], self.BL[k], which, block)
+
+    def _residual(self, X, rows=None):
+        """B - A X per right-hand side (X: one solution per row, [leaves | root]), formed in long double from the CSR of A"""
+        B = self.B if rows is None else self.B[rows]
+        return B.astype(np.longdouble) - np.add.reduceat(self._data[None, :] * np.asarray(X, dtype=np.longdouble)[:, self._indices], self._indptr, axis=1)
+
+    def measures(self, X0, XL, k=None):
+        """backward, root_rows, forward_root, forward_leaf (see above) of the solutions (X0: root part, XL: leaf part; one per row) of all the
+        right-hand sides, or of right-hand side k alone"""
+        rows = np.arange(len(self.B)) if k is None else np.array([k])
+        X = np.hstack([np.atleast_2d(XL), np.atleast_2d(X0)]).astype(np.float64)
+        assert X.shape == (len(rows), self.A.shape[0])
+        nl = self.n_leaves
+        with np.errstate(all="ignore"):
+            R = np.abs(self._residual(X, rows)).astype(np.float64)
+            xn = np.abs(X).max(axis=1)
+            out = {}
+            for name, num, den in (("backward", R.max(axis=1), self.norm_A * xn + np.abs(self.B[rows]).max(axis=1)),
+                                   ("root_rows", R[:, nl:].max(axis=1), self.norm_A_root * xn + np.abs(self.B0[rows]).max(axis=1))):
+                q = np.where(num == 0.0, 0.0, num / np.where(den > 0.0, den, 1.0))
+                out[name] = np.where(np.isfinite(q), q, np.inf)
+            for name, sl in (("forward_root", slice(nl, None)), ("forward_leaf", slice(0, nl))):
+                q = np.abs(X[:, sl] - self.X_star[rows][:, sl]).max(axis=1)
+                out[name] = np.where(np.isfinite(q), q, np.inf)
+        bad = ~np.isfinite(X).all(axis=1) | (self.is_zero_rhs[rows] & X.any(axis=1))
+        return {name: np.where(bad, np.inf, q) for name, q in out.items()}
+
+    def ratios(self, X0, XL, k=None):
+        """the four measures, each over max(the same measure of X_ref0, 2^-53 x its scale): what the margin M bounds"""
+        rows = np.arange(len(self.B)) if k is None else np.array([k])
+        out = {}
+        for name, q in self.measures(X0, XL, k).items():
+            den = np.maximum(self.measures_ref0[name][rows], UNIT_ROUNDOFF * self.scales[name][rows])
+            with np.errstate(all="ignore"):
+                r = np.where(q == 0.0, 0.0, q / np.where(den > 0.0, den, 1.0))
+            out[name] = np.where(np.isfinite(r), r, np.inf)
+        return out
+
+    def accepts(self, X0, XL, M, k=None):
+        """the predicate, per right-hand side: all four ratios within M"""
+        assert M <= UNREFINED_M_CAP
+        return np.all([r <= M for r in self.ratios(X0, XL, k).values()], axis=0)
+
+
+# the cases: name -> how the problem is built.  Shapes are the smallest that still select each kernel (see the GPU module's docstring).
+ARROWHEAD_RHS = ("gaussian", "gaussian2", "b0_zero", "b_leaf_zero", "unit_b0_last", "zero")
+ARROWHEAD_SCHUR_WIDTHS = (1, 127, 128, 129, 257)
+ARROWHEAD_CASES = ("small", "dense_tail", "time_coupled") + tuple(f"width{S}" for S in ARROWHEAD_SCHUR_WIDTHS) + \
+                  ("hetero129", "general", "general_mz0", "two_link_6", "two_link_30", "small_scaled", "time_coupled_scaled")
+ARROWHEAD_WAY2_CASES = ("small", "time_coupled")          # the cases whose followers go way 2 on trust: no mutant may be skipped there
+# (case, mutant) that the predicate cannot be asked to reject on every Gaussian right-hand side - at most one per case, none on a way-2 case:
+#   width1: one Schur row, x0 has no two entries to swap;
+#   two_link_30: 580 linking rows - x_ref0's own forward error is 1e-12 of max|x|, and a root right-hand side off by a relative 1e-11 measures
+#   73 and 58 units of x_ref0's backward error on the two Gaussian right-hand sides: rejected on one of them (asserted), not on both
+ARROWHEAD_NOT_DISTINGUISHABLE = {"width1": "x0_entries_swapped", "two_link_30": "root_rhs_entry_off"}
+ARROWHEAD_GENERAL_DIMS = (3, 400, 160, 80, 20, 6, 0, 9, 5)
+ARROWHEAD_SECOND_DIAG_SCALE = 1.3
+
+
+def _arrowhead_narrow_diagonals(prob, seed):
+    # the primal diagonals (leaves and x0) span 1e-2 .. 1e2 instead of the generator's 1e-4 .. 1e4, as in unrefined_batch_problem and schur_problem:
+    # over eight decades, with the dual regularisation of 1e-8, the plain FP64 algorithm itself loses five digits of x0 (forward error 1e-12 .. 1e-11
+    # of max|x0| on the small and the two-link shapes), and a root right-hand side wrong at a relative 1e-11 passed the predicate at M = 64
+    for b, blk in enumerate(prob.blocks, 1):
+        blk["diag"][:prob.n_i] = pa.gen_diagonal(seed, b, prob.n_i, -2.0, 2.0)
+        blk["K"].val[blk["dpos"]] = blk["diag"]
+    prob.x_diag0 = pa.gen_diagonal(seed, 0, prob.n0, -2.0, 2.0)
+    return prob
+
+
+def arrowhead_problem(case):
+    """(problem, diag_scale) of a case of ARROWHEAD_CASES; problems are built once and shared"""
+    scale = ARROWHEAD_SECOND_DIAG_SCALE if case.endswith("_scaled") else 1.0
+    name = case[:-len("_scaled")] if case.endswith("_scaled") else case
+    key = ("problem", name)
+    if key not in _arrowhead_cache:
+        if name == "small":
+            prob = _arrowhead_narrow_diagonals(Problem(5, 3, 200, 100, 12, 10, 0.05), 5)
+        elif name == "dense_tail":
+            prob = _arrowhead_narrow_diagonals(Problem(3, 4, 1000, 500, 100, 100, 0.01), 3)
+        elif name == "time_coupled":
+            prob = _arrowhead_narrow_diagonals(TimeCoupledProblem(5, 3, 3000, 1500, 10, 8, 6), 5)
+        elif name.startswith("width"):
+            prob = schur_problem(170, int(name[5:]), 1, "full")
+        elif name == "hetero129":
+            prob = schur_problem(400, 129, 3, "hetero")
+        elif name.startswith("general"):
+            from tests.test_general_gpu import GeneralProblem
+            dims = list(ARROWHEAD_GENERAL_DIMS)
+            dims[6] = 4 if name == "general_mz0" else 0
+            prob = GeneralProblem(21, *dims, 0.02)
+        else:
+            from tests.test_sparse_root_gpu import TwoLinkProblem
+            N, n_i, my_i, n0, L = {"two_link_6": (6, 120, 60, 4, 3), "two_link_30": (30, 60, 30, 5, 20)}[name]
+            prob = _arrowhead_narrow_diagonals(TwoLinkProblem(77, N, n_i, my_i, n0, L, 5.0 / n_i), 77)
+        _arrowhead_cache[key] = prob
+    return _arrowhead_cache[key], scale
+
+
+def arrowhead_rhs(sysm, seed):
+    """(B0, BL), one right-hand side per row, in the order of ARROWHEAD_RHS: two Gaussian ones, one with b0 = 0, one with b_leaf = 0 (only the
+    border path carries anything in the forward half), e of the last Schur index in b0 alone, and the all-zero one"""
+    rng = np.random.default_rng(seed)
+    B0, BL = rng.standard_normal((6, sysm.S_full)), rng.standard_normal((6, sysm.N * sysm.n_leaf))
+    B0[2] = 0.0
+    BL[3] = 0.0
+    B0[4], BL[4] = 0.0, 0.0
+    B0[4, sysm.S_full - 1] = 1.0
+    B0[5], BL[5] = 0.0, 0.0
+    return B0, BL
+
+
+_arrowhead_cache = {}
+
+
+def arrowhead_reference(case):
+    """The shared ArrowheadReference of a case of ARROWHEAD_CASES (.sys.prob: its problem)"""
+    if case not in _arrowhead_cache:
+        prob, scale = arrowhead_problem(case)
+        sysm = ArrowheadSystem(prob, scale)
+        _arrowhead_cache[case] = ArrowheadReference(sysm, *arrowhead_rhs(sysm, 4000 + ARROWHEAD_CASES.index(case)))
+    return _arrowhead_cache[case]
