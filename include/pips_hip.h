@@ -56,6 +56,11 @@ int pips_hip_ldl_set_deterministic(void* handle, int on);
 int pips_hip_ldl_analyze(void* handle);
 /* = DoubleLinearSolver::matrixChanged(): numeric LDL^T of the current values (host array of length nnz, CSR order) */
 int pips_hip_ldl_factor(void* handle, const double* vals_host);
+/* the values alone (host array of length nnz, CSR order), the leaf handle's twin of pips_hip_batch_set_values: uploads them and keeps the
+ * factors.  Later solves refine against these values with the factors they have - the sweeps read the factors only, the residual and the
+ * measure of the refinement read the values.  PIPS_ERR_STATE before the first factorisation, and for a handle whose newest factors are a
+ * batch's (pips_hip_ldl_factor_schur_batch). */
+int pips_hip_ldl_set_values(void* handle, const double* K_val_host);
 /* = DoubleLinearSolver::solve(int nrhss, double* rhss, int* colSparsity) (PardisoSolver.C:276-352): nrhs contiguous
  * right-hand sides of length ld >= n, overwritten by the solutions; all-zero right-hand sides are left out of the transfer and
  * of the solve, as the reference's packing does.  nrhs = 1 is DoubleLinearSolver::solve(Vector&). */
@@ -94,7 +99,8 @@ int pips_hip_ldl_solve_batch(void* const* handles, int n, double* const* rhs_ino
 int pips_hip_ldl_solve_batch_dev(void* const* handles, int n, double* x_dev);
 int pips_hip_ldl_inertia_batch(void* const* handles, int n, int* pos, int* neg, int* zero);
 /* diagnostics of the symbolic phase: what[0]=nnz(L) what[1]=n_head what[2]=tail m what[3]=#head supernodes
- * what[4]=#levels what[5]=factor flops (rounded); and what[6]=refinement steps the last solve took, what[7]=how the last solve(nrhs) went
+ * what[4]=#levels what[5]=factor flops (rounded); and what[6]=refinement steps the last solve took (solve(nrhs) goes chunk by chunk: the
+ * steps of the last chunk that took any, not their sum), what[7]=how the last solve(nrhs) went
  * (0 one sweep per right-hand side, 1 interleaved panels on the matrix pipe, 2 the same with the deterministic forward substitution) */
 int pips_hip_ldl_info(void* handle, int64_t* what, int n_what);
 /* copies the fill-reducing permutation (perm[k] = original index eliminated k-th) */
@@ -180,7 +186,9 @@ double pips_hip_batch_last_refinement_measure(void* handle);
 int pips_hip_batch_last_refinement_steps(void* handle);
 /* symbolic phase for all blocks (n_threads host threads) + device setup */
 int pips_hip_batch_analyze(void* handle, int n_threads);
-/* upload all values of K_b (CSR order, host) — needed once; afterwards only diagonals change (a2) */
+/* upload all values of K_b (CSR order, host) — needed once; afterwards only diagonals change (a2).  It only copies: factors that exist
+ * stay as they are and stay in use (it has always behaved this way), so solves between this call and the next pips_hip_batch_factor sweep
+ * with the old factors and refine against the new values */
 int pips_hip_batch_set_values(void* handle, int b, const double* K_val_host);
 /* K diagonals of all blocks from one flat device vector (block after block, rows in [x|y|z] order):
  * put_primal_diagonal / clear_dual_equality_diagonal / put_dual_inequalites_diagonal / add_regularization_local_kkt

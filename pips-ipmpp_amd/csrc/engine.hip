@@ -1886,12 +1886,16 @@ struct Engine : EngineAnalysis, BatchLayout {
       const bool det_multi = deterministic && head_slots && use_multi(nrhs) && vslots_total > 0 && (double)vslots_total * MQ * sizeof(double) <= 4e9;
       last_multi_path = det_multi ? 2 : (deterministic || !use_multi(nrhs)) ? 0 : 1;
       if (deterministic && !det_multi) {   // one right-hand side at a time through the atomics-free sweeps
-         for (int r = 0; r < nrhs; ++r)
+         int steps = 0;   // (as below: the steps of the last right-hand side that took any)
+         for (int r = 0; r < nrhs; ++r) {
             if (int rc = solve(X_dev + (long long)r * x_stride)) return rc;
+            if (last_refine_steps > 0) steps = last_refine_steps;
+         }
+         last_refine_steps = steps;
          return PIPS_OK;
       }
       if (det_multi && !d_mvslot) PIPS_TRY(d_mvslot.alloc((size_t)vslots_total * MQ));
-      last_refine_steps = 0;   // (over the chunks: the steps of the last one that took any)
+      last_refine_steps = 0;   // (over the chunks: the steps of the last one that took any - not their sum)
       const bool multi = use_multi(nrhs);
       const int chunk_max = det_multi ? MQ : multi ? MULTI_CHUNK_MAX : 32;   // (the per-right-hand-side sweeps keep their 32 work vectors)
       int rc0 = ensure_multi_buffers(std::min(nrhs, chunk_max));
@@ -1904,6 +1908,7 @@ struct Engine : EngineAnalysis, BatchLayout {
                                      (size_t)n_total * sizeof(double), nr, hipMemcpyDeviceToDevice, stream));
          int rc = multi ? solve_once_multi(X, nr, x_stride, d_mx_xw) : solve_once(X, nr, x_stride, d_mx_xw);
          if (rc) return rc;
+         int chunk_steps = 0;
          for (int it = 0; it < refine_steps; ++it) {
             HIP_TRY(hipMemcpyAsync(d_mx_res, d_mx_rhs, (size_t)nr * n_total * sizeof(double), hipMemcpyDeviceToDevice, stream));
             // r = rhs - K x for every right-hand side: x at stride x_stride, r contiguous -> a contiguous view of x where the caller's is not
@@ -1946,8 +1951,9 @@ struct Engine : EngineAnalysis, BatchLayout {
             if (rc) return rc;
             if (n_fix < nr) hipLaunchKernelGGL(k_maxpy_idx, dim3(grid_for(n_total, 256, 1024), n_fix), dim3(256), 0, stream, X, x_stride, d_mx_res, n_total, 1.0, n_total, d_midx);
             else hipLaunchKernelGGL(k_maxpy, dim3(grid_for(n_total, 256, 1024), nr), dim3(256), 0, stream, X, x_stride, d_mx_res, n_total, 1.0, n_total);
-            ++last_refine_steps;
+            ++chunk_steps;
          }
+         if (chunk_steps > 0) last_refine_steps = chunk_steps;
       }
       HIP_TRY(hipGetLastError());
       return PIPS_OK;
@@ -3215,6 +3221,17 @@ int pips_hip_ldl_factor(void* handle, const double* vals_host) {
    h->newest_in_group = false;      // (the batch's copy of this leaf is the older one now)
    HIP_TRY(hipStreamSynchronize(h->eng.stream));
    return PIPS_OK;
+}
+
+// The values alone: the twin of pips_hip_batch_set_values for a leaf handle.  The factors stay as they are - the solve sweeps read only
+// them - and the residual and the measure of the refinement read the new values: later solves refine against these values with the
+// factors they have.  (A handle whose newest factors are a group's has its values there, not here.)
+int pips_hip_ldl_set_values(void* handle, const double* K_val_host) {
+   LdlHandle* h = (LdlHandle*)handle;
+   if (!h || !K_val_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_set_values: bad arguments");
+   if (ldl_uses_group(h)) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_set_values: the newest factors of this handle are a batch's (pips_hip_ldl_factor_schur_batch)");
+   if (!h->eng.factored) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_set_values: factor first");
+   return pips_hip_batch_set_values(&h->eng, 0, K_val_host);
 }
 
 // The leaf's Schur term without dense border columns over PCIe.  The border Br_i^T (S x n CSR, rows = Schur column ids: the

@@ -49,7 +49,7 @@ lib.pips_hip_device_bytes_live.restype = C.c_longlong
 SYMBOLS = [
     "pips_hip_last_error", "pips_hip_device_count",
     "pips_hip_ldl_create", "pips_hip_ldl_set_inertia_hint", "pips_hip_ldl_set_pivot_rule", "pips_hip_ldl_set_refinement", "pips_hip_ldl_set_refinement_backward_error", "pips_hip_ldl_set_deterministic",
-    "pips_hip_ldl_analyze", "pips_hip_ldl_factor", "pips_hip_ldl_solve", "pips_hip_ldl_inertia", "pips_hip_ldl_info",
+    "pips_hip_ldl_analyze", "pips_hip_ldl_factor", "pips_hip_ldl_set_values", "pips_hip_ldl_solve", "pips_hip_ldl_inertia", "pips_hip_ldl_info",
     "pips_hip_ldl_get_perm", "pips_hip_ldl_set_border", "pips_hip_ldl_factor_schur", "pips_hip_ldl_destroy",
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
     "pips_hip_ldl_inertia_batch",
@@ -368,6 +368,13 @@ class HipLdlSolver:
 
     def matrixChanged(self):
         _check(lib.pips_hip_ldl_factor(self._h, _ptr(self.K.val)), "pips_hip_ldl_factor")
+
+    def set_values_only(self, vals):
+        """Upload values (CSR order, length nnz) and keep the factors: later solves sweep with the factors of the last matrixChanged() and
+        refine against these values."""
+        vals = _f64(vals)
+        assert vals.shape == self.K.val.shape
+        _check(lib.pips_hip_ldl_set_values(self._h, _ptr(vals)), "pips_hip_ldl_set_values")
 
     def set_border(self, Bt):
         """Declare Br^T (Csr, S rows = Schur column ids over the n rows of K) before analyze(): level 1.5 of INTEGRATION.md."""

@@ -1376,3 +1376,393 @@ def arrowhead_reference(case):
         sysm = ArrowheadSystem(prob, scale)
         _arrowhead_cache[case] = ArrowheadReference(sysm, *arrowhead_rhs(sysm, 4000 + ARROWHEAD_CASES.index(case)))
     return _arrowhead_cache[case]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# refinement residual, measure and column choice judged row by row (tests/test_refinement_reference_cpu.py, tests/test_refinement_judged_gpu.py)
+# ----------------------------------------------------------------------------------------------------------------------
+# The lever: set_values only copies into the device's CSR values and the solve sweeps never read them.  factor() with K1, then values K2 =
+# K1 + E: x0 = K1^-1 b, the refinement residual is b - K2 x0 = -E x0 + rounding - a signal of any size in any row - and one correction
+# leaves K1 x1 = b - E x0 row by row.
+REFINE_FULL_LONG_ROW = 512            # csrc/records.h FULL_LONG_ROW: longer full rows go to k_full_spmv_sub_long (the CPU module reads the header)
+REFINE_SIGNAL = 2.0 ** 14             # every row's |(E x*)_i| over noise_b: 256 x UNREFINED_M_CAP
+REFINE_COLUMN_GAP = 2.0 ** 20         # eta* of the dirty columns over eta* of the others
+REFINE_EPS_WORST, REFINE_EPS_OTHER = 2.0 ** -10, 2.0 ** -13
+REFINE_FAINT = 2.0 ** -24             # the part on J of a faint column's xs, relative to a dirty one's
+
+
+def refine_perturbed_values(K, eps, seed, rows=None, coherent=False):
+    """K2's values (CSR order of the lower K): K_ij (1 + s_ij eps), s_ij = +-1 at random, on every stored entry - or on those with row and
+    column in `rows` (E confined to J x J) - but the block's largest entries (max|K1_b| is taken at factor() and kept).  coherent: s_ij =
+    sign(K_ij), E = eps |K1|: against a positive x no row of E x cancels."""
+    val = np.asarray(K.val, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    s = np.sign(val) if coherent else rng.choice([-1.0, 1.0], len(val))
+    touch = np.abs(val) < np.abs(val).max()
+    if rows is not None:
+        inJ = np.zeros(K.nrows, bool)
+        inJ[rows] = True
+        row_of = np.repeat(np.arange(K.nrows), np.diff(K.rowptr))
+        touch &= inJ[row_of] & inJ[K.colidx]
+    return np.where(touch, val * (1.0 + s * eps), val)
+
+
+class RefinementReference:
+    """One block: K1 (lower CSR, the values that are factorised), K2's values (the ones the refinement sees), right-hand sides (one per row
+    of B).  Holds the full symmetric K1, K2 and E = K2 - K1 (exact) in long double; XS = x*, the oracle's twice refined solution of K1 x = b;
+    X1S = x1* = x* - K1^-1 E x*; X0_ref, X1_ref, X2_ref: the oracle's unrefined FP64 solve and one / two FP64 corrections against K2
+    (refine_fp64).  Everything residual-like is summed in long double, per right-hand side, over every row.  Computed once, read-only."""
+
+    def __init__(self, K, n_primal, val2, B):
+        self.K, self.n_primal, self.n = K, n_primal, K.nrows
+        self.val1, self.val2 = np.asarray(K.val, dtype=np.float64).copy(), np.asarray(val2, dtype=np.float64).copy()
+        nnz = len(self.val1)
+        src = sp.csr_matrix((np.arange(1, nnz + 1, dtype=np.float64), K.colidx, K.rowptr), shape=(self.n, self.n))
+        full = (src + sp.tril(src, -1).T).tocsr()
+        full.sort_indices()
+        assert np.all(np.diff(full.indptr) > 0)
+        self.indptr, self.indices = full.indptr.copy(), full.indices.copy()
+        self.src = full.data.astype(np.int64) - 1                          # the stored entry a full entry reads (the device's fsrc)
+        self.row_of = np.repeat(np.arange(self.n), np.diff(self.indptr))
+        self.upper = self.indices > self.row_of                            # the copies above the diagonal
+        self.row_len = np.diff(self.indptr)
+        self.K1 = self.val1[self.src].astype(np.longdouble)
+        self.K2 = self.val2[self.src].astype(np.longdouble)
+        self.E = self.K2 - self.K1                                         # (exact: neighbours in FP64)
+        self.norm_K1 = float(np.add.reduceat(np.abs(self.val1[self.src]), self.indptr[:-1]).max())
+        self.amax1 = float(np.abs(self.val1).max())
+        assert float(np.abs(self.val2).max()) == self.amax1                # E leaves the largest entry alone
+        self.B = np.ascontiguousarray(np.atleast_2d(B), dtype=np.float64)
+        Ksp = sp.csr_matrix((self.val1.copy(), K.colidx, K.rowptr), shape=(self.n, self.n))
+        self._o0 = orc.OracleLdl(Ksp, n_primal=n_primal, refine_steps=0)
+        self._o0.matrixChanged()
+        o2 = orc.OracleLdl(Ksp, n_primal=n_primal, refine_steps=2)
+        o2.matrixChanged()
+        self.inertia = self._o0.get_inertia()
+        self.XS = o2.solve(self.B.copy())
+        self.EXS = self.matvec(self.E, self.XS)
+        self.X1S = self.XS - o2.solve(np.ascontiguousarray(self.EXS.astype(np.float64)))
+        self.EX1S = self.matvec(self.E, self.X1S)
+        self.X0_ref = self.solve0(self.B)
+        self.X1_ref = refine_fp64(self, self.X0_ref, 1)
+        self.X2_ref = refine_fp64(self, self.X1_ref, 1)
+        for a in (self.B, self.XS, self.X1S, self.X0_ref, self.X1_ref, self.X2_ref, self.val1, self.val2):
+            a.setflags(write=False)
+
+    def solve0(self, R):
+        """the oracle's unrefined FP64 solve with the factors of K1, one right-hand side per row"""
+        return self._o0.solve(np.ascontiguousarray(np.atleast_2d(R), dtype=np.float64).copy())
+
+    def matvec(self, data, X):
+        """(A x) per row of X, A the full symmetric matrix with the entries `data` - in the precision of data and X (long double)"""
+        X = np.atleast_2d(X).astype(data.dtype)
+        return np.add.reduceat(data[None, :] * X[:, self.indices], self.indptr[:-1], axis=1)
+
+    def noise(self, X):
+        """noise_b = 2^-53 (||K1_b||inf ||x_b||inf + ||b_b||inf) per right-hand side"""
+        return UNIT_ROUNDOFF * (self.norm_K1 * np.abs(np.atleast_2d(X)).max(axis=1) + np.abs(self.B).max(axis=1))
+
+    def _ratios(self, X, target):
+        X = np.atleast_2d(X)
+        with np.errstate(all="ignore"):
+            dev = np.abs(self.matvec(self.K1, X) - target).max(axis=1).astype(np.float64)
+            nz = self.noise(X)
+            q = np.where(dev == 0.0, 0.0, dev / np.where(nz > 0.0, nz, 1.0))
+        return np.where(np.isfinite(q), q, np.inf)
+
+    def ratios_uncorrected(self, X):
+        """max_i |K1 x - b|_i / noise_b per right-hand side"""
+        return self._ratios(X, self.B.astype(np.longdouble))
+
+    def ratios_once(self, X):
+        """max_i |K1 x - (b - E x*)|_i / noise_b"""
+        return self._ratios(X, self.B.astype(np.longdouble) - self.EXS)
+
+    def ratios_twice(self, X):
+        """max_i |K1 x - (b - E x1*)|_i / noise_b"""
+        return self._ratios(X, self.B.astype(np.longdouble) - self.EX1S)
+
+    def uncorrected(self, X, M):
+        assert M <= UNREFINED_M_CAP
+        return self.ratios_uncorrected(X) <= M
+
+    def corrected_once(self, X, M):
+        assert M <= UNREFINED_M_CAP
+        return self.ratios_once(X) <= M
+
+    def corrected_twice(self, X, M):
+        assert M <= UNREFINED_M_CAP
+        return self.ratios_twice(X) <= M
+
+    def signal_over_noise(self, rows=None):
+        """min over the rows (all of them, or `rows`) of |(E x*)_i| / noise_b(x*) per right-hand side"""
+        sig = np.abs(self.EXS).astype(np.float64)
+        if rows is not None:
+            sig = sig[:, rows]
+        nz = self.noise(self.XS)
+        return sig.min(axis=1) / np.where(nz > 0.0, nz, 1.0)
+
+    def target_swap_over_noise(self):
+        """what replacing x0 by x* in the target costs, from x0_ref: max_i |E (x0_ref - x*)|_i / noise_b - to be far below 1"""
+        cost = np.abs(self.matvec(self.E, self.X0_ref.astype(np.longdouble) - self.XS)).max(axis=1).astype(np.float64)
+        nz = self.noise(self.XS)
+        return cost / np.where(nz > 0.0, nz, 1.0)
+
+    def measure_parts(self, X, mode):
+        """(||r||inf, den, gamma) per right-hand side, r = b - K2 x in long double; den of mode 1: max|K1_b| ||x||inf + ||b||inf, of mode 0:
+        ||b||inf; gamma = max_i (nnz_i + 2) 2^-53 (|K2| |x| + |b|)_i - what a row sum in FP64, in any order, can be off by"""
+        X = np.atleast_2d(X)
+        Bl = self.B.astype(np.longdouble)
+        num = np.abs(Bl - self.matvec(self.K2, X)).max(axis=1).astype(np.float64)
+        bn = np.abs(self.B).max(axis=1)
+        den = self.amax1 * np.abs(X).max(axis=1) + bn if mode == 1 else bn
+        gam = ((self.row_len + 2)[None, :] * UNIT_ROUNDOFF * (self.matvec(np.abs(self.K2), np.abs(X)) + np.abs(Bl))).max(axis=1).astype(np.float64)
+        return num, den, gam
+
+    def measures(self, X, mode):
+        """eta*(x) per right-hand side (0 where the denominator is 0, as the device leaves such a block out)"""
+        num, den, _ = self.measure_parts(X, mode)
+        return np.where(den > 0.0, num / np.where(den > 0.0, den, 1.0), 0.0)
+
+
+def refine_fp64(ref, X, steps, mutant=None, row=None):
+    """Host emulation of the device's refinement in plain FP64 on one block: `steps` times x += solve0(b - K2 x).  mutant (tests/
+    test_refinement_reference_cpu.py): "skip_row" - residual row `row` comes out 0; "stale_upper" - the copies above the diagonal still hold
+    K1's values; "shift_rows" - the residual lands one row further down; "long_row_missing" - row `row` is never subtracted (r = b there)."""
+    X = np.array(np.atleast_2d(X), dtype=np.float64)
+    data = ref.val2[ref.src]
+    if mutant == "stale_upper":
+        data = np.where(ref.upper, ref.val1[ref.src], data)
+    A = sp.csr_matrix((data, ref.indices, ref.indptr), shape=(ref.n, ref.n))
+    for _ in range(steps):
+        R = ref.B - (A @ X.T).T
+        if mutant == "skip_row":
+            R[:, row] = 0.0
+        elif mutant == "shift_rows":
+            R = np.roll(R, 1, axis=1)
+        elif mutant == "long_row_missing":
+            R[:, row] = ref.B[:, row]
+        X += ref.solve0(R)
+    return X
+
+
+def refine_measure_fp64(refs, xs, mode, mutant=None):
+    """Host emulation of the device's measure over the blocks of a batch (refs[b], right-hand side 0, xs[b] its iterate), plain FP64: the worst
+    block of ||r_b|| / den_b.  mutant: "worst_block_dropped", "x_norm_missing" (mode 1 without max|K_b| ||x_b||), "second_largest_row"."""
+    q = []
+    for ref, x in zip(refs, xs):
+        A = sp.csr_matrix((ref.val2[ref.src], ref.indices, ref.indptr), shape=(ref.n, ref.n))
+        r = np.sort(np.abs(ref.B[0] - A @ x))
+        num = r[-2] if mutant == "second_largest_row" else r[-1]
+        bn = np.abs(ref.B[0]).max()
+        den = ref.amax1 * np.abs(x).max() + bn if (mode == 1 and mutant != "x_norm_missing") else bn
+        q.append(num / den if den > 0.0 else 0.0)
+    if mutant == "worst_block_dropped":
+        q.remove(max(q))
+    return max(q)
+
+
+def refine_batch_measure(refs, xs, mode):
+    """(eta*, slack) of a batch: eta* = max_b ||r_b|| / den_b in long double from xs[b], slack = max_b gamma_b / den_b + 4 2^-53 eta* - the
+    device's FP64 row sums are the only rounding source in the norms, the quotient adds a few more roundings (derived, not measured)"""
+    eta, slack = 0.0, 0.0
+    for ref, x in zip(refs, xs):
+        num, den, gam = (float(v[0]) for v in ref.measure_parts(np.asarray(x)[None, :], mode))
+        if den > 0.0:
+            eta, slack = max(eta, num / den), max(slack, gam / den)
+    return eta, slack + 4 * UNIT_ROUNDOFF * eta
+
+
+def refine_measure_close(dev, refs, xs, mode):
+    eta, slack = refine_batch_measure(refs, xs, mode)
+    return abs(dev - eta) <= slack
+
+
+# ---- the cases ----
+REFINE_DIAG = (-1.0, 2.0)      # the primal diagonals span 1e-1 .. 1e2 (see refine_block_matrix)
+
+
+def refine_long_row_leaf(seed=23):
+    """(K, n_i, my_i, the long row): primal column 0 sits in 530 of the 560 equality rows, three random entries per row besides, primal
+    diagonal within 1e-1 .. 1e2: the full row of column 0 holds 531 entries, above FULL_LONG_ROW"""
+    n_i, my_i = 700, 560
+    rng = np.random.default_rng(seed)
+    rows, cols = [], []
+    hub = np.sort(rng.choice(my_i, 530, replace=False))
+    for r in range(my_i):
+        cs = rng.choice(np.arange(1, n_i), 3, replace=False)
+        rows += [r] * 3
+        cols += list(cs)
+    rows += list(hub)
+    cols += [0] * len(hub)
+    W = sp.csr_matrix((rng.uniform(0.5, 1.5, len(rows)) * rng.choice([-1.0, 1.0], len(rows)), (rows, cols)), shape=(my_i, n_i))
+    W.sort_indices()
+    K, dpos = pa.kkt_leaf_assemble(n_i, pa.Csr(my_i, n_i, W.indptr, W.indices, W.data))
+    K.val[dpos] = np.concatenate([pa.gen_diagonal(seed, 1, n_i, *REFINE_DIAG), -1e-8 * np.ones(my_i)])
+    return K, n_i, my_i, 0
+
+
+# the blocks of the one-right-hand-side batch, in the batch's order: Problem blocks of 127, 256, 257 and 2049 rows, the long-row leaf (third),
+# a time-coupled block of 900 rows
+REFINE_BATCH_BLOCKS = ("p127", "p256", "long_row", "p257", "tc900", "p2049")
+REFINE_BATCH_WORST = (0, 3, 5, 2)        # the block with the large perturbation: first, middle, last, the long-row block
+REFINE_BIG_SHAPE = (11000, 5500)         # one time-coupled block of 16 500 rows: absmax_chunks() = 2
+_REFINE_RANDOM = {"p127": (85, 42, 0.1), "p256": (171, 85, 0.1), "p257": (171, 86, 0.1), "p2049": (1366, 683, 6.0 / 1366)}
+
+
+def refine_block_matrix(name):
+    """(K, n_primal) of a block of the table (or "big").  Every primal diagonal is gen_diagonal(.., -1, 2), 1e-1 .. 1e2: the factors grow
+    like 1 / (smallest primal diagonal), and with 1e-2 the oracle's own unrefined residual stands 7 .. 15 x noise_b on the blocks of 256, 2049
+    and on the long-row leaf - `uncorrected` is a statement about the residual's rounding level, and the reference has to pass it at M = 4.
+    (The time-coupled blocks: with the generator's default 1e-4 .. 1e4, ||K1||inf = 1e4 lifts noise_b above the signal of 2^-13.)"""
+    k = ("matrix", name)
+    if k not in _refine_cache:
+        if name == "long_row":
+            K, n_i, _, _ = refine_long_row_leaf()
+        elif name in ("tc900", "big"):
+            n_i, my_i = (600, 300) if name == "tc900" else REFINE_BIG_SHAPE
+            blk = TimeCoupledProblem(5, 1, n_i, my_i, 0, 0, 6).blocks[0]
+            K = blk["K"]
+            K.val[blk["dpos"][:n_i]] = pa.gen_diagonal(5, 1, n_i, *REFINE_DIAG)
+        else:
+            n_i, my_i, rho = _REFINE_RANDOM[name]
+            K = Problem(17, 1, n_i, my_i, 0, 0, rho, diag_lo=REFINE_DIAG[0], diag_hi=REFINE_DIAG[1]).blocks[0]["K"]
+        K.val.setflags(write=False)
+        _refine_cache[k] = (K, n_i)
+    return _refine_cache[k]
+
+
+def refine_generic_xs(n, seed):
+    """|xs_i| in [1, 2] with random signs"""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(1.0, 2.0, n) * rng.choice([-1.0, 1.0], n)
+
+
+def _refine_rhs(K, xs):
+    """b = K1 xs per row of xs, FP64 (any b will do: x* is defined by b)"""
+    Ks = sp.csr_matrix((np.asarray(K.val), K.colidx, K.rowptr), shape=(K.nrows, K.nrows))
+    Kf = (Ks + sp.tril(Ks, -1).T).tocsr()
+    return np.ascontiguousarray((Kf @ np.atleast_2d(xs).T).T)
+
+
+_refine_cache = {}
+
+
+def refine_block_reference(name, eps):
+    """The shared RefinementReference of a block of the table ("big" too) under E = eps (+-1) K_ij on every stored entry, one right-hand side
+    b = K1 xs"""
+    k = ("block", name, eps)
+    if k not in _refine_cache:
+        K, n_i = refine_block_matrix(name)
+        seed = 7000 + sum(map(ord, name))
+        _refine_cache[k] = RefinementReference(K, n_i, refine_perturbed_values(K, eps, seed), _refine_rhs(K, refine_generic_xs(K.nrows, seed + 1)))
+    return _refine_cache[k]
+
+
+def refine_batch_references(worst):
+    """the references of the six blocks, block `worst` perturbed by 2^-10 and the others by 2^-13"""
+    return [refine_block_reference(name, REFINE_EPS_WORST if b == worst else REFINE_EPS_OTHER) for b, name in enumerate(REFINE_BATCH_BLOCKS)]
+
+
+# several right-hand sides on one handle: which columns are dirty.  Column 1 is all zero (but in "all"); the others are clean (xs = 0 on J)
+# and, every third of them, faint (xs on J scaled by REFINE_FAINT: below tau, yet telling "corrected" from "left alone" in its rows)
+REFINE_MULTI_NRHS = (2, 8, 33, 257)
+REFINE_MULTI_SETS = ("all", "none", "one", "mixed", "first_chunk", "second_chunk", "all_entries")
+
+
+def refine_multi_kinds(nrhs, dirty_set):
+    """per column: "dirty", "clean", "faint" or "zero" """
+    if dirty_set in ("all", "all_entries"):
+        return ["dirty"] * nrhs
+    if dirty_set == "none":
+        dirty = set()
+    elif dirty_set == "one":
+        dirty = {0 if nrhs == 2 else nrhs // 2}
+    elif dirty_set in ("first_chunk", "second_chunk"):
+        assert nrhs == 257
+        dirty = {256} if dirty_set == "second_chunk" else {0, 5}
+    else:   # the first and last column of a chunk of 32 (one sweep per right-hand side, deterministic panels) and of 256, and a few inside
+        dirty = {c for c in (0, 5, 6, 31, 32, 40, 63, 64, 200, 255, 256) if c < nrhs}
+    kinds = []
+    for c in range(nrhs):
+        kinds.append("zero" if c == 1 else "dirty" if c in dirty else "faint" if c % 3 == 0 else "clean")
+    return kinds
+
+
+def refine_multi_problem():
+    """unrefined_multi_problem() - the same W, head and tail - with its primal diagonal redrawn within 1e-1 .. 1e2 (refine_block_matrix says
+    why; here the default's 1e-4 .. 1e4 also leaves primal rows without a constraint entry whose signal is 40 x noise_b)"""
+    k = ("problem", "multi")
+    if k not in _refine_cache:
+        n_i = 1500
+        _refine_cache[k] = Problem(5, 1, n_i, n_i // 2, 4, 4, 6.0 / n_i, diag_lo=REFINE_DIAG[0], diag_hi=REFINE_DIAG[1])
+    return _refine_cache[k]
+
+
+def refine_multi_reference(nrhs, dirty_set):
+    """The shared reference of a case: the block of refine_multi_problem(), E = 2^-10 (+-1) K_ij on J x J, J a random half of the rows (on
+    every stored entry for "all_entries"), and .kinds, .J, .tau (the geometric mean of the smallest dirty and the largest other eta*, mode 1,
+    from X0_ref; without one of the two a factor 2^10 from the other), .eta0"""
+    k = ("multi", nrhs, dirty_set)
+    if k not in _refine_cache:
+        prob = refine_multi_problem()
+        K, n = prob.blocks[0]["K"], prob.n_leaf
+        rng = np.random.default_rng(900 + nrhs)
+        J = np.sort(rng.choice(n, n // 2, replace=False))
+        kinds = refine_multi_kinds(nrhs, dirty_set)
+        XSgen = np.stack([refine_generic_xs(n, 50 * nrhs + c) for c in range(nrhs)])
+        if dirty_set == "all_entries":      # E = eps |K1| against positive xs: with random signs some row of some column always cancels
+            XSgen = np.abs(XSgen)           # below 2^14 noise_b (33 columns x 2250 rows: the smallest stood at 3.8e3)
+        for c, kind in enumerate(kinds):
+            if kind == "zero":
+                XSgen[c] = 0.0
+            elif kind != "dirty":
+                XSgen[c, J] *= 0.0 if kind == "clean" else REFINE_FAINT
+        ref = RefinementReference(K, prob.n_i, refine_perturbed_values(K, REFINE_EPS_WORST, 31, None if dirty_set == "all_entries" else J, coherent=dirty_set == "all_entries"),
+                                  _refine_rhs(K, XSgen))
+        ref.kinds, ref.J = kinds, J
+        ref.eta0 = ref.measures(ref.X0_ref, 1)
+        d = np.array([kd == "dirty" for kd in kinds])
+        lo = ref.eta0[~d].max() if (~d).any() and ref.eta0[~d].max() > 0.0 else None
+        hi = ref.eta0[d].min() if d.any() else None
+        ref.tau = float(np.sqrt(lo * hi)) if lo and hi else float(hi * 2.0 ** -10) if hi else float(lo * 2.0 ** 10)
+        _refine_cache[k] = ref
+    return _refine_cache[k]
+
+
+def refine_multi_fp64(ref, fix, ld, mutant=None):
+    """Host emulation of solve(nrhs) with one correction for the columns `fix`, in a flat array of rows of length ld (padding 7.5): x0_ref, then
+    x(:, fix[i]) += correction i.  mutant: "neighbour_column" - the corrections land one column further on; "stride_n" - they are added at
+    distance n, not ld."""
+    nrhs, n = ref.B.shape
+    flat = np.full(nrhs * ld, 7.5)
+    X = flat.reshape(nrhs, ld)
+    X[:, :n] = ref.X0_ref
+    A = sp.csr_matrix((ref.val2[ref.src], ref.indices, ref.indptr), shape=(n, n))
+    fix = list(fix)
+    if fix:
+        C = ref.solve0(ref.B[fix] - (A @ ref.X0_ref[fix].T).T)
+        for i, c in enumerate(fix):
+            if mutant == "neighbour_column":
+                c = (c + 1) % nrhs
+            off = c * (n if mutant == "stride_n" else ld)
+            flat[off:off + n] += C[i]
+    return X
+
+
+def refine_multi_judge(ref, X, M):
+    """(ok, ratio) per column of X (nrhs x n): a column whose host measure eta* exceeds tau passes corrected_once at M and fails `uncorrected`
+    even at the cap; a faint one the other way round; a clean one passes `uncorrected` (E x* is zero to rounding there and the two targets
+    coincide: nothing can fail); the zero column is exact zeros.  ratio: the figure of the predicate that has to pass."""
+    assert M <= UNREFINED_M_CAP
+    X = np.atleast_2d(X)
+    unc, once = ref.ratios_uncorrected(X), ref.ratios_once(X)
+    ok, ratio = np.zeros(len(ref.kinds), bool), np.zeros(len(ref.kinds))
+    for c, kind in enumerate(ref.kinds):
+        if kind == "zero":
+            ok[c] = not X[c].any()
+        elif ref.eta0[c] > ref.tau:
+            ok[c], ratio[c] = once[c] <= M and unc[c] > UNREFINED_M_CAP, once[c]
+        else:
+            ok[c], ratio[c] = unc[c] <= M and (kind == "clean" or once[c] > UNREFINED_M_CAP), unc[c]
+    return ok, ratio
