@@ -61,6 +61,13 @@ public:
    void matrixChanged_and_add_schur_term(double* SC, int ldSC) {
       check(pips_hip_ldl_factor_schur(h, mat.getStorage().M, border->getStorage().M, SC, ldSC), "factor_schur");
    }
+   // ... the same for a host whose Schur complement is sparse (hasSparseKkt): the branch sparse_res = true of the reference's routine
+   // (DistributedLinearSystem.C:766-770, 1050-1113, 1180-1190) adds into a SparseSymmetricMatrix, the upper triangle in CSR.  One kind of
+   // target per solver for its life: the dense overload or this one
+   void matrixChanged_and_add_schur_term(SparseSymmetricMatrix& SC) {
+      auto& st = SC.getStorage();
+      check(pips_hip_ldl_factor_schur_sparse(h, mat.getStorage().M, border->getStorage().M, st.m, st.krowM, st.jcolM, st.M, 0), "factor_schur_sparse");
+   }
    // ---- level 1.5b: the leaf solvers of a rank as ONE batch.  sLinsysRootAug::assembleLocalKKT (:210-227) hands its loop over the children
    //      over: instead of children[it]->addTermToSchurComplBlocked(...) one after the other, collect the children's solvers and call this
    //      once - all leaves run in every launch, one S x S term comes back.  Likewise Lsolve / Ltsolve (:323-365) for their per-child solves.
@@ -68,6 +75,12 @@ public:
       std::vector<void*> hs; std::vector<const double*> kv, bv;
       for (const HipLdlSolver* l : leaves) { hs.push_back(l->h); kv.push_back(l->mat.getStorage().M); bv.push_back(l->border ? l->border->getStorage().M : nullptr); }
       check(pips_hip_ldl_factor_schur_batch(hs.data(), (int)hs.size(), kv.data(), bv.data(), SC, ldSC), "factor_schur_batch");
+   }
+   static void matrixChanged_and_add_schur_terms(const std::vector<HipLdlSolver*>& leaves, SparseSymmetricMatrix& SC) {
+      std::vector<void*> hs; std::vector<const double*> kv, bv;
+      for (const HipLdlSolver* l : leaves) { hs.push_back(l->h); kv.push_back(l->mat.getStorage().M); bv.push_back(l->border ? l->border->getStorage().M : nullptr); }
+      auto& st = SC.getStorage();
+      check(pips_hip_ldl_factor_schur_sparse_batch(hs.data(), (int)hs.size(), kv.data(), bv.data(), st.m, st.krowM, st.jcolM, st.M, 0), "factor_schur_sparse_batch");
    }
    static void solve_all(const std::vector<HipLdlSolver*>& leaves, const std::vector<double*>& rhs /* one per leaf, nullptr: none */) {
       std::vector<void*> hs;

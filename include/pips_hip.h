@@ -98,10 +98,36 @@ int pips_hip_ldl_factor_schur_batch(void* const* handles, int n, const double* c
 int pips_hip_ldl_solve_batch(void* const* handles, int n, double* const* rhs_inout_host);
 int pips_hip_ldl_solve_batch_dev(void* const* handles, int n, double* x_dev);
 int pips_hip_ldl_inertia_batch(void* const* handles, int n, int* pos, int* neg, int* zero);
+/* The same two entries for a host whose Schur complement is sparse (hasSparseKkt): the branch sparse_res = true of
+ * addBiTLeftKiBiRightToResBlockedParallelSolvers (DistributedLinearSystem.C:766-770, 1050-1113, 1180-1190), which adds the term into a
+ * SparseSymmetricMatrix through multMatSymUpper.  sc_rowptr / sc_colidx: the CSR pattern of one triangle of the symmetric S x S Schur
+ * complement - lower = 0 the upper one (row i holds columns >= i: the reference's SparseSymmetricMatrix of the sparse KKT), lower = 1 the
+ * lower one (what pips_hip_kkt_get_schur_sparse returns); sc_val_host its sc_rowptr[S] values.  The call factorises as the dense entry
+ * does and ADDS the term's entries at their positions; every other value keeps its bits.  Solves, inertia and info afterwards as after
+ * the dense entries.  A leaf without non-empty border columns adds nothing; sc_val_host == NULL (batch entry): factorise only.
+ * Only the rows of the leaves' non-empty border columns are consulted; their columns must ascend, and they must hold the clique of
+ * every leaf's non-empty border columns, the diagonal included.
+ * The device never holds S x S nor sc_rowptr[S] doubles: the target is the T distinct pattern positions the leaves' cliques touch (one
+ * leaf: the lower half of its own nb x nb block), addressed through the position tables of the sparse root; one copy of T doubles
+ * comes back per call.  The host keeps those T positions, S, the number of entries and a 64-bit hash of the consulted rows.
+ * Errors, all before any value of sc_val_host changes:
+ *   PIPS_ERR_ARG    S differs from the border's; a consulted row does not ascend or holds an index out of range; a later call passes
+ *                   another pattern (S, entries, triangle or the hash differ)
+ *   PIPS_ERR_STATE  the pattern lacks an entry of a leaf's clique - the message names it as (row, column); the handle or the bound
+ *                   group has had a dense Schur target (pips_hip_ldl_factor_schur / _batch), or the dense entries are called after
+ *                   these: one kind per handle for its life
+ * Deterministic mode: pips_hip_ldl_set_deterministic on the handle (batch entry: on the first handle), or PIPS_HIP_DETERMINISTIC=1 in the
+ * environment at the first call. */
+int pips_hip_ldl_factor_schur_sparse(void* handle, const double* K_vals_host, const double* Bt_vals_host, int S, const int* sc_rowptr,
+                                     const int* sc_colidx, double* sc_val_host, int lower);
+int pips_hip_ldl_factor_schur_sparse_batch(void* const* handles, int n, const double* const* K_vals_host, const double* const* Bt_vals_host,
+                                           int S, const int* sc_rowptr, const int* sc_colidx, double* sc_val_host, int lower);
 /* diagnostics of the symbolic phase: what[0]=nnz(L) what[1]=n_head what[2]=tail m what[3]=#head supernodes
  * what[4]=#levels what[5]=factor flops (rounded); and what[6]=refinement steps the last solve took (solve(nrhs) goes chunk by chunk: the
  * steps of the last chunk that took any, not their sum), what[7]=how the last solve(nrhs) went
- * (0 one sweep per right-hand side, 1 interleaved panels on the matrix pipe, 2 the same with the deterministic forward substitution) */
+ * (0 one sweep per right-hand side, 1 interleaved panels on the matrix pipe, 2 the same with the deterministic forward substitution);
+ * of the engine that holds the leaf's newest factors (its own, or the batch it is bound into): what[8]=the Schur mode its analysis took
+ * (1 augmented partial factorisation, 2 blocked solves), what[9]=doubles of its compact sparse Schur target (0: none) */
 int pips_hip_ldl_info(void* handle, int64_t* what, int n_what);
 /* copies the fill-reducing permutation (perm[k] = original index eliminated k-th) */
 int pips_hip_ldl_get_perm(void* handle, int* perm);
@@ -662,6 +688,15 @@ int pips_ipm_layout_probe(int n_blocks, const pips_ipm_block* blocks, const pips
  * border columns; *nb_max their maximum = the right-hand sides of the packed solves; local_of_row[b] (S entries each): the local index
  * of Schur column s in block b, ascending in s, -1 for an empty column. */
 int pips_schur_pack_probe(int nblk, int S, const int* const* bt_rowptr, int* nb, int* nb_max, int* const* local_of_row);
+
+/* The compact target of the sparse Schur entries of section 1 (pips_hip_ldl_factor_schur_sparse / _batch), without a device; the code
+ * the entries build theirs with, errors included.  bt_rowptr[b]: the S + 1 row pointers of block b's border (NULL: no border);
+ * sc_rowptr / sc_colidx / lower: the caller's pattern as in section 1.  nb[b] (nblk entries): the block's non-empty border columns;
+ * *n_touched = T, the distinct pattern positions any block's clique touches; pos (when cap >= T): those positions, ascending;
+ * tab[b] (NULL: skipped; else nb[b] x nb[b] entries): entry la * nb[b] + lb, la >= lb, is the index into pos of the pair's place - (bm[lb],
+ * bm[la]) of an upper pattern, (bm[la], bm[lb]) of a lower one, bm the block's non-empty columns ascending; the other half is 0. */
+int pips_schur_target_probe(int nblk, int S, const int* const* bt_rowptr, const int* sc_rowptr, const int* sc_colidx, int lower, int* nb,
+                            long long* n_touched, long long* pos, long long cap, int* const* tab);
 
 /* ---- 6. input files ---------------------------------------------------------------------------------------------------
  * One block of a block-structured LP from a "jacobian" GDX file, the format gmspips_reader opens per block

@@ -20,6 +20,7 @@
 #include "devmem.h"
 #include "layout.h"
 #include "detplan.h"
+#include "schurtarget.h"
 #include "kernels.hip.h"
 #include "rootkernel.hip.h"
 #include "tailkernel.hip.h"
@@ -2212,6 +2213,8 @@ static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs
    if (const char* sp = getenv("PIPS_HIP_MF_SPLIT")) opt.mf_split_nb_max = atoi(sp) == 0 ? 0 : std::min(176, std::max(atoi(sp), 2));   // border split: 0 = off, else the largest nb
    knobs.deterministic = e && e->deterministic;
    knobs.schur_mode = e ? e->schur_mode : 0;
+   // (tests: forces a Schur mode where no setter reaches - the leaf handles and the batch they are bound into - and the caller left it to the model)
+   if (e && knobs.schur_mode == 0) knobs.schur_mode = std::max(0, std::min(2, env_int("PIPS_HIP_SCHUR_MODE", 0)));
    knobs.mf_lds_doubles = opt.mf_lds_doubles;
    knobs.mf_wanted = env_int("PIPS_HIP_MF", 1) != 0;
    if (!knobs.mf_wanted) opt.mf_split_nb_max = 0;   // the border split (compact front panels) only exists with the multifrontal head
@@ -3087,9 +3090,25 @@ __global__ void k_schur_take_block(double* __restrict__ SC, int ld, const int* _
    }
 }
 
+// Where a handle's (or a bound group's) Schur term goes: the caller's dense S x S matrix (pips_hip_ldl_factor_schur / _batch) or its
+// sparse one (pips_hip_ldl_factor_schur_sparse / _batch).  The first call with a Schur complement settles it for the handle's life: the
+// sparse entries move the kernels' targets into position tables (Engine::set_sc_tables), the dense ones address S x S.
+enum { SC_KIND_NONE = 0, SC_KIND_DENSE = 1, SC_KIND_SPARSE = 2 };
+// The sparse target (schurtarget.h): T doubles on the device, the T positions they belong to in the caller's value array, and what
+// identifies the pattern in later calls - nothing of size S x S or nnz
+struct SparseSchurBind {
+   bool bound = false;
+   SchurPatternId id;
+   std::vector<long long> pos;
+   DevBuf<double> d_val;
+   std::vector<double> h_val;
+};
+
 struct LdlHandle {
    Engine eng;
    bool have_perm = false;
+   int sc_kind = SC_KIND_NONE;
+   SparseSchurBind sparse_sc;
    DevBuf<double> d_sc;           // compact nb x nb Schur term of this leaf (pips_hip_ldl_factor_schur)
    std::vector<double> h_sc;
    std::shared_ptr<LdlGroup> group;   // the leaves of a rank bound into one batch engine (pips_hip_ldl_factor_schur_batch)
@@ -3110,6 +3129,8 @@ struct LdlGroup {
    std::vector<LdlHandle*> members;
    DevBuf<double> d_sc, d_x;
    std::vector<double> h_sc;
+   int sc_kind = SC_KIND_NONE;
+   SparseSchurBind sparse_sc;
 };
 // a handle that goes away leaves an empty slot in its group: the siblings keep the batch's factors (their own solves go through
 // group_solve_rows, which needs no sibling), the next array-of-handles call sees another array and binds anew
@@ -3260,6 +3281,8 @@ int pips_hip_ldl_factor_schur(void* handle, const double* K_vals_host, const dou
    const int S = e.S;
    if (S <= 0 || e.in[0].btrow.empty()) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur: no border declared (pips_hip_ldl_set_border)");
    if (ldSC < S) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur: ldSC %d < S %d", ldSC, S);
+   if (h->sc_kind == SC_KIND_SPARSE) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur: the Schur target of this handle is sparse (pips_hip_ldl_factor_schur_sparse): one kind per handle");
+   h->sc_kind = SC_KIND_DENSE;
    int rc;
    if (!e.analyzed && (rc = pips_hip_ldl_analyze(handle))) return rc;
    HIP_TRY(hipSetDevice(e.device));
@@ -3445,11 +3468,24 @@ int pips_hip_ldl_solve_sparse(void* handle, int nrhs, double* rhs, int ld, const
 }
 
 // ---- array-of-handles entries
-static int ldl_group_of(void* const* handles, int n, std::shared_ptr<LdlGroup>& out) {
+// one kind of Schur target per handle and per bound group for their lives: refuse the other one, else take this one
+static int ldl_group_kind(LdlGroup& g, int kind, const char* who) {
+   bool other = g.sc_kind != SC_KIND_NONE && g.sc_kind != kind;
+   for (LdlHandle* m : g.members) other = other || (m && m->sc_kind != SC_KIND_NONE && m->sc_kind != kind);
+   if (other)
+      PIPS_FAIL(PIPS_ERR_STATE, "%s: the Schur target of these handles is %s: one kind per handle", who,
+                kind == SC_KIND_DENSE ? "sparse (pips_hip_ldl_factor_schur_sparse / _batch)" : "dense (pips_hip_ldl_factor_schur / _batch)");
+   g.sc_kind = kind;
+   for (LdlHandle* m : g.members) if (m) m->sc_kind = kind;
+   return PIPS_OK;
+}
+
+// want_det (the sparse entries): the batch engine in deterministic mode - a binding that is not is replaced
+static int ldl_group_of(void* const* handles, int n, std::shared_ptr<LdlGroup>& out, bool want_det = false) {
    if (!handles || n <= 0) PIPS_FAIL(PIPS_ERR_ARG, "array of leaf handles: bad arguments");
    LdlHandle* h0 = (LdlHandle*)handles[0];
    if (!h0) PIPS_FAIL(PIPS_ERR_ARG, "array of leaf handles: null handle");
-   bool same = h0->group && (int)h0->group->members.size() == n;
+   bool same = h0->group && (int)h0->group->members.size() == n && (!want_det || h0->group->eng.deterministic);
    for (int i = 0; i < n && same; ++i) same = handles[i] && h0->group->members[i] == (LdlHandle*)handles[i];
    if (same) { out = h0->group; return PIPS_OK; }
    // bind: one batch engine over the patterns (and borders) the handles hold
@@ -3460,6 +3496,7 @@ static int ldl_group_of(void* const* handles, int n, std::shared_ptr<LdlGroup>& 
    e.device = h0->eng.device;
    e.thr_rel = h0->eng.thr_rel; e.repl_rel = h0->eng.repl_rel;
    e.refine_steps = h0->eng.refine_steps; e.refine_tol = h0->eng.refine_tol; e.refine_mode = h0->eng.refine_mode;
+   e.deterministic = want_det;
    e.in.resize(n);
    for (int i = 0; i < n; ++i) {
       LdlHandle* h = (LdlHandle*)handles[i];
@@ -3486,6 +3523,9 @@ int pips_hip_ldl_factor_schur_batch(void* const* handles, int n, const double* c
    const int S = e.S;
    const bool schur = SC_host != nullptr;
    if (schur && (S <= 0 || ldSC < S || !Bt_vals_host)) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_batch: Schur term asked for without border / ldSC %d < S %d", ldSC, S);
+   if (schur) {
+      if ((rc = ldl_group_kind(*g, SC_KIND_DENSE, "pips_hip_ldl_factor_schur_batch"))) return rc;
+   }
    HIP_TRY(hipSetDevice(e.device));
    for (int i = 0; i < n; ++i) {
       if (!K_vals_host[i]) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_batch: no values for leaf %d", i);
@@ -3523,6 +3563,119 @@ int pips_hip_ldl_factor_schur_batch(void* const* handles, int n, const double* c
    } else
       HIP_TRY(hipStreamSynchronize(e.stream));
    return e.sweep.take_error("pips_hip_ldl_factor_schur_batch");
+}
+
+// ---- the sparse Schur entries (INTEGRATION.md levels 1.5 / 1.5b for hosts with hasSparseKkt): the branch sparse_res = true of
+// addBiTLeftKiBiRightToResBlockedParallelSolvers (DistributedLinearSystem.C:766-770, 1050-1113, 1180-1190), which adds the term into a
+// SparseSymmetricMatrix.  The first call builds the position tables of the engine's blocks against the caller's pattern (schurtarget.cpp)
+// and hands them to set_sc_tables: from then on every kernel that writes the Schur complement - tile SYRK, head scatters,
+// k_border_schur_add, the packed blocked solves of Schur mode 2, deterministic mode's group buffers - addresses T doubles, the distinct
+// pattern positions the blocks' cliques touch.  Later calls compare S, nnz, the triangle and the hash of the consulted rows.
+static int sparse_schur_bind(Engine& e, SparseSchurBind& sb, int S, const int* sc_rowptr, const int* sc_colidx, int lower, const char* who) {
+   std::vector<const int*> bt((size_t)e.nblk, nullptr);
+   for (int b = 0; b < e.nblk; ++b) if (!e.in[b].btrow.empty()) bt[b] = e.in[b].btrow.data();
+   SchurPatternId id;
+   int rc;
+   if (sb.bound) {
+      if ((rc = build_schur_target(e.nblk, S, bt.data(), sc_rowptr, sc_colidx, lower, nullptr, id))) return rc;
+      if (!(id == sb.id))
+         PIPS_FAIL(PIPS_ERR_ARG, "%s: another pattern than the first call's (S %d / %d, %lld / %lld entries, %s / %s triangle, or other consulted rows)", who, S, sb.id.S,
+                   id.nnz, sb.id.nnz, id.lower ? "lower" : "upper", sb.id.lower ? "lower" : "upper");
+      return PIPS_OK;
+   }
+   SchurTarget t;
+   if ((rc = build_schur_target(e.nblk, S, bt.data(), sc_rowptr, sc_colidx, lower, &t, id))) return rc;
+   // (a target of at least one double: a length of 0 reads as "dense, S x S" in det_gstride)
+   if ((rc = e.set_sc_tables(t.tab, t.off, std::max<long long>((long long)t.pos.size(), 1)))) return rc;
+   if (e.deterministic && (rc = e.set_det_groups(0, 1))) return rc;   // group buffers as long as the compact array
+   PIPS_TRY(sb.d_val.alloc(t.pos.size()));
+   sb.pos = std::move(t.pos);
+   sb.id = id;
+   sb.bound = true;
+   return PIPS_OK;
+}
+// clear the compact array, factorise into it, one copy of its T doubles, sc_val_host[pos[t]] += values[t]
+static int sparse_schur_factor(Engine& e, SparseSchurBind& sb, double* sc_val_host, const char* who, LdlHandle* leaf, LdlGroup* group) {
+   const size_t T = sb.pos.size();
+   const bool schur = sc_val_host && T > 0;
+   int rc;
+   if (schur) HIP_TRY(hipMemsetAsync(sb.d_val, 0, T * sizeof(double), e.stream));
+   if ((rc = e.factor(schur ? sb.d_val.get() : nullptr, 0))) return rc;
+   // who holds the newest factors, as after the dense entries: the leaf itself, or the batch for every member
+   if (leaf) leaf->newest_in_group = false;
+   if (group)
+      for (LdlHandle* m : group->members) if (m) m->newest_in_group = true;
+   if (schur) {
+      sb.h_val.resize(T);
+      HIP_TRY(hipMemcpyAsync(sb.h_val.data(), sb.d_val, T * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+   }
+   HIP_TRY(hipStreamSynchronize(e.stream));
+   if ((rc = e.sweep.take_error(who))) return rc;
+   if (schur)
+      for (size_t t = 0; t < T; ++t) sc_val_host[sb.pos[t]] += sb.h_val[t];
+   return PIPS_OK;
+}
+static bool env_deterministic() {
+   const char* d = getenv("PIPS_HIP_DETERMINISTIC");
+   return d && atoi(d) != 0;
+}
+
+int pips_hip_ldl_factor_schur_sparse(void* handle, const double* K_vals_host, const double* Bt_vals_host, int S, const int* sc_rowptr, const int* sc_colidx,
+                                     double* sc_val_host, int lower) {
+   LdlHandle* h = (LdlHandle*)handle;
+   if (!h || !K_vals_host || !Bt_vals_host || !sc_rowptr || !sc_colidx || !sc_val_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_sparse: bad arguments");
+   Engine& e = h->eng;
+   if (e.S <= 0 || e.in[0].btrow.empty()) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur_sparse: no border declared (pips_hip_ldl_set_border)");
+   if (S != e.S) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_sparse: S %d, the border was declared with %d", S, e.S);
+   if (h->sc_kind == SC_KIND_DENSE) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur_sparse: the Schur target of this handle is dense (pips_hip_ldl_factor_schur): one kind per handle");
+   int rc;
+   if (!e.analyzed) {
+      if (env_deterministic()) e.deterministic = true;   // (the default, as for batches: pips_hip_batch_create)
+      if ((rc = pips_hip_ldl_analyze(handle))) return rc;
+   }
+   HIP_TRY(hipSetDevice(e.device));
+   if ((rc = sparse_schur_bind(e, h->sparse_sc, S, sc_rowptr, sc_colidx, lower, "pips_hip_ldl_factor_schur_sparse"))) return rc;
+   h->sc_kind = SC_KIND_SPARSE;
+   if ((rc = pips_hip_batch_set_values(&e, 0, K_vals_host))) return rc;
+   if (e.nnzB_total > 0) HIP_TRY(hipMemcpyAsync(e.d_bval, Bt_vals_host, (size_t)e.nnzB_total * sizeof(double), hipMemcpyHostToDevice, e.stream));
+   return sparse_schur_factor(e, h->sparse_sc, sc_val_host, "pips_hip_ldl_factor_schur_sparse", h, nullptr);
+}
+
+int pips_hip_ldl_factor_schur_sparse_batch(void* const* handles, int n, const double* const* K_vals_host, const double* const* Bt_vals_host, int S,
+                                           const int* sc_rowptr, const int* sc_colidx, double* sc_val_host, int lower) {
+   const char* who = "pips_hip_ldl_factor_schur_sparse_batch";
+   std::shared_ptr<LdlGroup> g;
+   const bool want_det = handles && n > 0 && handles[0] && (((LdlHandle*)handles[0])->eng.deterministic || env_deterministic());
+   int rc = ldl_group_of(handles, n, g, want_det);
+   if (rc) return rc;
+   if (!K_vals_host) PIPS_FAIL(PIPS_ERR_ARG, "%s: no values", who);
+   Engine& e = g->eng;
+   const bool schur = sc_val_host != nullptr;
+   HIP_TRY(hipSetDevice(e.device));
+   if (schur) {
+      if (e.S <= 0 || !Bt_vals_host || !sc_rowptr || !sc_colidx) PIPS_FAIL(PIPS_ERR_ARG, "%s: Schur term asked for without border or pattern", who);
+      if (S != e.S) PIPS_FAIL(PIPS_ERR_ARG, "%s: S %d, the borders were declared with %d", who, S, e.S);
+      bool other = g->sc_kind == SC_KIND_DENSE;
+      for (LdlHandle* m : g->members) other = other || (m && m->sc_kind == SC_KIND_DENSE);
+      if (other) PIPS_FAIL(PIPS_ERR_STATE, "%s: the Schur target of these handles is dense (pips_hip_ldl_factor_schur / _batch): one kind per handle", who);
+      if ((rc = sparse_schur_bind(e, g->sparse_sc, S, sc_rowptr, sc_colidx, lower, who))) return rc;
+      if ((rc = ldl_group_kind(*g, SC_KIND_SPARSE, who))) return rc;
+   }
+   for (int i = 0; i < n; ++i) {
+      if (!K_vals_host[i]) PIPS_FAIL(PIPS_ERR_ARG, "%s: no values for leaf %d", who, i);
+      if (schur && !e.in[i].btcol.empty() && !Bt_vals_host[i]) PIPS_FAIL(PIPS_ERR_ARG, "%s: no border values for leaf %d", who, i);
+   }
+   for (int i = 0; i < n; ++i)
+      HIP_TRY(hipMemcpyAsync(e.d_kval + e.kptr[i], K_vals_host[i], (size_t)(e.kptr[i + 1] - e.kptr[i]) * sizeof(double), hipMemcpyHostToDevice, e.stream));
+   if (schur && e.nnzB_total > 0) {
+      long long off = 0;
+      for (int i = 0; i < n; ++i) {
+         const size_t cnt = e.in[i].btcol.size();
+         if (cnt > 0) HIP_TRY(hipMemcpyAsync(e.d_bval + off, Bt_vals_host[i], cnt * sizeof(double), hipMemcpyHostToDevice, e.stream));
+         off += (long long)cnt;
+      }
+   }
+   return sparse_schur_factor(e, g->sparse_sc, schur ? sc_val_host : nullptr, who, nullptr, g.get());
 }
 
 int pips_hip_ldl_solve_batch_dev(void* const* handles, int n, double* x_dev) {
@@ -3582,10 +3735,17 @@ int pips_hip_ldl_inertia(void* handle, int* pos, int* neg, int* zero) {
 
 int pips_hip_ldl_info(void* handle, int64_t* what, int n_what) {
    LdlHandle* h = (LdlHandle*)handle;
-   if (!h || h->eng.sym.empty()) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_info: analyze first");
-   const BlockSym& s = h->eng.sym[0];
-   int64_t v[8] = {s.nnzL, s.n_head, s.m, (int64_t)s.sn.size(), s.n_levels, (int64_t)s.flops_factor, (int64_t)h->eng.last_refine_steps, (int64_t)h->eng.last_multi_path};
-   for (int i = 0; i < n_what && i < 8; ++i) what[i] = v[i];
+   const bool grp = h && ldl_uses_group(h);
+   if (!h || (h->eng.sym.empty() && !grp)) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_info: analyze first");
+   // (a handle that was only ever factorised through its batch has its analysis there)
+   const BlockSym& s = h->eng.sym.empty() ? h->group->eng.sym[h->group_index] : h->eng.sym[0];
+   // [8], [9]: of the engine that holds this leaf's newest factors - the Schur mode its analysis took and the doubles of its compact
+   // sparse Schur target (0: none, the target is dense)
+   const Engine& cur = grp ? h->group->eng : h->eng;
+   const SparseSchurBind& sb = grp ? h->group->sparse_sc : h->sparse_sc;
+   int64_t v[10] = {s.nnzL, s.n_head, s.m, (int64_t)s.sn.size(), s.n_levels, (int64_t)s.flops_factor, (int64_t)h->eng.last_refine_steps, (int64_t)h->eng.last_multi_path,
+                    (int64_t)cur.schur_mode_eff, sb.bound ? (int64_t)sb.pos.size() : 0};
+   for (int i = 0; i < n_what && i < 10; ++i) what[i] = v[i];
    return PIPS_OK;
 }
 

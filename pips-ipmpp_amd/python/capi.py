@@ -52,7 +52,7 @@ SYMBOLS = [
     "pips_hip_ldl_analyze", "pips_hip_ldl_factor", "pips_hip_ldl_set_values", "pips_hip_ldl_solve", "pips_hip_ldl_inertia", "pips_hip_ldl_info",
     "pips_hip_ldl_get_perm", "pips_hip_ldl_set_border", "pips_hip_ldl_factor_schur", "pips_hip_ldl_destroy",
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
-    "pips_hip_ldl_inertia_batch",
+    "pips_hip_ldl_inertia_batch", "pips_hip_ldl_factor_schur_sparse", "pips_hip_ldl_factor_schur_sparse_batch",
     "pips_hip_dense_ldl_create", "pips_hip_dense_ldl_factor", "pips_hip_dense_ldl_factor_dev", "pips_hip_dense_ldl_solve",
     "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_ipm_layout_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
     "pips_hip_batch_create", "pips_hip_batch_set_block", "pips_hip_batch_set_options", "pips_hip_batch_set_schur_mode", "pips_hip_batch_set_deterministic", "pips_hip_batch_get_schur_mode", "pips_hip_batch_add_regularization", "pips_hip_batch_set_refinement",
@@ -74,7 +74,7 @@ SYMBOLS = [
     "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
-    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe", "pips_det_plan_probe",
+    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe", "pips_det_plan_probe", "pips_schur_target_probe",
 ]
 
 # problem scalers (pips_ipm_create_general_scaled; the order of the reference's ScalerType)
@@ -293,6 +293,31 @@ def schur_pack_probe(Bts, S):
     return nb, int(nb_max.value), local[:, :S]
 
 
+def schur_target_probe(Bts, sc_rowptr, sc_colidx, S, lower=False):
+    """The compact target of HipLdlSolver.factor_schur_sparse / _batch for the borders Bts (CSR with S rows each, None: a block without
+    border) and the caller's pattern (one triangle of the S x S Schur complement in CSR), from the host code the entries use, errors
+    included: (nb per block, pos = the T touched positions of the value array ascending, one nb_b x nb_b table of indices into pos per
+    block - only its la >= lb half is meaningful).  A border or a pattern with another number of rows than S is refused as the entries
+    refuse it (code 1)."""
+    nblk = len(Bts)
+    ip = C.POINTER(C.c_int)
+    rp, ci = _i32(sc_rowptr), _i32(sc_colidx)
+    if len(rp) != S + 1 or any(Bt is not None and Bt.nrows != S for Bt in Bts):
+        raise PipsHipError(f"pips_schur_target_probe failed (code 1): S {S}, the pattern has {len(rp) - 1} rows, "
+                           f"the borders {[Bt.nrows for Bt in Bts if Bt is not None]}")
+    rps = [None if Bt is None else _i32(Bt.rowptr) for Bt in Bts]
+    bt = (ip * nblk)(*[ip() if r is None else r.ctypes.data_as(ip) for r in rps])
+    nb = np.zeros(nblk, np.int32)
+    T = C.c_longlong(0)
+    head = (C.c_int(nblk), C.c_int(S), bt, _ptr(rp), _ptr(ci), C.c_int(1 if lower else 0), _ptr(nb), C.byref(T))
+    _check(lib.pips_schur_target_probe(*head, None, C.c_longlong(0), None), "pips_schur_target_probe")
+    pos = np.zeros(max(int(T.value), 1), np.int64)
+    tabs = [np.zeros((int(nb[b]), int(nb[b])), np.int32) for b in range(nblk)]
+    tp = (ip * nblk)(*[(t.ctypes.data_as(ip) if t.size else ip()) for t in tabs])
+    _check(lib.pips_schur_target_probe(*head, _ptr(pos), C.c_longlong(len(pos)), tp), "pips_schur_target_probe")
+    return nb, pos[:int(T.value)], tabs
+
+
 def det_plan_probe(blocks, S, rank=0, n_ranks=1, n_panels=1):
     """The host plans of deterministic mode for the blocks (K lower CSR, n_primal, border CSR with S rows or None) this rank of
     n_ranks holds, without a device (pips_det_plan_probe): a dict of the scalars and of the 16 sections as int64 arrays (rows where
@@ -428,6 +453,33 @@ class HipLdlSolver:
                                                    C.c_int(SC.shape[1] if SC is not None else 0)), "pips_hip_ldl_factor_schur_batch")
 
     @staticmethod
+    def _sparse_pattern(sc, S):
+        assert sc.format == "csr" and sc.shape == (S, S) and sc.data.dtype == np.float64 and sc.data.flags.c_contiguous
+        return _i32(sc.indptr), _i32(sc.indices)
+
+    def factor_schur_sparse(self, sc, lower=False):
+        """matrixChanged() + addTermToSchurComplBlocked() into a sparse Schur complement: sc, a scipy CSR matrix holding one triangle of the
+        symmetric S x S matrix (lower=False: the upper one, the reference's SparseSymmetricMatrix; True: the lower one), has
+        -Br^T K^-1 Br added to sc.data in place at the positions of this leaf's clique; every other value keeps its bits."""
+        rp, ci = HipLdlSolver._sparse_pattern(sc, sc.shape[0])
+        _check(lib.pips_hip_ldl_factor_schur_sparse(self._h, _ptr(self.K.val), _ptr(self.Bt.val), C.c_int(sc.shape[0]), _ptr(rp), _ptr(ci), _ptr(sc.data),
+                                                    C.c_int(1 if lower else 0)), "pips_hip_ldl_factor_schur_sparse")
+
+    @staticmethod
+    def factor_schur_sparse_batch(solvers, sc, lower=False):
+        """factor_schur_batch into a sparse Schur complement (sc as in factor_schur_sparse, sc.data updated in place; None: factorise only)"""
+        hs = HipLdlSolver._handle_array(solvers)
+        n = len(solvers)
+        kv = (C.c_void_p * n)(*[s.K.val.ctypes.data for s in solvers])
+        bv = (C.c_void_p * n)(*[(s.Bt.val.ctypes.data if getattr(s, "Bt", None) is not None else None) for s in solvers])
+        if sc is None:
+            tail = (C.c_int(0), None, None, None, C.c_int(0))
+        else:
+            rp, ci = HipLdlSolver._sparse_pattern(sc, sc.shape[0])
+            tail = (C.c_int(sc.shape[0]), _ptr(rp), _ptr(ci), _ptr(sc.data), C.c_int(1 if lower else 0))
+        _check(lib.pips_hip_ldl_factor_schur_sparse_batch(hs, C.c_int(n), kv, bv, *tail), "pips_hip_ldl_factor_schur_sparse_batch")
+
+    @staticmethod
     def solve_batch(solvers, rhs_list):
         """one right-hand side per leaf (numpy arrays of length n_i, or None), overwritten by the solutions"""
         hs = HipLdlSolver._handle_array(solvers)
@@ -461,10 +513,11 @@ class HipLdlSolver:
         return perm
 
     def info(self):
-        what = np.zeros(8, np.int64)
-        _check(lib.pips_hip_ldl_info(self._h, _ptr(what), C.c_int(8)), "pips_hip_ldl_info")
+        what = np.zeros(10, np.int64)
+        _check(lib.pips_hip_ldl_info(self._h, _ptr(what), C.c_int(10)), "pips_hip_ldl_info")
         return dict(nnzL=int(what[0]), n_head=int(what[1]), m=int(what[2]), n_sn=int(what[3]), n_levels=int(what[4]),
-                    flops=int(what[5]), last_refinement_steps=int(what[6]), last_multi_path=int(what[7]))
+                    flops=int(what[5]), last_refinement_steps=int(what[6]), last_multi_path=int(what[7]), schur_mode=int(what[8]),
+                    sparse_schur_len=int(what[9]))
 
     def close(self):
         if self._h:
