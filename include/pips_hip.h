@@ -244,7 +244,9 @@ int pips_hip_batch_tail_to_host(void* handle, int b, int which, double* out, int
  * what[13]=1 if solveCompressed takes its Ltsolve from the augmented factor (one backward sweep) while no pivot is perturbed
  * what[14]=1 multifrontal head ... what[24]=blocks analysed with the border split of the fronts; what[26]=right-hand sides of the packed
  * blocked solves (max over the blocks of their non-empty border columns; Schur mode 2 with the sparse root), 0 where that path is
- * not active (python/capi.py LeafBatch.info names all) */
+ * not active; what[27]=1 where the tails are written once, assembled in LDS column by column (k_tail_first_touch: multifrontal head, no
+ * deterministic mode, tallest tail column within the LDS budget; PIPS_HIP_TAIL_FIRST_TOUCH=0 refuses it), 0 where they are cleared and
+ * added to (python/capi.py LeafBatch.info names all) */
 int pips_hip_batch_info(void* handle, int64_t* what, int n_what);
 int pips_hip_batch_sync(void* handle);
 /* per-phase device time in ms (HIP events on the handle's stream) of the last pips_hip_batch_factor
@@ -642,6 +644,25 @@ int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* co
 int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol,
                          int S, const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head,
                          int* col_tasks, long long col_cap, int* grp_tasks, long long grp_cap, int64_t* counts);
+
+/* The first-touch plan of the tails, without a device (csrc/layout.cpp layout_first_touch; inputs as pips_layout_probe, force_n_head as
+ * pips_tail_plan_probe; lds_bytes > 0 replaces the LDS budget of a column): the layout as the analysis decides it, and the layout with
+ * the first touch refused, as 14 sections of integers back to back in out, at most cap of them (cap 0: sizes only):
+ *   0 per block, rows of 12: n, n_head, m, m_pad, nb, ldT, mf_split, T_in (arena offset where the tail is assembled), first K value,
+ *     border entries, root fronts, tile columns
+ *   1 first global column of every block (blocks + 1)        2 / 4 offsets of the columns' init entries / front pieces (columns + 1 each)
+ *   3 init entries, rows (row inside the tail panel, source: >= 0 index of the K value, < 0 ~index of the border value)
+ *   5 front pieces, rows (front, offset of the first value among the update matrices, offset of the first row index, entries)
+ *   6 the simple leaves whose products into the tail and the Schur complement are deferred
+ *   7 / 8 scatter targets of the K values without / with the first touch (arena offsets, -1: not scattered)    9 / 10 the same for the border
+ *   11 root fronts in k_root_assemble's order, rows (block, front, r, rb, offset of its update matrix, offset of its row indices)
+ *   12 the row indices of all supernodes     13 simple leaves, rows (supernode, block, r, update segments, offset of its row indices)
+ * Sections 1 - 6 are empty where the path is refused.  counts (22 entries): [0] first touch taken, [1] multifrontal head, [2] single-launch
+ * tails, [3] Schur mode taken, [4] doubles of update matrices, [5] K values, [6] border values, [7] integers in all sections,
+ * [8 + k] integers of section k. */
+int pips_first_touch_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol,
+                           int S, const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head, int deterministic,
+                           long long lds_bytes, long long free_device_bytes, long long* out, long long cap, int64_t* counts);
 
 /* The host plans of deterministic mode, without a device (csrc/detplan.cpp; tests): the layout of a deterministic analysis (inputs as
  * pips_layout_probe with deterministic set), then the planners the engine runs for this rank of n_ranks that need no recording of the

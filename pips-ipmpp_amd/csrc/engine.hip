@@ -880,6 +880,12 @@ struct EngineAnalysis {
    DevBuf<double> d_mfU;                // update matrices of the fronts
    DevBuf<double> d_mfLV;               // d and l of the simple leaves below fronts, front by front
    DevBuf<int> d_roots, d_root_off;     // fronts without a head parent, per block (k_root_assemble)
+   // first touch of the tails (BatchLayout::tail_first_touch): per tail column the entries of K and of the border and the pieces of the
+   // root fronts (k_tail_first_touch); the simple leaves whose products follow (k_leaf_products)
+   DevBuf<long long> d_ft_colbase;
+   DevBuf<int> d_ft_init_off, d_ft_piece_off, d_ft_leaves;
+   DevBuf<FtInit> d_ft_init;
+   DevBuf<FtPiece> d_ft_piece;
    DevBuf<BbBatch> d_bb_batches;        // border split (k_border_schur): batches of supernodes with border rows, block after block
    DevBuf<BbMeta> d_bb_meta;
    DevBuf<int> d_bb_off, d_bb_pos;      // batches of block b: [d_bb_off[b], d_bb_off[b + 1]); compressed border ids of the staged rows
@@ -1242,6 +1248,17 @@ struct Engine : EngineAnalysis, BatchLayout {
          PIPS_TRY(d_br_src.upload(h_br_src));
       }
       PIPS_TRY(d_nprimal.upload(h_nprimal));
+      if (tail_first_touch) {   // (behind the others: the arenas keep their addresses)
+         // a column of more than 64 KB of LDS: the kernel is told once per analysis, not per factorisation
+         if ((size_t)ft_ld_max * sizeof(double) > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void*)k_tail_first_touch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ft_ld_max * sizeof(double))));
+         PIPS_TRY(d_ft_colbase.upload(h_ft_colbase));
+         PIPS_TRY(d_ft_init_off.upload(h_ft_init_off));
+         PIPS_TRY(d_ft_init.upload(h_ft_init));
+         PIPS_TRY(d_ft_piece_off.upload(h_ft_piece_off));
+         PIPS_TRY(d_ft_piece.upload(h_ft_piece));
+         PIPS_TRY(d_ft_leaves.upload(h_ft_leaves));
+      }
       return PIPS_OK;
    }
 
@@ -1250,7 +1267,7 @@ struct Engine : EngineAnalysis, BatchLayout {
       if (L.simple_cnt > 0)
          hipLaunchKernelGGL(k_head_factor_simple, dim3((L.simple_cnt + 255) / 256), dim3(256), 0, stream, d_sns, L.simple_begin,
                             L.simple_cnt, d_blks, d_rowidx, d_upd, d_psign, d_psign_off, d_bmap, d_arena, SC, ldSC, d_inertia, d_pref, d_sctab, sx,
-                            mf ? 1 : 0, d_mfLV, d_lf_pos, d_lf_val, d_arena);
+                            mf ? 1 : 0, d_mfLV, d_lf_pos, d_lf_val, d_arena, tail_first_touch ? 1 : 0);
       if (mf) return;
       if (L.small_cnt > 0)
          hipLaunchKernelGGL((k_head_factor<64, 8, 640>), dim3(L.small_cnt), dim3(64), (size_t)std::max(L.small_lds, 1) * sizeof(double), stream, d_sns,
@@ -1471,7 +1488,8 @@ struct Engine : EngineAnalysis, BatchLayout {
       hipLaunchKernelGGL(k_block_absmax_finish, dim3((nblk + 255) / 256), dim3(256), 0, stream, d_blks, nblk, thr_rel, repl_rel);
       // multifrontal head: no panel of the head is read before it is written (simple leaves: every entry of the panel is an entry of K or
       // of the border and comes with k_scatter; fronts: assembled in LDS, written out whole) - only the tails are cleared
-      hipLaunchKernelGGL(k_arena_clear, dim3(256, nblk), dim3(256), 0, stream, d_blks, d_arena, mf ? 1 : 0);
+      // (first touch of the tails: k_tail_first_touch writes every tail column once, assembled, after the head - no clear, no padding diagonal here)
+      if (!tail_first_touch) hipLaunchKernelGGL(k_arena_clear, dim3(256, nblk), dim3(256), 0, stream, d_blks, d_arena, mf ? 1 : 0);
       HIP_TRY(hipMemsetAsync(d_inertia, 0, (size_t)3 * nblk * sizeof(int), stream));
       if (!d_gemm_ctr) PIPS_TRY(d_gemm_ctr.alloc((size_t)GEMM_CTR_SLOTS * 8));
       HIP_TRY(hipMemsetAsync(d_gemm_ctr, 0, (size_t)GEMM_CTR_SLOTS * 8 * sizeof(int), stream));
@@ -1480,7 +1498,7 @@ struct Engine : EngineAnalysis, BatchLayout {
          hipLaunchKernelGGL(k_scatter, dim3(grid_for(nnzK_total, 256)), dim3(256), 0, stream, d_kdst, d_kval, d_arena, nnzK_total);
       if (nnzB_total > 0 && schur_mode_eff == 1)
          hipLaunchKernelGGL(k_scatter, dim3(grid_for(nnzB_total, 256)), dim3(256), 0, stream, d_bdst, d_bval, d_arena, nnzB_total);
-      hipLaunchKernelGGL(k_tail_pad_diag, dim3(nblk), dim3(128), 0, stream, d_blks, d_arena, nblk);
+      if (!tail_first_touch) hipLaunchKernelGGL(k_tail_pad_diag, dim3(nblk), dim3(128), 0, stream, d_blks, d_arena, nblk);
       hipLaunchKernelGGL(k_pref_rows, dim3(32, nblk), dim3(256), 0, stream, d_blks, d_kval, d_kdiag, d_res, d_nprimal, d_krowptr, d_kcolidx);   // (d_res: scratch of the solves)
       hipLaunchKernelGGL(k_pref_init, dim3(32, nblk), dim3(256), 0, stream, d_blks, d_perm, d_perm_off, (const double*)d_res, d_pref);
       return PIPS_OK;
@@ -1489,6 +1507,12 @@ struct Engine : EngineAnalysis, BatchLayout {
    void launch_root_assemble(double* SC, int ldSC) {
       // about 2048 workgroups in the launch (what is resident at once): half of a block's chunks on the tail's columns, half on the border's
       const int asm_half = std::max(1, std::min(32, 1024 / std::max(nblk, 1)));
+      if (tail_first_touch) {   // the tails were assembled column by column (launch_tail_first_touch): only the border x border part is left
+         if (SC && n_roots > 0)
+            hipLaunchKernelGGL(k_root_assemble, dim3(nblk, asm_half), dim3(256), 0, stream, (const int*)nullptr, d_root_off, d_roots, d_sns, d_blks, d_rowidx, d_bmap,
+                               d_arena, d_mfU, SC, ldSC, d_sctab, (double*)nullptr, 0LL, (const int*)nullptr, 0, asm_half);
+         return;
+      }
       if (deterministic && d_gbuf && SC && d_round_blk) {
          for (size_t k = 0; k + 1 < det.round_off.size(); ++k) {
             const int cnt = det.round_off[k + 1] - det.round_off[k];
@@ -1499,6 +1523,17 @@ struct Engine : EngineAnalysis, BatchLayout {
       } else
          hipLaunchKernelGGL(k_root_assemble, dim3(nblk, 2 * asm_half), dim3(256), 0, stream, (const int*)nullptr, d_root_off, d_roots, d_sns, d_blks, d_rowidx, d_bmap,
                             d_arena, d_mfU, SC, ldSC, d_sctab, (double*)nullptr, 0LL, (const int*)nullptr, asm_half, asm_half);
+   }
+   // first touch of the tails: every tail column written once - the entries of K and of the border, the padding diagonal, the root fronts'
+   // update matrices - and then the products of the simple leaves that have no front above them
+   int launch_tail_first_touch(double* SC, int ldSC) {
+      const size_t lds = (size_t)ft_ld_max * sizeof(double);
+      hipLaunchKernelGGL(k_tail_first_touch, dim3(ft_cols_max, nblk), dim3(64), lds, stream, d_blks, d_ft_colbase, d_ft_init_off, d_ft_init, d_ft_piece_off,
+                         d_ft_piece, d_rowidx, d_kval, d_bval, d_mfU, d_arena);
+      if (n_ft_leaves > 0)
+         hipLaunchKernelGGL(k_leaf_products, dim3((n_ft_leaves + 255) / 256), dim3(256), 0, stream, d_ft_leaves, n_ft_leaves, d_sns, d_blks, d_rowidx, d_bmap,
+                            d_arena, SC, ldSC, d_sctab);
+      return PIPS_OK;
    }
    // the head by levels, then what follows from its finished panels; one phase-1 record per level and per stage that runs
    int factor_head(double* SC, int ldSC) {
@@ -1517,6 +1552,7 @@ struct Engine : EngineAnalysis, BatchLayout {
             gather(g_sc_grp, d_slot_val, d_gbuf);
          } else if (SC) gather(g_sc, d_slot_val, SC);
       }
+      if (tail_first_touch) { PhaseTimer::Scope phase(&timer, stream, 1); PIPS_TRY(launch_tail_first_touch(SC, ldSC)); }
       if (mf && n_roots > 0) { PhaseTimer::Scope phase(&timer, stream, 1); launch_root_assemble(SC, ldSC); }
       if (mf && d_kb_list) {   // fronts on the rows of K only: their border rows now, level by level, from the finished panels; then the head's part
                                // of the dense tail's border rows.  (Forming level l on a second stream beside the fronts above it, which need
@@ -2224,6 +2260,8 @@ static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs
    opt.mf_konly = opt.mf_split_nb_max > 0 && !knobs.deterministic && opt.max_sn_width <= 16 && env_int("PIPS_HIP_MF_KONLY", 0) != 0;
    knobs.spine = env_flag("PIPS_HIP_SPINE");                      // 0: no spine kernels
    knobs.tail_single = env_flag("PIPS_HIP_TAIL_SINGLE");          // 0 / 1 forces one side (default: batches of up to 16 blocks)
+   knobs.tail_first_touch = env_flag("PIPS_HIP_TAIL_FIRST_TOUCH");   // 0: the tails are cleared and added to as before (default: first touch where the batch allows it)
+   knobs.ft_lds_bytes = std::min(FT_LDS_MAX, std::max(0LL, (long long)env_int("PIPS_HIP_FIRST_TOUCH_LDS", (int)FT_LDS_BUDGET)));   // (tests: a small budget refuses the path; never more than a workgroup can have)
    knobs.border_backward = env_flag("PIPS_HIP_BORDER_BACKWARD");  // 0 / 1 instead of the cost rule of the border-backward sweep
    knobs.aug_sweeps = env_flag("PIPS_HIP_AUG_SWEEPS");            // 0 / 1 instead of the cost rule of the sweeps of the augmented factor
    knobs.sweep_launches = getenv("PIPS_HIP_SWEEP_LAUNCHES") != nullptr;   // (SweepRt::build: the single-launch sweeps are off)
@@ -3035,6 +3073,7 @@ int pips_hip_batch_info(void* handle, int64_t* what, int n_what) {
    if (n_what > 24) { what[24] = 0; for (const BlockSym& s : e->sym) what[24] += s.mf_split ? 1 : 0; }   // blocks with the border split
    if (n_what > 25) { what[25] = 0; for (const BlockSym& s : e->sym) what[25] += (e->mf && s.mf_konly) ? 1 : 0; }   // ... whose fronts hold the rows of K only
    if (n_what > 26) what[26] = e->packed_rhs;   // right-hand sides of the packed blocked solves (Schur mode 2 with the sparse root), else 0
+   if (n_what > 27) what[27] = e->tail_first_touch ? 1 : 0;   // the tails are written once, assembled (k_tail_first_touch), not cleared and added to
    return PIPS_OK;
 }
 
@@ -4304,6 +4343,81 @@ int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int*
       }
    }
    counts[0] = nc; counts[1] = ng; counts[2] = plan.ntc_max; counts[3] = pp.n_groups; counts[4] = launches_col; counts[5] = launches_grp;
+   return PIPS_OK;
+}
+
+// ---- first-touch plan probe (CPU only): the layout of a batch twice - with the first touch of the tails refused (PIPS_HIP_TAIL_FIRST_TOUCH=0
+// does the same) and as the analysis decides it - as sections of integers (include/pips_hip.h)
+int pips_first_touch_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
+                           const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head, int deterministic, long long lds_bytes,
+                           long long free_device_bytes, long long* out, long long cap, int64_t* counts) {
+   std::vector<BlockInput> in;
+   PIPS_TRY(probe_inputs("pips_first_touch_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
+   if (!counts || cap < 0 || (cap > 0 && !out)) PIPS_FAIL(PIPS_ERR_ARG, "pips_first_touch_probe: bad arguments");
+   AnalyzeOptions opt;
+   AnalyzeKnobs knobs;
+   read_layout_knobs(nullptr, opt, knobs);
+   if (deterministic) { knobs.deterministic = true; opt.mf_konly = false; }   // (as pips_layout_probe)
+   opt.force_n_head = force_n_head;
+   knobs.free_device_bytes = free_device_bytes;
+   if (lds_bytes > 0) knobs.ft_lds_bytes = lds_bytes;
+   std::vector<BlockSym> sym;
+   BatchLayout old, lay;
+   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+   PIPS_TRY(analyze_symbolic(in, S, n_threads, opt, knobs, sym));
+   PIPS_TRY(build_batch_layout(in, sym, S, knobs, lay));
+   PIPS_TRY(check_batch_layout(in, sym, S, knobs, lay));
+   knobs.tail_first_touch = 0;
+   PIPS_TRY(build_batch_layout(in, sym, S, knobs, old));
+   long long at = 0;
+   int section = 0;
+   auto put = [&](long long v) { if (at < cap) out[at] = v; ++at; };
+   long long from = 0;
+   auto end = [&]() { counts[8 + section++] = at - from; from = at; };
+   for (int b = 0; b < nblk; ++b) {
+      const BlkDesc& d = lay.h_blks[b];
+      put(d.n); put(d.n_head); put(d.m); put(d.m_pad); put(d.nb); put(d.ldT); put(d.mf_split); put(d.T_in); put(lay.kptr[b]);
+      put((long long)in[b].btcol.size()); put(lay.mf ? lay.h_root_off[b + 1] - lay.h_root_off[b] : 0); put(d.ntc);
+   }
+   end();
+   for (long long v : lay.h_ft_colbase) put(v);
+   end();
+   for (int v : lay.h_ft_init_off) put(v);
+   end();
+   for (const FtInit& e : lay.h_ft_init) { put(e.row); put(e.src); }
+   end();
+   for (int v : lay.h_ft_piece_off) put(v);
+   end();
+   for (const FtPiece& e : lay.h_ft_piece) { put(e.front); put(e.u); put(e.rows); put(e.cnt); }
+   end();
+   for (int v : lay.h_ft_leaves) put(v);
+   end();
+   for (long long v : old.h_kdst) put(v);
+   end();
+   for (long long v : lay.h_kdst) put(v);
+   end();
+   for (long long v : old.h_bdst) put(v);
+   end();
+   for (long long v : lay.h_bdst) put(v);
+   end();
+   for (int b = 0; b < nblk && lay.mf; ++b)   // the root fronts k_root_assemble walks, in its order
+      for (int q = lay.h_root_off[b]; q < lay.h_root_off[b + 1]; ++q) {
+         const SnDesc& sn = lay.h_sns[lay.h_roots[q]];
+         put(b); put(lay.h_roots[q]); put(sn.r); put(sn.rb); put(sn.U); put(sn.rows);
+      }
+   end();
+   for (int v : lay.h_rowidx) put(v);
+   end();
+   if (!lay.levels.empty()) {   // the simple leaves
+      const LevelRange& L0 = lay.levels[0];
+      for (int i = L0.simple_begin; i < L0.simple_begin + L0.simple_cnt; ++i) {
+         const SnDesc& sn = lay.h_sns[i];
+         put(i); put(sn.blk); put(sn.r); put(sn.n_useg); put(sn.rows);
+      }
+   }
+   end();
+   const int64_t head[8] = {lay.tail_first_touch, lay.mf, lay.tail_single, lay.schur_mode_eff, lay.mfU_total, lay.nnzK_total, lay.nnzB_total, at};
+   std::copy(head, head + 8, counts);
    return PIPS_OK;
 }
 

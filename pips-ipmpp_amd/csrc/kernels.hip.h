@@ -477,7 +477,8 @@ __global__ __launch_bounds__(256) void k_head_factor_simple(const SnDesc* __rest
                                                            const int* __restrict__ sctab,
                                                            ScatterCtx sx = ScatterCtx{0, nullptr, nullptr, nullptr, nullptr}, int mf = 0,
                                                            double* __restrict__ lvals = nullptr, const int* __restrict__ lfpos = nullptr,
-                                                           double* __restrict__ lfval = nullptr, double* __restrict__ bbarena = nullptr) {
+                                                           double* __restrict__ lfval = nullptr, double* __restrict__ bbarena = nullptr,
+                                                           int defer = 0) {
    __shared__ int cnt_s[3];
    __shared__ int blk_s;
    const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -549,6 +550,9 @@ __global__ __launch_bounds__(256) void k_head_factor_simple(const SnDesc* __rest
             b_head = sb1;
          }
       }
+      // first touch of the tails (defer): the tail is not there yet - the products into the tail and the Schur complement follow from
+      // the panel once its columns are written (k_leaf_products)
+      if (defer) b_head = r;
 #pragma unroll
       for (int b = 0; b < SIMPLE_RMAX; ++b) {
          if (b < r && b >= b_head) {
@@ -572,6 +576,51 @@ __global__ __launch_bounds__(256) void k_head_factor_simple(const SnDesc* __rest
    }
    __syncthreads();
    if (threadIdx.x < 3 && cnt_s[threadIdx.x]) atomicAdd(&inertia[3 * blk_s + threadIdx.x], cnt_s[threadIdx.x]);
+}
+
+// First touch of the tails: the rank-one products of the simple leaves without a front above them (all their rows lie in the tail or
+// the border), from d and l as k_head_factor_simple left them in the panel - the same FP64 atomics into the tail and the Schur
+// complement, after k_tail_first_touch has written the columns.  One thread per leaf of the list.
+__global__ __launch_bounds__(256) void k_leaf_products(const int* __restrict__ leaves, int cnt, const SnDesc* __restrict__ sns,
+                                                      const BlkDesc* __restrict__ blks, const int* __restrict__ rowidx,
+                                                      const int* __restrict__ bmap, double* __restrict__ arena, double* __restrict__ SC,
+                                                      int ldSC, const int* __restrict__ sctab) {
+   const int t = blockIdx.x * blockDim.x + threadIdx.x;
+   if (t >= cnt) return;
+   const SnDesc sn = sns[leaves[t]];
+   const BlkDesc bd = blks[sn.blk];
+   const int r = sn.r;
+   const double* P = arena + sn.panel;
+   const int* rows = rowidx + sn.rows;
+   const double d = P[0];
+   double l[SIMPLE_RMAX];
+   int ro[SIMPLE_RMAX];
+#pragma unroll
+   for (int a = 0; a < SIMPLE_RMAX; ++a)
+      if (a < r) { ro[a] = rows[a]; l[a] = P[1 + a]; }
+   double* T = arena + bd.T_in;
+   const int* bm = bmap + bd.bmap_off;
+   const int n = bd.n, n_head = bd.n_head;
+#pragma unroll
+   for (int b = 0; b < SIMPLE_RMAX; ++b) {
+      if (b < r) {
+         const int cb = ro[b];
+         const double lbd = l[b] * d;
+#pragma unroll
+         for (int a = b; a < SIMPLE_RMAX; ++a) {
+            if (a < r) {
+               const int ra = ro[a];
+               const double u = l[a] * lbd;
+               if (cb < n) {
+                  const int tr = ra < n ? ra - n_head : bd.m_pad + (ra - n);
+                  atomic_add_f64(T + tr + (long long)(cb - n_head) * bd.ldT, -u);
+               } else if (SC) {
+                  atomic_add_f64(sc_entry(SC, ldSC, bm, sctab, bd.sctab_off, bd.nb, ra - n, cb - n), -u);
+               }
+            }
+         }
+      }
+   }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -926,6 +975,7 @@ __global__ __launch_bounds__(256) void k_root_assemble(const int* __restrict__ b
    const int n = bd.n, n_head = bd.n_head, c = blockIdx.y;
    double* S_ = gbuf ? gbuf + gstride * blk_group[blk] : SC;
    const bool tail_chunk = c < nt;
+   const bool ordered = tail_chunk || gbuf;   // (atomics into the Schur complement: nothing orders those adds anyway - no barrier per front)
    if (!tail_chunk && (!S_ || bd.mf_split)) return;   // (border split: the update matrices hold no border x border part, k_border_schur forms it)
    // block-local row ids [lo, hi) whose columns this workgroup owns
    int lo, hi;
@@ -975,9 +1025,98 @@ __global__ __launch_bounds__(256) void k_root_assemble(const int* __restrict__ b
                if (gbuf) *tgt += u; else atomic_add_f64(tgt, u);
             }
          }
-         __syncthreads();   // the next front may reach the same entries from other threads
+         if (ordered) __syncthreads();   // the next front may reach the same entries from other threads
       }
    }
+}
+
+// First touch of the tails: every tail column c < m_pad of every block is written ONCE, assembled, instead of being cleared
+// (k_arena_clear) and then added to through device memory (k_scatter, k_tail_pad_diag, k_root_assemble's tail chunks).  One wave owns a
+// column and keeps its rows r0 .. ldT-1 (r0 = top of the diagonal tile: the range k_arena_clear writes) in LDS:
+//   1. zero the LDS column;  2. store the column's entries of K and of the border (FtInit) and the 1 of a padding diagonal;
+//   3. add the column's pieces of the root fronts' update matrices (FtPiece: column b of a front whose row b is this column - the entries
+//      k_root_assemble's rule gives to this column), in ascending front order like k_root_assemble; inside a piece the rows are distinct.
+//      The values and row indices of FT_PF pieces are requested together, before the first is added: the dependent chain is LDS only;
+//   4. write the column with 16-byte stores.
+// The sums keep k_root_assemble's order: the value of K first, then the fronts ascending.  No atomics; no barrier - the LDS operations
+// of one wave complete in the order they were issued (the wavefront-scope fences keep the compiler from moving them across the steps).
+// The zeroing loop and the write-out go by pairs of doubles (16-byte LDS and device accesses): ldT - r0 is even and a column starts at
+// an even arena offset T_in + c ldT + r0 - what k_arena_clear relies on as well; layout_first_touch refuses the path otherwise.
+// grid (max m_pad, blocks), 64 threads, 8 * max ldT bytes of dynamic LDS.  (A workgroup of two or four waves per column - the first wave
+// sums, all of them zero the LDS and write the column out, two barriers - measured 3.16 ms against 2.97 on the configs[1] blocks: fewer
+// columns in flight per compute unit for the same LDS.  profiles/tail_first_touch_ab.txt)
+constexpr int FT_PF = 8;   // pieces requested together
+__global__ __launch_bounds__(64) void k_tail_first_touch(const BlkDesc* __restrict__ blks, const long long* __restrict__ colbase,
+                                                        const int* __restrict__ init_off, const FtInit* __restrict__ init,
+                                                        const int* __restrict__ piece_off, const FtPiece* __restrict__ piece,
+                                                        const int* __restrict__ rowidx, const double* __restrict__ kval,
+                                                        const double* __restrict__ bval, const double* __restrict__ uarena,
+                                                        double* __restrict__ arena) {
+   extern __shared__ __align__(16) double ft_col[];
+   typedef double double2_t __attribute__((ext_vector_type(2)));
+   const BlkDesc bd = blks[blockIdx.y];
+   const int c = blockIdx.x, lane = threadIdx.x;
+   if (c >= bd.m_pad) return;
+   const int r0 = c / TILE * TILE, len = bd.ldT - r0;
+   const long long g = colbase[blockIdx.y] + c;
+   const int i0 = init_off[g], i1 = init_off[g + 1], p0 = piece_off[g], p1 = piece_off[g + 1];
+   const int n = bd.n, n_head = bd.n_head, m_pad = bd.m_pad;
+   // Every request of the column leaves before the LDS is touched: its first 64 entries of K / the border, and the first FT_PF pieces -
+   // the first 128 rows of each, one or two per lane.  The pieces are then added one after the other from registers; a batch of pieces
+   // costs one round trip to memory, not one per piece (4.7 pieces per column on the configs[1] blocks).
+   FtPiece d[FT_PF];
+   int ra[FT_PF][2];
+   double u[FT_PF][2];
+   auto request = [&](int pb) {
+#pragma unroll
+      for (int k = 0; k < FT_PF; ++k) {
+         d[k] = pb + k < p1 ? piece[pb + k] : FtPiece{0, 0, 0, 0};
+#pragma unroll
+         for (int h = 0; h < 2; ++h) {
+            ra[k][h] = 0; u[k][h] = 0.0;
+            if (lane + 64 * h < d[k].cnt) { ra[k][h] = rowidx[d[k].rows + lane + 64 * h]; u[k][h] = uarena[d[k].u + lane + 64 * h]; }
+         }
+      }
+   };
+   auto slot = [&](int row) { return (row < n ? row - n_head : m_pad + (row - n)) - r0; };
+   FtInit e0 = FtInit{0, 0};
+   if (i0 + lane < i1) e0 = init[i0 + lane];
+   request(p0);
+   double v0 = 0.0;
+   if (i0 + lane < i1) v0 = e0.src >= 0 ? kval[e0.src] : bval[~e0.src];
+   const double2_t z = {0.0, 0.0};
+   for (int i = 2 * lane; i < len; i += 128) *(double2_t*)(ft_col + i) = z;
+   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+   if (i0 + lane < i1) ft_col[e0.row - r0] = v0;
+   for (int q = i0 + 64 + lane; q < i1; q += 64) {   // (more than 64 entries in one column)
+      const FtInit e = init[q];
+      ft_col[e.row - r0] = e.src >= 0 ? kval[e.src] : bval[~e.src];
+   }
+   if (c >= bd.m && lane == 0) ft_col[c - r0] = 1.0;
+   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+   for (int pb = p0; pb < p1;) {
+#pragma unroll
+      for (int k = 0; k < FT_PF; ++k) {
+         const int cnt = d[k].cnt;   // (wave-uniform; 0 behind the column's last piece)
+         if (lane < cnt) ft_col[slot(ra[k][0])] += u[k][0];
+         if (lane + 64 < cnt) ft_col[slot(ra[k][1])] += u[k][1];
+         for (int i = 128 + lane; i < cnt; i += 64)   // (a front with more than 128 rows below this one)
+            ft_col[slot(rowidx[d[k].rows + i])] += uarena[d[k].u + i];
+         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the next piece may reach the same rows from other lanes
+      }
+      pb += FT_PF;
+      if (pb < p1) request(pb);
+   }
+   // four LDS reads in flight per lane, then their stores (a read waited for per store left the wave idle most of the loop)
+   double2_t* dst = (double2_t*)(arena + bd.T_in + (long long)c * bd.ldT + r0);
+   constexpr int STEP = 128;
+   int i = 2 * lane;
+   for (; i + 3 * STEP < len; i += 4 * STEP) {
+      const double2_t a0 = *(const double2_t*)(ft_col + i), a1 = *(const double2_t*)(ft_col + i + STEP);
+      const double2_t a2 = *(const double2_t*)(ft_col + i + 2 * STEP), a3 = *(const double2_t*)(ft_col + i + 3 * STEP);
+      dst[i >> 1] = a0; dst[(i + STEP) >> 1] = a1; dst[(i + 2 * STEP) >> 1] = a2; dst[(i + 3 * STEP) >> 1] = a3;
+   }
+   for (; i < len; i += STEP) dst[i >> 1] = *(const double2_t*)(ft_col + i);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -583,6 +583,81 @@ int layout_index_arrays(const std::vector<BlockInput>& in, const std::vector<Blo
    return PIPS_OK;
 }
 
+// ---- first-touch plan of the tails (layout.h): decided per batch.  It needs the multifrontal head (fronts hand their update matrices on,
+// only the root fronts' reach the tail; no spine kernels) without deterministic mode (its slot records hold tail addresses and its sums
+// keep today's order bit for bit), so that before the tail factorisation nothing but k_scatter, k_tail_pad_diag, the simple leaves and
+// k_root_assemble writes the tails; and the tallest column has to fit the LDS budget.  Takes the tail targets out of h_kdst / h_bdst.
+int layout_first_touch(const std::vector<BlockSym>& sym, const Bases& B, const LayoutKnobs& knobs, BatchLayout& o) {
+   const int nblk = (int)sym.size();
+   o.tail_first_touch = false;
+   o.ft_ld_max = 0; o.ft_cols_max = 0;
+   for (const BlkDesc& bd : o.h_blks) { o.ft_ld_max = std::max(o.ft_ld_max, bd.ldT); o.ft_cols_max = std::max(o.ft_cols_max, bd.m_pad); }
+   if (knobs.tail_first_touch == 0 || !o.mf || knobs.deterministic || o.spine_total > 0 || o.ft_cols_max == 0 || o.levels.empty() ||
+       8LL * o.ft_ld_max > std::min(knobs.ft_lds_bytes, FT_LDS_MAX) || o.nnzK_total >= INT_MAX || o.nnzB_total >= INT_MAX)
+      return PIPS_OK;
+   // the kernel zeroes and writes a column in pairs of doubles (16-byte LDS and device accesses, like k_arena_clear): every column starts
+   // at an even offset and holds an even number of rows (ldT is a multiple of the tile, T_in of the panels' padding of 16)
+   for (const BlkDesc& bd : o.h_blks)
+      if ((bd.ldT & 1) || (bd.T_in & 1)) return PIPS_OK;
+   o.h_ft_colbase.assign(nblk + 1, 0);
+   for (int b = 0; b < nblk; ++b) o.h_ft_colbase[b + 1] = o.h_ft_colbase[b] + o.h_blks[b].m_pad;
+   if (o.h_ft_colbase[nblk] >= INT_MAX) return PIPS_OK;
+   const size_t ncols = (size_t)o.h_ft_colbase[nblk];
+   struct Init { int col, row, src; };
+   struct Piece { int col; FtPiece p; };
+   std::vector<Init> ini;
+   std::vector<Piece> pcs;
+   for (int b = 0; b < nblk; ++b) {
+      const BlockSym& s = sym[b];
+      const BlkDesc& bd = o.h_blks[b];
+      const int cb = (int)o.h_ft_colbase[b];
+      auto take = [&](const std::vector<int64_t>& dst, std::vector<long long>& out, long long base, bool border) -> int {
+         for (size_t p = 0; p < dst.size(); ++p) {
+            if (out[(size_t)base + p] < 0 || dst[p] < s.T_off) continue;
+            const long long rel = dst[p] - s.T_off;
+            const int c = (int)(rel / bd.ldT), row = (int)(rel % bd.ldT);
+            if (c >= bd.m_pad || row < c / TILE * TILE) PIPS_FAIL(PIPS_ERR_STATE, "analyze: internal error, entry %zu of block %d lands above the diagonal tile of tail column %d", p, b, c);
+            ini.push_back(Init{cb + c, row, border ? ~(int)(base + (long long)p) : (int)(base + (long long)p)});
+            out[(size_t)base + p] = -1;
+         }
+         return PIPS_OK;
+      };
+      if (int rc = take(s.a_dst, o.h_kdst, o.kptr[b], false)) return rc;
+      if (o.schur_mode_eff == 1)   // (Schur mode 2 scatters no border)
+         if (int rc = take(s.b_dst, o.h_bdst, B.bptr[b], true)) return rc;
+      for (int q = o.h_root_off[b]; q < o.h_root_off[b + 1]; ++q) {
+         const SnDesc& sn = o.h_sns[o.h_roots[q]];
+         const int r = bd.mf_split == 2 ? sn.rb : sn.r;   // (fronts on the rows of K only hand over a K x K update matrix)
+         const int* rows = o.h_rowidx.data() + sn.rows;
+         for (int a = 0; a < r; ++a) {   // rows ascend; the first lies in the tail or the border, the last inside the column's LDS
+            const int tr = rows[a] < bd.n ? rows[a] - bd.n_head : bd.m_pad + (rows[a] - bd.n);
+            if (rows[a] < bd.n_head || tr >= bd.ldT || (a > 0 && rows[a] <= rows[a - 1]))
+               PIPS_FAIL(PIPS_ERR_STATE, "analyze: internal error, row %d of root front %d of block %d", a, o.h_roots[q], b);
+         }
+         for (int bcol = 0; bcol < std::min(sn.rb, r); ++bcol)
+            pcs.push_back(Piece{cb + rows[bcol] - bd.n_head,
+                                FtPiece{sn.U + (long long)bcol * r - (long long)bcol * (bcol - 1) / 2, sn.rows + bcol, r - bcol, o.h_roots[q]}});
+      }
+   }
+   // by column, in the order met (K before border; fronts ascending): counting sort
+   o.h_ft_init_off.assign(ncols + 1, 0); o.h_ft_piece_off.assign(ncols + 1, 0);
+   for (const Init& e : ini) ++o.h_ft_init_off[(size_t)e.col + 1];
+   for (const Piece& e : pcs) ++o.h_ft_piece_off[(size_t)e.col + 1];
+   for (size_t g = 0; g < ncols; ++g) { o.h_ft_init_off[g + 1] += o.h_ft_init_off[g]; o.h_ft_piece_off[g + 1] += o.h_ft_piece_off[g]; }
+   o.h_ft_init.assign(ini.size(), FtInit{0, 0}); o.h_ft_piece.assign(pcs.size(), FtPiece{0, 0, 0, 0});
+   {
+      std::vector<int> fi(o.h_ft_init_off.begin(), o.h_ft_init_off.end() - 1), fp(o.h_ft_piece_off.begin(), o.h_ft_piece_off.end() - 1);
+      for (const Init& e : ini) o.h_ft_init[(size_t)fi[(size_t)e.col]++] = FtInit{e.row, e.src};
+      for (const Piece& e : pcs) o.h_ft_piece[(size_t)fp[(size_t)e.col]++] = e.p;
+   }
+   const LevelRange& L0 = o.levels[0];
+   for (int i = L0.simple_begin; i < L0.simple_begin + L0.simple_cnt; ++i)
+      if (o.h_sns[i].n_useg == 0 && o.h_sns[i].r > 0) o.h_ft_leaves.push_back(i);
+   o.n_ft_leaves = (int)o.h_ft_leaves.size();
+   o.tail_first_touch = true;
+   return PIPS_OK;
+}
+
 // ---- both triangles, row by row: entry (i, j) of the lower CSR also appears in row j as (j, i)
 void layout_full_rows(const std::vector<BlockInput>& in, const std::vector<BlockSym>& sym, BatchLayout& o) {
    const int nblk = (int)in.size();
@@ -775,6 +850,7 @@ int build_batch_layout(const std::vector<BlockInput>& in, const std::vector<Bloc
    layout_spine_lists(sym, sorted_id, lstar, out);
    layout_tail_single(sym, knobs, out);
    if ((rc = layout_index_arrays(in, sym, sorted_id, B, out))) return rc;
+   if ((rc = layout_first_touch(sym, B, knobs, out))) return rc;
    layout_full_rows(in, sym, out);
    layout_border_csr(in, S, B, out);
    layout_leaf_gather(out);
@@ -955,7 +1031,8 @@ void BatchLayout::drop_uploaded() {
    drop(h_rowidx, h_sncol, h_bmap, h_perm, h_upd, h_mfint, h_nprimal, h_psign, h_psign_off, h_perm_off, h_kdst, h_bdst, h_kdiag, h_rowbase,
         h_krowptr, h_kcolidx, h_frowptr, h_fcol, h_fsrc, h_flong, h_bt_rowptr, h_bt_colidx, h_bt_xoff, h_bval, h_br_rowptr, h_br_sc, h_br_src,
         h_schur_slot, h_leafdesc, h_lf_rows, h_lf_ptr, h_lf_src, h_lf_pos, h_lb_list, tile_first, h_roots, h_bb_batches, h_bb_meta, h_bb_pos,
-        h_kb_rec, h_kb_list, h_kb_tail, h_kb_off, h_spine, h_spine_off);
+        h_kb_rec, h_kb_list, h_kb_tail, h_kb_off, h_spine, h_spine_off, h_ft_colbase, h_ft_init_off, h_ft_piece_off, h_ft_init, h_ft_piece,
+        h_ft_leaves);
 }
 
 }  // namespace pips

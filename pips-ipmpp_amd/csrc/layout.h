@@ -57,6 +57,11 @@ BbPlanSize bb_plan_size(const std::vector<BlockSym>& sym);
 size_t bb_lds_bytes(const BbPlanSize& z);
 inline bool bb_fits(const BbPlanSize& z) { return bb_lds_bytes(z) <= 160 * 1024 && z.poscap <= 4 * 512 && z.stage <= 2 * 6 * 512; }
 
+// k_tail_first_touch keeps one tail column (8 ldT bytes) per wave in LDS: half of a compute unit's 160 KB, so that at least two
+// columns are resident per compute unit
+constexpr long long FT_LDS_BUDGET = 80 * 1024;
+constexpr long long FT_LDS_MAX = 160 * 1024;   // what a workgroup can have at all: a larger budget (LayoutKnobs::ft_lds_bytes) counts as this
+
 // Every switch the layout depends on, as values (Engine: read_layout_knobs).  A switch with "-1: not set" takes the layout's own rule.
 struct LayoutKnobs {
    bool deterministic = false;
@@ -68,6 +73,8 @@ struct LayoutKnobs {
    int border_backward = -1, aug_sweeps = -1;   // 0 / 1 instead of the cost rules of the sweeps of the augmented factor
    bool sweep_launches = false; // the launch-per-tile-column solve sweeps are selected (the single-launch sweeps are off)
    long long free_device_bytes = 0;   // the one runtime input: free device memory, decides tail_single
+   int tail_first_touch = -1;   // 0: the tails are cleared and added to (k_arena_clear, k_root_assemble) whatever the batch looks like
+   long long ft_lds_bytes = FT_LDS_BUDGET;   // LDS a column of k_tail_first_touch may take (tests: a small value forces the fallback)
    // settled by analyze_symbolic
    bool mf = false;             // multifrontal head taken
    int schur_mode_eff = 1;
@@ -135,6 +142,21 @@ struct BatchLayout {
    std::vector<int> h_spine, h_spine_off;
    bool tail_single = false;    // the tails as one launch: they are then assembled in a scratch region (BlkDesc::T_in)
    long long tail_scratch = 0;  // doubles of that region, behind the panels and the border-row arena
+   // First-touch plan of the tails (layout_first_touch): every tail column c < m_pad is written once, assembled, by one wave of
+   // k_tail_first_touch instead of being cleared (k_arena_clear) and added to (k_scatter, k_tail_pad_diag, k_root_assemble).  Column c of
+   // block b is global column ft_colbase[b] + c; its init entries (entries of K and of the border whose scatter target lies in it; their
+   // targets in h_kdst / h_bdst are -1 then) and its front pieces (the (front, b) pairs with b < rb whose row b is column c - what
+   // k_root_assemble's rule "the column of an entry is the smaller of its two indices" assigns to it - in ascending front order) lie at
+   // [off[g], off[g + 1]).  ft_leaves: the simple leaves without a front above them; their rank-one products into the tail and the
+   // Schur complement wait until the columns are written (k_leaf_products).
+   bool tail_first_touch = false;
+   int ft_ld_max = 0, ft_cols_max = 0;   // tallest column (max ldT: the kernel's LDS) and most columns of a block (max m_pad)
+   int n_ft_leaves = 0;
+   std::vector<long long> h_ft_colbase;            // nblk + 1
+   std::vector<int> h_ft_init_off, h_ft_piece_off; // columns + 1 each
+   std::vector<FtInit> h_ft_init;
+   std::vector<FtPiece> h_ft_piece;
+   std::vector<int> h_ft_leaves;
    std::vector<int> schur_cols;   // non-empty Schur columns (any block), ascending
    std::vector<int> h_bt_rowsc, h_bt_rownnz, h_bt_rowblk;   // per row of the global border CSR: Schur column, entries, block
    int n_flong = 0;

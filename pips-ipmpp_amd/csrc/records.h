@@ -92,8 +92,19 @@ struct LeafDesc {
 // between them) and the first of the supernode's columns in the work vector.
 struct BgEntry { long long off; unsigned y; unsigned short stride, w; };
 
+// First touch of the tails (k_tail_first_touch; layout.h "first-touch plan"), per tail column.
+// An entry of K or of the border that lands in the column: its row inside the tail panel and its place in the value array
+// (src >= 0: K value src; src < 0: border value ~src).
+struct FtInit { int row, src; };
+// One column b of a root front's update matrix: cnt entries from uarena[u], going to the rows rowidx[rows .. rows + cnt)
+struct FtPiece {
+   long long u, rows;
+   int cnt, front;   // front: the root front's supernode id (pieces of a column ascend by it)
+};
+
 constexpr int FULL_LONG_ROW = 512;
 
+static_assert(sizeof(FtInit) == 8 && sizeof(FtPiece) == 24, "record layout read by the kernels");
 static_assert(sizeof(SnDesc) == 96 && sizeof(BlkDesc) == 176 && sizeof(TileTask) == 16, "record layout read by the kernels");
 static_assert(sizeof(BbMeta) == 32 && sizeof(BbBatch) == 40 && sizeof(LeafDesc) == 24 && sizeof(BgEntry) == 16, "record layout read by the kernels");
 

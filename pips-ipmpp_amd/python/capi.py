@@ -54,7 +54,7 @@ SYMBOLS = [
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
     "pips_hip_ldl_inertia_batch", "pips_hip_ldl_factor_schur_sparse", "pips_hip_ldl_factor_schur_sparse_batch",
     "pips_hip_dense_ldl_create", "pips_hip_dense_ldl_factor", "pips_hip_dense_ldl_factor_dev", "pips_hip_dense_ldl_solve",
-    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_ipm_layout_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
+    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_first_touch_probe", "pips_ipm_layout_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
     "pips_hip_batch_create", "pips_hip_batch_set_block", "pips_hip_batch_set_options", "pips_hip_batch_set_schur_mode", "pips_hip_batch_set_deterministic", "pips_hip_batch_get_schur_mode", "pips_hip_batch_add_regularization", "pips_hip_batch_set_refinement",
     "pips_hip_batch_last_refinement_steps", "pips_hip_batch_set_refinement_backward_error",
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
@@ -690,12 +690,12 @@ class LeafBatch:
         return (out.T if w < 2 else out), (m, m_pad, nb, ldT)
 
     def info(self):
-        what = np.zeros(27, np.int64)
-        _check(lib.pips_hip_batch_info(self._h, _ptr(what), C.c_int(27)), "pips_hip_batch_info")
+        what = np.zeros(28, np.int64)
+        _check(lib.pips_hip_batch_info(self._h, _ptr(what), C.c_int(28)), "pips_hip_batch_info")
         keys = ["nnzL", "n", "n_head", "m", "n_sn", "n_levels", "flops_factor", "flops_border", "arena_bytes", "ntc", "upd_table_bytes", "nb", "nnzK",
                 "ltsolve_from_augmented_factor", "multifrontal_head", "max_front", "update_matrix_bytes", "fronts_in_device_memory", "nnzL_head", "head_row_indices",
                 "nnzL_border", "augmented_sweeps", "augmented_passes", "tail_border_entries", "blocks_with_border_split", "blocks_with_k_only_fronts",
-                "packed_schur_rhs"]
+                "packed_schur_rhs", "tail_first_touch"]
         return {k: int(v) for k, v in zip(keys, what)}
 
     def sync(self):
