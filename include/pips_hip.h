@@ -544,7 +544,10 @@ enum {
    PIPS_SCALER_EQUILIBRIUM = 1,             /* EquilibriumScaler: one pass, max |entry| of every row and column becomes 1 */
    PIPS_SCALER_GEOMETRIC_MEAN = 2,          /* GeometricMeanScaler: up to 10 passes of 1 / sqrt(min max), kept if it gains 15 % */
    PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM = 3,   /* the same followed by an equilibrium pass */
-   PIPS_SCALER_CURTIS_REID = 4              /* reserved: PIPS_ERR_ARG */
+   PIPS_SCALER_CURTIS_REID = 4,             /* reserved: PIPS_ERR_ARG */
+   PIPS_SCALER_RUIZ = 5                     /* not in the reference: Ruiz equilibration of [Q J^T; J 0] by diag(col, row), ten simultaneous
+                                               passes of d <- d / sqrt(max |row of D K D|) with no early stop; the only scaler that sees a
+                                               Hessian.  Without one: Ruiz on [0 J^T; J 0] */
 };
 /* pips_ipm_create_general with a scaler, chosen at creation (the leaf borders are fixed by the analysis).  J = [A; C] becomes
  * R J Cs with R = diag(row_eq, row_ineq) and Cs = diag(col); c, b, the row and variable bounds and the linking right-hand sides
@@ -560,7 +563,8 @@ int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_b
 /* the factors in the harness order: col (nx) for x = [x0 | own blocks], row_eq (my) and row_ineq (mz) for [root | linking | own
  * blocks]; any pointer may be NULL.  info8 = {scaling applied (0/1), row ratio before, column ratio before, row ratio after,
  * column ratio after, geometric passes made, geometric stage kept (0/1), host waits of the scaler}.  A handle without scaling
- * returns factors of 1 and zeros in info8. */
+ * returns factors of 1 and zeros in info8.  PIPS_SCALER_RUIZ reports {1, J's ratios before and after (J's on a QP too), 10 (its
+ * passes), 0, 2 (the read before and the read after)}. */
 int pips_ipm_get_scaling(void* handle, double* col, double* row_eq, double* row_ineq, double* info8);
 int pips_ipm_outer_solve(void* handle, const double* G_host, const double* L_host, const double* rhs_host, double tol, double* sol_host,
                          double* info6);
@@ -578,11 +582,23 @@ int pips_ipm_outer_solve(void* handle, const double* G_host, const double* L_hos
  * result7[0] and trace column 2 hold c^T x + 1/2 x^T Q x; result7[5] and trace column 3 hold the Lagrangian dual
  * b^T y + clow^T lambda - cupp^T pi + xlow^T gamma - xupp^T phi - 1/2 x^T Q x, so that their difference is the reference's duality gap
  * (Residuals.cpp:69-165) - the reference's own dual_objective field omits the quadratic term.
- * Not offered: problem scaling together with a Hessian (there is no _scaled variant of this entry), the cross Hessian between x0 and
- * x_i, and Hessians through the pips_ipm_create shorthand. */
+ * Not offered: the cross Hessian between x0 and x_i, and Hessians through the pips_ipm_create shorthand. */
 int pips_ipm_create_qp(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl,
                        const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp,
                        double dual_reg, int device, void* comm, int rank, int n_ranks);
+/* pips_ipm_create_qp with a scaler.  With x = Cs x' the Hessian becomes Q' = Cs Q Cs beside J' = R J Cs: the stored entry (r, c) of a
+ * block's lower triangle is (q col_r) col_c, scaled on the host; the flat symmetric copy on the device is built from the scaled
+ * triangles and stays exactly symmetric.  The objective c'^T x' + 1/2 x'^T Q' x' is the original problem's value; the data norm of
+ * the scaled problem (start point) takes max |Q'|, the original one (termination) max |Q|; the unscaled residual keeps its weights
+ * (rQ' = Cs rQ).  The equilibrium and geometric-mean scalers take their factors from J alone, as the reference's Scaler does (its
+ * applyScaling leaves Q untouched), and Q follows the column factors; PIPS_SCALER_RUIZ equilibrates [Q J^T; J 0] and is the one to use
+ * on a badly scaled QP.  pips_ipm_get_scaling, pips_ipm_get_solution, pips_ipm_get_iterate and the trace behave as on a scaled LP
+ * handle; pips_ipm_mult, pips_ipm_outer_solve and pips_ipm_hessian_mult act on the scaled system (Q' v).
+ * scaler == PIPS_SCALER_NONE is pips_ipm_create_qp, Q == NULL (or no Q[i] present) pips_ipm_create_general_scaled, call for call.
+ * PIPS_ERR_ARG for PIPS_SCALER_CURTIS_REID and for any value outside 0-5. */
+int pips_ipm_create_qp_scaled(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl,
+                              const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp,
+                              double dual_reg, int device, void* comm, int rank, int n_ranks, int scaler);
 /* out = Q in over x = [x0 | own blocks] (Problem::hessian_multiplication; parity tests).  Zeros on a handle without Hessian. */
 int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host);
 void pips_ipm_destroy(void* handle);
@@ -686,7 +702,7 @@ int pips_det_plan_probe(int nblk, const int* n, const int* n_primal, const int* 
  * before it touches the device.  Inputs as pips_ipm_create_qp without device and comm; eliminate_z0: whether the root inequality rows are
  * eliminated from the root system (what PIPS_IPM_ROOT_INEQ_ELIMINATE / PIPS_IPM_SPARSE_ROOT decide at creation); col (nx) and
  * row ([row_eq | row_ineq], my + mz): both NULL, or scaling factors the data is scaled with first, as pips_ipm_create_general_scaled
- * scales it with its scaler's.
+ * and pips_ipm_create_qp_scaled scale it with their scaler's (the Hessians too: Q' = Cs Q Cs).
  * dims (PIPS_IPML_DIMS): N n0 my0 mz0 myl mzl ry rzr nx my mz ncp nxyz NP ND nleaf e_mz0 e_mzl S has_q.  scalars: this rank's
  * complementarity pairs and data norm.  Arrays by size-then-fill: with out == NULL sizes[k] receives the entry count of array k; with
  * out given, sizes must hold those counts and out[k] receives array k (out[k] may be NULL where sizes[k] is 0).  The arrays

@@ -386,6 +386,25 @@ __global__ __launch_bounds__(256) void k_scale_csr(int nrows, int transposed, co
       for (int p = b; p < e; ++p) v[p] = transposed ? (v[p] * col[r]) * row[ci[p]] : (v[p] * col[ci[p]]) * row[r];
    }
 }
+// Epilogue of one Ruiz pass on K = [Q J^T; J 0] scaled by diag(col, row): d <- d / sqrt(max |row of D K D|), both vectors from the
+// factors at the start of the pass.  mr_i = max_j |a_ij col_j|, mc_j = max_i |a_ij row_i|, mq_j = max_k |q_jk col_k| (nullptr: no
+// Hessian) are the deferred maxima of the sweeps; the row's own positive factor is pulled out of the maximum (exact: rounding is
+// monotone).  An empty row keeps its factor.
+__global__ __launch_bounds__(256) void k_ruiz_epilogue(int nr, int nx, const double* __restrict__ mr, const double* __restrict__ mc,
+                                                       const double* __restrict__ mq, const double* __restrict__ row,
+                                                       const double* __restrict__ col, double* __restrict__ trow, double* __restrict__ tcol) {
+   const long long n = nr > nx ? nr : nx;
+   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+      if (i < nr) {
+         const double rmax = mr[i] * row[i];
+         trow[i] = rmax > 0.0 ? row[i] / sqrt(rmax) : row[i];
+      }
+      if (i < nx) {
+         const double cmax = (mq ? fmax(mc[i], mq[i]) : mc[i]) * col[i];
+         tcol[i] = cmax > 0.0 ? col[i] / sqrt(cmax) : col[i];
+      }
+   }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // element-wise kernels of Residuals / LinearSystem
@@ -1379,6 +1398,12 @@ struct Ipm {
       return PIPS_OK;
    }
 
+   // the flat symmetric Q and its long-row list to the device (before upload_J, which sizes long_scratch by nQ_long too)
+   int upload_Q(const IpmLayout& L) {
+      Q_nnz = L.Q_nnz; nQ_long = L.nQ_long;
+      TRY(up(&Q_rp, L.Q_rp)); TRY(up(&Q_ci, L.Q_ci)); TRY(up(&Q_v, L.Q_v)); TRY(up(&Q_long, L.Q_long));
+      return PIPS_OK;
+   }
    // J, J^T and their long-row lists to the device
    int upload_J(const HostCsr& h) {
       nJ_long = h.n_long; nJt_long = h.n_tlong;
@@ -1417,18 +1442,37 @@ struct Ipm {
       const int g = egrid(a.nrows), nl = transposed ? nJt_long : nJ_long;
       hipLaunchKernelGGL(k_scale_sweep, dim3(g), dim3(256), 0, stream, a);
       if (nl > 0) hipLaunchKernelGGL(k_scale_sweep_long, dim3(nl), dim3(256), 0, stream, a, transposed ? Jt_long : J_long, g);
-      if (!a.fuse) {   // replicated rows: extrema over the ranks, one slot pair per rank of a summed vector
-         const int na = transposed ? n0 : ry, b0 = transposed ? 0 : my, nb = transposed ? 0 : rzr;
-         const long long ns = 2LL * (na + nb) * n_ranks;
-         if (ns > 0) {
-            HIP_TRYH(hipMemsetAsync(sc_slots, 0, ns * sizeof(double), stream));
-            hipLaunchKernelGGL(k_scale_rep, dim3(egrid(na + nb)), dim3(256), 0, stream, 0, na, b0, nb, rank, n_ranks, sc_mn, sc_mx, sc_slots);
-            TRY(pips_hip_allreduce_sum(comm, sc_slots, (size_t)ns, stream));
-            hipLaunchKernelGGL(k_scale_rep, dim3(egrid(na + nb)), dim3(256), 0, stream, 1, na, b0, nb, rank, n_ranks, sc_mn, sc_mx, sc_slots);
-         }
+      if (!a.fuse) {
+         TRY(sc_rep(transposed, sc_mn, sc_mx));
          hipLaunchKernelGGL(k_scale_epilogue, dim3(g), dim3(256), 0, stream, a);
       }
       hipLaunchKernelGGL(k_scale_ratio_final, dim3(1), dim3(256), 0, stream, (const double*)sc_part, g + (a.fuse ? nl : 0), ratio_dev);
+      HIP_TRYH(hipGetLastError());
+      return PIPS_OK;
+   }
+   // replicated rows of J (transposed: of J^T): extrema over the ranks, one slot pair per rank of a summed vector
+   int sc_rep(bool transposed, double* mn, double* mx) {
+      const int na = transposed ? n0 : ry, b0 = transposed ? 0 : my, nb = transposed ? 0 : rzr;
+      const long long ns = 2LL * (na + nb) * n_ranks;
+      if (ns <= 0) return PIPS_OK;
+      HIP_TRYH(hipMemsetAsync(sc_slots, 0, ns * sizeof(double), stream));
+      hipLaunchKernelGGL(k_scale_rep, dim3(egrid(na + nb)), dim3(256), 0, stream, 0, na, b0, nb, rank, n_ranks, mn, mx, sc_slots);
+      TRY(pips_hip_allreduce_sum(comm, sc_slots, (size_t)ns, stream));
+      hipLaunchKernelGGL(k_scale_rep, dim3(egrid(na + nb)), dim3(256), 0, stream, 1, na, b0, nb, rank, n_ranks, mn, mx, sc_slots);
+      return PIPS_OK;
+   }
+   // the row maxima alone, in the sweeps' deferred form: which = 0 the rows of J, 1 of J^T, 2 of the flat symmetric Q (a rank's own
+   // block rows and the root's, identical on every rank: no reduction); the minima go to sc_mn and are not used
+   int sc_max(int which, const double* sc, double* mx) {
+      ScaleArgs a;
+      a.nrows = which == 0 ? my + mz : nx;
+      a.rp = which == 0 ? J_rp : which == 1 ? Jt_rp : Q_rp; a.ci = which == 0 ? J_ci : which == 1 ? Jt_ci : Q_ci;
+      a.v = which == 0 ? J_v : which == 1 ? Jt_v : Q_v;
+      a.sc = sc; a.mn = sc_mn; a.mx = mx; a.fac = nullptr; a.partial = sc_part; a.op = SC_RATIO; a.fuse = 0;
+      const int nl = which == 0 ? nJ_long : which == 1 ? nJt_long : nQ_long;
+      hipLaunchKernelGGL(k_scale_sweep, dim3(egrid(a.nrows)), dim3(256), 0, stream, a);
+      if (nl > 0) hipLaunchKernelGGL(k_scale_sweep_long, dim3(nl), dim3(256), 0, stream, a, which == 0 ? J_long : which == 1 ? Jt_long : Q_long, 0);
+      if (n_ranks > 1 && which != 2) TRY(sc_rep(which == 1, sc_mn, mx));
       HIP_TRYH(hipGetLastError());
       return PIPS_OK;
    }
@@ -1448,7 +1492,8 @@ struct Ipm {
       return PIPS_OK;
    }
    // EquilibriumScaler::scale / GeometricMeanScaler::scale (with postEquiScale) on J, J^T as uploaded; with_sides false, no
-   // bit-shifting (PreprocessFactory::make_scaler).  Ends with the factors in h_col / h_row and J, J^T scaled in place.
+   // bit-shifting (PreprocessFactory::make_scaler); PIPS_SCALER_RUIZ, which the reference does not have, also sees Q.  Ends with the
+   // factors in h_col / h_row and J, J^T scaled in place (Q is scaled on the host: make_scaled).
    int run_scaler(int type) {
       const long long nr = (long long)my + mz;
       sc_waits = 0;
@@ -1470,6 +1515,28 @@ struct Ipm {
       if (type == PIPS_SCALER_EQUILIBRIUM) {   // from factors of 1 the ratios of postEquiScale are the ones before scaling
          TRY(post_equi(r));
          sc_info[1] = r[0]; sc_info[2] = r[1];
+         applied = true;
+      } else if (type == PIPS_SCALER_RUIZ) {
+         // Ruiz equilibration of K = [Q J^T; J 0] (Q_rp: the original Hessian, uploaded by prescale(); none: [0 J^T; J 0]): RUIZ_PASSES
+         // simultaneous passes, no early stop, no host read in the loop.  J's ratios before and after are the report's.
+         constexpr int RUIZ_PASSES = 10;   // OSQP's default
+         double *mc = nullptr, *mq = nullptr;
+         TRY(alloc(&mc, nx));
+         if (Q_rp) TRY(alloc(&mq, nx));
+         TRY(sc_sweep(false, nullptr, nullptr, SC_RATIO, sc_rat));
+         TRY(sc_sweep(true, nullptr, nullptr, SC_RATIO, sc_rat + 1));
+         TRY(sc_read(r));
+         sc_info[1] = r[0]; sc_info[2] = r[1];
+         for (int i = 0; i < RUIZ_PASSES; ++i) {
+            TRY(sc_max(0, sc_col, sc_mx));
+            TRY(sc_max(1, sc_row, mc));
+            if (mq) TRY(sc_max(2, sc_col, mq));
+            hipLaunchKernelGGL(k_ruiz_epilogue, dim3(egrid(std::max<long long>(nr, nx))), dim3(256), 0, stream, (int)nr, nx, (const double*)sc_mx,
+                               (const double*)mc, (const double*)mq, (const double*)sc_row, (const double*)sc_col, sc_trow, sc_tcol);
+            std::swap(sc_row, sc_trow); std::swap(sc_col, sc_tcol);
+         }
+         HIP_TRYH(hipGetLastError());
+         passes = RUIZ_PASSES;
          applied = true;
       } else {
          TRY(sc_sweep(false, nullptr, nullptr, SC_RATIO, sc_rat));
@@ -1649,8 +1716,12 @@ struct Ipm {
       npack = (long long)L.pack.size();
       TRY(up(&d_pack, L.pack)); TRY(up(&d_code, L.code));
       if (has_q) {   // device copy of Q, its diagonal, the product vector
-         Q_nnz = L.Q_nnz; nQ_long = L.nQ_long;
-         TRY(up(&Q_rp, L.Q_rp)); TRY(up(&Q_ci, L.Q_ci)); TRY(up(&Q_v, L.Q_v)); TRY(up(&Q_long, L.Q_long)); TRY(up(&qdiag, L.qdiag));
+         if (!Q_rp) TRY(upload_Q(L));
+         else {   // a scaled handle holds the original Q since prescale(): the scaled values into the same pattern
+            if (L.Q_nnz != Q_nnz) PIPS_FAIL(PIPS_ERR_STATE, "pips_ipm_create_qp_scaled: the scaled Hessian has %lld entries, the original one %lld", L.Q_nnz, Q_nnz);
+            HIP_TRYH(hipMemcpy(Q_v, L.Q_v.data(), L.Q_v.size() * sizeof(double), hipMemcpyHostToDevice));
+         }
+         TRY(up(&qdiag, L.qdiag));
          TRY(alloc(&qx, nx));
       }
       if (!J_v) TRY(upload_J(L.J));   // a scaled handle holds J since prescale()
@@ -1714,13 +1785,18 @@ int prescale(Ipm* p, const IpmInput& in, const IpmKnobs& knobs, int device, int 
    IpmLayout L;
    TRY(ipm_dims(in, knobs.eliminate_z0, L));
    p->set_dims(L);
+   TRY(ipm_hessians(in, L));
+   if (L.has_q) {   // Q of the original data for the scaler that sees it; upload() replaces the values by the scaled ones (same pattern)
+      ipm_flat_hessian(in, L);
+      TRY(p->upload_Q(L));
+   }
    ipm_rows_J(in, p->rank, L);
    TRY(p->upload_J(L.J));
    L.J = HostCsr{};
    TRY(p->sc_alloc());
    TRY(p->alloc(&p->d_red, 64 * (long long)p->n_ranks));
    TRY(p->run_scaler(scaler));
-   p->dnorm_orig = ipm_data_norm(in, {});
+   p->dnorm_orig = ipm_data_norm(in, L.hq);
    if (p->scaled) make_scaled(in, L, p->h_col.data(), p->h_row.data(), sd);
    std::vector<double> ri2(2 * (size_t)p->mz), col2(2 * (size_t)p->nx);
    for (int k = 0; k < p->mz; ++k) ri2[k] = ri2[(size_t)p->mz + k] = p->h_row[(size_t)p->my + k];
@@ -1814,6 +1890,14 @@ int build(Ipm* p, const IpmInput& in, const IpmKnobs& knobs, int device) {
    return p->alloc_state();
 }
 
+int check_scaler(int scaler, const char* who) {
+   if (scaler == PIPS_SCALER_CURTIS_REID) PIPS_FAIL(PIPS_ERR_ARG, "%s: scaler %d (Curtis-Reid) is not supported", who, scaler);
+   if (scaler < PIPS_SCALER_NONE || scaler > PIPS_SCALER_RUIZ)
+      PIPS_FAIL(PIPS_ERR_ARG, "%s: scaler %d is not supported (0 none, 1 equilibrium, 2 geometric mean, 3 geometric mean + equilibrium, 5 Ruiz)", who,
+                scaler);
+   return PIPS_OK;
+}
+
 // who: the entry point the "bad arguments" message names
 int create(void** handle, const IpmInput& in, double dual_reg, int device, void* comm, int rank, int n_ranks, int scaler, const char* who) {
    if (!handle || (n_ranks > 1 && !comm)) PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments", who);
@@ -1842,22 +1926,35 @@ int pips_ipm_create_general(void** handle, int n_blocks, const pips_ipm_block* b
 int pips_ipm_create_general_scaled(void** handle, int n_blocks, const pips_ipm_block* blocks, int myl, int mzl, const double* bL,
                                    const double* dlow, const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device,
                                    void* comm, int rank, int n_ranks, int scaler) {
-   if (scaler == PIPS_SCALER_CURTIS_REID)
-      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general_scaled: scaler %d (Curtis-Reid) is not supported", scaler);
-   if (scaler < PIPS_SCALER_NONE || scaler > PIPS_SCALER_CURTIS_REID)
-      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_general_scaled: scaler %d is not supported (0 none, 1 equilibrium, 2 geometric mean, "
-                              "3 geometric mean + equilibrium)", scaler);
+   TRY(check_scaler(scaler, "pips_ipm_create_general_scaled"));
    const IpmInput in{n_blocks, blocks, nullptr, myl, mzl, bL, dlow, dupp, idlow, idupp};
    return create(handle, in, dual_reg, device, comm, rank, n_ranks, scaler, "pips_ipm_create_general");
 }
 
 // The convex QP  min c^T x + 1/2 x^T Q x  over the same constraints, Q block-diagonal over the root and the blocks.  Without any
-// Hessian this is pips_ipm_create_general, call for call.  Problem scaling is not offered with a Hessian.
+// Hessian this is pips_ipm_create_general, call for call.
 int pips_ipm_create_qp(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL,
                        const double* dlow, const double* dupp, const double* idlow, const double* idupp, double dual_reg, int device, void* comm,
                        int rank, int n_ranks) {
    const IpmInput in{n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp};
    return create(handle, in, dual_reg, device, comm, rank, n_ranks, PIPS_SCALER_NONE, "pips_ipm_create_qp");
+}
+
+// pips_ipm_create_qp with a scaler: Q' = Cs Q Cs beside J' = R J Cs.  Without a scaler it is pips_ipm_create_qp, without any Hessian
+// pips_ipm_create_general_scaled, call for call.
+int pips_ipm_create_qp_scaled(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl,
+                              const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp, double dual_reg,
+                              int device, void* comm, int rank, int n_ranks, int scaler) {
+   TRY(check_scaler(scaler, "pips_ipm_create_qp_scaled"));
+   if (scaler == PIPS_SCALER_NONE)
+      return pips_ipm_create_qp(handle, n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device, comm, rank, n_ranks);
+   bool any = false;
+   for (int i = 0; Q && i < n_blocks; ++i) any = any || Q[i].rowptr != nullptr;
+   if (!any)
+      return pips_ipm_create_general_scaled(handle, n_blocks, blocks, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device, comm, rank, n_ranks,
+                                            scaler);
+   const IpmInput in{n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp};
+   return create(handle, in, dual_reg, device, comm, rank, n_ranks, scaler, "pips_ipm_create_qp_scaled");
 }
 
 int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host) {

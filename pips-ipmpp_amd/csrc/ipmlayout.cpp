@@ -367,6 +367,23 @@ void make_scaled(const IpmInput& in, const IpmLayout& L, const double* col, cons
    }
    sd.in = in;
    sd.in.blocks = sd.blk.data();
+   // Q' = Cs Q Cs on the lower triangles as given: (q col_r) col_c.  The flat symmetric copy is built from these, so it stays exactly
+   // symmetric ((q col_r) col_c and (q col_c) col_r round differently)
+   if (in.Q) {
+      sd.q.assign(in.Q, in.Q + in.n_blocks);
+      for (int i = 0; i <= L.N; ++i) {
+         pips_csr_view& m = sd.q[i];
+         const int n = in.blocks[i].n;
+         if (!m.rowptr || n <= 0 || m.rowptr[n] <= 0 || !m.colidx || !m.val) continue;
+         const double* cf = col + (i == 0 ? 0 : L.xoff[i]);
+         sd.keep.emplace_back((size_t)m.rowptr[n], 0.0);
+         std::vector<double>& v = sd.keep.back();
+         for (int r = 0; r < n; ++r)
+            for (int q = m.rowptr[r]; q < m.rowptr[r + 1]; ++q) v[q] = (m.val[q] * cf[r]) * cf[m.colidx[q]];
+         m.val = v.data();
+      }
+      sd.in.Q = sd.q.data();
+   }
    vec(sd.in.bL, L.myl, re + L.my0, false); vec(sd.in.dlow, L.mzl, ri + L.mz0, false); vec(sd.in.dupp, L.mzl, ri + L.mz0, false);
 }
 
@@ -386,6 +403,7 @@ extern "C" int pips_ipm_layout_probe(int n_blocks, const pips_ipm_block* blocks,
    ScaledData sd;
    if (col) {
       TRY(ipm_dims(in, eliminate_z0 != 0, L));
+      TRY(ipm_hessians(in, L));   // make_scaled indexes the factors by Q's rows and columns: checked first
       make_scaled(in, L, col, row, sd);
       in = sd.in;
    }

@@ -85,11 +85,13 @@ void ipm_flat_hessian(const IpmInput& in, IpmLayout& L);             // Q_*, qdi
 // all of them; with_J = false leaves J out (a scaled handle keeps the J its scaler scaled on the device)
 int ipm_layout(const IpmInput& in, int rank, bool eliminate_z0, bool with_J, IpmLayout& L);
 
-// The data scaled by the factors (Scaler::applyScaling): matrices (a col_j) row_i, c col, b / clow / cupp row, xlow / xupp / col.
+// The data scaled by the factors (Scaler::applyScaling): matrices (a col_j) row_i, c col, b / clow / cupp row, xlow / xupp / col, and
+// the lower-triangular Hessians (q col_r) col_c (x = Cs x': Q' = Cs Q Cs; the Hessians must have passed ipm_hessians).
 // col: nx factors, row: [row_eq (my) | row_ineq (mz)].  Host copies of O(nnz); `in` points into them and into the original indices.
 struct ScaledData {
    IpmInput in;
    std::vector<pips_ipm_block> blk;
+   std::vector<pips_csr_view> q;
    std::deque<std::vector<double>> keep;
 };
 void make_scaled(const IpmInput& in, const IpmLayout& L, const double* col, const double* row, ScaledData& sd);

@@ -71,7 +71,7 @@ SYMBOLS = [
     "pips_hip_vec_add_const", "pips_hip_vec_mul", "pips_hip_vec_div", "pips_hip_vec_add_product", "pips_hip_vec_add_quotient",
     "pips_hip_vec_divide_some", "pips_hip_vec_select_nonzeros", "pips_hip_vec_safe_invert", "pips_hip_vec_gondzio_projection", "pips_hip_vec_dot",
     "pips_hip_vec_one_norm", "pips_hip_vec_inf_norm", "pips_hip_vec_min", "pips_hip_vec_sumsq_scaled", "pips_hip_vec_stepbound",
-    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
+    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_create_qp_scaled", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
     "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe", "pips_det_plan_probe", "pips_schur_target_probe",
@@ -83,8 +83,9 @@ PIPS_SCALER_EQUILIBRIUM = 1
 PIPS_SCALER_GEOMETRIC_MEAN = 2
 PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM = 3
 PIPS_SCALER_CURTIS_REID = 4
+PIPS_SCALER_RUIZ = 5   # not in the reference: Ruiz equilibration of [Q J^T; J 0], the scaler that sees a Hessian
 SCALERS = {None: PIPS_SCALER_NONE, "none": PIPS_SCALER_NONE, "equilibrium": PIPS_SCALER_EQUILIBRIUM, "geometric": PIPS_SCALER_GEOMETRIC_MEAN,
-           "geometric_equilibrium": PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM, "curtis_reid": PIPS_SCALER_CURTIS_REID}
+           "geometric_equilibrium": PIPS_SCALER_GEOMETRIC_MEAN_EQUILIBRIUM, "curtis_reid": PIPS_SCALER_CURTIS_REID, "ruiz": PIPS_SCALER_RUIZ}
 
 
 def _check(rc, what):
@@ -1230,14 +1231,14 @@ class GeneralIpmSolver(IpmSolver):
 
     def __init__(self, blocks, dual_reg=0.0, device=-1, comm=None, rank=0, n_ranks=1, scaler=None, hessians=None):
         """scaler: None, "equilibrium", "geometric" or "geometric_equilibrium" (the reference's scale / scaleEqui, scaleGeo,
-        scaleGeoEqui); "curtis_reid" is reserved and raises, like any other name.
+        scaleGeoEqui), or "ruiz" (Ruiz equilibration of [Q J^T; J 0]: the one that sees the Hessians); "curtis_reid" is reserved and
+        raises, like any other name.
         hessians: None (an LP, created by pips_ipm_create_general), or a list as long as `blocks` whose entries are None or a
         dict rows / cols / rowptr / colidx / val like the matrices of the block dicts (or a Csr): the LOWER triangle of the block's
-        convex Hessian (pips_ipm_create_qp; convexity is the caller's contract).  Not together with a scaler."""
+        convex Hessian (pips_ipm_create_qp; convexity is the caller's contract).  With a scaler: pips_ipm_create_qp_scaled, the
+        handle holds Q' = Cs Q Cs."""
         if scaler not in SCALERS:
-            raise PipsHipError(f"unknown scaler {scaler!r}: one of None, 'equilibrium', 'geometric', 'geometric_equilibrium'")
-        if hessians is not None and scaler is not None:
-            raise PipsHipError("problem scaling together with Hessians is not supported")
+            raise PipsHipError(f"unknown scaler {scaler!r}: one of None, 'equilibrium', 'geometric', 'geometric_equilibrium', 'ruiz'")
         if hessians is not None and len(hessians) != len(blocks):
             raise PipsHipError(f"hessians has {len(hessians)} entries for {len(blocks)} blocks")
         keep, cb, cq, tail = _ipm_input(blocks, hessians)
@@ -1247,7 +1248,9 @@ class GeneralIpmSolver(IpmSolver):
         self._h = C.c_void_p()
         args = (C.byref(self._h), C.c_int(len(blocks)), cb, *tail, C.c_double(dual_reg), C.c_int(device),
                 comm._h if comm is not None else None, C.c_int(rank), C.c_int(n_ranks))
-        if hessians is not None:
+        if hessians is not None and scaler is not None:
+            _check(lib.pips_ipm_create_qp_scaled(*args[:3], cq, *args[3:], C.c_int(SCALERS[scaler])), "pips_ipm_create_qp_scaled")
+        elif hessians is not None:
             _check(lib.pips_ipm_create_qp(*args[:3], cq, *args[3:]), "pips_ipm_create_qp")
         elif scaler is None:
             _check(lib.pips_ipm_create_general(*args), "pips_ipm_create_general")
