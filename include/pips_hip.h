@@ -26,6 +26,14 @@ int pips_hip_host_wait_sites(char* buf, int cap);
  * a diagnostic: equal values before and after a create ... destroy sequence mean that nothing leaked */
 long long pips_hip_device_allocs_live(void);
 long long pips_hip_device_bytes_live(void);
+/* the environment switches the library reads - every one of them, from the one table they are read through (csrc/knobs.h) - as lines
+ * "name kind default when effect" written into buf (at most cap bytes, NUL-terminated); returns the bytes written.  kind: set (present, any
+ * value), int, tri (-1 not set, else 0 / 1), real, text; default "-": none; when: create, analyze, call, process, or two of them joined by "+" */
+int pips_hip_knobs(char* buf, int cap);
+/* what the library would make of the switch `name` right now: *value is the parsed number (set and text: whether the variable is there),
+ * text (may be NULL; at most cap bytes) the value of a text switch, else empty.  PIPS_ERR_ARG for a name that is not in the table.
+ * Neither call touches the device. */
+int pips_hip_knob_value(const char* name, double* value, char* text, int cap);
 /* number of visible HIP devices (0 without a GPU; never fails) */
 int pips_hip_device_count(void);
 

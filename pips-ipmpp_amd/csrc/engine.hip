@@ -20,6 +20,7 @@
 #include "devmem.h"
 #include "layout.h"
 #include "detplan.h"
+#include "knobs.h"
 #include "schurtarget.h"
 #include "kernels.hip.h"
 #include "rootkernel.hip.h"
@@ -63,17 +64,8 @@ const char* last_error() { return g_last_error.c_str(); }
       if (int _rc = (expr)) return _rc;   \
    } while (0)
 
-// environment switches: value of an integer switch, dflt when it is not set
-static int env_int(const char* name, int dflt) {
-   const char* v = getenv(name);
-   return v ? atoi(v) : dflt;
-}
-
-// ... of an on / off switch: -1 when it is not set, else whether its value is non-zero
-static int env_flag(const char* name) {
-   const char* v = getenv(name);
-   return v ? (atoi(v) != 0 ? 1 : 0) : -1;
-}
+// deterministic mode by the environment: the default of the batches (pips_hip_batch_create) and of the leaf handles' sparse Schur calls
+static bool env_deterministic() { return knob_int<K_DETERMINISTIC>() != 0; }
 
 static inline int grid_for(long long n, int block, int cap = 4096) {
    long long g = (n + block - 1) / block;
@@ -310,7 +302,7 @@ struct PanelPlan {
 };
 
 // Single-launch tail sweeps (kernels.hip.h k_tail_rows_fwd / _bwd): task list (block, tile row) sorted by row, ticket and flag
-// storage.  PIPS_HIP_SWEEP_LAUNCHES=1 keeps the launch-per-tile-column kernels.
+// storage.  PIPS_HIP_SWEEP_LAUNCHES (set to any value) keeps the launch-per-tile-column kernels.
 struct SweepRt {
    DevBuf<TileTask> d_tasks;
    int n_tasks = 0;
@@ -330,12 +322,13 @@ struct SweepRt {
       if (!w) return PIPS_OK;
       HIP_TRY(hipMemset(d_ints + 2 * SWEEP_NRHS_MAX, 0, sizeof(int)));
       PIPS_FAIL(PIPS_ERR_HIP, "%s: a single-launch solve sweep gave up waiting for a piece of the solution after %lld polls (its output is NaN); "
-                              "another process holding the device for seconds can cause that - PIPS_HIP_SWEEP_LAUNCHES=1 selects the launch-per-column sweeps",
+                              "another process holding the device for seconds can cause that - PIPS_HIP_SWEEP_LAUNCHES (set to any value) selects the launch-per-column sweeps",
                 who, poll_limit);
    }
    int build(const std::vector<BlkDesc>& blks, const std::vector<const std::vector<int>*>* first) {
       *this = SweepRt();
-      if (const char* pl = getenv("PIPS_HIP_SWEEP_POLL_LIMIT")) poll_limit = atoll(pl);
+      static_assert(KNOBS[K_SWEEP_POLL_LIMIT].dflt == SWEEP_POLL_LIMIT, "the table's default is the kernels' limit");
+      poll_limit = knob_int<K_SWEEP_POLL_LIMIT>();
       const int nblk = (int)blks.size();
       int ntc_max = 0;
       for (auto& b : blks) ntc_max = std::max(ntc_max, b.ntc);
@@ -365,7 +358,7 @@ struct SweepRt {
       const size_t ints = (size_t)(2 * SWEEP_NRHS_MAX + 2 + n_flags * SWEEP_NRHS_MAX);
       PIPS_TRY(d_ints.alloc_zero(ints));
       epoch = 0;
-      enabled = n_tasks > 0 && !getenv("PIPS_HIP_SWEEP_LAUNCHES");
+      enabled = n_tasks > 0 && !knob_set<K_SWEEP_LAUNCHES>();
       return PIPS_OK;
    }
    SweepArgs args(long long xw_stride, hipStream_t st) {
@@ -641,7 +634,7 @@ static int dump_tail_trace(const TailCtx& c, DevBuf<long long>& d_trace, size_t 
 // the leaf tails as one dependency-driven launch (tailkernel.hip.h): flags from their template, tickets cleared, k_tail_ldl
 static int tail_single_launch(const TailCtx& c) {
    const TailSingle& ts = *c.single;
-   const char* trace_file = getenv("PIPS_HIP_TAIL_TRACE");   // diagnostics, read at every call
+   const char* trace_file = knob_text<K_TAIL_TRACE>();
    DevBuf<long long> d_trace;
    const size_t n_trace = (size_t)3 * ts.n_tasks + 32 * (size_t)(c.plan->ntc_max + 1);
    {
@@ -796,9 +789,9 @@ static int tail_schur(const TailCtx& c, double* SC, int ldSC) {
 static int tail_factor(const TailCtx& c, double* SC, int ldSC) {
    // trsm of the leaf tails in the static pivot order: Winv is lower triangular, k_tile_gemm<5> skips the products with its zeros
    // (PIPS_HIP_TRSM_DENSE=1: the dense product, for A/B runs and the test that compares the two bit for bit)
-   const bool trsm_tri = !c.bunch_kaufman && !c.is_root && env_int("PIPS_HIP_TRSM_DENSE", 0) == 0;
+   const bool trsm_tri = !c.bunch_kaufman && !c.is_root && knob_int<K_TRSM_DENSE>() == 0;
    // ... and group by group, unless PIPS_HIP_TAIL_PANEL=0 (or the dense trsm) asks for the column launches
-   if (!c.single && c.panels && c.side && trsm_tri && env_int("PIPS_HIP_TAIL_PANEL", 1) != 0) PIPS_TRY(tail_panels(c));
+   if (!c.single && c.panels && c.side && trsm_tri && knob_int<K_TAIL_PANEL>() != 0) PIPS_TRY(tail_panels(c));
    else if (!c.single) PIPS_TRY(tail_columns(c, trsm_tri));
    else if (c.single->n_tasks > 0) PIPS_TRY(tail_single_launch(c));
    PIPS_TRY(tail_schur(c, SC, ldSC));
@@ -1568,7 +1561,7 @@ struct Engine : EngineAnalysis, BatchLayout {
          hipLaunchKernelGGL((k_head_factor_spine<256, 32, 6144>), dim3(nblk), dim3(256), 0, stream, d_spine, d_spine_off, d_sns, d_blks,
                             d_rowidx, d_upd, d_psign, d_psign_off, d_bmap, d_arena, SC, ldSC, d_inertia, d_pref, d_sctab);
       }
-      if (mf && getenv("PIPS_HIP_MF_CLOCKS")) {   // (read at every factorisation)
+      if (mf && knob_set<K_MF_CLOCKS>()) {
          if (!d_mfdbg) PIPS_TRY(d_mfdbg.alloc((size_t)std::max(nsn_total, 1) * 8));
          else PIPS_TRY(dump_front_clocks());
       }
@@ -1801,9 +1794,9 @@ struct Engine : EngineAnalysis, BatchLayout {
    // panels whatever the size, 4 half panels
    struct MultiKnob { int from; int slices; };   // fewest right-hand sides of an interleaved sweep (0 = never); forced slicing (0 = none)
    static MultiKnob multi_knob() {
-      const char* f = getenv("PIPS_HIP_MULTI");
-      const int v = f ? atoi(f) : 1;
-      return MultiKnob{!f ? 8 : v != 0 ? 2 : 0, v == 2 ? 1 : v == 4 ? 2 : 0};
+      const bool given = knob_set<K_MULTI>();
+      const int v = (int)knob_int<K_MULTI>();
+      return MultiKnob{!given ? 8 : v != 0 ? 2 : 0, v == 2 ? 1 : v == 4 ? 2 : 0};
    }
    bool use_multi(int nr) const {
       const int from = multi_knob().from;
@@ -2240,34 +2233,36 @@ static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs
    // registers its rows take; factorisation 13.4 -> 12.5 ms, solveCompressed 9.3 -> 8.9 ms.  Random sparsity (config 2) has no
    // supernodes wider than one column in the head.
    opt.max_sn_width = 16;
-   if (const char* sw = getenv("PIPS_HIP_SN_WIDTH")) opt.max_sn_width = std::max(1, std::min(HEAD_WMAX, atoi(sw)));
+   if (knob_set<K_SN_WIDTH>()) opt.max_sn_width = std::max(1, std::min(HEAD_WMAX, (int)knob_int<K_SN_WIDTH>()));
    else if (e && e->sn_width > 0) opt.max_sn_width = std::min(HEAD_WMAX, e->sn_width);
-   if (const char* rz = getenv("PIPS_HIP_RELAX_ZEROS")) opt.relax_zeros = atof(rz);   // share of explicit zeros per panel
-   if (const char* ndd = getenv("PIPS_HIP_ND_DEPTH")) opt.nd_depth = atoi(ndd);        // dissection levels (0 = off)
-   if (const char* ndm = getenv("PIPS_HIP_ND_MIN")) opt.nd_min_size = atoi(ndm);      // smallest segment that is still dissected
-   if (const char* ml = getenv("PIPS_HIP_MF_LDS")) opt.mf_lds_doubles = atoll(ml);   // LDS budget of a front in doubles (tests: small values force the device-memory variant)
-   if (const char* sp = getenv("PIPS_HIP_MF_SPLIT")) opt.mf_split_nb_max = atoi(sp) == 0 ? 0 : std::min(176, std::max(atoi(sp), 2));   // border split: 0 = off, else the largest nb
+   // (a switch that is not set leaves what opt holds: the values of AnalyzeOptions, or what an earlier analysis of this engine left)
+   if (knob_set<K_RELAX_ZEROS>()) opt.relax_zeros = knob_real<K_RELAX_ZEROS>();
+   if (knob_set<K_ND_DEPTH>()) opt.nd_depth = (int)knob_int<K_ND_DEPTH>();
+   if (knob_set<K_ND_MIN>()) opt.nd_min_size = (int)knob_int<K_ND_MIN>();
+   if (knob_set<K_MF_LDS>()) opt.mf_lds_doubles = knob_int<K_MF_LDS>();
+   if (knob_set<K_MF_SPLIT>()) { const int sp = (int)knob_int<K_MF_SPLIT>(); opt.mf_split_nb_max = sp == 0 ? 0 : std::min(176, std::max(sp, 2)); }
    knobs.deterministic = e && e->deterministic;
    knobs.schur_mode = e ? e->schur_mode : 0;
    // (tests: forces a Schur mode where no setter reaches - the leaf handles and the batch they are bound into - and the caller left it to the model)
-   if (e && knobs.schur_mode == 0) knobs.schur_mode = std::max(0, std::min(2, env_int("PIPS_HIP_SCHUR_MODE", 0)));
+   if (e && knobs.schur_mode == 0) knobs.schur_mode = std::max(0, std::min(2, (int)knob_int<K_SCHUR_MODE>()));
    knobs.mf_lds_doubles = opt.mf_lds_doubles;
-   knobs.mf_wanted = env_int("PIPS_HIP_MF", 1) != 0;
+   knobs.mf_wanted = knob_int<K_MF>() != 0;
    if (!knobs.mf_wanted) opt.mf_split_nb_max = 0;   // the border split (compact front panels) only exists with the multifrontal head
    // fronts on the rows of K only where the border split applies (value 1; off by default: on the configs[3] share the fronts fall
    // from 9.7 to 4.0 ms, forming the border rows afterwards costs 8.0 - DESIGN.md 4.1c): not in deterministic mode (the border rows of the dense
    // tail take their head contributions with atomics, k_border_tail) and with supernodes of at most 16 columns (k_border_rows<., 16>)
-   opt.mf_konly = opt.mf_split_nb_max > 0 && !knobs.deterministic && opt.max_sn_width <= 16 && env_int("PIPS_HIP_MF_KONLY", 0) != 0;
-   knobs.spine = env_flag("PIPS_HIP_SPINE");                      // 0: no spine kernels
-   knobs.tail_single = env_flag("PIPS_HIP_TAIL_SINGLE");          // 0 / 1 forces one side (default: batches of up to 16 blocks)
-   knobs.tail_first_touch = env_flag("PIPS_HIP_TAIL_FIRST_TOUCH");   // 0: the tails are cleared and added to as before (default: first touch where the batch allows it)
-   knobs.ft_lds_bytes = std::min(FT_LDS_MAX, std::max(0LL, (long long)env_int("PIPS_HIP_FIRST_TOUCH_LDS", (int)FT_LDS_BUDGET)));   // (tests: a small budget refuses the path; never more than a workgroup can have)
-   knobs.border_backward = env_flag("PIPS_HIP_BORDER_BACKWARD");  // 0 / 1 instead of the cost rule of the border-backward sweep
-   knobs.aug_sweeps = env_flag("PIPS_HIP_AUG_SWEEPS");            // 0 / 1 instead of the cost rule of the sweeps of the augmented factor
-   knobs.sweep_launches = getenv("PIPS_HIP_SWEEP_LAUNCHES") != nullptr;   // (SweepRt::build: the single-launch sweeps are off)
-   const int poll = env_int("PIPS_HIP_ROOT_POLL_LIMIT", 400000);
-   knobs.tail_poll_limit = poll > 0 ? (long long)poll * 50 : 0;   // (a deep update runs a millisecond)
-   knobs.tail_diag_blocked = env_int("PIPS_HIP_ROOT_DIAG_BARRIERS", 0) ? 0 : 1;
+   opt.mf_konly = opt.mf_split_nb_max > 0 && !knobs.deterministic && opt.max_sn_width <= 16 && knob_int<K_MF_KONLY>() != 0;
+   knobs.spine = knob_tri<K_SPINE>();
+   knobs.tail_single = knob_tri<K_TAIL_SINGLE>();
+   knobs.tail_first_touch = knob_tri<K_TAIL_FIRST_TOUCH>();
+   static_assert(KNOBS[K_FIRST_TOUCH_LDS].dflt == FT_LDS_BUDGET, "the table's default is the layout's budget");
+   knobs.ft_lds_bytes = std::min(FT_LDS_MAX, std::max(0LL, knob_int<K_FIRST_TOUCH_LDS>()));   // (never more than a workgroup can have)
+   knobs.border_backward = knob_tri<K_BORDER_BACKWARD>();
+   knobs.aug_sweeps = knob_tri<K_AUG_SWEEPS>();
+   knobs.sweep_launches = knob_set<K_SWEEP_LAUNCHES>();   // (SweepRt::build: the single-launch sweeps are off)
+   const long long poll = knob_int<K_ROOT_POLL_LIMIT>();
+   knobs.tail_poll_limit = poll > 0 ? poll * 50 : 0;   // (a deep update runs a millisecond)
+   knobs.tail_diag_blocked = knob_int<K_ROOT_DIAG_BARRIERS>() ? 0 : 1;
 }
 
 
@@ -2318,21 +2313,21 @@ struct DenseLdl {
    SweepRt sweep;
    // ---- the factorisation as ONE dependency-driven launch (rootkernel.hip.h, rootplan.cpp): static pivot order on one rank.  Bunch-Kaufman
    // (a 454-register diagonal kernel) and the root distributed over ranks keep the launch-per-step driver (tail_factor / factor_distributed);
-   // PIPS_HIP_ROOT_LAUNCHES=1 keeps it everywhere (the tests run both).
-   bool single_launch = !getenv("PIPS_HIP_ROOT_LAUNCHES");
+   // PIPS_HIP_ROOT_LAUNCHES (set to any value) keeps it everywhere (the tests run both).
+   bool single_launch = !knob_set<K_ROOT_LAUNCHES>();
    bool last_single = false;       // which driver the last factorisation took (pips_hip_dense_ldl_info)
    DevBuf<double> d_C;             // the accumulating tiles (scratch): L goes to d_R, U to d_U, each written once per launch
    DevBuf<TileTask> d_rtasks;
    int n_rtasks = 0, n_rbulk = 0;
    DevBuf<int> d_rflags;           // ctl[8] | prog[ntc * ntc] | rowdone[ntc] | dready[ntc]
    double plan_makespan_us = 0.0;
-   long long root_poll_limit = 400000;   // polls before a wait inside the launch gives up (some 0.1 s: a factorisation takes 2 - 40 ms)
+   long long root_poll_limit = 0;   // PIPS_HIP_ROOT_POLL_LIMIT (ensure_single_launch): polls before a wait inside the launch gives up (some 0.1 s: a factorisation takes 2 - 40 ms)
    bool root_error_pending = false;
    int ensure_single_launch() {
       if (d_rtasks) return PIPS_OK;
       const int ntc = npad / TILE;
       RootPlanParams pp;
-      if (const char* q = getenv("PIPS_HIP_ROOT_CHAIN_CU")) pp.chain_slots = atoi(q) != 0 ? 2 : 0;   // 0: one list, the chain wherever its workgroups land (A/B)
+      if (const int cu = knob_tri<K_ROOT_CHAIN_CU>(); cu >= 0) pp.chain_slots = cu ? 2 : 0;
       if (pp.chain_slots == 0) pp.workers = 512;
       std::vector<int> t, tc;
       int rc = build_root_plan(ntc, pp, t, tc, &plan_makespan_us);
@@ -2344,7 +2339,7 @@ struct DenseLdl {
       HIP_TRY(hipMemcpy(d_rtasks, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
       PIPS_TRY(d_rflags.alloc(((size_t)8 + (size_t)ntc * ntc + 2 * (size_t)ntc)));
       PIPS_TRY(d_C.alloc((size_t)npad * npad));
-      if (const char* pl = getenv("PIPS_HIP_ROOT_POLL_LIMIT")) root_poll_limit = atoll(pl);
+      root_poll_limit = knob_int<K_ROOT_POLL_LIMIT>();
       return PIPS_OK;
    }
    int factor_single_launch() {
@@ -2355,8 +2350,8 @@ struct DenseLdl {
       a.C = d_C; a.R = d_R; a.U = d_U; a.winv = d_winv; a.dtail = d_dtail; a.pref = d_pref; a.psign = d_psign; a.inertia = d_inertia;
       a.ctl = d_rflags; a.prog = d_rflags + 8; a.rowdone = a.prog + (size_t)ntc * ntc; a.dready = a.rowdone + ntc;
       a.blk = d_blks; a.poll_limit = root_poll_limit;
-      a.diag_blocked = getenv("PIPS_HIP_ROOT_DIAG_BARRIERS") ? 0 : 1;
-      const char* trace_file = getenv("PIPS_HIP_ROOT_TRACE");   // diagnostics: per-task clocks of this launch into a file (tools/root_trace.py)
+      a.diag_blocked = knob_int<K_ROOT_DIAG_BARRIERS>() ? 0 : 1;
+      const char* trace_file = knob_text<K_ROOT_TRACE>();
       DevBuf<long long> d_trace;
       if (trace_file) {
          PIPS_TRY(d_trace.alloc(((size_t)3 * n_rtasks + 32 * (size_t)ntc)));
@@ -2396,7 +2391,7 @@ struct DenseLdl {
       HIP_TRY(hipMemcpyAsync(&w, d_rflags + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));
       if (w) PIPS_FAIL(PIPS_ERR_HIP, "%s: the single-launch root factorisation gave up waiting for a tile after %lld polls (its factors are invalid); "
-                                     "PIPS_HIP_ROOT_LAUNCHES=1 selects the launch-per-step factorisation", who, root_poll_limit);
+                                     "PIPS_HIP_ROOT_LAUNCHES (set to any value) selects the launch-per-step factorisation", who, root_poll_limit);
       return PIPS_OK;
    }
    int init() {
@@ -2667,7 +2662,7 @@ struct DenseLdl {
          // One column of lookahead.  Panel j is applied in two pieces: this rank's tiles of column j + 1 on the main stream - the owner of that
          // column goes on to factorise and broadcast it - and its columns >= j + 2 (the bulk) on the side stream, beside that.  Column j + 1
          // also takes the bulk of panel j - 1: the main stream joins it first (ev_rest as recorded before this iteration's bulk).
-         const bool ahead = side && !getenv("PIPS_HIP_DIST_NO_LOOKAHEAD");
+         const bool ahead = side && !knob_set<K_DIST_NO_LOOKAHEAD>();
          hipStream_t bulk = ahead ? side : stream;
          if (ahead) {
             if (side_busy) HIP_TRY(hipStreamWaitEvent(stream, ev_rest, 0));
@@ -2806,7 +2801,7 @@ int pips_hip_batch_create(void** handle, int n_blocks, int S, int device, void* 
    e->device = device;   // resolved at analyze time so that set_block / symbolic work without a GPU
    e->stream = (hipStream_t)stream;
    e->in.assign(n_blocks, BlockInput());
-   if (const char* d = getenv("PIPS_HIP_DETERMINISTIC")) e->deterministic = atoi(d) != 0;   // default of pips_hip_batch_set_deterministic
+   e->deterministic = env_deterministic();   // default of pips_hip_batch_set_deterministic
    *handle = e.release();
    return PIPS_OK;
 }
@@ -3654,10 +3649,6 @@ static int sparse_schur_factor(Engine& e, SparseSchurBind& sb, double* sc_val_ho
       for (size_t t = 0; t < T; ++t) sc_val_host[sb.pos[t]] += sb.h_val[t];
    return PIPS_OK;
 }
-static bool env_deterministic() {
-   const char* d = getenv("PIPS_HIP_DETERMINISTIC");
-   return d && atoi(d) != 0;
-}
 
 int pips_hip_ldl_factor_schur_sparse(void* handle, const double* K_vals_host, const double* Bt_vals_host, int S, const int* sc_rowptr, const int* sc_colidx,
                                      double* sc_val_host, int lower) {
@@ -4147,7 +4138,7 @@ int pips_symbolic_probe(int n, int n_primal, const int* krow, const int* jcol, i
       what[16] = 0;
       for (const HeadSupernode& hs : bs.sn) if (hs.ld < hs.w + hs.r) what[16] += (int64_t)hs.w * (hs.r - hs.rb);
    }
-   if (const char* dump = getenv("PIPS_HIP_DUMP_SN")) {   // development aid: one line per head supernode
+   if (const char* dump = knob_text<K_DUMP_SN>()) {   // development aid
       if (FILE* f = fopen(dump, "w")) {
          const BlockSym& bs = sym[0];
          for (size_t si = 0; si < bs.sn.size(); ++si) {

@@ -41,6 +41,7 @@
 #include "common.h"
 #include "devmem.h"
 #include "ipmlayout.h"
+#include "knobs.h"
 #include "pips_hip.h"
 
 extern "C" {
@@ -1771,10 +1772,10 @@ struct IpmKnobs {
 };
 IpmKnobs read_ipm_knobs() {
    IpmKnobs k;
-   const char* e;
-   k.sparse_root = (e = getenv("PIPS_IPM_SPARSE_ROOT")) && atoi(e) != 0;
-   k.eliminate_z0 = (e = getenv("PIPS_IPM_ROOT_INEQ_ELIMINATE")) ? atoi(e) != 0 : !k.sparse_root;
-   k.schur_mode = getenv("PIPS_IPM_SCHUR_MODE");
+   k.sparse_root = knob_int<K_IPM_SPARSE_ROOT>() != 0;
+   const int eliminate = knob_tri<K_IPM_ROOT_INEQ_ELIMINATE>();
+   k.eliminate_z0 = eliminate >= 0 ? eliminate != 0 : !k.sparse_root;
+   k.schur_mode = knob_text<K_IPM_SCHUR_MODE>();
    return k;
 }
 

@@ -1,7 +1,7 @@
 // Fused two-level KKT system of one rank: leaves (Engine) + replicated root (DenseLdl, or a one-block sparse Engine) + Schur reduction.
 // Mirrors DistributedRootLinearSystem::factor2 (:206-243) and DistributedLinearSystem::solveCompressed (:409-420)
 // with sLinsysRootAug::{finalizeKKTdense, Lsolve, Dsolve, Ltsolve} (sLinsysRootAug.C:1769-1796, 323-365).
-// Included once by engine.hip, inside namespace pips, after Engine and DenseLdl; the pips_hip_kkt_* entry points there call the
+// Included once by engine.hip, inside namespace pips, after Engine and DenseLdl (the switches: knobs.h, which engine.hip includes); the pips_hip_kkt_* entry points there call the
 // methods of KktSystem.
 #pragma once
 
@@ -147,7 +147,7 @@ struct KktSystem {
    // off for these factors (aug_failed_gen).  Several ranks keep the refined witness: the decision to repeat a solveCompressed would
    // have to be taken by all ranks together.  PIPS_HIP_AUG_WITNESS=0: the refined witness everywhere.
    long long aug_failed_gen = -1;
-   bool checked_witness = env_int("PIPS_HIP_AUG_WITNESS", 1) != 0;
+   bool checked_witness = knob_int<K_AUG_WITNESS>() != 0;
    // Every solveCompressed that goes by sweeps is measured like that (pips_hip_kkt_set_solve_check: every k-th one; 0 = the witness
    // only, rounds 4's behaviour): the reference's PARDISO measures and refines EVERY leaf solve (iparm[7] = 2,
    // PardisoProjectSolver.C:72), and one clean right-hand side does not bound the backward error of the next.  Several ranks decide
@@ -198,7 +198,7 @@ struct KktSystem {
       k->leaves = e; k->sparse = sparse_root;
       k->n0 = n0; k->my0 = my0; k->myl = myl; k->mzl = mzl; k->S = S;
       k->comm = comm; k->rank = rank; k->n_ranks = n_ranks;
-      k->force_reduce = comm && getenv("PIPS_HIP_FORCE_REDUCE") != nullptr;
+      k->force_reduce = comm && knob_set<K_FORCE_REDUCE>();
       const int rc = sparse_root ? k->init_sparse_root(rows, n_blocks_global, blk_cols_ptr, blk_cols) : k->init_dense_root(rows);
       if (rc) return rc;
       *handle = k.release();
@@ -256,7 +256,7 @@ struct KktSystem {
       if (rc) return rc;
       // several ranks: the dense root factorised column-cyclically over the ranks instead of redundantly on every one of them
       // (PIPS_HIP_ROOT_DISTRIBUTED=1; untimed - see DenseLdl::set_distributed)
-      if (comm && n_ranks > 1 && env_int("PIPS_HIP_ROOT_DISTRIBUTED", 0) != 0 && (rc = root->set_distributed(comm, rank, n_ranks))) return rc;
+      if (comm && n_ranks > 1 && knob_int<K_ROOT_DISTRIBUTED>() != 0 && (rc = root->set_distributed(comm, rank, n_ranks))) return rc;
       PIPS_TRY(d_SC.alloc((size_t)S * S));
       PIPS_TRY(d_t.alloc(std::max<size_t>((size_t)e->n_total, 1)));
       // SC is column-major with the lower triangle valid: (r,c) -> r + c*S.
@@ -268,9 +268,9 @@ struct KktSystem {
       if (comm && (n_ranks > 1 || force_reduce) && !e->deterministic) {
          // default: panels only where the reduction is worth hiding (S >= 4096: >= 64 MB packed; splitting the SYRK costs ~1 ms)
          int panels = S >= 4096 ? 4 : 1;
-         if (const char* pp = getenv("PIPS_HIP_SC_PANELS")) panels = atoi(pp);
+         if (knob_set<K_SC_PANELS>()) panels = (int)knob_int<K_SC_PANELS>();
          if ((rc = e->set_sc_panels(panels))) return rc;
-         if (const char* m = getenv("PIPS_HIP_SC_REDUCE")) use_rsag = std::string(m) == "rsag";
+         if (const char* m = knob_text<K_SC_REDUCE>()) use_rsag = std::string(m) == "rsag";
       }
       return PIPS_OK;
    }
@@ -318,8 +318,8 @@ struct KktSystem {
       r->in[0].n = S; r->in[0].n_primal = n0;
       r->in[0].krow = sc_rowptr; r->in[0].kcol = sc_colidx;
       // elimination order (sparse_root_order, rootplan.cpp)
-      const char* f = getenv("PIPS_HIP_SPARSE_ROOT_BAND");   // tests: force a path
-      const int forced = f ? atoi(f) : 0;
+      const bool f = knob_set<K_SPARSE_ROOT_BAND>();   // tests: force a path
+      const int forced = (int)knob_int<K_SPARSE_ROOT_BAND>();
       int cut = 0;
       root_order_mode = sparse_root_order(S, n0 + my0, sc_rowptr, sc_colidx, TILE, ROOT_ND_MAX_COLCOUNT, f ? &forced : nullptr, root_perm, root_colcount, cut);
       if (root_order_mode == 2) {
@@ -471,9 +471,8 @@ struct KktSystem {
    // and made it opt-in; 148 full-size runs and 60 small ones in round 5 (tools/stress_exit.sh, tools/stress_async.sh, every run under a
    // watchdog) all ended, and the mechanism is the dense root's, which has been the default since round 2.
    bool root_async() const {
-      static const bool sync_env = getenv("PIPS_HIP_ROOT_SYNC") != nullptr;
-      static const bool sparse_async_env = env_int("PIPS_HIP_SPARSE_ROOT_ASYNC", 1) != 0;
-      return !sync_env && root_own_stream && (sparse ? sparse_async_env : root->dist_P <= 1);   // the distributed root issues collectives: main stream
+      const ProcessKnobs& env = knob_process();   // PIPS_HIP_ROOT_SYNC, PIPS_HIP_SPARSE_ROOT_ASYNC: once per process
+      return !env.root_sync && root_own_stream && (sparse ? env.sparse_root_async : root->dist_P <= 1);   // the distributed root issues collectives: main stream
    }
    template <class Factor>
    int factor_root(hipStream_t& rstream, Factor factor) {

@@ -54,7 +54,7 @@ SYMBOLS = [
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
     "pips_hip_ldl_inertia_batch", "pips_hip_ldl_factor_schur_sparse", "pips_hip_ldl_factor_schur_sparse_batch",
     "pips_hip_dense_ldl_create", "pips_hip_dense_ldl_factor", "pips_hip_dense_ldl_factor_dev", "pips_hip_dense_ldl_solve",
-    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_first_touch_probe", "pips_ipm_layout_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
+    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_first_touch_probe", "pips_ipm_layout_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_knobs", "pips_hip_knob_value", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
     "pips_hip_batch_create", "pips_hip_batch_set_block", "pips_hip_batch_set_options", "pips_hip_batch_set_schur_mode", "pips_hip_batch_set_deterministic", "pips_hip_batch_get_schur_mode", "pips_hip_batch_add_regularization", "pips_hip_batch_set_refinement",
     "pips_hip_batch_last_refinement_steps", "pips_hip_batch_set_refinement_backward_error",
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
@@ -122,6 +122,26 @@ def host_wait_sites():
         k, v = ln.rsplit(" ", 1)
         out[k] = int(v)
     return out
+
+
+def knobs():
+    """the library's environment switches, from its own table: {name: {"kind", "default", "when", "effect"}}"""
+    buf = C.create_string_buffer(32768)
+    n = lib.pips_hip_knobs(buf, 32768)
+    assert 0 < n < 32767
+    out = {}
+    for ln in buf.value.decode().splitlines():
+        name, kind, default, when, effect = ln.split(" ", 4)
+        out[name] = {"kind": kind, "default": default, "when": when, "effect": effect}
+    return out
+
+
+def knob_value(name):
+    """what the library makes of the switch `name` right now: (number, text) - text is the value of a text switch, else ''"""
+    v = C.c_double()
+    text = C.create_string_buffer(4096)
+    _check(lib.pips_hip_knob_value(name.encode(), C.byref(v), text, 4096), "pips_hip_knob_value")
+    return v.value, text.value.decode()
 
 
 def _ptr(a):
