@@ -217,6 +217,11 @@ void sc_lower_pattern(int S, int n0, const RootRows (&root)[3], const std::vecto
 // of the choice by the tile envelope (2 still falls back to 1 without separators).
 int sparse_root_order(int S, int n_hubs, const std::vector<int>& rowptr, const std::vector<int>& colidx, int tile, int max_head_colcount,
                       const int* force_mode, std::vector<int>& perm, std::vector<int>& colcount, int& head_cut);
+// Largest column count the dissected sparse root admits in its head (pips_hip_kkt_create_sparse, pips_symbolic_probe_hubs): a front of
+// colcount + 1 rows must fit the LDS as a packed triangle (19 200 doubles: 195 rows).  Measured (tools/sparse_root_probe.py, 64 blocks):
+// 31 linking rows per pair (fronts <= 188 rows) factorize 4.3 ms as a band, 2.6 ms dissected; 100 rows per pair (fronts of 308 rows:
+// update matrices in device memory) 10.1 ms as a band, 11.1 ms dissected and solveCompressed 2.1 -> 4.3 ms - those stay a band.
+constexpr int ROOT_ND_MAX_COLCOUNT = 192;
 
 }  // namespace pips
 

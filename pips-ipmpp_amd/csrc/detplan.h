@@ -10,8 +10,6 @@
 
 namespace pips {
 
-struct TaskList { long long off = 0; int cnt = 0; };
-
 // A gather list: the recorded contributions (target, slot) sorted by (target, slot), then the CSR "target -> its slots"
 struct SlotEntry { long long target, slot; };
 struct HostGather {

@@ -13,13 +13,13 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "common.h"
 #include "devmem.h"
 #include "layout.h"
 #include "detplan.h"
+#include "tileplan.h"
 #include "knobs.h"
 #include "schurtarget.h"
 #include "kernels.hip.h"
@@ -77,223 +77,27 @@ static inline int grid_for(long long n, int block, int cap = 4096) {
 // ---------------------------------------------------------------------------------------------------------------
 // tiled dense LDL^T driver shared by the leaf tails and the dense root
 // ---------------------------------------------------------------------------------------------------------------
-struct TailPlan {
-   int ntc_max = 0;
-   std::vector<TaskList> upd, upd_diag, diag, trsm, fwd, bwd, trail, trail_next;
-   TaskList schur;
+// The task plans are made on the host (tileplan.h); the four structs here add the device copies.
+// The column plan (ColumnPlan) and its tasks on the device
+struct TailPlan : ColumnPlan {
    DevBuf<TileTask> d_tasks;
-   std::vector<TileTask> h_tasks;   // host copy (the single-launch factorisation re-lists them: TailSingle::build)
-
-   // panel == 0: pure left-looking (tile column j is updated once, with everything to its left: minimal traffic on C,
-   //   one task per tile of the column - right when many blocks share every launch).
-   // panel == P > 0: blocked right-looking with panels of P tile columns (the dense root, a single block: a left-looking
-   //   column launch has at most ntr workgroups with a K as deep as the matrix; here the column update only reaches back
-   //   to the start of its panel and each finished panel is applied to the whole trailing matrix in one launch of
-   //   (ntr - p1)^2 / 2 tiles with K = P * TILE).  The K range rides in TileTask::pad = k0 | k1 << 16 (tile columns).
-   // split_diag (left-looking batches): the update of the diagonal tile of column j gets a task list of its own (upd_diag),
-   // so that the driver can factorise that tile on a side stream while the rest of the column is still being updated.
-   // first: per block the tile-row envelope of its tail (BlockSym::tile_first); tiles left of it hold structural zeros and
-   // get no task, update depths start at the envelope (a banded tail costs band^2 per column instead of column^2)
-   int build(const std::vector<BlkDesc>& blks, int panel = 0, bool lookahead = false, bool split_diag = false,
-             const std::vector<const std::vector<int>*>* first = nullptr, bool diag_ahead = false, int pair2 = 1) {
-      lists(blks, panel, lookahead, split_diag, first, diag_ahead, pair2);
+   int build_leaf(const std::vector<BlkDesc>& blks, const TileFirst& first, int group) {
+      ColumnPlan::build_leaf(blks, first, group);
       return d_tasks.upload(h_tasks);
    }
-   // ... its host part: the lists and h_tasks, no device call (pips_tail_plan_probe)
-   void lists(const std::vector<BlkDesc>& blks, int panel, bool lookahead, bool split_diag, const std::vector<const std::vector<int>*>* first,
-              bool diag_ahead, int pair2) {
-      std::vector<TileTask> all;
-      ntc_max = 0;
-      for (auto& b : blks) ntc_max = std::max(ntc_max, b.ntc);
-      upd.assign(ntc_max, {});
-      upd_diag.assign(ntc_max, {});
-      diag.assign(ntc_max, {});
-      trsm.assign(ntc_max, {});
-      fwd.assign(ntc_max, {});
-      bwd.assign(ntc_max, {});
-      trail.assign(ntc_max, {});
-      trail_next.assign(ntc_max, {});
-      const int nblk = (int)blks.size();
-      auto begin = [&](TaskList& l) { l.off = (long long)all.size(); };
-      auto end = [&](TaskList& l) { l.cnt = (int)((long long)all.size() - l.off); };
-      for (int j = 0; j < ntc_max; ++j) {
-         const int p0 = panel > 0 ? j / panel * panel : 0;   // first tile column of j's panel
-         auto fst = [&](int b, int t) { return first ? (*(*first)[b])[t] : 0; };
-         // diag_ahead: the diagonal tile of column j+1 takes its update with the columns < j inside the launch of column j
-         // (same depth as the other tiles of that launch); the list of its own only holds the last step, with column j-1.
-         // The side stream then has a K = TILE product and the tile factorisation on the path to trsm(j), not a product as
-         // deep as the matrix done by one workgroup per block.
-         begin(upd_diag[j]);
-         if (j > p0 && split_diag)
-            for (int b = 0; b < nblk; ++b)
-               if (blks[b].ntc > j) {
-                  const int k0 = std::max(p0, fst(b, j));
-                  if (k0 < j) all.push_back({b, j, j, (diag_ahead ? std::max(k0, j - 1) : k0) | (j << 16)});
-               }
-         end(upd_diag[j]);
-         begin(upd[j]);
-         // pair2 = P (left-looking batches with the diagonal tiles ahead): the tile columns of a group g .. g + P - 1 share the launch of column
-         // g for everything left of the group - the tiles of a tile row read the same rows of L, side by side in the task list (one XCD, one
-         // after the other) - and column g + q takes the rest, the q columns of its own group, in the launch of its own (q tiles deep).  The
-         // diagonal tiles up to the next group's first ride along the same way, so that the short launches hold no deep task.
-         const int P = (pair2 > 1 && panel == 0 && split_diag && diag_ahead) ? pair2 : 1;
-         const int g = j / P * P, q = j - g;
-         if (j > p0 && split_diag && diag_ahead)
-            for (int b = 0; b < nblk; ++b)
-               if (blks[b].ntc > j + 1) {
-                  const int k0 = std::max(p0, fst(b, j + 1)), lo = q > 0 ? std::max(k0, g) : k0;
-                  if (lo < j) all.push_back({b, j + 1, j + 1, lo | (j << 16)});
-               }
-         if (P > 1 && q == 0 && j > p0)
-            for (int b = 0; b < nblk; ++b)
-               for (int d = j + 2; d <= j + P && d < blks[b].ntc; ++d) {
-                  const int k0 = std::max(p0, fst(b, d));
-                  if (k0 < j) all.push_back({b, d, d, k0 | (j << 16)});
-               }
-         if (j > p0)
-            for (int b = 0; b < nblk; ++b)
-               if (blks[b].ntc > j)
-                  for (int ti = split_diag ? j + 1 : j; ti < blks[b].ntr; ++ti) {
-                     if (j >= fst(b, ti)) {                                         // (else outside the envelope: stays zero)
-                        const int k0 = std::max({p0, fst(b, ti), fst(b, j)}), lo = q > 0 ? std::max(k0, g) : k0;
-                        if (lo < j) all.push_back({b, ti, j, lo | (j << 16)});
-                     }
-                     if (P > 1 && q == 0)
-                        for (int c = j + 1; c < j + P && c < blks[b].ntc && c < ti; ++c)
-                           if (c >= fst(b, ti)) {
-                              const int k0 = std::max({p0, fst(b, ti), fst(b, c)});
-                              if (k0 < j) all.push_back({b, ti, c, k0 | (j << 16)});
-                           }
-                  }
-         end(upd[j]);
-         begin(diag[j]);
-         for (int b = 0; b < nblk; ++b)
-            if (blks[b].ntc > j) all.push_back({b, j, j, 0});
-         end(diag[j]);
-         begin(trsm[j]);
-         for (int b = 0; b < nblk; ++b)
-            if (blks[b].ntc > j)
-               for (int ti = j + 1; ti < blks[b].ntr; ++ti)
-                  if (j >= fst(b, ti)) all.push_back({b, ti, j, 0});
-         end(trsm[j]);
-         begin(fwd[j]);
-         for (int b = 0; b < nblk; ++b)
-            if (blks[b].ntc > j)
-               for (int ti = j; ti < blks[b].ntc; ++ti)
-                  if (ti == j || (j >= 1 && j - 1 >= fst(b, ti))) all.push_back({b, ti, j, 0});   // L(ti, j-1) inside the envelope
-         end(fwd[j]);
-         begin(bwd[j]);
-         for (int b = 0; b < nblk; ++b)
-            if (blks[b].ntc > j)
-               for (int tj = 0; tj <= j; ++tj)
-                  if (tj == j || (j + 1 < blks[b].ntc && tj >= fst(b, j + 1))) all.push_back({b, tj, j, 0});   // L(j+1, tj)
-         end(bwd[j]);
-         // panel [p0, j] complete: apply it to every tile right of it.  The next tile column is listed separately
-         // (trail_next) so that the driver can finish it first and overlap the next diagonal tile with the rest.
-         if (panel > 0 && (j + 1) % panel == 0) {
-            begin(trail_next[j]);
-            if (lookahead)
-               for (int b = 0; b < nblk; ++b)
-                  if (j + 1 < blks[b].ntc)
-                     for (int ti = j + 1; ti < blks[b].ntr; ++ti) all.push_back({b, ti, j + 1, p0 | ((j + 1) << 16)});
-            end(trail_next[j]);
-            begin(trail[j]);
-            for (int b = 0; b < nblk; ++b)
-               for (int tj = j + (lookahead ? 2 : 1); tj < blks[b].ntc; ++tj)
-                  for (int ti = tj; ti < blks[b].ntr; ++ti) all.push_back({b, ti, tj, p0 | ((j + 1) << 16)});
-            end(trail[j]);
-         }
-      }
-      begin(schur);
-      for (int b = 0; b < nblk; ++b)
-         if (blks[b].ntc > 0 && blks[b].nb > 0) {
-            const int nt = blks[b].nb_pad / TILE;
-            for (int ti = 0; ti < nt; ++ti)
-               for (int tj = 0; tj <= ti; ++tj) all.push_back({b, ti, tj, 0});
-         }
-      end(schur);
-      h_tasks = std::move(all);
+   int build_root(const std::vector<BlkDesc>& blks, int panel, bool lookahead) {
+      ColumnPlan::build_root(blks, panel, lookahead);
+      return d_tasks.upload(h_tasks);
    }
 };
 
-// The update and trsm tasks of a left-looking column plan (TailPlan with diag_ahead and pair2 = P) regrouped by groups of P tile columns
-// (tail_panels): the same tasks, each exactly once, in lists of their own array.  With g the first column of a group and a task's launch
-// column j = its k1 (updates) or tile column (trsm), a task of a tile row >= g + P belongs to the main stream -
-//   deep[g / P]    the updates of launch column g (K left of the group), one launch;
-//   strips[g / P]  the rest per (block, tile row) in column order - trsm(ti, g), update(ti, g + 1; K = [g, g + 1)), trsm(ti, g + 1), ... - one
-//                  workgroup each of one k_tile_panel launch;
-// and a task of a tile row inside the group to the chain on the side stream that finishes the group's diagonal block beside the deep launch -
-//   pre[g / P]         the diagonal tile (g, g) with the columns g - P .. g - 2 (the column plan has it ride in the launch of column g - 1),
-//   block_deep[g / P]  the block's tiles with everything left of the group (for (g, g): its last step, with column g - 1),
-//   upd_in[j], trsm_in[j]  per column of the group the block's short updates before, and its trsm after, the diagonal tile of column j.
-// No list holds two tasks of one tile, and a tile meets its tasks in the column plan's order: the sums keep their order.
-struct PanelPlan {
-   int P = 0, n_groups = 0;
-   std::vector<TaskList> deep, pre, block_deep, strips;   // per group (strips: a range of h_strips / d_strips)
-   std::vector<TaskList> upd_in, trsm_in;                 // per tile column
-   std::vector<TileTask> h_tasks;
-   std::vector<TileStrip> h_strips;                       // (offsets into h_tasks)
+// A leaf column plan regrouped by groups of P tile columns (GroupPlan), tasks and strips on the device
+struct PanelPlan : GroupPlan {
    DevBuf<TileTask> d_tasks;
    DevBuf<TileStrip> d_strips;
-   void lists(const TailPlan& p, int P_) {
-      *this = PanelPlan();
-      P = P_;
-      n_groups = (p.ntc_max + P - 1) / P;
-      struct Group { std::vector<TileTask> deep, pre, block_deep; std::map<std::pair<int, int>, std::vector<TileTask>> strips; };
-      std::vector<Group> gs(n_groups);
-      std::vector<std::vector<TileTask>> ui(p.ntc_max), ti(p.ntc_max);
-      auto each = [&](const TaskList& l, auto&& f) {
-         for (long long q = l.off; q < l.off + l.cnt; ++q)
-            if (p.h_tasks[q].blk >= 0) f(p.h_tasks[q]);
-      };
-      auto update = [&](const TileTask& t) {
-         const int k1 = t.pad >> 16, g = k1 / P * P;
-         if (t.ti >= g + P) {
-            if (k1 == g) gs[g / P].deep.push_back(t);
-            else if (t.ti == t.tj) gs[t.tj / P].pre.push_back(t);
-            else gs[g / P].strips[{t.blk, t.ti}].push_back(t);
-         } else if (k1 == g)
-            gs[g / P].block_deep.push_back(t);
-         else
-            ui[k1].push_back(t);
-      };
-      for (int j = 0; j < p.ntc_max; ++j) {
-         each(p.upd_diag[j], update);
-         each(p.upd[j], update);
-         each(p.trsm[j], [&](const TileTask& t) {
-            const int g = j / P * P;
-            if (t.ti >= g + P) gs[g / P].strips[{t.blk, t.ti}].push_back(t);
-            else ti[j].push_back(t);
-         });
-      }
-      auto put = [&](TaskList& l, const std::vector<TileTask>& v) {
-         l.off = (long long)h_tasks.size(); l.cnt = (int)v.size();
-         h_tasks.insert(h_tasks.end(), v.begin(), v.end());
-      };
-      deep.assign(n_groups, {}); pre.assign(n_groups, {}); block_deep.assign(n_groups, {}); strips.assign(n_groups, {});
-      upd_in.assign(p.ntc_max, {}); trsm_in.assign(p.ntc_max, {});
-      // a strip's order: the update with columns < k1 before the trsm of column k1 and after that of column k1 - 1
-      auto step = [](const TileTask& t) { return t.pad ? 2 * (t.pad >> 16) : 2 * t.tj + 1; };
-      for (int i = 0; i < n_groups; ++i) {
-         put(deep[i], gs[i].deep);
-         put(pre[i], gs[i].pre);
-         put(block_deep[i], gs[i].block_deep);
-         strips[i].off = (long long)h_strips.size();
-         for (auto& kv : gs[i].strips) {   // (block, tile row) ascending: a block's strips side by side
-            std::vector<TileTask>& v = kv.second;
-            std::stable_sort(v.begin(), v.end(), [&](const TileTask& a, const TileTask& b) { return step(a) != step(b) ? step(a) < step(b) : a.tj < b.tj; });
-            h_strips.push_back({(int)h_tasks.size(), (int)v.size()});
-            h_tasks.insert(h_tasks.end(), v.begin(), v.end());
-         }
-         strips[i].cnt = (int)((long long)h_strips.size() - strips[i].off);
-         for (int j = i * P; j < std::min((i + 1) * P, p.ntc_max); ++j) {
-            put(upd_in[j], ui[j]);
-            put(trsm_in[j], ti[j]);
-         }
-      }
-   }
    int build(const TailPlan& p, int P_) {
-      lists(p, P_);
+      *this = PanelPlan();
+      GroupPlan::build(p, P_);
       if (h_tasks.empty()) h_tasks.push_back({-1, 0, 0, 0});
       if (h_strips.empty()) h_strips.push_back({0, 0});
       PIPS_TRY(d_tasks.upload(h_tasks));
@@ -325,36 +129,21 @@ struct SweepRt {
                               "another process holding the device for seconds can cause that - PIPS_HIP_SWEEP_LAUNCHES (set to any value) selects the launch-per-column sweeps",
                 who, poll_limit);
    }
-   int build(const std::vector<BlkDesc>& blks, const std::vector<const std::vector<int>*>* first) {
+   int build(const std::vector<BlkDesc>& blks, const TileFirst* first) {
       *this = SweepRt();
       static_assert(KNOBS[K_SWEEP_POLL_LIMIT].dflt == SWEEP_POLL_LIMIT, "the table's default is the kernels' limit");
       poll_limit = knob_int<K_SWEEP_POLL_LIMIT>();
-      const int nblk = (int)blks.size();
-      int ntc_max = 0;
-      for (auto& b : blks) ntc_max = std::max(ntc_max, b.ntc);
-      std::vector<TileTask> tasks;
-      for (int i = 0; i < ntc_max; ++i)
-         for (int b = 0; b < nblk; ++b)
-            if (i < blks[b].ntc) tasks.push_back({b, i, 0, 0});
-      n_tasks = (int)tasks.size();
-      std::vector<long long> foff(nblk), tfoff(nblk);
-      std::vector<int> tf;
-      long long nf = 0;
-      for (int b = 0; b < nblk; ++b) {
-         foff[b] = nf;
-         nf += blks[b].ntc;
-         tfoff[b] = (long long)tf.size();
-         if (first)   // tail rows and, behind them, the border tile rows (border-backward sweep)
-            for (int i = 0; i < blks[b].ntr; ++i) tf.push_back(i < blks[b].ntc ? std::min(i, (*(*first)[b])[i]) : (*(*first)[b])[i]);
-      }
+      SweepLists l;
+      l.build(blks, first);
+      n_tasks = (int)l.tasks.size();
       int rc;
-      if ((rc = d_tasks.upload(tasks))) return rc;
-      if ((rc = d_flag_off.upload(foff))) return rc;
+      if ((rc = d_tasks.upload(l.tasks))) return rc;
+      if ((rc = d_flag_off.upload(l.flag_off))) return rc;
       if (first) {
-         if ((rc = d_tfirst.upload(tf))) return rc;
-         if ((rc = d_tfirst_off.upload(tfoff))) return rc;
+         if ((rc = d_tfirst.upload(l.tfirst))) return rc;
+         if ((rc = d_tfirst_off.upload(l.tfirst_off))) return rc;
       }
-      n_flags = std::max<long long>(nf, 1);
+      n_flags = std::max<long long>(l.n_flags, 1);
       const size_t ints = (size_t)(2 * SWEEP_NRHS_MAX + 2 + n_flags * SWEEP_NRHS_MAX);
       PIPS_TRY(d_ints.alloc_zero(ints));
       epoch = 0;
@@ -424,8 +213,8 @@ struct PhaseTimer {
    ~PhaseTimer() { for (auto e : pool) (void)hipEventDestroy(e); }
 };
 
-// Host side of k_tail_ldl (tailkernel.hip.h): the tasks of the column launches of a TailPlan as ONE list in the driver's order, dealt to
-// eight lists by tile row; the flags and the template they start from.
+// Device side of the single tail launch k_tail_ldl (tailkernel.hip.h): the eight task lists (TailSingleLists), the flags, the template
+// they start from and the tickets
 struct TailSingle {
    TailLdlArgs args{};
    DevBuf<TileTask> d_tasks;
@@ -435,65 +224,16 @@ struct TailSingle {
    int n_tasks = 0, n_blocks = 0;
    int build(const TailPlan& p, const std::vector<BlkDesc>& blks, hipStream_t stream) {
       *this = TailSingle();
-      const int nblk = (int)blks.size();
-      n_blocks = nblk;
-      std::vector<long long> foff(nblk + 1, 0);
-      for (int b = 0; b < nblk; ++b) foff[b + 1] = foff[b] + (long long)blks[b].ntr * blks[b].ntc + blks[b].ntr + blks[b].ntc;
-      n_flags = foff[nblk];
-      // the template: prog of a tile = the first K its first update starts from (an update waits for prog >= its k0: the one before it has
-      // stored the tile), = its tile column where it takes no update at all (trsm / the diagonal role wait for prog >= tile column)
-      std::vector<int> init((size_t)std::max<long long>(n_flags, 1), 0);
-      for (int b = 0; b < nblk; ++b)
-         for (int ti = 0; ti < blks[b].ntr; ++ti)
-            for (int tj = 0; tj < blks[b].ntc; ++tj) init[foff[b] + (long long)ti * blks[b].ntc + tj] = -1;
-      std::vector<TileTask> order;
-      auto take = [&](const TaskList& l, int kind) {
-         for (long long q = l.off; q < l.off + l.cnt; ++q) {
-            TileTask t = p.h_tasks[q];
-            if (t.blk < 0) continue;
-            if (kind == ROOT_UPD) {
-               int& pr = init[foff[t.blk] + (long long)t.ti * blks[t.blk].ntc + t.tj];
-               if (pr < 0) pr = t.pad & 0xffff;
-            } else
-               t.pad = 0;
-            t.blk |= kind << 24;
-            order.push_back(t);
-         }
-      };
-      // first tile column of every tile row (its envelope): the trsm of a row commit in column order from there (root_do)
-      std::vector<int> row_first((size_t)std::max<long long>(n_flags, 1), 1 << 20);
-      for (int j = 0; j < p.ntc_max; ++j)
-         for (long long q = p.trsm[j].off; q < p.trsm[j].off + p.trsm[j].cnt; ++q) {
-            const TileTask& t = p.h_tasks[q];
-            if (t.blk >= 0) { int& f = row_first[foff[t.blk] + t.ti]; f = std::min(f, t.tj); }
-         }
-      for (int j = 0; j < p.ntc_max; ++j) {
-         take(p.upd_diag[j], ROOT_UPD);
-         take(p.diag[j], ROOT_DIAG);
-         take(p.upd[j], ROOT_UPD);
-         const size_t before = order.size();
-         take(p.trsm[j], ROOT_TRSM);
-         for (size_t q = before; q < order.size(); ++q) order[q].pad = row_first[foff[order[q].blk & 0xffffff] + order[q].ti];
-      }
-      for (int b = 0; b < nblk; ++b)
-         for (int ti = 0; ti < blks[b].ntr; ++ti)
-            for (int tj = 0; tj < blks[b].ntc; ++tj) { int& pr = init[foff[b] + (long long)ti * blks[b].ntc + tj]; if (pr < 0) pr = tj; }
-      // eight lists: runs of tasks of one (block, tile row) go to the lists round-robin, every list keeps the order
-      std::vector<std::vector<TileTask>> lists(8);
-      int run = -1, last_b = -2, last_i = -2;
-      for (const TileTask& t : order) {
-         const int b = t.blk & 0xffffff;
-         if (b != last_b || t.ti != last_i) { ++run; last_b = b; last_i = t.ti; }
-         lists[run & 7].push_back(t);
-      }
-      std::vector<TileTask> all;
-      for (int x = 0; x < 8; ++x) { args.xoff[x] = (int)all.size(); all.insert(all.end(), lists[x].begin(), lists[x].end()); }
-      args.xoff[8] = (int)all.size();
-      n_tasks = (int)all.size();
-      if (all.empty()) all.push_back({0, 0, 0, 0});
+      TailSingleLists l;
+      l.build(p, blks);
+      n_blocks = (int)blks.size();
+      n_flags = l.n_flags;
+      n_tasks = l.n_tasks;
+      std::copy(l.xoff, l.xoff + 9, args.xoff);
+      if (l.tasks.empty()) l.tasks.push_back({0, 0, 0, 0});
       int rc;
-      if ((rc = d_tasks.upload(all)) || (rc = d_flags_init.upload(init)) || (rc = d_flag_off.upload(foff))) return rc;
-      PIPS_TRY(d_flags.alloc(init.size()));
+      if ((rc = d_tasks.upload(l.tasks)) || (rc = d_flags_init.upload(l.init)) || (rc = d_flag_off.upload(l.foff))) return rc;
+      PIPS_TRY(d_flags.alloc(l.init.size()));
       PIPS_TRY(d_ctl.alloc(16));
       HIP_TRY(hipMemsetAsync(d_ctl, 0, 16 * sizeof(int), stream));
       args.tasks = d_tasks; args.flags = d_flags; args.flag_off = d_flag_off; args.ctl = d_ctl;
@@ -837,14 +577,6 @@ static int tail_bwd(const TailCtx& c, double* xw, int nrhs = 1, long long xw_str
 // ---------------------------------------------------------------------------------------------------------------
 // batched leaf engine (BlockInput, LevelRange, MfLaunch and the host pass of the analysis: layout.h)
 // ---------------------------------------------------------------------------------------------------------------
-// What one analyze() call reads from the environment: the layout's switches, and the two of the single-launch tail factorisation
-struct AnalyzeKnobs : LayoutKnobs {
-   long long tail_poll_limit = 0;
-   int tail_diag_blocked = 1;
-};
-struct Engine;
-static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs& knobs);
-
 // What an analysis owns on the device and what belongs to it on the host: Engine::release() resets exactly this (a move-assignment
 // from a fresh one), so a buffer declared here is freed and reset without a second mention anywhere.  The settings that survive a
 // re-analysis, the inputs and the streams are members of Engine itself.
@@ -1098,7 +830,8 @@ struct Engine : EngineAnalysis, BatchLayout {
       for (int b = 0; b < nblk; ++b)
          if (in[b].n <= 0) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_batch_analyze: block %d was never set", b);
       AnalyzeKnobs knobs;
-      read_layout_knobs(this, opt, knobs);
+      const EngineSettings settings{sn_width, deterministic, schur_mode};
+      read_layout_knobs(&settings, opt, knobs);
       HIP_TRY(hipSetDevice(device));
       release();
       {
@@ -1116,10 +849,10 @@ struct Engine : EngineAnalysis, BatchLayout {
       if ((rc = upload_layout())) return rc;
       // the diagonal tile of a column runs ahead on the side stream, its update first; tile rows start at their envelope (variants of the
       // tail factorisation without either: docs/HISTORY_r1_r2.md)
-      // tile columns per launch of the left-looking tail update (TailPlan::build, pair2).  configs[1], ms per unit / ms of update, two boxes:
+      // tile columns per launch of the left-looking tail update (ColumnPlan::build_leaf, group).  configs[1], ms per unit / ms of update, two boxes:
       // 1 column 125.0 - 126.8 / 73.8 - 74.7; 2: 123.6 - 124.0 / 72.4; 3: 122.0 / 70.8; 4: 120.0 - 121.7 / 70.3 - 71.0; 6: 120.5 / 70.3; 8: 120.8 / 70.9
       const int pair2 = 4;   // (1: a column per launch; the switch that chose it went with round 6)
-      if ((rc = plan.build(h_blks, 0, false, true, &tile_first, true, pair2))) return rc;
+      if ((rc = plan.build_leaf(h_blks, tile_first, pair2))) return rc;
       if ((rc = sweep.build(h_blks, &tile_first))) return rc;
       if (tail_single) {
          if ((rc = tsingle.build(plan, h_blks, stream))) return rc;
@@ -2223,49 +1956,6 @@ struct Engine : EngineAnalysis, BatchLayout {
    }
 };
 
-// Every switch an analysis depends on, read in one place at every analyze() call (tests set them before
-// analysing).  e == nullptr: the CPU probes - no engine settings, no deterministic mode.
-static void read_layout_knobs(const Engine* e, AnalyzeOptions& opt, AnalyzeKnobs& knobs) {
-   // Tile geometry + the cost-model / amalgamation knobs (environment overrides are for tuning runs only).
-   opt.tile = TILE;
-   // Supernode width cap.  16 instead of the kernels' limit of 32: on the time-coupled family (tools/config3_probe.py, 64 x 50 000)
-   // narrower supernodes carry fewer explicit zeros (nnz(L) 164 M -> 151 M), halve the dependent pivot chain of a front and the
-   // registers its rows take; factorisation 13.4 -> 12.5 ms, solveCompressed 9.3 -> 8.9 ms.  Random sparsity (config 2) has no
-   // supernodes wider than one column in the head.
-   opt.max_sn_width = 16;
-   if (knob_set<K_SN_WIDTH>()) opt.max_sn_width = std::max(1, std::min(HEAD_WMAX, (int)knob_int<K_SN_WIDTH>()));
-   else if (e && e->sn_width > 0) opt.max_sn_width = std::min(HEAD_WMAX, e->sn_width);
-   // (a switch that is not set leaves what opt holds: the values of AnalyzeOptions, or what an earlier analysis of this engine left)
-   if (knob_set<K_RELAX_ZEROS>()) opt.relax_zeros = knob_real<K_RELAX_ZEROS>();
-   if (knob_set<K_ND_DEPTH>()) opt.nd_depth = (int)knob_int<K_ND_DEPTH>();
-   if (knob_set<K_ND_MIN>()) opt.nd_min_size = (int)knob_int<K_ND_MIN>();
-   if (knob_set<K_MF_LDS>()) opt.mf_lds_doubles = knob_int<K_MF_LDS>();
-   if (knob_set<K_MF_SPLIT>()) { const int sp = (int)knob_int<K_MF_SPLIT>(); opt.mf_split_nb_max = sp == 0 ? 0 : std::min(176, std::max(sp, 2)); }
-   knobs.deterministic = e && e->deterministic;
-   knobs.schur_mode = e ? e->schur_mode : 0;
-   // (tests: forces a Schur mode where no setter reaches - the leaf handles and the batch they are bound into - and the caller left it to the model)
-   if (e && knobs.schur_mode == 0) knobs.schur_mode = std::max(0, std::min(2, (int)knob_int<K_SCHUR_MODE>()));
-   knobs.mf_lds_doubles = opt.mf_lds_doubles;
-   knobs.mf_wanted = knob_int<K_MF>() != 0;
-   if (!knobs.mf_wanted) opt.mf_split_nb_max = 0;   // the border split (compact front panels) only exists with the multifrontal head
-   // fronts on the rows of K only where the border split applies (value 1; off by default: on the configs[3] share the fronts fall
-   // from 9.7 to 4.0 ms, forming the border rows afterwards costs 8.0 - DESIGN.md 4.1c): not in deterministic mode (the border rows of the dense
-   // tail take their head contributions with atomics, k_border_tail) and with supernodes of at most 16 columns (k_border_rows<., 16>)
-   opt.mf_konly = opt.mf_split_nb_max > 0 && !knobs.deterministic && opt.max_sn_width <= 16 && knob_int<K_MF_KONLY>() != 0;
-   knobs.spine = knob_tri<K_SPINE>();
-   knobs.tail_single = knob_tri<K_TAIL_SINGLE>();
-   knobs.tail_first_touch = knob_tri<K_TAIL_FIRST_TOUCH>();
-   static_assert(KNOBS[K_FIRST_TOUCH_LDS].dflt == FT_LDS_BUDGET, "the table's default is the layout's budget");
-   knobs.ft_lds_bytes = std::min(FT_LDS_MAX, std::max(0LL, knob_int<K_FIRST_TOUCH_LDS>()));   // (never more than a workgroup can have)
-   knobs.border_backward = knob_tri<K_BORDER_BACKWARD>();
-   knobs.aug_sweeps = knob_tri<K_AUG_SWEEPS>();
-   knobs.sweep_launches = knob_set<K_SWEEP_LAUNCHES>();   // (SweepRt::build: the single-launch sweeps are off)
-   const long long poll = knob_int<K_ROOT_POLL_LIMIT>();
-   knobs.tail_poll_limit = poll > 0 ? poll * 50 : 0;   // (a deep update runs a millisecond)
-   knobs.tail_diag_blocked = knob_int<K_ROOT_DIAG_BARRIERS>() ? 0 : 1;
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------
 // dense root solver (DeSymIndefSolver replacement) on the same tile kernels
 // ---------------------------------------------------------------------------------------------------------------
@@ -2409,7 +2099,7 @@ struct DenseLdl {
       const int panel = d.ntc <= 64 ? 1 : 2;
       // lookahead (second stream) pays once the trailing update of a panel outlasts a diagonal tile: S >= 6000 measured
       const bool lookahead = d.ntc >= 48;
-      if ((rc = plan.build(h_blks, panel, lookahead))) return rc;
+      if ((rc = plan.build_root(h_blks, panel, lookahead))) return rc;
       if ((rc = sweep.build(h_blks, nullptr))) return rc;
       if (lookahead) {
          int prio_lo = 0, prio_hi = 0;
@@ -3021,20 +2711,6 @@ int pips_hip_batch_tail_to_host(void* handle, int b, int which, double* out, int
    HIP_TRY(hipStreamSynchronize(e->stream));
    if (n > 0) HIP_TRY(hipMemcpy(out, src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
    return PIPS_OK;
-}
-
-static void sym_info(const std::vector<BlockSym>& sym, int64_t* what, int n_what) {
-   int64_t v[13] = {0};
-   for (const BlockSym& s : sym) {
-      v[10] += (int64_t)s.upd.size() * 4;
-      v[11] += s.nb;
-      v[12] += (int64_t)s.a_dst.size();
-      v[0] += s.nnzL; v[1] += s.n; v[2] += s.n_head; v[3] += s.m; v[4] += (int64_t)s.sn.size();
-      v[5] = std::max<int64_t>(v[5], s.n_levels);
-      v[6] += (int64_t)s.flops_factor; v[7] += (int64_t)s.flops_border; v[8] += s.arena * 8;
-      v[9] = std::max<int64_t>(v[9], s.m_pad / TILE);
-   }
-   for (int i = 0; i < n_what && i < 13; ++i) what[i] = v[i];
 }
 
 int pips_hip_batch_info(void* handle, int64_t* what, int n_what) {
@@ -4114,378 +3790,5 @@ int pips_hip_kkt_sparse_root_info(void* handle, int64_t* what, int n_what) {
 }
 
 void pips_hip_kkt_destroy(void* handle) { delete (KktSystem*)handle; }
-
-// ---- symbolic probe (CPU only) -------------------------------------------------------------------------------------
-int pips_symbolic_probe(int n, int n_primal, const int* krow, const int* jcol, int S, const int* Bt_rowptr,
-                        const int* Bt_colidx, int force_n_head, int64_t* what, int n_what, int* perm, int* colcount) {
-   if (n <= 0 || !krow || !jcol) PIPS_FAIL(PIPS_ERR_ARG, "pips_symbolic_probe: bad arguments");
-   AnalyzeOptions opt;
-   AnalyzeKnobs knobs;
-   read_layout_knobs(nullptr, opt, knobs);
-   opt.force_n_head = force_n_head;
-   CsrPattern K{n, n, krow, jcol};
-   CsrPattern B{0, n, nullptr, nullptr};
-   if (Bt_rowptr && S > 0) B = CsrPattern{S, n, Bt_rowptr, Bt_colidx};
-   std::vector<BlockSym> sym(1);
-   int rc = analyze_block(K, B, n_primal, opt, sym[0]);
-   if (rc) return rc;
-   if (what) sym_info(sym, what, n_what);
-   if (what && n_what > 16) {   // multifrontal head: usable, border split taken, doubles of update matrices, doubles of border rows kept beside the panels
-      const BlockSym& bs = sym[0];
-      what[13] = bs.mf_ok ? 1 : 0;
-      what[14] = bs.mf_split ? (bs.mf_konly ? 2 : 1) : 0;
-      what[15] = bs.mf_U_total;
-      what[16] = 0;
-      for (const HeadSupernode& hs : bs.sn) if (hs.ld < hs.w + hs.r) what[16] += (int64_t)hs.w * (hs.r - hs.rb);
-   }
-   if (const char* dump = knob_text<K_DUMP_SN>()) {   // development aid
-      if (FILE* f = fopen(dump, "w")) {
-         const BlockSym& bs = sym[0];
-         for (size_t si = 0; si < bs.sn.size(); ++si) {
-            const HeadSupernode& s = bs.sn[si];
-            const int* rows = bs.rowidx.data() + s.rows;
-            int nh = 0, nt = 0;
-            for (int a = 0; a < s.r; ++a) { if (rows[a] < bs.n_head) ++nh; else if (rows[a] < bs.n) ++nt; }
-            // c0 w r level rows-in-head rows-in-tail border-rows update-segments parent-supernode (index, -1: none in the head)
-            fprintf(f, "%d %d %d %d %d %d %d %d %d\n", s.c0, s.w, s.r, s.level, nh, nt, s.r - nh - nt, s.n_useg,
-                    si < bs.sn_parent.size() ? bs.sn_parent[si] : -1);
-         }
-         fclose(f);
-         fprintf(stderr, "[pips_hip] multifrontal: ok %d, largest front %d, update matrices %lld doubles, records %zu ints\n", (int)bs.mf_ok, bs.mf_max_front,
-                 (long long)bs.mf_U_total, bs.mf_int.size());
-         if (bs.mf_konly) {   // gather-form records: pairs per front and their sizes, level by level
-            std::vector<long long> lp, lf, lmax, lwork;
-            long long pairs = 0, fronts = 0, work = 0, rowsum = 0;
-            for (size_t si = 0; si < bs.sn.size(); ++si) {
-               if (bs.kb_off[si] < 0) continue;
-               const HeadSupernode& s = bs.sn[si];
-               const int* R = bs.kb_rec.data() + bs.kb_off[si];
-               if ((int)lp.size() <= s.level) { lp.resize(s.level + 1, 0); lf.resize(s.level + 1, 0); lmax.resize(s.level + 1, 0); lwork.resize(s.level + 1, 0); }
-               long long wk = 0;
-               for (int q = 0; q < R[0]; ++q) {
-                  const HeadSupernode& c = bs.sn[R[2 + 2 * q]];
-                  const int ns = (R[3 + 2 * q] >> 16) - (R[3 + 2 * q] & 0xffff);
-                  wk += (long long)(c.r - c.rb) * ns * c.w;
-                  rowsum += c.r - c.rb;
-               }
-               lp[s.level] += R[0]; ++lf[s.level]; lmax[s.level] = std::max<long long>(lmax[s.level], R[0]); lwork[s.level] += wk;
-               pairs += R[0]; ++fronts; work += wk;
-            }
-            fprintf(stderr, "[pips_hip] gather-form border rows: %lld fronts, %lld pairs (%.1f border rows each), %lld multiply-adds, %zu tail runs\n", fronts, pairs,
-                    pairs ? (double)rowsum / pairs : 0.0, work, bs.kb_tail.size() / 2);
-            for (size_t l = 0; l < lp.size(); ++l)
-               fprintf(stderr, "   level %2zu: %6lld fronts %7lld pairs, most %4lld, %9lld multiply-adds\n", l, lf[l], lp[l], lmax[l], lwork[l]);
-         }
-      }
-   }
-   if (perm) std::copy(sym[0].perm.begin(), sym[0].perm.end(), perm);
-   if (colcount) std::copy(sym[0].colcount.begin(), sym[0].colcount.end(), colcount);
-   return PIPS_OK;
-}
-
-// the order the sparse root takes for a chain-like Schur complement (hub_dissected_order: hubs last, the rest dissected) and the
-// symbolic analysis under it; PIPS_ERR_STATE when the graph without the hubs has no separators
-int pips_symbolic_probe_hubs(int n, int n_primal, const int* krow, const int* jcol, int n_hubs, const int* hubs, int min_size, int64_t* what,
-                             int n_what, int* perm, int* colcount) {
-   if (n <= 0 || !krow || !jcol || n_hubs < 0 || (n_hubs > 0 && !hubs)) PIPS_FAIL(PIPS_ERR_ARG, "pips_symbolic_probe_hubs: bad arguments");
-   std::vector<int> ap(n + 1, 0), ai;
-   for (int r = 0; r < n; ++r)
-      for (int p = krow[r]; p < krow[r + 1]; ++p) {
-         if (jcol[p] < 0 || jcol[p] > r) PIPS_FAIL(PIPS_ERR_ARG, "pips_symbolic_probe_hubs: K must be lower-triangular CSR");
-         if (jcol[p] != r) { ++ap[r + 1]; ++ap[jcol[p] + 1]; }
-      }
-   for (int i = 0; i < n; ++i) ap[i + 1] += ap[i];
-   ai.resize(ap[n]);
-   {
-      std::vector<int> fill(ap.begin(), ap.end() - 1);
-      for (int r = 0; r < n; ++r)
-         for (int p = krow[r]; p < krow[r + 1]; ++p)
-            if (jcol[p] != r) { ai[fill[r]++] = jcol[p]; ai[fill[jcol[p]]++] = r; }
-   }
-   std::vector<int> hv(hubs, hubs + n_hubs), pv, cc;
-   if (!hub_dissected_order(n, ap, ai, hv, min_size, pv, cc)) PIPS_FAIL(PIPS_ERR_STATE, "pips_symbolic_probe_hubs: no separators");
-   AnalyzeOptions opt;
-   AnalyzeKnobs knobs;
-   read_layout_knobs(nullptr, opt, knobs);
-   opt.mf_konly = false;   // (the sparse root's order: plain fronts)
-   opt.user_perm = pv.data();
-   opt.user_colcount = cc.data();
-   {  // (the cut pips_hip_kkt_create_sparse takes)
-      int cut = 0;
-      while (cut < n - n_hubs && cc[cut] <= ROOT_ND_MAX_COLCOUNT) ++cut;
-      opt.force_n_head = cut;
-   }
-   CsrPattern K{n, n, krow, jcol};
-   CsrPattern B{0, n, nullptr, nullptr};
-   std::vector<BlockSym> sym(1);
-   int rc = analyze_block(K, B, n_primal, opt, sym[0]);
-   if (rc) return rc;
-   if (what) sym_info(sym, what, n_what);
-   if (perm) std::copy(sym[0].perm.begin(), sym[0].perm.end(), perm);
-   if (colcount) std::copy(sym[0].colcount.begin(), sym[0].colcount.end(), colcount);
-   return PIPS_OK;
-}
-
-// ---- layout probe (CPU only): symbolic analysis and host layout of a batch as Engine::analyze forms them, and the layout's invariants
-static int probe_inputs(const char* who, int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
-                        const int* const* bt_rowptr, const int* const* bt_colidx, std::vector<BlockInput>& in) {
-   if (nblk <= 0 || !n || !krow || !kcol || S < 0) PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments", who);
-   in.assign(nblk, BlockInput());
-   for (int b = 0; b < nblk; ++b) {
-      if (n[b] <= 0 || !krow[b] || !kcol[b]) PIPS_FAIL(PIPS_ERR_ARG, "%s: block %d is empty", who, b);
-      in[b].n = n[b];
-      in[b].n_primal = n_primal ? n_primal[b] : -1;
-      in[b].krow.assign(krow[b], krow[b] + n[b] + 1);
-      in[b].kcol.assign(kcol[b], kcol[b] + krow[b][n[b]]);
-      if (S > 0 && bt_rowptr && bt_colidx && bt_rowptr[b] && bt_colidx[b]) {
-         in[b].btrow.assign(bt_rowptr[b], bt_rowptr[b] + S + 1);
-         in[b].btcol.assign(bt_colidx[b], bt_colidx[b] + bt_rowptr[b][S]);
-         in[b].btval.assign(in[b].btcol.size(), 0.0);
-      }
-   }
-   return PIPS_OK;
-}
-
-int pips_layout_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
-                      const int* const* bt_rowptr, const int* const* bt_colidx, int deterministic, long long free_device_bytes,
-                      int64_t* what, int n_what) {
-   std::vector<BlockInput> in;
-   PIPS_TRY(probe_inputs("pips_layout_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
-   AnalyzeOptions opt;
-   AnalyzeKnobs knobs;
-   read_layout_knobs(nullptr, opt, knobs);
-   if (deterministic) { knobs.deterministic = true; opt.mf_konly = false; }
-   knobs.free_device_bytes = free_device_bytes;
-   std::vector<BlockSym> sym;
-   BatchLayout lay;
-   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-   int rc = analyze_symbolic(in, S, n_threads, opt, knobs, sym);
-   if (!rc) rc = build_batch_layout(in, sym, S, knobs, lay);
-   if (!rc) rc = check_batch_layout(in, sym, S, knobs, lay);
-   if (rc) return rc;
-   int64_t v[21] = {lay.arena_total, lay.xw_total, lay.uarena_total, lay.nsn_total, (int64_t)lay.levels.size(), (int64_t)lay.levels_top.size(),
-                    (int64_t)lay.mf_launches.size(), 0, lay.n_bb, lay.bb_stage, lay.tail_single, lay.border_backward_ok, lay.aug_sweeps_ok,
-                    lay.slots_total, lay.vslots_total, lay.n_total, lay.mf, lay.schur_mode_eff, lay.bb_doubles, lay.mfU_total, lay.spine_total};
-   for (const MfLaunch& m : lay.mf_launches) if (m.cls >= 6) v[7] += m.cnt;
-   for (int i = 0; what && i < n_what && i < 21; ++i) what[i] = v[i];
-   return PIPS_OK;
-}
-
-// ---- tail plan probe (CPU only): the task plans of a leaf batch's launch-per-step tail factorisation as Engine::analyze forms them - the
-// column plan (TailPlan) and its regrouping by groups of tile columns (PanelPlan) - as rows of integers (include/pips_hip.h)
-int pips_tail_plan_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
-                         const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head, int* col_tasks, long long col_cap,
-                         int* grp_tasks, long long grp_cap, int64_t* counts) {
-   std::vector<BlockInput> in;
-   PIPS_TRY(probe_inputs("pips_tail_plan_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
-   if (!counts || col_cap < 0 || grp_cap < 0 || (col_cap > 0 && !col_tasks) || (grp_cap > 0 && !grp_tasks))
-      PIPS_FAIL(PIPS_ERR_ARG, "pips_tail_plan_probe: bad arguments");
-   AnalyzeOptions opt;
-   AnalyzeKnobs knobs;
-   read_layout_knobs(nullptr, opt, knobs);
-   opt.force_n_head = force_n_head;
-   knobs.free_device_bytes = 0;
-   std::vector<BlockSym> sym;
-   BatchLayout lay;
-   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-   PIPS_TRY(analyze_symbolic(in, S, n_threads, opt, knobs, sym));
-   PIPS_TRY(build_batch_layout(in, sym, S, knobs, lay));
-   TailPlan plan;
-   plan.lists(lay.h_blks, 0, false, true, &lay.tile_first, true, 4);
-   PanelPlan pp;
-   pp.lists(plan, 4);
-   long long nc = 0, ng = 0, launches_col = 0, launches_grp = 0;
-   auto col = [&](const TaskList& l, int kind) {
-      launches_col += l.cnt > 0;
-      for (long long q = l.off; q < l.off + l.cnt; ++q, ++nc) {
-         const TileTask& t = plan.h_tasks[q];
-         if (nc < col_cap) { int* r = col_tasks + 6 * nc; r[0] = kind; r[1] = t.blk; r[2] = t.ti; r[3] = t.tj; r[4] = t.pad & 0xffff; r[5] = t.pad >> 16; }
-      }
-   };
-   auto grp = [&](long long off, int cnt, int list, int group, int index) {
-      for (int q = 0; q < cnt; ++q, ++ng) {
-         const TileTask& t = pp.h_tasks[off + q];
-         if (ng < grp_cap) {
-            int* r = grp_tasks + 9 * ng;
-            r[0] = list; r[1] = group; r[2] = index; r[3] = q; r[4] = t.blk; r[5] = t.ti; r[6] = t.tj; r[7] = t.pad & 0xffff; r[8] = t.pad >> 16;
-         }
-      }
-   };
-   auto grp_list = [&](const TaskList& l, int list, int group, int index) { launches_grp += l.cnt > 0; grp(l.off, l.cnt, list, group, index); };
-   for (int j = 0; j < plan.ntc_max; ++j) {
-      col(plan.upd_diag[j], 0);
-      col(plan.upd[j], 0);
-      launches_col += plan.diag[j].cnt > 0;
-      col(plan.trsm[j], 1);
-   }
-   for (int i = 0; i < pp.n_groups; ++i) {
-      grp_list(pp.deep[i], 0, i, 0);
-      grp_list(pp.pre[i], 1, i, 0);
-      grp_list(pp.block_deep[i], 2, i, 0);
-      for (int j = i * pp.P; j < std::min((i + 1) * pp.P, plan.ntc_max); ++j) {
-         grp_list(pp.upd_in[j], 3, i, j);
-         launches_grp += plan.diag[j].cnt > 0;
-         grp_list(pp.trsm_in[j], 4, i, j);
-      }
-      launches_grp += pp.strips[i].cnt > 0;
-      for (int q = 0; q < pp.strips[i].cnt; ++q) {
-         const TileStrip& st = pp.h_strips[pp.strips[i].off + q];
-         grp(st.off, st.cnt, 5, i, q);
-      }
-   }
-   counts[0] = nc; counts[1] = ng; counts[2] = plan.ntc_max; counts[3] = pp.n_groups; counts[4] = launches_col; counts[5] = launches_grp;
-   return PIPS_OK;
-}
-
-// ---- first-touch plan probe (CPU only): the layout of a batch twice - with the first touch of the tails refused (PIPS_HIP_TAIL_FIRST_TOUCH=0
-// does the same) and as the analysis decides it - as sections of integers (include/pips_hip.h)
-int pips_first_touch_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
-                           const int* const* bt_rowptr, const int* const* bt_colidx, int force_n_head, int deterministic, long long lds_bytes,
-                           long long free_device_bytes, long long* out, long long cap, int64_t* counts) {
-   std::vector<BlockInput> in;
-   PIPS_TRY(probe_inputs("pips_first_touch_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
-   if (!counts || cap < 0 || (cap > 0 && !out)) PIPS_FAIL(PIPS_ERR_ARG, "pips_first_touch_probe: bad arguments");
-   AnalyzeOptions opt;
-   AnalyzeKnobs knobs;
-   read_layout_knobs(nullptr, opt, knobs);
-   if (deterministic) { knobs.deterministic = true; opt.mf_konly = false; }   // (as pips_layout_probe)
-   opt.force_n_head = force_n_head;
-   knobs.free_device_bytes = free_device_bytes;
-   if (lds_bytes > 0) knobs.ft_lds_bytes = lds_bytes;
-   std::vector<BlockSym> sym;
-   BatchLayout old, lay;
-   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-   PIPS_TRY(analyze_symbolic(in, S, n_threads, opt, knobs, sym));
-   PIPS_TRY(build_batch_layout(in, sym, S, knobs, lay));
-   PIPS_TRY(check_batch_layout(in, sym, S, knobs, lay));
-   knobs.tail_first_touch = 0;
-   PIPS_TRY(build_batch_layout(in, sym, S, knobs, old));
-   long long at = 0;
-   int section = 0;
-   auto put = [&](long long v) { if (at < cap) out[at] = v; ++at; };
-   long long from = 0;
-   auto end = [&]() { counts[8 + section++] = at - from; from = at; };
-   for (int b = 0; b < nblk; ++b) {
-      const BlkDesc& d = lay.h_blks[b];
-      put(d.n); put(d.n_head); put(d.m); put(d.m_pad); put(d.nb); put(d.ldT); put(d.mf_split); put(d.T_in); put(lay.kptr[b]);
-      put((long long)in[b].btcol.size()); put(lay.mf ? lay.h_root_off[b + 1] - lay.h_root_off[b] : 0); put(d.ntc);
-   }
-   end();
-   for (long long v : lay.h_ft_colbase) put(v);
-   end();
-   for (int v : lay.h_ft_init_off) put(v);
-   end();
-   for (const FtInit& e : lay.h_ft_init) { put(e.row); put(e.src); }
-   end();
-   for (int v : lay.h_ft_piece_off) put(v);
-   end();
-   for (const FtPiece& e : lay.h_ft_piece) { put(e.front); put(e.u); put(e.rows); put(e.cnt); }
-   end();
-   for (int v : lay.h_ft_leaves) put(v);
-   end();
-   for (long long v : old.h_kdst) put(v);
-   end();
-   for (long long v : lay.h_kdst) put(v);
-   end();
-   for (long long v : old.h_bdst) put(v);
-   end();
-   for (long long v : lay.h_bdst) put(v);
-   end();
-   for (int b = 0; b < nblk && lay.mf; ++b)   // the root fronts k_root_assemble walks, in its order
-      for (int q = lay.h_root_off[b]; q < lay.h_root_off[b + 1]; ++q) {
-         const SnDesc& sn = lay.h_sns[lay.h_roots[q]];
-         put(b); put(lay.h_roots[q]); put(sn.r); put(sn.rb); put(sn.U); put(sn.rows);
-      }
-   end();
-   for (int v : lay.h_rowidx) put(v);
-   end();
-   if (!lay.levels.empty()) {   // the simple leaves
-      const LevelRange& L0 = lay.levels[0];
-      for (int i = L0.simple_begin; i < L0.simple_begin + L0.simple_cnt; ++i) {
-         const SnDesc& sn = lay.h_sns[i];
-         put(i); put(sn.blk); put(sn.r); put(sn.n_useg); put(sn.rows);
-      }
-   }
-   end();
-   const int64_t head[8] = {lay.tail_first_touch, lay.mf, lay.tail_single, lay.schur_mode_eff, lay.mfU_total, lay.nnzK_total, lay.nnzB_total, at};
-   std::copy(head, head + 8, counts);
-   return PIPS_OK;
-}
-
-// ---- plan probe of deterministic mode (CPU only): the layout of a deterministic analysis, then the planners of detplan.h that need no
-// recording, as Engine::upload_layout / set_det_groups / set_sc_panels call them - sections of integers (include/pips_hip.h)
-int pips_det_plan_probe(int nblk, const int* n, const int* n_primal, const int* const* krow, const int* const* kcol, int S,
-                        const int* const* bt_rowptr, const int* const* bt_colidx, int rank, int n_ranks, int n_panels, long long* out,
-                        long long cap, int64_t* counts) {
-   std::vector<BlockInput> in;
-   PIPS_TRY(probe_inputs("pips_det_plan_probe", nblk, n, n_primal, krow, kcol, S, bt_rowptr, bt_colidx, in));
-   if (!counts || cap < 0 || (cap > 0 && !out) || n_ranks < 1 || rank < 0 || rank >= n_ranks) PIPS_FAIL(PIPS_ERR_ARG, "pips_det_plan_probe: bad arguments");
-   AnalyzeOptions opt;
-   AnalyzeKnobs knobs;
-   read_layout_knobs(nullptr, opt, knobs);
-   knobs.deterministic = true; opt.mf_konly = false;   // (as pips_layout_probe with deterministic set)
-   knobs.free_device_bytes = 0;
-   std::vector<BlockSym> sym;
-   BatchLayout lay;
-   const int n_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-   PIPS_TRY(analyze_symbolic(in, S, n_threads, opt, knobs, sym));
-   PIPS_TRY(build_batch_layout(in, sym, S, knobs, lay));
-   const BorderGathers bg = lay.bt_rows_total > 0 ? border_product_gathers(lay) : BorderGathers();
-   const DetGroupPlan p = build_det_group_plan(lay, sym, S, rank, n_ranks, (long long)S * S, ScKept(), PackedTables());
-   const ScPanelPlan sp = sc_panel_plan(lay, sym, S, n_panels);
-   long long at = 0;
-   int section = 0;
-   auto put = [&](long long v) { if (at < cap) out[at] = v; ++at; };
-   auto end = [&](long long& from) { counts[16 + section++] = at - from; from = at; };
-   auto gather = [&](const HostGather& g) {
-      put((long long)g.tgt.size());
-      for (long long v : g.tgt) put(v);
-      for (long long v : g.off) put(v);
-      for (long long v : g.slots) put(v);
-   };
-   long long from = 0, aug_rows = 0;
-   for (const SnDesc& sn : lay.h_sns) aug_rows += sn.r - sn.rb;
-   for (int b = 0; b < nblk; ++b) put(p.grp[b]);
-   end(from);
-   for (int b = 0; b < nblk; ++b) {
-      const BlkDesc& d = lay.h_blks[b];
-      put(d.ntc); put(d.nb); put(d.nb_pad); put(lay.mf ? lay.h_root_off[b + 1] - lay.h_root_off[b] : 0);
-      put(lay.n_bb > 0 ? lay.h_bb_off[b + 1] - lay.h_bb_off[b] : 0); put((long long)sym[b].bmap.size());
-   }
-   end(from);
-   for (size_t k = 0; k < p.rounds.size(); ++k)
-      for (long long q = p.rounds[k].off; q < p.rounds[k].off + p.rounds[k].cnt; ++q) { put((long long)k); put(p.tasks[q].blk); put(p.tasks[q].ti); put(p.tasks[q].tj); }
-   end(from);
-   for (size_t k = 0; k + 1 < p.round_off.size(); ++k)
-      for (int q = p.round_off[k]; q < p.round_off[k + 1]; ++q) { put((long long)k); put(p.round_blk[q]); }
-   end(from);
-   for (size_t k = 0; k + 1 < p.bb_round_off.size(); ++k)
-      for (int q = p.bb_round_off[k]; q < p.bb_round_off[k + 1]; ++q) { put((long long)k); put(p.bb_round_blk[q]); }
-   end(from);
-   gather(p.btm_grp); end(from);
-   gather(bg.btm); end(from);
-   gather(bg.bm); end(from);
-   gather(p.aug.bslot_grp); end(from);
-   for (const BgEntry& e : p.aug.ent) { put(e.off); put(e.y); put(e.stride); put(e.w); }
-   end(from);
-   for (long long v : p.aug.ptr) put(v);
-   end(from);
-   for (int v : p.aug.idx) put(v);
-   end(from);
-   for (long long v : p.aug.slot) put(v);
-   end(from);
-   for (int v : sp.row_begin) put(v);
-   end(from);
-   for (size_t g = 0; g < sp.groups.size(); ++g)
-      for (long long q = sp.groups[g].off; q < sp.groups[g].off + sp.groups[g].cnt; ++q) { put((long long)g); put(sp.tasks[q].blk); put(sp.tasks[q].ti); put(sp.tasks[q].tj); }
-   end(from);
-   for (int b = 0; b < nblk; ++b)
-      for (int v : sym[b].bmap) put(v);
-   end(from);
-   const int64_t head[16] = {p.n_groups, p.first_slot, p.slots, p.global, p.aug.ready, p.aug_sweeps_ok, lay.aug_sweeps_ok, lay.mf, lay.n_bb, lay.n_roots,
-                             lay.schur_mode_eff, (int64_t)sp.groups.size(), p.aug.n_targets, p.aug.n_ent, aug_rows, at};
-   std::copy(head, head + 16, counts);
-   return PIPS_OK;
-}
 
 }  // extern "C"

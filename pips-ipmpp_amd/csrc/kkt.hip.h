@@ -5,12 +5,6 @@
 // methods of KktSystem.
 #pragma once
 
-// Largest column count the dissected sparse root admits in its head: a front of colcount + 1 rows must fit the LDS as a packed triangle
-// (19 200 doubles: 195 rows).  Measured (tools/sparse_root_probe.py, 64 blocks): 31 linking rows per pair (fronts <= 188 rows) factorize
-// 4.3 ms as a band, 2.6 ms dissected; 100 rows per pair (fronts of 308 rows: update matrices in device memory) 10.1 ms as a band, 11.1 ms
-// dissected and solveCompressed 2.1 -> 4.3 ms - those stay a band.
-constexpr int ROOT_ND_MAX_COLCOUNT = 192;
-
 // SC[0:n0,0:n0] -= C0^T diag(zdiag)^-1 C0 (lower triangle; zdiag < 0): schur_complement_add_CTDC_block
 // (sLinsysRootAug.C:1276-1338, SparseStorage::matTransDinvMultMat SparseStorage.C:1257).  One thread per row of C0.
 // sc_rowptr != nullptr: SC is the value array of the sparse root's CSR pattern, whose x0 block is dense: (i, j), j <= i < n0,

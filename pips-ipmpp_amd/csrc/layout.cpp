@@ -9,6 +9,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "knobs.h"
+
 namespace pips {
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1033,6 +1035,60 @@ void BatchLayout::drop_uploaded() {
         h_schur_slot, h_leafdesc, h_lf_rows, h_lf_ptr, h_lf_src, h_lf_pos, h_lb_list, tile_first, h_roots, h_bb_batches, h_bb_meta, h_bb_pos,
         h_kb_rec, h_kb_list, h_kb_tail, h_kb_off, h_spine, h_spine_off, h_ft_colbase, h_ft_init_off, h_ft_piece_off, h_ft_init, h_ft_piece,
         h_ft_leaves);
+}
+
+void read_layout_knobs(const EngineSettings* e, AnalyzeOptions& opt, AnalyzeKnobs& knobs) {
+   // Tile geometry + the cost-model / amalgamation knobs (environment overrides are for tuning runs only).
+   opt.tile = TILE;
+   // Supernode width cap.  16 instead of the kernels' limit of 32: on the time-coupled family (tools/config3_probe.py, 64 x 50 000)
+   // narrower supernodes carry fewer explicit zeros (nnz(L) 164 M -> 151 M), halve the dependent pivot chain of a front and the
+   // registers its rows take; factorisation 13.4 -> 12.5 ms, solveCompressed 9.3 -> 8.9 ms.  Random sparsity (config 2) has no
+   // supernodes wider than one column in the head.
+   opt.max_sn_width = 16;
+   if (knob_set<K_SN_WIDTH>()) opt.max_sn_width = std::max(1, std::min(HEAD_WMAX, (int)knob_int<K_SN_WIDTH>()));
+   else if (e && e->sn_width > 0) opt.max_sn_width = std::min(HEAD_WMAX, e->sn_width);
+   // (a switch that is not set leaves what opt holds: the values of AnalyzeOptions, or what an earlier analysis of this engine left)
+   if (knob_set<K_RELAX_ZEROS>()) opt.relax_zeros = knob_real<K_RELAX_ZEROS>();
+   if (knob_set<K_ND_DEPTH>()) opt.nd_depth = (int)knob_int<K_ND_DEPTH>();
+   if (knob_set<K_ND_MIN>()) opt.nd_min_size = (int)knob_int<K_ND_MIN>();
+   if (knob_set<K_MF_LDS>()) opt.mf_lds_doubles = knob_int<K_MF_LDS>();
+   if (knob_set<K_MF_SPLIT>()) { const int sp = (int)knob_int<K_MF_SPLIT>(); opt.mf_split_nb_max = sp == 0 ? 0 : std::min(176, std::max(sp, 2)); }
+   knobs.deterministic = e && e->deterministic;
+   knobs.schur_mode = e ? e->schur_mode : 0;
+   // (tests: forces a Schur mode where no setter reaches - the leaf handles and the batch they are bound into - and the caller left it to the model)
+   if (e && knobs.schur_mode == 0) knobs.schur_mode = std::max(0, std::min(2, (int)knob_int<K_SCHUR_MODE>()));
+   knobs.mf_lds_doubles = opt.mf_lds_doubles;
+   knobs.mf_wanted = knob_int<K_MF>() != 0;
+   if (!knobs.mf_wanted) opt.mf_split_nb_max = 0;   // the border split (compact front panels) only exists with the multifrontal head
+   // fronts on the rows of K only where the border split applies (value 1; off by default: on the configs[3] share the fronts fall
+   // from 9.7 to 4.0 ms, forming the border rows afterwards costs 8.0 - DESIGN.md 4.1c): not in deterministic mode (the border rows of the dense
+   // tail take their head contributions with atomics, k_border_tail) and with supernodes of at most 16 columns (k_border_rows<., 16>)
+   opt.mf_konly = opt.mf_split_nb_max > 0 && !knobs.deterministic && opt.max_sn_width <= 16 && knob_int<K_MF_KONLY>() != 0;
+   knobs.spine = knob_tri<K_SPINE>();
+   knobs.tail_single = knob_tri<K_TAIL_SINGLE>();
+   knobs.tail_first_touch = knob_tri<K_TAIL_FIRST_TOUCH>();
+   static_assert(KNOBS[K_FIRST_TOUCH_LDS].dflt == FT_LDS_BUDGET, "the table's default is the layout's budget");
+   knobs.ft_lds_bytes = std::min(FT_LDS_MAX, std::max(0LL, knob_int<K_FIRST_TOUCH_LDS>()));   // (never more than a workgroup can have)
+   knobs.border_backward = knob_tri<K_BORDER_BACKWARD>();
+   knobs.aug_sweeps = knob_tri<K_AUG_SWEEPS>();
+   knobs.sweep_launches = knob_set<K_SWEEP_LAUNCHES>();   // (SweepRt::build: the single-launch sweeps are off)
+   const long long poll = knob_int<K_ROOT_POLL_LIMIT>();
+   knobs.tail_poll_limit = poll > 0 ? poll * 50 : 0;   // (a deep update runs a millisecond)
+   knobs.tail_diag_blocked = knob_int<K_ROOT_DIAG_BARRIERS>() ? 0 : 1;
+}
+
+void sym_info(const std::vector<BlockSym>& sym, int64_t* what, int n_what) {
+   int64_t v[13] = {0};
+   for (const BlockSym& s : sym) {
+      v[10] += (int64_t)s.upd.size() * 4;
+      v[11] += s.nb;
+      v[12] += (int64_t)s.a_dst.size();
+      v[0] += s.nnzL; v[1] += s.n; v[2] += s.n_head; v[3] += s.m; v[4] += (int64_t)s.sn.size();
+      v[5] = std::max<int64_t>(v[5], s.n_levels);
+      v[6] += (int64_t)s.flops_factor; v[7] += (int64_t)s.flops_border; v[8] += s.arena * 8;
+      v[9] = std::max<int64_t>(v[9], s.m_pad / TILE);
+   }
+   for (int i = 0; i < n_what && i < 13; ++i) what[i] = v[i];
 }
 
 }  // namespace pips

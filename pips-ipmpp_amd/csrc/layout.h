@@ -1,6 +1,6 @@
 // Host pass of a batch analysis: from the blocks' symbolic analyses (symbolic.cpp) to everything the engine uploads or keeps -
-// offsets, supernode order, launch lists, index arrays.  Plain C++: no device call, no environment read (the switches come in as
-// LayoutKnobs), so the pass runs and is tested without a GPU (pips_layout_probe, tests/test_layout_cpu.py).
+// offsets, supernode order, launch lists, index arrays.  Plain C++: no device call, and the pass itself reads no environment (the switches
+// come in as LayoutKnobs; read_layout_knobs fills them), so it runs and is tested without a GPU (pips_layout_probe, tests/test_layout_cpu.py).
 // Pipeline (DESIGN.md "analysis pipeline"): analyze_symbolic -> build_batch_layout -> Engine::analyze uploads -> task plans.
 #pragma once
 #include <cstdint>
@@ -62,7 +62,7 @@ inline bool bb_fits(const BbPlanSize& z) { return bb_lds_bytes(z) <= 160 * 1024 
 constexpr long long FT_LDS_BUDGET = 80 * 1024;
 constexpr long long FT_LDS_MAX = 160 * 1024;   // what a workgroup can have at all: a larger budget (LayoutKnobs::ft_lds_bytes) counts as this
 
-// Every switch the layout depends on, as values (Engine: read_layout_knobs).  A switch with "-1: not set" takes the layout's own rule.
+// Every switch the layout depends on, as values (read_layout_knobs).  A switch with "-1: not set" takes the layout's own rule.
 struct LayoutKnobs {
    bool deterministic = false;
    int schur_mode = 0;          // requested: 0 auto, 1 augmented partial factorisation, 2 blocked solves
@@ -79,6 +79,19 @@ struct LayoutKnobs {
    bool mf = false;             // multifrontal head taken
    int schur_mode_eff = 1;
 };
+
+// What one analyze() call reads from the environment: the layout's switches, and the two of the single-launch tail factorisation
+struct AnalyzeKnobs : LayoutKnobs {
+   long long tail_poll_limit = 0;
+   int tail_diag_blocked = 1;
+};
+// the settings of an engine that an analysis reads beside the environment
+struct EngineSettings { int sn_width; bool deterministic; int schur_mode; };
+// Every switch an analysis depends on, read in one place at every analyze() call through the accessors of knobs.h (DESIGN.md section 10;
+// tests set them before analysing).  e == nullptr: the CPU probes - no engine settings, no deterministic mode.
+void read_layout_knobs(const EngineSettings* e, AnalyzeOptions& opt, AnalyzeKnobs& knobs);
+// sums and maxima over the blocks' symbolic analyses: the first 13 entries of pips_hip_batch_info (include/pips_hip.h)
+void sym_info(const std::vector<BlockSym>& sym, int64_t* what, int n_what);
 
 // Every block's non-empty border columns from the border's row pointers alone - the column sets the sparse root's pattern, its position
 // tables and the packed blocked solves (Schur mode 2 with the sparse root: right-hand side q carries, in every block, that block's q-th

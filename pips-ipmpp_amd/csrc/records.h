@@ -52,6 +52,9 @@ struct BlkDesc {
 
 struct TileTask { int blk, ti, tj, pad; };
 struct TileStrip { int off, cnt; };   // k_tile_panel: the tasks [off, off + cnt) of one tile row, in the order they run
+struct TaskList { long long off = 0; int cnt = 0; };   // a launch's tasks: a range of a task array
+// kind of a task of the single-launch factorisations (rootkernel.hip.h, tailkernel.hip.h)
+constexpr int ROOT_UPD = 0, ROOT_TRSM = 1, ROOT_DIAG = 2;
 
 constexpr int HEAD_WMAX = 32;   // widest head supernode (solve kernels)
 constexpr int SIMPLE_RMAX = 16;

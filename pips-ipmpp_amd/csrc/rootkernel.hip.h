@@ -35,8 +35,7 @@ struct RootArgs {
    long long poll_limit;
    int diag_blocked;        // 1: root_diag_blocked, 0: the 128-barrier algorithm (A/B)
    long long* trace;        // diagnostics (PIPS_HIP_ROOT_TRACE): per ticket the 100 MHz clock at the draw, after the waits, at the end
-};
-constexpr int ROOT_UPD = 0, ROOT_TRSM = 1, ROOT_DIAG = 2;
+};   // (the kinds: ROOT_UPD / ROOT_TRSM / ROOT_DIAG, records.h)
 
 __device__ __forceinline__ void glds16_sc1(const double* gptr_lane, double* lds_base) {   // LDS-DMA past the L2 (agent scope)
    const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_base;

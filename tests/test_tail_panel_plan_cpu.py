@@ -1,4 +1,4 @@
-"""The regrouping of the leaf tails' column plan by groups of four tile columns (csrc/engine.hip PanelPlan), on the host:
+"""The regrouping of the leaf tails' column plan by groups of four tile columns (csrc/tileplan.cpp GroupPlan), on the host:
 pips_tail_plan_probe lists the tasks of the column launches and the lists of the groups - deep update, the side chain of the diagonal
 block, the strips of the panel launch - for the shapes of tests/tail_panel_cases.py.  Together the group lists hold every update and trsm
 task of the column plan exactly once, with the same block, tile and K range; a tile meets its tasks in the column plan's order; a strip
