@@ -458,7 +458,7 @@ int pips_hip_vec_dot_shifted(long long n, long long skip_root, const double* x_d
 /* ---------------------------------------------------------------------------------------------------------------
  * 4c. Host harness: Mehrotra predictor-corrector IPM with Gondzio correctors for the reference's full problem class
  *        min c^T x [+ 1/2 x^T Q x]   s.t.  A x = b,  clow <= C x <= cupp,  xlow <= x <= xupp      (every bound optional per row / entry)
- *     with block-angular A and C (and a block-diagonal convex Hessian through pips_ipm_create_qp), driving the fused KKT path (counterpart of PIPSIPMppSolver::solve / InteriorPointMethod /
+ *     with block-angular A and C (and a convex Hessian, block-diagonal through pips_ipm_create_qp or bordered through pips_ipm_create_qp_cross), driving the fused KKT path (counterpart of PIPSIPMppSolver::solve / InteriorPointMethod /
  *     LinearSystem::computeDiagonals, solve, solveXYZS, solveCompressedBiCGStab, system_mult / Residuals::evaluate /
  *     DistributedMatrix::mult).  One or several ranks.
  *     Input = the reader's per-block layout (GMSPIPSBlockData_t, Drivers/gams/gmspips/gmspipsio.h:5-58): block 0 is the root
@@ -590,7 +590,7 @@ int pips_ipm_outer_solve(void* handle, const double* G_host, const double* L_hos
  * result7[0] and trace column 2 hold c^T x + 1/2 x^T Q x; result7[5] and trace column 3 hold the Lagrangian dual
  * b^T y + clow^T lambda - cupp^T pi + xlow^T gamma - xupp^T phi - 1/2 x^T Q x, so that their difference is the reference's duality gap
  * (Residuals.cpp:69-165) - the reference's own dual_objective field omits the quadratic term.
- * Not offered: the cross Hessian between x0 and x_i, and Hessians through the pips_ipm_create shorthand. */
+ * The cross Hessian between x0 and x_i: pips_ipm_create_qp_cross below.  Not offered: Hessians through the pips_ipm_create shorthand. */
 int pips_ipm_create_qp(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl,
                        const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp,
                        double dual_reg, int device, void* comm, int rank, int n_ranks);
@@ -607,7 +607,29 @@ int pips_ipm_create_qp(void** handle, int n_blocks, const pips_ipm_block* blocks
 int pips_ipm_create_qp_scaled(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl,
                               const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp,
                               double dual_reg, int device, void* comm, int rank, int n_ranks, int scaler);
-/* out = Q in over x = [x0 | own blocks] (Problem::hessian_multiplication; parity tests).  Zeros on a handle without Hessian. */
+/* pips_ipm_create_qp_scaled with the reference's bordered (arrow-shaped) Hessian
+ *        [ Q0   R_1^T ... R_N^T ]
+ *   Q =  [ R_1  Q_1             ]      R_i : n_i x n0, the "left bordering blocks" of DistributedSymmetricMatrix
+ *        [ R_N              Q_N ]
+ * R[i] (i >= 1) is block i's cross Hessian with x0: GENERAL CSR, rows == n_i, cols == n0, rows in any order, duplicates added up; R[0]
+ * must be absent (rowptr NULL).  Several ranks: R[1..] belong to the rank's own blocks.  R == NULL, every R[i].rowptr == NULL or every
+ * R[i] without a stored entry is pips_ipm_create_qp_scaled, call for call.  PIPS_ERR_ARG with a message for R[i].rows != n_i or
+ * R[i].cols != n0, a column index out of range, R[0] present, and stored entries with n0 == 0.  Convexity of the WHOLE Q stays the
+ * caller's contract; a handle with R but without any Q[i] is a QP handle like any other.
+ * Where R enters: R_i is the first block of leaf i's border (the reference's BorderBiBlock {R, A, C, n_empty, F^T, G^T}), so the Schur
+ * complement, both root kinds and both Schur modes see it; the flat symmetric Hessian on the device holds (x_i row, x0 column) and its
+ * mirror from the one stored value, the x0 rows taking the long-row path once they pass 512 entries; rQ, the operator of the outer
+ * solve, pips_ipm_hessian_mult and the objectives carry the cross terms; the data norm takes max |R|; a scaler gives
+ * R'_i(r, c) = (v col[x_i row r]) col[x0 column c], the row's factor first; PIPS_SCALER_RUIZ sees R as part of Q.
+ * Several ranks: (Q x)_0 = Q0 x0 + sum_i R_i^T x_i is a sum over all ranks' blocks.  Rank 0 contributes Q0 x0 and its own blocks' terms,
+ * every other rank its own blocks' terms (its flat Q holds no Q0 block); the contributions ride in the replicated x0 rows of the J^T
+ * product and are summed with them - no further collective.  x^T Q x is the plain sum over the ranks of x . (Q x)_partial.  Whether any
+ * rank holds a cross Hessian is agreed at creation together with whether any holds a Hessian. */
+int pips_ipm_create_qp_cross(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, const pips_csr_view* R,
+                             int myl, int mzl, const double* bL, const double* dlow, const double* dupp, const double* idlow,
+                             const double* idupp, double dual_reg, int device, void* comm, int rank, int n_ranks, int scaler);
+/* out = Q in over x = [x0 | own blocks] (Problem::hessian_multiplication; parity tests), cross terms included; several ranks with a cross
+ * Hessian: the x0 part is the full sum on every rank (one collective).  Zeros on a handle without Hessian. */
 int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host);
 void pips_ipm_destroy(void* handle);
 
@@ -727,6 +749,15 @@ int pips_ipm_layout_probe(int n_blocks, const pips_ipm_block* blocks, const pips
                           const double* dlow, const double* dupp, const double* idlow, const double* idupp, int rank, int n_ranks,
                           int eliminate_z0, const double* col, const double* row, long long* dims, double* scalars, long long* sizes,
                           void* const* out);
+
+/* pips_ipm_layout_probe for an input with cross Hessians R (pips_ipm_create_qp_cross): the same dims, scalars and arrays.  R_i's entries
+ * stand in leaf i's border under the x0 Schur rows (slots 24-26) and in the flat Hessian (43-47); has_q is 1 with R alone; on a rank
+ * != 0 with a cross Hessian among its own blocks the flat Hessian holds no Q0 block (qdiag keeps Q0's diagonal); given factors scale R
+ * as pips_ipm_create_qp_cross does.  R == NULL: pips_ipm_layout_probe. */
+int pips_ipm_layout_probe_cross(int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, const pips_csr_view* R, int myl, int mzl,
+                                const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp, int rank,
+                                int n_ranks, int eliminate_z0, const double* col, const double* row, long long* dims, double* scalars,
+                                long long* sizes, void* const* out);
 
 /* The tables of the packed blocked solves (Schur mode 2 with the sparse root), without a device; the code the engine builds its own
  * with.  bt_rowptr[b]: the S + 1 row pointers of block b's border (NULL: no border).  nb[b] (nblk entries): the block's non-empty

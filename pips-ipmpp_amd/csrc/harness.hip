@@ -87,7 +87,7 @@ struct SpmvArgs {
    const double *e0, *e1, *e2, *e3;                  // epilogue operands, meaning per mode; e3: the Hessian product Q x of a QP handle
                                                      // (nullptr on an LP handle: a branch uniform over the launch)
    int split;                                        // SP_RAC: rows < split subtract e0[r], rows >= split subtract e1[r - split]
-   int lin, r0e, r1b, r1e;
+   int lin, r0e, r1b, r1e;                           // lin: 0 the special rank, 1 another one, 2 another one of a handle with a cross Hessian
    const int* pred;                                  // run only if *pred != 0 (nullptr: always)
 };
 
@@ -95,8 +95,11 @@ template <int MODE>
 __device__ __forceinline__ double spmv_epilogue(const SpmvArgs& a, int r, double s) {
    if (MODE == SP_QX) return s;                                                               // Q x (the matrix is Q; rows x0 replicated)
    const bool rep = a.lin && (r < a.r0e || (r >= a.r1b && r < a.r1e));
-   // QP handle: Q x joins the non-linear part of the x rows, which on replicated rows only rank 0 contributes
+   // QP handle: Q x joins the non-linear part of the x rows, which on replicated rows only rank 0 contributes - unless a cross Hessian
+   // couples x0 with the blocks (lin == 2, uniform over the launch): then e3 holds this rank's share of (Q x)_0, the terms R_i^T x_i of
+   // its own blocks, which joins the linear term and is summed over the ranks with it
    if (a.e3 && (MODE == SP_RQ || MODE == SP_KX || MODE == SP_RES_X)) {
+      if (a.lin == 2 && rep) return MODE == SP_KX ? a.e3[r] + s : MODE == SP_RQ ? a.e3[r] - s : -(a.e3[r] + s);
       if (MODE == SP_RQ) return rep ? -s : a.e0[r] + a.e3[r] - s - a.e1[r] + a.e2[r];         // rQ = c + Q x - J^T[y;z] - gamma + phi
       if (MODE == SP_KX) return rep ? s : a.e0[r] * a.e1[r] + a.e3[r] + s;                    // dd .* x + Q x + J^T[y;z]
       return rep ? -s : a.e2[r] - (a.e0[r] * a.e1[r] + a.e3[r] + s);                          // rhs_x - (K z)_x
@@ -786,11 +789,16 @@ struct Ipm {
    double* long_scratch = nullptr;   // LONG_PARTS partial sums per long row (k_spmv_long_part)
    // Hessian of a QP handle (pips_ipm_create_qp): the full symmetric CSR (both triangles) over the flat x order with its own long-row
    // list, its diagonal, and the product Q x the epilogues of the x rows read.  An LP handle holds none of this (has_q false).
-   bool has_q = false;
+   // cross: some rank's blocks have a cross Hessian R_i with x0 (pips_ipm_create_qp_cross), agreed over the ranks.  Several ranks: the
+   // x0 rows of qx then hold this rank's share of (Q x)_0 - Q0 x0 on rank 0 only (the others' flat Q has no Q0 block), R_i^T x_i of the
+   // own blocks - which the epilogues add on the replicated rows of every rank.
+   bool has_q = false, cross = false;
    int *Q_rp = nullptr, *Q_ci = nullptr, *Q_long = nullptr;
    double *Q_v = nullptr, *qdiag = nullptr, *qx = nullptr;
    int nQ_long = 0;
    long long Q_nnz = 0;
+   bool Q_omits_q0 = false;   // the device copy of Q was built without the Q0 block (IpmLayout::omit_q0)
+   size_t Q_owned = 0;        // first of its four buffers in `owned`
    long long J_nnz = 0, Jt_nnz = 0;
    // data
    double *c = nullptr, *bA = nullptr, *M = nullptr, *Bd = nullptr, *wG = nullptr, *wXYZ = nullptr, *wX = nullptr, *wY = nullptr;
@@ -898,7 +906,7 @@ struct Ipm {
       a.nrows = transposed ? nx : my + mz;
       a.rp = transposed ? Jt_rp : J_rp; a.ci = transposed ? Jt_ci : J_ci; a.v = transposed ? Jt_v : J_v;
       a.in = in; a.out = out; a.e0 = e0; a.e1 = e1; a.e2 = e2; a.e3 = e3; a.split = my;
-      a.lin = rank != 0;
+      a.lin = rank != 0 ? (cross ? 2 : 1) : 0;
       if (transposed) { a.r0e = n0; a.r1b = a.r1e = 0; }
       else { a.r0e = ry; a.r1b = my; a.r1e = my + rzr; }
       a.pred = pred;
@@ -925,7 +933,8 @@ struct Ipm {
    }
 
    // out = Q in (Problem::hessian_multiplication).  Several ranks: Q0 is replicated and every rank computes the same x0 rows - no
-   // reduction, so a predicate needs no staging either.  Sums in the fixed order of the block-angular products: no atomics.
+   // reduction, so a predicate needs no staging either.  With a cross Hessian the x0 rows are this rank's share of the sum (see `cross`),
+   // still without a reduction here.  Sums in the fixed order of the block-angular products: no atomics.
    int hess(const double* in, double* out, const int* pred = nullptr) {
       SpmvArgs a;
       a.nrows = nx;
@@ -968,7 +977,9 @@ struct Ipm {
          pk.n_terms = 9;
       }
       const int kq = pk.n_terms;
-      if (has_q) pk.t[pk.n_terms++] = term(R_DOT, nx, it.x, qx, nullptr, nullptr, wX);   // x^T Q x, root entries counted once
+      // x^T Q x, root entries counted once; with a cross Hessian the x0 rows of qx are per-rank shares of (Q x)_0, so every rank counts
+      // its own: the ranks' sums total x0^T Q0 x0 + 2 sum x_i^T R_i x0 + sum x_i^T Q_i x_i (one rank: the weights are 1 either way)
+      if (has_q) pk.t[pk.n_terms++] = term(R_DOT, nx, it.x, qx, nullptr, nullptr, cross && n_ranks > 1 ? nullptr : wX);
       double o[10];
       TRY(reduce(pk, o));
       if (scaled) o[3] = std::max(o[3], o[8]);
@@ -1400,8 +1411,12 @@ struct Ipm {
    }
 
    // the flat symmetric Q and its long-row list to the device (before upload_J, which sizes long_scratch by nQ_long too)
+   // (again, where the ranks' agreement took the Q0 block out of the pattern prescale() uploaded: the first copy is freed)
    int upload_Q(const IpmLayout& L) {
-      Q_nnz = L.Q_nnz; nQ_long = L.nQ_long;
+      if (Q_rp)
+         for (size_t k = 0; k < 4; ++k) owned[Q_owned + k].reset();
+      Q_nnz = L.Q_nnz; nQ_long = L.nQ_long; Q_omits_q0 = L.omit_q0;
+      Q_owned = owned.size();
       TRY(up(&Q_rp, L.Q_rp)); TRY(up(&Q_ci, L.Q_ci)); TRY(up(&Q_v, L.Q_v)); TRY(up(&Q_long, L.Q_long));
       return PIPS_OK;
    }
@@ -1425,6 +1440,7 @@ struct Ipm {
    double *sc_tcol = nullptr, *sc_trow = nullptr, *sc_mn = nullptr, *sc_mx = nullptr, *sc_part = nullptr, *sc_slots = nullptr, *sc_rat = nullptr;
    std::vector<double> h_col, h_row;                // host copies of the factors
    int sc_waits = 0;
+   bool sc_cross = false;                           // a cross Hessian in the Q the Ruiz scaler sees: the x0 rows' maxima are not rank-local
    int sc_alloc() {
       const long long nr = (long long)my + mz, nrep = std::max<long long>(n0, (long long)ry + rzr);
       TRY(alloc(&sc_col, nx)); TRY(alloc(&sc_row, nr)); TRY(alloc(&sc_tcol, nx)); TRY(alloc(&sc_trow, nr));
@@ -1463,7 +1479,9 @@ struct Ipm {
       return PIPS_OK;
    }
    // the row maxima alone, in the sweeps' deferred form: which = 0 the rows of J, 1 of J^T, 2 of the flat symmetric Q (a rank's own
-   // block rows and the root's, identical on every rank: no reduction); the minima go to sc_mn and are not used
+   // block rows and the root's, identical on every rank: no reduction - unless a cross Hessian puts the ranks' own R_i^T into the x0
+   // rows, sc_cross: then their maxima are combined like those of J^T's replicated rows; a rank without any Hessian of its own sends
+   // zeros); the minima go to sc_mn and are not used
    int sc_max(int which, const double* sc, double* mx) {
       ScaleArgs a;
       a.nrows = which == 0 ? my + mz : nx;
@@ -1471,24 +1489,31 @@ struct Ipm {
       a.v = which == 0 ? J_v : which == 1 ? Jt_v : Q_v;
       a.sc = sc; a.mn = sc_mn; a.mx = mx; a.fac = nullptr; a.partial = sc_part; a.op = SC_RATIO; a.fuse = 0;
       const int nl = which == 0 ? nJ_long : which == 1 ? nJt_long : nQ_long;
-      hipLaunchKernelGGL(k_scale_sweep, dim3(egrid(a.nrows)), dim3(256), 0, stream, a);
-      if (nl > 0) hipLaunchKernelGGL(k_scale_sweep_long, dim3(nl), dim3(256), 0, stream, a, which == 0 ? J_long : which == 1 ? Jt_long : Q_long, 0);
-      if (n_ranks > 1 && which != 2) TRY(sc_rep(which == 1, sc_mn, mx));
+      if (which != 2 || Q_rp) {
+         hipLaunchKernelGGL(k_scale_sweep, dim3(egrid(a.nrows)), dim3(256), 0, stream, a);
+         if (nl > 0) hipLaunchKernelGGL(k_scale_sweep_long, dim3(nl), dim3(256), 0, stream, a, which == 0 ? J_long : which == 1 ? Jt_long : Q_long, 0);
+      } else {   // no Hessian of its own: zeros at every pass (sc_rep below writes the ranks' maxima back into mx[0, n0))
+         HIP_TRYH(hipMemsetAsync(mx, 0, (size_t)std::max(nx, 1) * sizeof(double), stream));
+      }
+      if (n_ranks > 1 && (which != 2 || sc_cross)) TRY(sc_rep(which >= 1, sc_mn, mx));
       HIP_TRYH(hipGetLastError());
       return PIPS_OK;
    }
-   // the one host read of a (half-)pass: the row and column ratios in sc_rat[0..1], maxima over the ranks
-   int sc_read(double* r2) {
+   // the one host read of a (half-)pass: the row and column ratios in sc_rat[0..1], maxima over the ranks.  flag: one more slot of the
+   // same collective, summed - in: this rank's 0 / 1, out: whether any rank's is set
+   int sc_read(double* r2, bool* flag = nullptr) {
       double h[2];
       HIP_TRYH(hipMemcpyAsync(h, sc_rat, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
       HIP_TRYH(hipStreamSynchronize(stream));
       ++sc_waits;
       r2[0] = h[0]; r2[1] = h[1];
       if (n_ranks > 1) {
-         std::vector<double> slots(2 * (size_t)n_ranks, 0.0);
+         std::vector<double> slots(2 * (size_t)n_ranks + (flag ? 1 : 0), 0.0);
          slots[2 * rank] = h[0]; slots[2 * rank + 1] = h[1];
-         TRY(reduce_host(slots.data(), 2 * n_ranks));
+         if (flag) slots[2 * (size_t)n_ranks] = *flag ? 1.0 : 0.0;
+         TRY(reduce_host(slots.data(), 2 * n_ranks + (flag ? 1 : 0)));
          for (int q = 0; q < n_ranks; ++q) { r2[0] = std::max(r2[0], slots[2 * q]); r2[1] = std::max(r2[1], slots[2 * q + 1]); }
+         if (flag) *flag = slots[2 * (size_t)n_ranks] != 0.0;
       }
       return PIPS_OK;
    }
@@ -1523,10 +1548,10 @@ struct Ipm {
          constexpr int RUIZ_PASSES = 10;   // OSQP's default
          double *mc = nullptr, *mq = nullptr;
          TRY(alloc(&mc, nx));
-         if (Q_rp) TRY(alloc(&mq, nx));
          TRY(sc_sweep(false, nullptr, nullptr, SC_RATIO, sc_rat));
          TRY(sc_sweep(true, nullptr, nullptr, SC_RATIO, sc_rat + 1));
-         TRY(sc_read(r));
+         TRY(sc_read(r, &sc_cross));   // sc_cross: prescale() set it from this rank's blocks; now any rank's
+         if (Q_rp || (sc_cross && n_ranks > 1)) TRY(alloc(&mq, nx));
          sc_info[1] = r[0]; sc_info[2] = r[1];
          for (int i = 0; i < RUIZ_PASSES; ++i) {
             TRY(sc_max(0, sc_col, sc_mx));
@@ -1718,6 +1743,8 @@ struct Ipm {
       TRY(up(&d_pack, L.pack)); TRY(up(&d_code, L.code));
       if (has_q) {   // device copy of Q, its diagonal, the product vector
          if (!Q_rp) TRY(upload_Q(L));
+         else if (L.omit_q0 != Q_omits_q0) TRY(upload_Q(L));   // prescale() kept the Q0 block: it did not know of another rank's cross
+                                                               // Hessian yet
          else {   // a scaled handle holds the original Q since prescale(): the scaled values into the same pattern
             if (L.Q_nnz != Q_nnz) PIPS_FAIL(PIPS_ERR_STATE, "pips_ipm_create_qp_scaled: the scaled Hessian has %lld entries, the original one %lld", L.Q_nnz, Q_nnz);
             HIP_TRYH(hipMemcpy(Q_v, L.Q_v.data(), L.Q_v.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1788,16 +1815,18 @@ int prescale(Ipm* p, const IpmInput& in, const IpmKnobs& knobs, int device, int 
    p->set_dims(L);
    TRY(ipm_hessians(in, L));
    if (L.has_q) {   // Q of the original data for the scaler that sees it; upload() replaces the values by the scaled ones (same pattern)
+      L.omit_q0 = L.cross && p->rank != 0;
       ipm_flat_hessian(in, L);
       TRY(p->upload_Q(L));
    }
+   p->sc_cross = L.cross;
    ipm_rows_J(in, p->rank, L);
    TRY(p->upload_J(L.J));
    L.J = HostCsr{};
    TRY(p->sc_alloc());
    TRY(p->alloc(&p->d_red, 64 * (long long)p->n_ranks));
    TRY(p->run_scaler(scaler));
-   p->dnorm_orig = ipm_data_norm(in, L.hq);
+   p->dnorm_orig = ipm_data_norm(in, L.hq, L.hr);
    if (p->scaled) make_scaled(in, L, p->h_col.data(), p->h_row.data(), sd);
    std::vector<double> ri2(2 * (size_t)p->mz), col2(2 * (size_t)p->nx);
    for (int k = 0; k < p->mz; ++k) ri2[k] = ri2[(size_t)p->mz + k] = p->h_row[(size_t)p->my + k];
@@ -1852,7 +1881,8 @@ int make_kkt(Ipm* p, const IpmLayout& L, const IpmKnobs& knobs) {
    return PIPS_OK;
 }
 
-// data norms, pair count and the has-Q flag over the ranks
+// data norms, pair count and the has-Q flag over the ranks; a rank with a cross Hessian adds CROSS_FLAG to that flag's slot
+constexpr double CROSS_FLAG = 1048576.0;   // above any number of ranks
 int exchange(Ipm* p, const IpmLayout& L) {
    HIP_TRYH(hipGetDevice(&p->device));
    if (!p->d_red) TRY(p->alloc(&p->d_red, 64 * (long long)p->n_ranks));
@@ -1865,7 +1895,7 @@ int exchange(Ipm* p, const IpmLayout& L) {
       const int ns = p->n_ranks + 2 + (p->scaled ? p->n_ranks : 0);
       std::vector<double> slots(ns, 0.0);
       slots[p->rank] = p->dnorm; slots[p->n_ranks] = L.pairs;
-      slots[ns - 1] = p->has_q ? 1.0 : 0.0;
+      slots[ns - 1] = (p->has_q ? 1.0 : 0.0) + (p->cross ? CROSS_FLAG : 0.0);   // (sums of these stay exact)
       if (p->scaled) slots[p->n_ranks + 1 + p->rank] = p->dnorm_orig;
       TRY(p->reduce_host(slots.data(), ns));
       for (int r = 0; r < p->n_ranks; ++r) p->dnorm = std::max(p->dnorm, slots[r]);
@@ -1873,6 +1903,7 @@ int exchange(Ipm* p, const IpmLayout& L) {
          for (int r = 0; r < p->n_ranks; ++r) p->dnorm_orig = std::max(p->dnorm_orig, slots[p->n_ranks + 1 + r]);
       p->n_pairs = slots[p->n_ranks];
       p->has_q = slots[ns - 1] != 0.0;   // a rank whose own blocks have none then holds an empty Q, zero qdiag and qx: one path on all ranks
+      p->cross = slots[ns - 1] >= CROSS_FLAG;   // the epilogues of the replicated x0 rows and the weights of x^T Q x follow it on every rank
    }
    if (!p->scaled) p->dnorm_orig = p->dnorm;
    return PIPS_OK;
@@ -1883,10 +1914,16 @@ int build(Ipm* p, const IpmInput& in, const IpmKnobs& knobs, int device) {
    TRY(ipm_layout(in, p->rank, knobs.eliminate_z0, !p->J_v, L));   // (a scaled handle holds J since prescale())
    p->set_dims(L);
    p->has_q = L.has_q;
+   p->cross = L.cross;
    TRY(make_batch(p, L, knobs, device));
    TRY(make_kkt(p, L, knobs));
    TRY(exchange(p, L));
-   if (p->has_q && !L.has_q) ipm_flat_hessian(in, L);
+   // the flat Q again where the ranks' agreement changes it: none of its own, or a Q0 block another rank's cross Hessian takes out
+   const bool omit_q0 = p->cross && p->rank != 0;
+   if (p->has_q && (!L.has_q || omit_q0 != L.omit_q0)) {
+      L.omit_q0 = omit_q0;
+      ipm_flat_hessian(in, L);
+   }
    TRY(p->upload(L));
    return p->alloc_state();
 }
@@ -1958,6 +1995,23 @@ int pips_ipm_create_qp_scaled(void** handle, int n_blocks, const pips_ipm_block*
    return create(handle, in, dual_reg, device, comm, rank, n_ranks, scaler, "pips_ipm_create_qp_scaled");
 }
 
+// pips_ipm_create_qp_scaled with cross Hessians R_i between x0 and the blocks (include/pips_hip.h).  Without a stored entry in any R[i]
+// it is pips_ipm_create_qp_scaled, call for call.
+int pips_ipm_create_qp_cross(void** handle, int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, const pips_csr_view* R, int myl,
+                             int mzl, const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp,
+                             double dual_reg, int device, void* comm, int rank, int n_ranks, int scaler) {
+   TRY(check_scaler(scaler, "pips_ipm_create_qp_cross"));
+   const IpmInput in{n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp, R};
+   TRY(check_ipm_input(in, rank, n_ranks, "pips_ipm_create_qp_cross"));
+   IpmLayout L;
+   TRY(ipm_dims(in, true, L));
+   TRY(ipm_hessians(in, L));   // the refusals, whether or not an entry is stored
+   if (!L.cross)
+      return pips_ipm_create_qp_scaled(handle, n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp, dual_reg, device, comm, rank, n_ranks,
+                                       scaler);
+   return create(handle, in, dual_reg, device, comm, rank, n_ranks, scaler, "pips_ipm_create_qp_cross");
+}
+
 int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host) {
    Ipm* p = (Ipm*)handle;
    if (!p || !in_host || !out_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_hessian_mult: bad arguments");
@@ -1968,6 +2022,7 @@ int pips_ipm_hessian_mult(void* handle, const double* in_host, double* out_host)
    HIP_TRYH(hipSetDevice(p->device));
    HIP_TRYH(hipMemcpy(p->w_dx, in_host, (size_t)p->nx * sizeof(double), hipMemcpyHostToDevice));
    TRY(p->hess(p->w_dx, p->w_t));
+   if (p->cross) TRY(p->root_sum(p->w_t, p->n0));   // the ranks' shares of (Q x)_0
    HIP_TRYH(hipStreamSynchronize(p->stream));
    HIP_TRYH(hipMemcpy(out_host, p->w_t, (size_t)p->nx * sizeof(double), hipMemcpyDeviceToHost));
    return PIPS_OK;

@@ -82,13 +82,52 @@ static int check_hessian(int i, int n, const pips_csr_view& q, LowerQ& out) {
    return PIPS_OK;
 }
 
+// R_i, the cross Hessian of block i >= 1 with x0 (pips_ipm_create_qp_cross): general CSR, n_i x n0.  One without a stored entry counts
+// as absent.
+static int check_cross(int i, int n, int n0, const pips_csr_view& r, CrossR& out) {
+   out.have = false;
+   if (!r.rowptr) return PIPS_OK;
+   if (i == 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp_cross: R[0] is present - the root has no cross Hessian with itself (Q[0] holds its Hessian)");
+   if (r.rows != n || r.cols != n0)   // (before rowptr[rows] is read)
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp_cross: R[%d] is %d x %d but block %d has %d variables and the root %d", i, r.rows, r.cols, i, n, n0);
+   const bool stored = n > 0 && r.rowptr[n] > r.rowptr[0];
+   if (n0 == 0 && stored) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp_cross: R[%d] has stored entries but n0 == 0 - there is no x0 to couple with", i);
+   if (!stored) return PIPS_OK;
+   if (!r.colidx || !r.val) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp_cross: R[%d] lacks colidx / val", i);
+   out.have = true;
+   out.rp.assign((size_t)n + 1, 0);
+   std::vector<std::pair<int, double>> row;
+   for (int k = 0; k < n; ++k) {
+      row.clear();
+      for (int q = r.rowptr[k]; q < r.rowptr[k + 1]; ++q) {
+         const int c = r.colidx[q];
+         if (c < 0 || c >= n0) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_create_qp_cross: R[%d] row %d has column index %d outside [0, %d)", i, k, c, n0);
+         row.push_back({c, r.val[q]});
+      }
+      std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+      for (size_t j = 0; j < row.size(); ++j) {
+         if ((int)out.ci.size() > out.rp[k] && out.ci.back() == row[j].first) out.v.back() += row[j].second;
+         else { out.ci.push_back(row[j].first); out.v.push_back(row[j].second); }
+      }
+      out.rp[k + 1] = (int)out.ci.size();
+   }
+   out.ci.push_back(0); out.v.push_back(0.0);   // never empty arrays
+   return PIPS_OK;
+}
+
 int ipm_hessians(const IpmInput& in, IpmLayout& L) {
    L.hq.assign(in.n_blocks, LowerQ{});
-   L.has_q = false;
+   L.hr.assign(in.n_blocks, CrossR{});
+   L.has_q = L.cross = false;
    for (int i = 0; in.Q && i < in.n_blocks; ++i) {
       TRY(check_hessian(i, in.blocks[i].n, in.Q[i], L.hq[i]));
       L.has_q = L.has_q || L.hq[i].have;
    }
+   for (int i = 0; in.R && i < in.n_blocks; ++i) {
+      TRY(check_cross(i, in.blocks[i].n, in.blocks[0].n, in.R[i], L.hr[i]));
+      L.cross = L.cross || L.hr[i].have;
+   }
+   L.has_q = L.has_q || L.cross;
    return PIPS_OK;
 }
 
@@ -158,11 +197,14 @@ static int leaf_assemble(int nx, int my, int mz, const LowerQ& q, const View& B,
    s.kvals.assign(s.Krp[nk], 0.0);
    return call(s.Kci.data(), s.kvals.data(), dpos.data());
 }
-static int border_assemble(int nx, int my, int mz, const IpmLayout& L, const View& a, const View& c, const View& f, const View& g, LeafSystem& s) {
+// r: the block's cross Hessian R_i, whose entry (k, c) lands in Schur row c (an x0 column) at the leaf's x row k - the first block of
+// the reference's BorderBiBlock {R, A, C, n_empty, F^T, G^T}
+static int border_assemble(int nx, int my, int mz, const IpmLayout& L, const CrossR& r, const View& a, const View& c, const View& f, const View& g,
+                           LeafSystem& s) {
    auto rp = [](const View& m) { return present(m) ? m.rp : nullptr; };
    auto call = [&](int* ci, double* v) {
-      return pips_border_assemble(nx, my, mz, L.n0, L.my0, L.myl, L.e_mzl, nullptr, nullptr, nullptr, rp(a), a.ci, a.v, rp(c), c.ci, c.v, rp(f), f.ci, f.v,
-                                  rp(g), g.ci, g.v, s.Brd.data(), ci, v);
+      return pips_border_assemble(nx, my, mz, L.n0, L.my0, L.myl, L.e_mzl, r.have ? r.rp.data() : nullptr, r.ci.data(), r.v.data(), rp(a), a.ci, a.v,
+                                  rp(c), c.ci, c.v, rp(f), f.ci, f.v, rp(g), g.ci, g.v, s.Brd.data(), ci, v);
    };
    s.Brd.assign(L.S + 1, 0);
    TRY(call(nullptr, nullptr));
@@ -187,7 +229,7 @@ int ipm_leaf_systems(const IpmInput& in, IpmLayout& L) {
          g.rp = g_rp.data();
          g.rows = L.e_mzl;
       }
-      TRY(border_assemble(b.n, b.my, b.mz, L, view(b.A), view(b.C), view(b.BL), g, L.leaf[i - 1]));
+      TRY(border_assemble(b.n, b.my, b.mz, L, L.hr[i], view(b.A), view(b.C), view(b.BL), g, L.leaf[i - 1]));
    }
    return PIPS_OK;
 }
@@ -238,8 +280,8 @@ int ipm_flat_vectors(const IpmInput& in, IpmLayout& L) {
 }
 
 // every matrix entry (the root's on every rank), c, b, the bounds under their indicators (a bound without indicator array counts as
-// absent), and ||Q|| (Problem.cpp:81)
-double ipm_data_norm(const IpmInput& in, const std::vector<LowerQ>& hq) {
+// absent), and ||Q|| (Problem.cpp:81), the cross Hessians among it
+double ipm_data_norm(const IpmInput& in, const std::vector<LowerQ>& hq, const std::vector<CrossR>& hr) {
    double dn = 0.0;
    auto m = [&](const pips_csr_view& a) {
       if (present(view(a))) for (int q = a.rowptr[0]; q < a.rowptr[a.rows]; ++q) dn = std::max(dn, std::fabs(a.val[q]));
@@ -256,6 +298,8 @@ double ipm_data_norm(const IpmInput& in, const std::vector<LowerQ>& hq) {
    v(in.bL, in.myl); bound(in.dlow, in.idlow, in.mzl); bound(in.dupp, in.idupp, in.mzl);
    for (const LowerQ& q : hq)
       for (double x : q.v) dn = std::max(dn, std::fabs(x));
+   for (const CrossR& r : hr)
+      for (double x : r.v) dn = std::max(dn, std::fabs(x));
    return dn;
 }
 
@@ -293,7 +337,10 @@ void ipm_maps(IpmLayout& L) {
 }
 
 // Q for the device: both triangles over the flat x order, expanded once, and its diagonal.  Without any block Hessian: an empty Q
-// (a rank whose own blocks have none while another rank's have)
+// (a rank whose own blocks have none while another rank's have).  A cross Hessian's entry (r, c) goes to (xoff[i] + r, c) and to its
+// mirror, both from the one stored value: the copy stays exactly symmetric.  The x0 rows then hold an entry per coupled block variable
+// and go through the long-row list like the replicated columns of J.  omit_q0: the entries of the Q0 block are left out (its diagonal
+// stays in qdiag) - what the ranks != 0 hold where (Q x)_0 is summed over the ranks.
 void ipm_flat_hessian(const IpmInput& in, IpmLayout& L) {
    std::vector<std::vector<std::pair<int, double>>> qrows((size_t)L.nx);
    L.qdiag.assign((size_t)L.nx, 0.0);
@@ -301,12 +348,23 @@ void ipm_flat_hessian(const IpmInput& in, IpmLayout& L) {
       const LowerQ& h = L.hq[i];
       if (!h.have) continue;
       const int o = i == 0 ? 0 : L.xoff[i];
+      const bool omit = i == 0 && L.omit_q0;
       for (int r = 0; r < in.blocks[i].n; ++r)
          for (int q = h.rp[r]; q < h.rp[r + 1]; ++q) {
             const int c = h.ci[q];
+            if (c == r) L.qdiag[(size_t)o + r] = h.v[q];
+            if (omit) continue;
             qrows[(size_t)o + r].push_back({o + c, h.v[q]});
             if (c != r) qrows[(size_t)o + c].push_back({o + r, h.v[q]});
-            else L.qdiag[(size_t)o + r] = h.v[q];
+         }
+   }
+   for (int i = 1; i <= L.N; ++i) {
+      const CrossR& h = L.hr[i];
+      if (!h.have) continue;
+      for (int r = 0; r < in.blocks[i].n; ++r)
+         for (int q = h.rp[r]; q < h.rp[r + 1]; ++q) {
+            qrows[(size_t)L.xoff[i] + r].push_back({h.ci[q], h.v[q]});
+            qrows[(size_t)h.ci[q]].push_back({L.xoff[i] + r, h.v[q]});
          }
    }
    L.Q_rp.assign((size_t)L.nx + 1, 0); L.Q_ci.clear(); L.Q_v.clear();
@@ -327,9 +385,10 @@ int ipm_layout(const IpmInput& in, int rank, bool eliminate_z0, bool with_J, Ipm
    TRY(ipm_leaf_systems(in, L));
    ipm_root_matrices(in, L);
    TRY(ipm_flat_vectors(in, L));
-   L.norm = ipm_data_norm(in, L.hq);
+   L.norm = ipm_data_norm(in, L.hq, L.hr);
    ipm_weights(rank, L);
    ipm_maps(L);
+   L.omit_q0 = L.cross && rank != 0;
    if (L.has_q) ipm_flat_hessian(in, L);
    return PIPS_OK;
 }
@@ -384,6 +443,22 @@ void make_scaled(const IpmInput& in, const IpmLayout& L, const double* col, cons
       }
       sd.in.Q = sd.q.data();
    }
+   // R'_i = Cs_i R_i Cs_0: (r col_{x_i row}) col_{x0 column}, the row's factor first as for Q; border and flat copy are built from these
+   if (in.R) {
+      sd.r.assign(in.R, in.R + in.n_blocks);
+      for (int i = 1; i <= L.N; ++i) {
+         pips_csr_view& m = sd.r[i];
+         const int n = in.blocks[i].n;
+         if (!m.rowptr || n <= 0 || m.rowptr[n] <= 0 || !m.colidx || !m.val) continue;
+         const double* rf = col + L.xoff[i];
+         sd.keep.emplace_back((size_t)m.rowptr[n], 0.0);
+         std::vector<double>& v = sd.keep.back();
+         for (int r = 0; r < n; ++r)
+            for (int q = m.rowptr[r]; q < m.rowptr[r + 1]; ++q) v[q] = (m.val[q] * rf[r]) * col[m.colidx[q]];
+         m.val = v.data();
+      }
+      sd.in.R = sd.r.data();
+   }
    vec(sd.in.bL, L.myl, re + L.my0, false); vec(sd.in.dlow, L.mzl, ri + L.mz0, false); vec(sd.in.dupp, L.mzl, ri + L.mz0, false);
 }
 
@@ -392,13 +467,11 @@ void make_scaled(const IpmInput& in, const IpmLayout& L, const double* col, cons
 using namespace pips;
 
 // ---- the probe (include/pips_hip.h) ------------------------------------------------------------------------------------------------
-extern "C" int pips_ipm_layout_probe(int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL,
-                                     const double* dlow, const double* dupp, const double* idlow, const double* idupp, int rank, int n_ranks,
-                                     int eliminate_z0, const double* col, const double* row, long long* dims, double* scalars, long long* sizes,
-                                     void* const* out) {
-   IpmInput in{n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp};
-   TRY(check_ipm_input(in, rank, n_ranks, "pips_ipm_layout_probe"));
-   if (!dims || !scalars || !sizes || (col == nullptr) != (row == nullptr)) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_layout_probe: bad arguments");
+// who: the entry's name in the messages
+static int layout_probe(const char* who, IpmInput in, int rank, int n_ranks, int eliminate_z0, const double* col, const double* row, long long* dims,
+                        double* scalars, long long* sizes, void* const* out) {
+   TRY(check_ipm_input(in, rank, n_ranks, who));
+   if (!dims || !scalars || !sizes || (col == nullptr) != (row == nullptr)) PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments", who);
    IpmLayout L;
    ScaledData sd;
    if (col) {
@@ -445,9 +518,25 @@ extern "C" int pips_ipm_layout_probe(int n_blocks, const pips_ipm_block* blocks,
       si(L.Q_rp), si(L.Q_ci, L.Q_nnz), sd_(L.Q_v, L.Q_nnz), sd_(L.qdiag), si(L.Q_long, L.nQ_long)};
    for (int k = 0; k < PIPS_IPML_SLOTS; ++k) {
       if (!out) sizes[k] = slots[k].n;
-      else if (sizes[k] != slots[k].n) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_layout_probe: sizes[%d] is %lld, the layout has %lld", k, sizes[k], slots[k].n);
-      else if (slots[k].n > 0 && !out[k]) PIPS_FAIL(PIPS_ERR_ARG, "pips_ipm_layout_probe: out[%d] is NULL", k);
+      else if (sizes[k] != slots[k].n) PIPS_FAIL(PIPS_ERR_ARG, "%s: sizes[%d] is %lld, the layout has %lld", who, k, sizes[k], slots[k].n);
+      else if (slots[k].n > 0 && !out[k]) PIPS_FAIL(PIPS_ERR_ARG, "%s: out[%d] is NULL", who, k);
       else if (slots[k].n > 0) std::memcpy(out[k], slots[k].p, (size_t)slots[k].n * slots[k].w);
    }
    return PIPS_OK;
+}
+
+extern "C" int pips_ipm_layout_probe(int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, int myl, int mzl, const double* bL,
+                                     const double* dlow, const double* dupp, const double* idlow, const double* idupp, int rank, int n_ranks,
+                                     int eliminate_z0, const double* col, const double* row, long long* dims, double* scalars, long long* sizes,
+                                     void* const* out) {
+   const IpmInput in{n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp};
+   return layout_probe("pips_ipm_layout_probe", in, rank, n_ranks, eliminate_z0, col, row, dims, scalars, sizes, out);
+}
+
+extern "C" int pips_ipm_layout_probe_cross(int n_blocks, const pips_ipm_block* blocks, const pips_csr_view* Q, const pips_csr_view* R, int myl, int mzl,
+                                           const double* bL, const double* dlow, const double* dupp, const double* idlow, const double* idupp,
+                                           int rank, int n_ranks, int eliminate_z0, const double* col, const double* row, long long* dims,
+                                           double* scalars, long long* sizes, void* const* out) {
+   const IpmInput in{n_blocks, blocks, Q, myl, mzl, bL, dlow, dupp, idlow, idupp, R};
+   return layout_probe("pips_ipm_layout_probe_cross", in, rank, n_ranks, eliminate_z0, col, row, dims, scalars, sizes, out);
 }

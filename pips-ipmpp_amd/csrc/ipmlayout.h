@@ -19,13 +19,14 @@ struct View { int rows = 0, cols = 0; const int* rp = nullptr; const int* ci = n
 inline View view(const pips_csr_view& m) { return View{m.rows, m.cols, m.rowptr, m.colidx, m.val}; }
 inline bool present(const View& m) { return m.rp != nullptr && m.rows > 0; }
 
-// what every creation entry point is given: block 0 is the root, Q may be null (include/pips_hip.h section 4c)
+// what every creation entry point is given: block 0 is the root, Q and R may be null (include/pips_hip.h section 4c)
 struct IpmInput {
    int n_blocks = 0;
    const pips_ipm_block* blocks = nullptr;
    const pips_csr_view* Q = nullptr;
    int myl = 0, mzl = 0;
    const double *bL = nullptr, *dlow = nullptr, *dupp = nullptr, *idlow = nullptr, *idupp = nullptr;
+   const pips_csr_view* R = nullptr;   // cross Hessians R_i (n_i x n0) between x0 and block i >= 1 (pips_ipm_create_qp_cross)
 };
 // the argument check of the entry points; who: the function name the message carries
 int check_ipm_input(const IpmInput& in, int rank, int n_ranks, const char* who);
@@ -39,6 +40,9 @@ struct HostCsr {
 // One block's Hessian as the caller gave it, checked and with sorted rows (duplicates added up): lower-triangular CSR like the
 // reference's SparseSymmetricMatrix.
 struct LowerQ { bool have = false; std::vector<int> rp, ci; std::vector<double> v; };
+// One block's cross Hessian R_i (n_i x n0, general CSR) as the caller gave it, checked and with sorted rows (duplicates added up):
+// the reference's left bordering block.  have: it holds a stored entry.
+struct CrossR { bool have = false; std::vector<int> rp, ci; std::vector<double> v; };
 // K_i as lower CSR with its constant values, and the border of the leaf by Schur row (pips_kkt_leaf_assemble, pips_border_assemble)
 struct LeafSystem {
    std::vector<int> Krp, Kci, Brd, Bci;
@@ -54,7 +58,12 @@ struct IpmLayout {
    std::vector<int> xoff, yoff, zoff;   // N + 2 entries: block i covers [off[i], off[i + 1]); [0, off[1]) is the replicated part
    std::vector<long long> koff;         // rows of the leaves' K_i, back to back
    std::vector<LowerQ> hq;
-   bool has_q = false;
+   std::vector<CrossR> hr;
+   bool has_q = false;                  // a Hessian of either kind among this rank's blocks
+   bool cross = false;                  // a cross Hessian with a stored entry among this rank's blocks
+   // several ranks with a cross Hessian on any of them: (Q x)_0 is summed over the ranks, so the flat Q of the ranks != 0 leaves the
+   // Q0 block out (ipm_flat_hessian); set by ipm_layout from this rank's own blocks, by the harness once the ranks have agreed
+   bool omit_q0 = false;
    HostCsr J;                           // rows [y rows | z rows] over x; root rows on rank 0 only
    std::vector<LeafSystem> leaf;
    std::vector<double> c, b, M, Bd;     // M = [iclow | icupp | ixlow | ixupp], Bd the bounds in that order, masked
@@ -73,12 +82,13 @@ struct IpmLayout {
 
 // ---- the steps, in the order ipm_layout() runs them ------------------------------------------------------------------------------
 int ipm_dims(const IpmInput& in, bool eliminate_z0, IpmLayout& L);   // dimensions and offsets
-int ipm_hessians(const IpmInput& in, IpmLayout& L);                  // hq, has_q
+int ipm_hessians(const IpmInput& in, IpmLayout& L);                  // hq, hr, has_q, cross
 void ipm_rows_J(const IpmInput& in, int rank, IpmLayout& L);         // J, J^T, long rows
 int ipm_leaf_systems(const IpmInput& in, IpmLayout& L);              // K_i and border per leaf
 void ipm_root_matrices(const IpmInput& in, IpmLayout& L);            // A0, F0, C0, G0
 int ipm_flat_vectors(const IpmInput& in, IpmLayout& L);              // c, b, M, Bd
-double ipm_data_norm(const IpmInput& in, const std::vector<LowerQ>& hq);   // max |entry| of this rank's data, bounds under their indicators
+// max |entry| of this rank's data, bounds under their indicators
+double ipm_data_norm(const IpmInput& in, const std::vector<LowerQ>& hq, const std::vector<CrossR>& hr);
 void ipm_weights(int rank, IpmLayout& L);                            // wG, wGs, wXYZ, pairs
 void ipm_maps(IpmLayout& L);                                         // pack, code
 void ipm_flat_hessian(const IpmInput& in, IpmLayout& L);             // Q_*, qdiag
@@ -86,12 +96,13 @@ void ipm_flat_hessian(const IpmInput& in, IpmLayout& L);             // Q_*, qdi
 int ipm_layout(const IpmInput& in, int rank, bool eliminate_z0, bool with_J, IpmLayout& L);
 
 // The data scaled by the factors (Scaler::applyScaling): matrices (a col_j) row_i, c col, b / clow / cupp row, xlow / xupp / col, and
-// the lower-triangular Hessians (q col_r) col_c (x = Cs x': Q' = Cs Q Cs; the Hessians must have passed ipm_hessians).
+// the lower-triangular Hessians (q col_r) col_c and the cross Hessians (r col_{x_i row}) col_{x0 column} (x = Cs x': Q' = Cs Q Cs;
+// the Hessians must have passed ipm_hessians).
 // col: nx factors, row: [row_eq (my) | row_ineq (mz)].  Host copies of O(nnz); `in` points into them and into the original indices.
 struct ScaledData {
    IpmInput in;
    std::vector<pips_ipm_block> blk;
-   std::vector<pips_csr_view> q;
+   std::vector<pips_csr_view> q, r;
    std::deque<std::vector<double>> keep;
 };
 void make_scaled(const IpmInput& in, const IpmLayout& L, const double* col, const double* row, ScaledData& sd);

@@ -54,7 +54,7 @@ SYMBOLS = [
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
     "pips_hip_ldl_inertia_batch", "pips_hip_ldl_factor_schur_sparse", "pips_hip_ldl_factor_schur_sparse_batch",
     "pips_hip_dense_ldl_create", "pips_hip_dense_ldl_factor", "pips_hip_dense_ldl_factor_dev", "pips_hip_dense_ldl_solve",
-    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_first_touch_probe", "pips_ipm_layout_probe", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_knobs", "pips_hip_knob_value", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
+    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_first_touch_probe", "pips_ipm_layout_probe", "pips_ipm_layout_probe_cross", "pips_ipm_create_qp_cross", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_knobs", "pips_hip_knob_value", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
     "pips_hip_batch_create", "pips_hip_batch_set_block", "pips_hip_batch_set_options", "pips_hip_batch_set_schur_mode", "pips_hip_batch_set_deterministic", "pips_hip_batch_get_schur_mode", "pips_hip_batch_add_regularization", "pips_hip_batch_set_refinement",
     "pips_hip_batch_last_refinement_steps", "pips_hip_batch_set_refinement_backward_error",
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
@@ -1211,24 +1211,39 @@ class _IpmBlock(C.Structure):
                [(k, C.c_void_p) for k in ("c", "xlow", "xupp", "ixlow", "ixupp", "b", "clow", "cupp", "iclow", "icupp")]
 
 
+def _kept(keep, a, dtype=np.float64):
+    """the address of a as a contiguous array of dtype (None for an empty one); keep holds what must stay alive"""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    keep.append(a)
+    return a.ctypes.data_as(C.c_void_p).value if a.size else None
+
+
+def _csr_view(keep, m):
+    """a matrix dict (or Csr, or None) as a pips_csr_view"""
+    if m is None:
+        return _CsrView(0, 0, None, None, None)
+    if isinstance(m, Csr):
+        m = dict(rows=m.nrows, cols=m.ncols, rowptr=m.rowptr, colidx=m.colidx, val=m.val)
+    rp = np.ascontiguousarray(m["rowptr"], dtype=np.int32)
+    keep.append(rp)
+    return _CsrView(int(m["rows"]), int(m["cols"]), rp.ctypes.data_as(C.c_void_p).value, _kept(keep, m["colidx"], np.int32), _kept(keep, m["val"]))
+
+
+def _csr_views(keep, mats):
+    """a list of matrix dicts (or None) as an array of pips_csr_view, None as NULL"""
+    return (_CsrView * len(mats))(*[_csr_view(keep, m) for m in mats]) if mats is not None else None
+
+
 def _ipm_input(blocks, hessians):
     """The reader's block dicts (and Hessians) as the C structs of the creation entry points: (what must stay alive, blocks, Q or None,
     [myl, mzl, bL, dlow, dupp, idlow, idupp])."""
     keep = []
 
     def arr(a, dtype=np.float64):
-        a = np.ascontiguousarray(a, dtype=dtype)
-        keep.append(a)
-        return a.ctypes.data_as(C.c_void_p).value if a.size else None
+        return _kept(keep, a, dtype)
 
     def view(m):
-        if m is None:
-            return _CsrView(0, 0, None, None, None)
-        if isinstance(m, Csr):
-            m = dict(rows=m.nrows, cols=m.ncols, rowptr=m.rowptr, colidx=m.colidx, val=m.val)
-        rp = np.ascontiguousarray(m["rowptr"], dtype=np.int32)
-        keep.append(rp)
-        return _CsrView(int(m["rows"]), int(m["cols"]), rp.ctypes.data_as(C.c_void_p).value, arr(m["colidx"], np.int32), arr(m["val"]))
+        return _csr_view(keep, m)
 
     root = blocks[0]
     cb = (_IpmBlock * len(blocks))()
@@ -1239,7 +1254,7 @@ def _ipm_input(blocks, hessians):
         cb[k].B, cb[k].D = (view(None), view(None)) if k == 0 else (view(b["B"]), view(b["D"]))
         for f in ("c", "xlow", "xupp", "ixlow", "ixupp", "b", "clow", "cupp", "iclow", "icupp"):
             setattr(cb[k], f, arr(b[f]))
-    cq = (_CsrView * len(blocks))(*[view(h) for h in hessians]) if hessians is not None else None
+    cq = _csr_views(keep, hessians)
     tail = [C.c_int(int(root["mBL"])), C.c_int(int(root["mDL"]))] + [C.c_void_p(arr(root[f])) for f in ("bL", "dlow", "dupp", "idlow", "idupp")]
     return keep, cb, cq, tail
 
@@ -1249,26 +1264,34 @@ class GeneralIpmSolver(IpmSolver):
     and linking rows), fed with the reader's per-block dicts (fields of GMSPIPSBlockData_t as gdx.read_block / gdx_read_block
     return them): blocks[0] is the root.  Several ranks: blocks = [root] + this rank's blocks."""
 
-    def __init__(self, blocks, dual_reg=0.0, device=-1, comm=None, rank=0, n_ranks=1, scaler=None, hessians=None):
+    def __init__(self, blocks, dual_reg=0.0, device=-1, comm=None, rank=0, n_ranks=1, scaler=None, hessians=None, cross_hessians=None):
         """scaler: None, "equilibrium", "geometric" or "geometric_equilibrium" (the reference's scale / scaleEqui, scaleGeo,
         scaleGeoEqui), or "ruiz" (Ruiz equilibration of [Q J^T; J 0]: the one that sees the Hessians); "curtis_reid" is reserved and
         raises, like any other name.
         hessians: None (an LP, created by pips_ipm_create_general), or a list as long as `blocks` whose entries are None or a
         dict rows / cols / rowptr / colidx / val like the matrices of the block dicts (or a Csr): the LOWER triangle of the block's
         convex Hessian (pips_ipm_create_qp; convexity is the caller's contract).  With a scaler: pips_ipm_create_qp_scaled, the
-        handle holds Q' = Cs Q Cs."""
+        handle holds Q' = Cs Q Cs.
+        cross_hessians: None, or a list as long as `blocks`, [None, R_1, ...]: entry i >= 1 is None or block i's cross Hessian with
+        x0 in the same layout, ni x n0, general CSR (pips_ipm_create_qp_cross, with or without hessians and a scaler); entry 0 must
+        be None."""
         if scaler not in SCALERS:
             raise PipsHipError(f"unknown scaler {scaler!r}: one of None, 'equilibrium', 'geometric', 'geometric_equilibrium', 'ruiz'")
         if hessians is not None and len(hessians) != len(blocks):
             raise PipsHipError(f"hessians has {len(hessians)} entries for {len(blocks)} blocks")
+        if cross_hessians is not None and len(cross_hessians) != len(blocks):
+            raise PipsHipError(f"cross_hessians has {len(cross_hessians)} entries for {len(blocks)} blocks")
         keep, cb, cq, tail = _ipm_input(blocks, hessians)
+        cr = _csr_views(keep, cross_hessians)
         self.n_blocks = len(blocks)
-        self._keep = (keep, cb, cq)
+        self._keep = (keep, cb, cq, cr)
         self._comm = comm
         self._h = C.c_void_p()
         args = (C.byref(self._h), C.c_int(len(blocks)), cb, *tail, C.c_double(dual_reg), C.c_int(device),
                 comm._h if comm is not None else None, C.c_int(rank), C.c_int(n_ranks))
-        if hessians is not None and scaler is not None:
+        if cross_hessians is not None:
+            _check(lib.pips_ipm_create_qp_cross(*args[:3], cq, cr, *args[3:], C.c_int(SCALERS[scaler])), "pips_ipm_create_qp_cross")
+        elif hessians is not None and scaler is not None:
             _check(lib.pips_ipm_create_qp_scaled(*args[:3], cq, *args[3:], C.c_int(SCALERS[scaler])), "pips_ipm_create_qp_scaled")
         elif hessians is not None:
             _check(lib.pips_ipm_create_qp(*args[:3], cq, *args[3:]), "pips_ipm_create_qp")
@@ -1341,18 +1364,22 @@ IPM_LAYOUT_ARRAYS = (
     [("Q_rp", np.int32), ("Q_ci", np.int32), ("Q_v", np.float64), ("qdiag", np.float64), ("Q_long", np.int32)])
 
 
-def ipm_layout_probe(blocks, hessians=None, rank=0, n_ranks=1, eliminate_z0=True, col=None, row=None):
+def ipm_layout_probe(blocks, hessians=None, rank=0, n_ranks=1, eliminate_z0=True, col=None, row=None, cross_hessians=None):
     """The host layout pass of an IPM handle's creation, without a device (pips_ipm_layout_probe): a dict of the dimensions
     (IPM_LAYOUT_DIMS), `pairs`, `norm` and the arrays (IPM_LAYOUT_ARRAYS; per-leaf and per-block arrays back to back).  blocks /
-    hessians as GeneralIpmSolver takes them; col, row = [row_eq | row_ineq]: factors the data is scaled with first."""
+    hessians / cross_hessians as GeneralIpmSolver takes them (with cross_hessians: pips_ipm_layout_probe_cross); col, row =
+    [row_eq | row_ineq]: factors the data is scaled with first."""
     keep, cb, cq, tail = _ipm_input(blocks, hessians)
+    cr = _csr_views(keep, cross_hessians)
+    probe, name, rarg = (lib.pips_ipm_layout_probe_cross, "pips_ipm_layout_probe_cross", (cr,)) if cr is not None else \
+        (lib.pips_ipm_layout_probe, "pips_ipm_layout_probe", ())
     col, row = (None, None) if col is None else (_f64(col), _f64(row))
     dims, scal, sizes = (C.c_longlong * len(IPM_LAYOUT_DIMS))(), (C.c_double * 2)(), (C.c_longlong * len(IPM_LAYOUT_ARRAYS))()
-    head = (C.c_int(len(blocks)), cb, cq, *tail, C.c_int(rank), C.c_int(n_ranks), C.c_int(1 if eliminate_z0 else 0), _ptr(col), _ptr(row), dims, scal, sizes)
-    _check(lib.pips_ipm_layout_probe(*head, None), "pips_ipm_layout_probe")
+    head = (C.c_int(len(blocks)), cb, cq, *rarg, *tail, C.c_int(rank), C.c_int(n_ranks), C.c_int(1 if eliminate_z0 else 0), _ptr(col), _ptr(row), dims, scal, sizes)
+    _check(probe(*head, None), name)
     arrays = [np.zeros(int(sizes[k]), dtype=t) for k, (_, t) in enumerate(IPM_LAYOUT_ARRAYS)]
     out = (C.c_void_p * len(arrays))(*[a.ctypes.data_as(C.c_void_p).value if a.size else None for a in arrays])
-    _check(lib.pips_ipm_layout_probe(*head, out), "pips_ipm_layout_probe")
+    _check(probe(*head, out), name)
     res = {k: int(dims[i]) for i, k in enumerate(IPM_LAYOUT_DIMS)}
     res.update(pairs=float(scal[0]), norm=float(scal[1]))
     res.update({k: a for (k, _), a in zip(IPM_LAYOUT_ARRAYS, arrays)})

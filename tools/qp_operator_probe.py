@@ -1,7 +1,8 @@
 """Cost of the Hessian product in the operator of the outer solve: one Ipm::kmult (HIP events, median of 20 after a warm-up) on the
-time-coupled family - by default the configs[3] share, 256 blocks x 50 000 variables - as an LP handle and as a QP handle with a
-tridiagonal Hessian (2 on the diagonal, -1 beside it) on the root and on every block.
-    python tools/qp_operator_probe.py [--blocks 256] [--n 50000] [--out profiles/qp_operator.txt]
+time-coupled family - by default the configs[3] share, 256 blocks x 50 000 variables - as an LP handle, as a QP handle with a
+tridiagonal Hessian (2 on the diagonal, -1 beside it) on the root and on every block, and with --cross K as that QP handle with a
+sparse cross Hessian R_i of K entries per row between x0 and every block (pips_ipm_create_qp_cross).
+    python tools/qp_operator_probe.py [--blocks 256] [--n 50000] [--cross 2] [--out profiles/qp_operator.txt]
 Builds tools/libqp_kmult_probe.so from tools/qp_operator_probe.hip on first use (hipcc, gfx950)."""
 import argparse
 import ctypes as C
@@ -57,11 +58,19 @@ def tridiagonal(n):
     return dict(rows=n, cols=n, rowptr=rowptr, colidx=colidx, val=val)
 
 
+def sparse_cross(n, n0, k):
+    """n x n0, k entries per row in distinct columns (k <= n0): the operator's cost does not depend on the values"""
+    r = np.arange(n, dtype=np.int64)
+    colidx = np.sort(np.stack([(7 * r + (n0 // k) * j) % n0 for j in range(k)], axis=1), axis=1).astype(np.int32).ravel()
+    return dict(rows=n, cols=n0, rowptr=(k * np.arange(n + 1)).astype(np.int32), colidx=colidx, val=np.full(k * n, 1e-3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=256)
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--cross", type=int, default=0, help="entries per row of a cross Hessian R_i on a third handle (0: none)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import families
@@ -70,8 +79,13 @@ def main():
     chain = families.config3_chain(a.n).prefix(a.blocks)
     blocks = general_blocks(chain, a.blocks, 20261004)
     lines = [f"one Ipm::kmult (HIP events, median of {a.reps} after 3 warm-up applications), time-coupled family: {a.blocks} blocks x {a.n} variables"]
-    for name, hess in (("LP handle", None), ("QP handle, tridiagonal Hessian on every block", [tridiagonal(a.n if k else chain.n0) for k in range(a.blocks + 1)])):
-        ipm = pa.GeneralIpmSolver(blocks, hessians=hess)
+    tri = [tridiagonal(a.n if k else chain.n0) for k in range(a.blocks + 1)]
+    handles = [("LP handle", {}), ("QP handle, tridiagonal Hessian on every block", dict(hessians=tri))]
+    if a.cross > 0:
+        handles.append((f"the same with R_i of {a.cross} entries per row",
+                        dict(hessians=tri, cross_hessians=[None] + [sparse_cross(a.n, chain.n0, a.cross) for _ in range(a.blocks)])))
+    for name, kw in handles:
+        ipm = pa.GeneralIpmSolver(blocks, **kw)
         ms = (C.c_float * a.reps)()
         dims = (C.c_longlong * 3)()
         rc = lib.qp_probe_kmult(ipm._h, C.c_int(3), C.c_int(a.reps), ms, dims)
