@@ -1023,6 +1023,14 @@ class vec:
         _check(lib.pips_hip_vec_scale(vec._n(y), C.c_double(a), _ptr(y), None), "vec_scale")
 
     @staticmethod
+    def copy(x, y):
+        _check(lib.pips_hip_vec_copy(vec._n(y), _ptr(x), _ptr(y), None), "vec_copy")
+
+    @staticmethod
+    def set(a, y):
+        _check(lib.pips_hip_vec_set(vec._n(y), C.c_double(a), _ptr(y), None), "vec_set")
+
+    @staticmethod
     def add_const(a, y):
         _check(lib.pips_hip_vec_add_const(vec._n(y), C.c_double(a), _ptr(y), None), "vec_add_const")
 
@@ -1093,6 +1101,10 @@ class vec:
     @staticmethod
     def min(x):
         return vec._red(lib.pips_hip_vec_min, vec._n(x), _ptr(x))
+
+    @staticmethod
+    def sumsq_scaled(x, scale_inv, skip_root=0):
+        return vec._red(lib.pips_hip_vec_sumsq_scaled, vec._n(x), C.c_longlong(skip_root), C.c_double(scale_inv), _ptr(x))
 
     @staticmethod
     def two_norm(x):
