@@ -1,5 +1,6 @@
 // Device engine of the MI355X KKT backend: batched numeric factorisation / solves for all leaf blocks of one GPU,
-// the dense root solver, and the C ABI declared in include/pips_hip.h.
+// and the C ABI declared in include/pips_hip.h.  Three layers of this translation unit have files of their own, included where they
+// stand: the dense root solver (denseroot.hip.h), the fused KKT system (kkt.hip.h), the per-leaf handles (ldlhandle.hip.h).
 //
 // Reference call sites replaced (see include/pips_hip.h for the per-entry citations):
 //   DistributedLeafLinearSystem::factor2 -> solver->matrixChanged()          (DistributedLeafLinearSystem.C:74-86)
@@ -680,14 +681,12 @@ struct EngineAnalysis {
    ScPanelPlan scp;                     // the groups and the panels' first rows (its tasks are dropped once uploaded)
    std::vector<hipEvent_t> ev_sc;       // one per group (destroyed by Engine::release / set_sc_panels)
    DevBuf<TileTask> d_sc_tasks;
-   // ---- multi-RHS solve (Engine::ensure_multi_buffers) and the host-pointer solves of a leaf handle
+   // ---- multi-RHS solve (Engine::ensure_multi_buffers)
    DevBuf<double> d_mx_xw, d_mx_rhs, d_mx_res;
    int mx_cap = 0;
    DevBuf<double> d_mmeasure;           // solve_multi: the refinement measure per right-hand side (device / pinned) ...
    PinnedBuf<double> h_mmeasure;
    DevBuf<int> d_midx;                  // ... and the columns that take the correction solve
-   DevBuf<double> d_hostx;              // device copy of host right-hand sides (pips_hip_ldl_solve), kept between calls
-   DevBuf<double> d_hostpack;           // packed rows + their indices of pips_hip_ldl_solve_sparse, kept between calls likewise
    // ---- inertia counters in pinned host memory (Engine::fetch_inertia)
    PinnedBuf<int> h_inertia_pin;
    hipEvent_t ev_inertia = nullptr;     // (destroyed by Engine::release)
@@ -1956,476 +1955,18 @@ struct Engine : EngineAnalysis, BatchLayout {
    }
 };
 
-// ---------------------------------------------------------------------------------------------------------------
-// dense root solver (DeSymIndefSolver replacement) on the same tile kernels
-// ---------------------------------------------------------------------------------------------------------------
-extern "C" int pips_hip_allreduce_sum(void* comm, double* buf_dev, size_t n, void* stream);
-extern "C" int pips_hip_all_gather(void* comm, double* buf_dev, size_t chunk, int n_parts, void* stream);
-extern "C" int pips_hip_broadcast(void* comm, double* buf_dev, size_t n, int root, void* stream);
-extern "C" int pips_hip_comm_has_broadcast(void* comm);
-
-__global__ void k_inertia_to_double(const int* __restrict__ in, double* __restrict__ out, int back, int* __restrict__ in_out) {
-   if (threadIdx.x < 3) { if (!back) out[threadIdx.x] = (double)in[threadIdx.x]; else in_out[threadIdx.x] = (int)(out[threadIdx.x] + 0.5); }
+// resolves -1 to the current device and checks the range (the entry points that create something on a device)
+static int resolve_device(int device, int* out) {
+   int cnt = 0;
+   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0)
+      PIPS_FAIL(PIPS_ERR_NO_DEVICE, "no HIP device visible: the MI355X backend has no CPU fallback");
+   if (device < 0) { HIP_TRY(hipGetDevice(&device)); }
+   if (device >= cnt) PIPS_FAIL(PIPS_ERR_ARG, "device %d out of range (%d visible)", device, cnt);
+   *out = device;
+   return PIPS_OK;
 }
 
-struct DenseLdl {
-   int device = 0, n = 0, npad = 0, n_primal = -1;
-   // 0: static pivot order with the expected signs of the inertia hint (right for the quasi-definite Schur complement the fused
-   //    path builds itself: no search on the critical path of the 128 dependent pivots of a tile);
-   // 1: Bunch-Kaufman 1 x 1 / 2 x 2 pivoting bounded to the diagonal tile (k_tile_diag_bk): what a drop-in for DeSymIndefSolver
-   //    needs - dsytrf takes any symmetric matrix (DeSymIndefSolver.C:78)
-   int pivoting = 0;
-   hipStream_t stream = nullptr;
-   double thr_rel = 1e-13, repl_rel = 1e-8;
-   bool factored = false;
-   std::vector<BlkDesc> h_blks;
-   TailPlan plan;
-   DevBuf<BlkDesc> d_blks;
-   DevBuf<double> d_R, d_winv, d_dtail, d_xw, d_in, d_pref;
-   DevBuf<double> d_U;   // U = L D (npad x npad), B operand of the updates
-   DevBuf<signed char> d_psign;
-   DevBuf<long long> d_psign_off, d_kptr;
-   DevBuf<int> d_inertia;
-   int h_inertia[3] = {0, 0, 0};
-   hipStream_t side = nullptr;
-   hipEvent_t ev_panel = nullptr, ev_rest = nullptr;
-   // staging copy of a host matrix: only the host-pointer entry points need it (the fused KKT path hands over d_SC)
-   int ensure_input_buffer() {
-      if (!d_in) PIPS_TRY(d_in.alloc((size_t)std::max(n, 1) * std::max(n, 1)));
-      return PIPS_OK;
-   }
-
-   ~DenseLdl() {
-      if (side) (void)hipStreamDestroy(side);
-      if (ev_panel) (void)hipEventDestroy(ev_panel);
-      if (ev_rest) (void)hipEventDestroy(ev_rest);
-   }
-   SweepRt sweep;
-   // ---- the factorisation as ONE dependency-driven launch (rootkernel.hip.h, rootplan.cpp): static pivot order on one rank.  Bunch-Kaufman
-   // (a 454-register diagonal kernel) and the root distributed over ranks keep the launch-per-step driver (tail_factor / factor_distributed);
-   // PIPS_HIP_ROOT_LAUNCHES (set to any value) keeps it everywhere (the tests run both).
-   bool single_launch = !knob_set<K_ROOT_LAUNCHES>();
-   bool last_single = false;       // which driver the last factorisation took (pips_hip_dense_ldl_info)
-   DevBuf<double> d_C;             // the accumulating tiles (scratch): L goes to d_R, U to d_U, each written once per launch
-   DevBuf<TileTask> d_rtasks;
-   int n_rtasks = 0, n_rbulk = 0;
-   DevBuf<int> d_rflags;           // ctl[8] | prog[ntc * ntc] | rowdone[ntc] | dready[ntc]
-   double plan_makespan_us = 0.0;
-   long long root_poll_limit = 0;   // PIPS_HIP_ROOT_POLL_LIMIT (ensure_single_launch): polls before a wait inside the launch gives up (some 0.1 s: a factorisation takes 2 - 40 ms)
-   bool root_error_pending = false;
-   int ensure_single_launch() {
-      if (d_rtasks) return PIPS_OK;
-      const int ntc = npad / TILE;
-      RootPlanParams pp;
-      if (const int cu = knob_tri<K_ROOT_CHAIN_CU>(); cu >= 0) pp.chain_slots = cu ? 2 : 0;
-      if (pp.chain_slots == 0) pp.workers = 512;
-      std::vector<int> t, tc;
-      int rc = build_root_plan(ntc, pp, t, tc, &plan_makespan_us);
-      if (rc) return rc;
-      n_rbulk = (int)(t.size() / 4);
-      t.insert(t.end(), tc.begin(), tc.end());
-      n_rtasks = (int)(t.size() / 4);
-      PIPS_TRY(d_rtasks.alloc(std::max<size_t>(t.size() / 4, 1)));
-      HIP_TRY(hipMemcpy(d_rtasks, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
-      PIPS_TRY(d_rflags.alloc(((size_t)8 + (size_t)ntc * ntc + 2 * (size_t)ntc)));
-      PIPS_TRY(d_C.alloc((size_t)npad * npad));
-      root_poll_limit = knob_int<K_ROOT_POLL_LIMIT>();
-      return PIPS_OK;
-   }
-   int factor_single_launch() {
-      const int ntc = npad / TILE;
-      HIP_TRY(hipMemsetAsync(d_rflags, 0, ((size_t)8 + (size_t)ntc * ntc + 2 * (size_t)ntc) * sizeof(int), stream));
-      RootArgs a{};
-      a.tasks = d_rtasks; a.n_tasks = n_rtasks; a.n_bulk = n_rbulk; a.ntc = ntc; a.ld = npad;
-      a.C = d_C; a.R = d_R; a.U = d_U; a.winv = d_winv; a.dtail = d_dtail; a.pref = d_pref; a.psign = d_psign; a.inertia = d_inertia;
-      a.ctl = d_rflags; a.prog = d_rflags + 8; a.rowdone = a.prog + (size_t)ntc * ntc; a.dready = a.rowdone + ntc;
-      a.blk = d_blks; a.poll_limit = root_poll_limit;
-      a.diag_blocked = knob_int<K_ROOT_DIAG_BARRIERS>() ? 0 : 1;
-      const char* trace_file = knob_text<K_ROOT_TRACE>();
-      DevBuf<long long> d_trace;
-      if (trace_file) {
-         PIPS_TRY(d_trace.alloc(((size_t)3 * n_rtasks + 32 * (size_t)ntc)));
-         HIP_TRY(hipMemsetAsync(d_trace, 0, ((size_t)3 * n_rtasks + 32 * (size_t)ntc) * sizeof(long long), stream));
-         a.trace = d_trace;
-      }
-      hipLaunchKernelGGL(k_root_ldl, dim3(n_rtasks), dim3(512), 0, stream, a);
-      HIP_TRY(hipGetLastError());
-      root_error_pending = true;
-      if (trace_file) {
-         std::vector<long long> h((size_t)3 * n_rtasks + 32 * (size_t)ntc);
-         std::vector<int> ht((size_t)4 * n_rtasks);
-         HIP_TRY(hipStreamSynchronize(stream));
-         HIP_TRY(hipMemcpy(h.data(), d_trace, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-         HIP_TRY(hipMemcpy(ht.data(), d_rtasks, ht.size() * sizeof(int), hipMemcpyDeviceToHost));
-         d_trace.reset();
-         if (FILE* f = fopen(trace_file, "w")) {
-            for (int t = 0; t < n_rtasks; ++t)
-               fprintf(f, "%d %d %d %d %d %lld %lld %lld\n", t, ht[4 * t], ht[4 * t + 1], ht[4 * t + 2], ht[4 * t + 3], h[3 * (size_t)t], h[3 * (size_t)t + 1], h[3 * (size_t)t + 2]);
-            fclose(f);
-         }
-         if (FILE* f = fopen((std::string(trace_file) + ".diag").c_str(), "w")) {   // phase clocks of the diagonal tiles (blocked variant)
-            for (int jj = 0; jj < ntc; ++jj) {
-               for (int q = 0; q < 26; ++q) fprintf(f, "%lld ", h[(size_t)3 * n_rtasks + 32 * (size_t)jj + q]);
-               fprintf(f, "\n");
-            }
-            fclose(f);
-         }
-      }
-      return PIPS_OK;
-   }
-   // a wait inside the launch that gave up raised the error word; read at the host's next synchronisation point with this handle
-   int take_root_error(const char* who) {
-      if (!root_error_pending || !d_rflags) return PIPS_OK;
-      root_error_pending = false;
-      int w = 0;
-      HIP_TRY(hipMemcpyAsync(&w, d_rflags + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (w) PIPS_FAIL(PIPS_ERR_HIP, "%s: the single-launch root factorisation gave up waiting for a tile after %lld polls (its factors are invalid); "
-                                     "PIPS_HIP_ROOT_LAUNCHES (set to any value) selects the launch-per-step factorisation", who, root_poll_limit);
-      return PIPS_OK;
-   }
-   int init() {
-      HIP_TRY(hipSetDevice(device));
-      int rc = PIPS_OK;
-      npad = (n + TILE - 1) / TILE * TILE;
-      BlkDesc d{};
-      d.n = n; d.n_head = 0; d.m = n; d.m_pad = npad; d.nb = 0; d.nb_pad = 0; d.ldT = npad;
-      d.ntc = d.ntr = npad / TILE;
-      d.thr_rel = 0; d.repl_rel = 1e-8; d.repl_abs = 1;
-      h_blks.assign(1, d);
-      if ((rc = d_blks.upload(h_blks))) return rc;
-      // one block only: right-looking (measured on MI355X, tools/root_probe.py: S=2000 4.3 -> 2.3 ms, S=16000 183 -> 45 ms;
-      // panels of 1 tile column are best up to S = 8000, 2-3 beyond)
-      const int panel = d.ntc <= 64 ? 1 : 2;
-      // lookahead (second stream) pays once the trailing update of a panel outlasts a diagonal tile: S >= 6000 measured
-      const bool lookahead = d.ntc >= 48;
-      if ((rc = plan.build_root(h_blks, panel, lookahead))) return rc;
-      if ((rc = sweep.build(h_blks, nullptr))) return rc;
-      if (lookahead) {
-         int prio_lo = 0, prio_hi = 0;
-         HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-         HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, prio_lo));   // the bulk update: behind the diagonal chain
-         HIP_TRY(hipEventCreateWithFlags(&ev_panel, hipEventDisableTiming));
-         HIP_TRY(hipEventCreateWithFlags(&ev_rest, hipEventDisableTiming));
-      }
-      std::vector<signed char> ps(npad, 1);
-      for (int i = 0; i < n; ++i) ps[i] = n_primal < 0 ? 0 : (i < n_primal ? 1 : -1);
-      if ((rc = d_psign.upload(ps))) return rc;
-      std::vector<long long> zero(1, 0), kp = {0, (long long)npad};   // fallback magnitude from the diagonal only
-      if ((rc = d_psign_off.upload(zero))) return rc;
-      if ((rc = d_kptr.upload(kp))) return rc;
-      PIPS_TRY(d_R.alloc((size_t)npad * npad));
-      PIPS_TRY(d_U.alloc((size_t)npad * npad));
-      PIPS_TRY(d_winv.alloc((size_t)npad * TILE));
-      PIPS_TRY(d_dtail.alloc((size_t)npad));
-      PIPS_TRY(d_xw.alloc((size_t)npad));
-      PIPS_TRY(d_pref.alloc((size_t)npad));
-      PIPS_TRY(d_inertia.alloc(3));
-      return PIPS_OK;
-   }
-   TailCtx ctx() {
-      TailCtx c;
-      c.d_blks = d_blks; c.plan = &plan; c.d_arena = d_R; c.d_uarena = d_U; c.d_dtail = d_dtail; c.d_winv = d_winv;
-      c.d_psign = d_psign; c.d_psign_off = d_psign_off; c.d_inertia = d_inertia; c.d_pref = d_pref;
-      c.stream = stream; c.side = side; c.ev_panel = ev_panel; c.ev_rest = ev_rest;
-      c.is_root = true; c.sweep = &sweep; c.bunch_kaufman = pivoting == 1;
-      if (pivoting == 1) {
-         c.d_pert_cnt = d_pert_cnt; c.d_pert_list = d_pert_list;
-         c.bk_orig = last_A; c.bk_orig_ld = last_lda; c.bk_orig_rowmajor = last_rowmajor; c.d_bk_perm = perm.empty() ? nullptr : d_perm;
-         c.bk_isolate = bk_isolate;
-      }
-      return c;
-   }
-   // ---- Bunch-Kaufman beyond the tile.  k_tile_diag_bk searches its 128 x 128 tile; dsytrf searches the whole column
-   // (DeSymIndefSolver.C:78).  Where a tile finds no pivot for an index (a zero leading block coupled only to later rows: [[0 A^T]; [A 0]])
-   // the kernel records the row of the column's largest entry in the panel below.  check_pivots() - at the next host synchronisation
-   // point: the end of the host-pointer factor call, or the join with the root's stream before the first Dsolve - then moves every such
-   // row next to its column (a symmetric permutation P kept for the following factorisations: the structure that needed it comes back
-   // every iteration), factorises P A P^T again and goes on until no index is left without a pivot (at most BK_RETRIES times).  The
-   // pair then sits inside one tile, where the 2 x 2 pivot is found.  Solves permute their right-hand side in and out.
-   static constexpr int BK_RETRIES = 8;
-   static constexpr int BK_MAX_COLUMNS = 2048;   // columns per round whose original entries travel to the host for the partner choice
-   std::vector<int> perm;              // perm[i] = original index at position i (empty: identity)
-   DevBuf<int> d_perm;
-   DevBuf<int> d_pert_cnt, d_pert_list;
-   const double* last_A = nullptr;     // the matrix of the last factor_dev (the caller keeps it until the next factorisation)
-   int last_lda = 0, last_rowmajor = 0;
-   bool check_pending = false;
-   int bk_isolate = 1;                 // factorisations check_pivots will look at take an index without a pivot OUT of the matrix (k_tile_diag_bk)
-   int bk_refactorizations = 0;        // how often check_pivots had to factorise again (diagnostics / tests)
-   // indices (positions in the current order) the last factorisation found no pivot for: one rank - what its tile kernels recorded, in
-   // their order; a root distributed over several ranks - every rank recorded those of its own tile columns, the union (ascending) reaches
-   // every rank through an all-reduce of a 0 / 1 vector, so that all ranks go on to build the SAME pivot order
-   DevBuf<double> d_flagvec;
-   int flagged_positions(std::vector<int>& pos) {
-      pos.clear();
-      int cnt = 0;
-      HIP_TRY(hipMemcpyAsync(&cnt, d_pert_cnt, sizeof(int), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      cnt = std::min(cnt, npad);   // (an index flagged by the tile kernel AND the growth check counts twice: the kernels stop writing at npad records)
-      std::vector<int> rec((size_t)2 * std::max(cnt, 0));
-      if (cnt > 0) HIP_TRY(hipMemcpy(rec.data(), d_pert_list, rec.size() * sizeof(int), hipMemcpyDeviceToHost));
-      if (dist_P <= 1) {
-         for (int q = 0; q < cnt; ++q) pos.push_back(rec[2 * q]);
-         return PIPS_OK;
-      }
-      std::vector<double> flag((size_t)npad, 0.0);
-      for (int q = 0; q < cnt; ++q) if (rec[2 * q] >= 0 && rec[2 * q] < npad) flag[rec[2 * q]] = 1.0;
-      if (!d_flagvec) PIPS_TRY(d_flagvec.alloc((size_t)npad));
-      HIP_TRY(hipMemcpy(d_flagvec, flag.data(), flag.size() * sizeof(double), hipMemcpyHostToDevice));
-      int rc = pips_hip_allreduce_sum(dist_comm, d_flagvec, (size_t)npad, stream);
-      if (rc) return rc;
-      HIP_TRY(hipStreamSynchronize(stream));
-      HIP_TRY(hipMemcpy(flag.data(), d_flagvec, flag.size() * sizeof(double), hipMemcpyDeviceToHost));
-      for (int i = 0; i < n; ++i) if (flag[i] > 0.0) pos.push_back(i);
-      return PIPS_OK;
-   }
-   int check_pivots() {
-      if (!check_pending) return PIPS_OK;
-      check_pending = false;
-      if (pivoting != 1 || !d_pert_cnt) return PIPS_OK;
-      HIP_TRY(hipSetDevice(device));
-      std::vector<int> fpos;
-      for (int attempt = 0; attempt < BK_RETRIES; ++attempt) {
-         int rcf = flagged_positions(fpos);
-         if (rcf) return rcf;
-         const int cnt = (int)fpos.size();
-         if (cnt <= 0) return PIPS_OK;
-         std::vector<int> rec((size_t)2 * cnt, -1);
-         for (int q = 0; q < cnt; ++q) rec[2 * q] = fpos[q];
-         if (dist_P > 1) HIP_TRY(hipMemcpy(d_pert_list, rec.data(), std::min(rec.size(), (size_t)2 * npad) * sizeof(int), hipMemcpyHostToDevice));   // (k_bk_gather_columns reads the positions there)
-         // positions (in the current order) -> partner positions.  For every index without a pivot the column of the ORIGINAL matrix comes
-         // to the host; in the order the tiles reported them each takes the row with its largest entry that is still free (not itself
-         // without a pivot, not taken by an earlier column): the row a 2 x 2 pivot with this column needs ([[0 A^T]; [A 0]]: a row of A).
-         const int n_use = std::min(cnt, BK_MAX_COLUMNS);
-         std::vector<double> cols((size_t)n_use * n);
-         {
-            DevBuf<double> d_cols;
-            PIPS_TRY(d_cols.alloc(cols.size()));
-            hipLaunchKernelGGL(k_bk_gather_columns, dim3(std::max(1, std::min(64, (n + 255) / 256)), n_use), dim3(256), 0, stream, last_A, last_lda, last_rowmajor,
-                               perm.empty() ? (const int*)nullptr : (const int*)d_perm, n, d_pert_list, n_use, d_cols);
-            const hipError_t ec = hipMemcpy(cols.data(), d_cols, cols.size() * sizeof(double), hipMemcpyDeviceToHost);
-            d_cols.reset();
-            if (ec != hipSuccess) PIPS_FAIL(PIPS_ERR_HIP, "dense root: %s", hipGetErrorString(ec));
-         }
-         std::vector<int> partner(n, -1);
-         std::vector<char> taken(n, 0), flagged(n, 0);
-         for (int q = 0; q < cnt; ++q) if (rec[2 * q] >= 0 && rec[2 * q] < n) flagged[rec[2 * q]] = 1;
-         bool any = false;
-         for (int q = 0; q < n_use; ++q) {
-            const int c = rec[2 * q];
-            if (c < 0 || c >= n || partner[c] >= 0) continue;
-            const double* col = cols.data() + (size_t)q * n;
-            int best = -1;
-            for (int i = 0; i < n; ++i)
-               if (!flagged[i] && !taken[i] && col[i] > 0.0 && (best < 0 || col[i] > col[best])) best = i;
-            if (best < 0) continue;
-            partner[c] = best; taken[best] = 1; any = true;
-         }
-         if (!any) break;               // nothing below to pair with
-         std::vector<int> cur(n);
-         for (int i = 0; i < n; ++i) cur[i] = perm.empty() ? i : perm[i];
-         std::vector<int> next;
-         next.reserve(n);
-         std::vector<int> deferred;     // a pair must not straddle a tile boundary: an unpaired index goes in between
-         for (int i = 0; i < n; ++i) {
-            if (taken[i]) continue;      // emitted right behind its column (wherever it stood)
-            if (partner[i] >= 0) {
-               if ((int)next.size() % TILE == TILE - 1) {
-                  int filler = -1;
-                  for (int t = i + 1; t < n && filler < 0; ++t) if (!taken[t] && partner[t] < 0 && t != i && !flagged[t] && std::find(deferred.begin(), deferred.end(), t) == deferred.end()) filler = t;
-                  if (filler >= 0) { next.push_back(cur[filler]); deferred.push_back(filler); }
-               }
-               next.push_back(cur[i]);
-               next.push_back(cur[partner[i]]);
-            } else if (std::find(deferred.begin(), deferred.end(), i) == deferred.end())
-               next.push_back(cur[i]);
-         }
-         if ((int)next.size() != n) PIPS_FAIL(PIPS_ERR_STATE, "dense root: internal error building the pivot order (%zu of %d)", next.size(), n);
-         perm.swap(next);
-         if (!d_perm) PIPS_TRY(d_perm.alloc((size_t)std::max(n, 1)));
-         HIP_TRY(hipMemcpy(d_perm, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-         ++bk_refactorizations;
-         int rc = factor_enqueue();
-         if (rc) return rc;
-      }
-      // indices without a pivot are left: they get the usual small replacement (and are reported as perturbed pivots - what the
-      // regularisation loop of the caller reacts to) instead of being taken out of the matrix
-      {
-         int rcf = flagged_positions(fpos);
-         if (rcf) return rcf;
-         if (!fpos.empty()) {
-            bk_isolate = 0;
-            const int rc = factor_enqueue();
-            bk_isolate = 1;
-            if (rc) return rc;
-         }
-      }
-      return PIPS_OK;
-   }
-
-   // ---- distributed factorisation (several ranks, each with the whole reduced Schur complement): tile column j belongs to rank
-   // j mod P (1-D column-cyclic).  The owner factorises the diagonal tile and solves the column's panel, the panel (Winv_j, d_j, L(:, j),
-   // U(:, j)) goes to every rank, and every rank applies it to the tile columns it owns - 1 / P of the S^3 / 3 flops per rank instead
-   // of all of them on every rank (DistributedRootLinearSystem.C:1436-1464 has every rank call dsytrf on the same matrix).  At the
-   // end every rank holds the complete factor, so the solves stay local and replicated.  The panel travels by pips_hip_broadcast
-   // (ncclBroadcast / the host's broadcast callback; a host communicator without one: as an all-reduce in which the other ranks
-   // contribute zeros - exact, twice the bytes).  One column of lookahead (round 5): see factor_distributed.  NOT TIMED: the GPU box has one
-   // device; correctness with 2 and 4 processes sharing it (tests/test_dist_root_gpu.py).
-   void* dist_comm = nullptr;
-   int dist_rank = 0, dist_P = 1;
-   std::vector<TaskList> dist_diag, dist_trsm, dist_next, dist_upd;   // dist_next[j]: this rank's tiles of column j + 1 under panel j; dist_upd[j]: of its columns >= j + 2
-   DevBuf<TileTask> d_dist_tasks;
-   DevBuf<double> d_panel;
-   int set_distributed(void* comm, int rank, int P) {
-      if (P <= 1 || !comm) { dist_comm = nullptr; dist_P = 1; return PIPS_OK; }
-      if (rank < 0 || rank >= P) PIPS_FAIL(PIPS_ERR_ARG, "distributed root: rank %d of %d", rank, P);
-      HIP_TRY(hipSetDevice(device));
-      dist_comm = comm; dist_rank = rank; dist_P = P;
-      const int ntc = npad / TILE;
-      std::vector<TileTask> all;
-      dist_diag.assign(ntc, {}); dist_trsm.assign(ntc, {}); dist_next.assign(ntc, {}); dist_upd.assign(ntc, {});
-      for (int j = 0; j < ntc; ++j) {
-         dist_diag[j].off = (long long)all.size();
-         all.push_back({0, j, j, 0});
-         dist_diag[j].cnt = 1;
-         dist_trsm[j].off = (long long)all.size();
-         for (int ti = j + 1; ti < ntc; ++ti) all.push_back({0, ti, j, 0});
-         dist_trsm[j].cnt = (int)((long long)all.size() - dist_trsm[j].off);
-         dist_next[j].off = (long long)all.size();
-         if (j + 1 < ntc && (j + 1) % P == rank)
-            for (int ti = j + 1; ti < ntc; ++ti) all.push_back({0, ti, j + 1, j | ((j + 1) << 16)});   // C(ti, tk) -= L(ti, j) U(tk, j)^T
-         dist_next[j].cnt = (int)((long long)all.size() - dist_next[j].off);
-         dist_upd[j].off = (long long)all.size();
-         for (int tk = j + 2; tk < ntc; ++tk)
-            if (tk % P == rank)
-               for (int ti = tk; ti < ntc; ++ti) all.push_back({0, ti, tk, j | ((j + 1) << 16)});
-         dist_upd[j].cnt = (int)((long long)all.size() - dist_upd[j].off);
-      }
-      int rc = d_dist_tasks.upload(all);
-      if (rc) return rc;
-      if (!d_panel) PIPS_TRY(d_panel.alloc(((size_t)TILE * TILE + TILE + 8 + 2 * (size_t)npad * TILE)));
-      if (!side) {   // one column of lookahead: the bulk of a panel's update runs beside the factorisation and the broadcast of the next column
-         HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-         HIP_TRY(hipEventCreateWithFlags(&ev_panel, hipEventDisableTiming));
-         HIP_TRY(hipEventCreateWithFlags(&ev_rest, hipEventDisableTiming));
-      }
-      return PIPS_OK;
-   }
-   int factor_distributed() {
-      const TailCtx c = ctx();
-      const int ntc = npad / TILE;
-      const size_t ld_bytes = (size_t)npad * sizeof(double);
-      bool side_busy = false;
-      for (int j = 0; j < ntc; ++j) {
-         const int owner = j % dist_P;
-         const size_t rows = (size_t)npad - (size_t)(j + 1) * TILE;
-         const size_t head = (size_t)TILE * TILE + TILE + 8, count = head + 2 * rows * TILE;
-         double* Lp = d_panel + head;
-         double* Up = Lp + rows * TILE;
-         const size_t col0 = (size_t)(j + 1) * TILE + (size_t)j * TILE * npad;   // first entry below the diagonal tile of column j
-         if (owner == dist_rank) {
-            launch_tile_diag(c, d_dist_tasks, dist_diag[j], stream);   // (one tile: the list holds the diagonal tile of column j)
-            if (dist_trsm[j].cnt > 0) launch_tile_gemm<1>(c, d_dist_tasks, dist_trsm[j], stream);
-            // (the owner looks for multipliers a whole-column search would not allow, as on one rank: DenseLdl::check_pivots)
-            if (c.bunch_kaufman && c.d_pert_cnt && dist_trsm[j].cnt > 0)
-               hipLaunchKernelGGL(k_bk_growth, dim3(TILE), dim3(256), 0, stream, c.d_blks, c.d_arena, j, 1e8, c.d_pert_cnt, c.d_pert_list);
-            HIP_TRY(hipMemcpyAsync(d_panel, d_winv + (size_t)j * TILE * TILE, (size_t)TILE * TILE * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_panel + (size_t)TILE * TILE, d_dtail + (size_t)j * TILE, TILE * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemsetAsync(d_panel + (size_t)TILE * TILE + TILE, 0, 8 * sizeof(double), stream));
-            if (rows > 0) {
-               HIP_TRY(hipMemcpy2DAsync(Lp, rows * sizeof(double), d_R + col0, ld_bytes, rows * sizeof(double), TILE, hipMemcpyDeviceToDevice, stream));
-               HIP_TRY(hipMemcpy2DAsync(Up, rows * sizeof(double), d_U + col0, ld_bytes, rows * sizeof(double), TILE, hipMemcpyDeviceToDevice, stream));
-            }
-         } else if (!pips_hip_comm_has_broadcast(dist_comm))
-            HIP_TRY(hipMemsetAsync(d_panel, 0, count * sizeof(double), stream));   // (no broadcast primitive: the panel travels as an all-reduce of zeros)
-         int rc = pips_hip_broadcast(dist_comm, d_panel, count, owner, stream);
-         if (rc) return rc;
-         if (owner != dist_rank) {
-            HIP_TRY(hipMemcpyAsync(d_winv + (size_t)j * TILE * TILE, d_panel, (size_t)TILE * TILE * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_dtail + (size_t)j * TILE, d_panel + (size_t)TILE * TILE, TILE * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            if (rows > 0) {
-               HIP_TRY(hipMemcpy2DAsync(d_R + col0, ld_bytes, Lp, rows * sizeof(double), rows * sizeof(double), TILE, hipMemcpyDeviceToDevice, stream));
-               HIP_TRY(hipMemcpy2DAsync(d_U + col0, ld_bytes, Up, rows * sizeof(double), rows * sizeof(double), TILE, hipMemcpyDeviceToDevice, stream));
-            }
-         }
-         // One column of lookahead.  Panel j is applied in two pieces: this rank's tiles of column j + 1 on the main stream - the owner of that
-         // column goes on to factorise and broadcast it - and its columns >= j + 2 (the bulk) on the side stream, beside that.  Column j + 1
-         // also takes the bulk of panel j - 1: the main stream joins it first (ev_rest as recorded before this iteration's bulk).
-         const bool ahead = side && !knob_set<K_DIST_NO_LOOKAHEAD>();
-         hipStream_t bulk = ahead ? side : stream;
-         if (ahead) {
-            if (side_busy) HIP_TRY(hipStreamWaitEvent(stream, ev_rest, 0));
-            HIP_TRY(hipEventRecord(ev_panel, stream));          // panel j is in d_R / d_U on this rank
-            HIP_TRY(hipStreamWaitEvent(side, ev_panel, 0));
-         }
-         if (dist_upd[j].cnt > 0) launch_tile_gemm<3>(c, d_dist_tasks, dist_upd[j], bulk);
-         if (ahead) { HIP_TRY(hipEventRecord(ev_rest, side)); side_busy = true; }
-         if (dist_next[j].cnt > 0) launch_tile_gemm<3>(c, d_dist_tasks, dist_next[j], stream);
-      }
-      if (side_busy) HIP_TRY(hipStreamWaitEvent(stream, ev_rest, 0));
-      // every rank counted the pivots of its own diagonal tiles: the sum is the inertia
-      hipLaunchKernelGGL(k_inertia_to_double, dim3(1), dim3(64), 0, stream, d_inertia, d_panel, 0, d_inertia);
-      HIP_TRY(hipMemsetAsync(d_panel + 3, 0, 5 * sizeof(double), stream));
-      int rc = pips_hip_allreduce_sum(dist_comm, d_panel, 8, stream);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_inertia_to_double, dim3(1), dim3(64), 0, stream, d_inertia, d_panel, 1, d_inertia);
-      HIP_TRY(hipGetLastError());
-      return PIPS_OK;
-   }
-
-   // A_dev: n x n, symmetric, column-major with the lower triangle authoritative (== row-major with the upper one)
-   // rowmajor = 1: A_dev is row-major (the reference's DenseStorage), 0: column-major; lower triangle authoritative
-   int factor_dev(const double* A_dev, int lda, int rowmajor) {
-      last_A = A_dev; last_lda = lda; last_rowmajor = rowmajor;
-      int rc = factor_enqueue();
-      check_pending = pivoting == 1;
-      return rc;
-   }
-   int factor_enqueue() {
-      const double* A_dev = last_A;
-      const int lda = last_lda, rowmajor = last_rowmajor;
-      HIP_TRY(hipSetDevice(device));
-      if (pivoting == 1) {
-         if (!d_pert_cnt) {
-            PIPS_TRY(d_pert_cnt.alloc(1));
-            PIPS_TRY(d_pert_list.alloc((size_t)2 * std::max(npad, 1)));
-         }
-         HIP_TRY(hipMemsetAsync(d_pert_cnt, 0, sizeof(int), stream));
-      }
-      const bool single = single_launch && pivoting == 0 && dist_P <= 1;
-      last_single = single;
-      if (single) { const int rcs = ensure_single_launch(); if (rcs) return rcs; }
-      double* d_work = single ? d_C : d_R;   // where the matrix is accumulated: a scratch copy (single launch) or in place
-      hipLaunchKernelGGL(k_copy_lower_to_padded, dim3(grid_for((long long)npad * npad, 256)), dim3(256), 0, stream, A_dev,
-                         lda, n, d_work, npad, npad, rowmajor, perm.empty() ? (const int*)nullptr : (const int*)d_perm);
-      hipLaunchKernelGGL(k_pref_tail, dim3(8, 1), dim3(256), 0, stream, d_blks, d_work, d_pref, 1);
-      hipLaunchKernelGGL(k_block_absmax_init, dim3(1), dim3(256), 0, stream, d_blks, 1);
-      hipLaunchKernelGGL(k_block_absmax, dim3(8, 1), dim3(256), 0, stream, d_pref, d_kptr, d_blks);
-      hipLaunchKernelGGL(k_block_absmax_finish, dim3(1), dim3(256), 0, stream, d_blks, 1, thr_rel, repl_rel);
-      HIP_TRY(hipMemsetAsync(d_inertia, 0, 3 * sizeof(int), stream));
-      int rc = single ? factor_single_launch() : (dist_P > 1 ? factor_distributed() : tail_factor(ctx(), nullptr, 0));
-      if (rc) return rc;
-      factored = true;
-      return PIPS_OK;
-   }
-   int solve_dev(double* x_dev) {
-      if (!factored) PIPS_FAIL(PIPS_ERR_STATE, "dense solve called before factor");
-      HIP_TRY(hipSetDevice(device));
-      int rc = check_pivots();     // (a factorisation whose pivots were not looked at yet: host-pointer callers come here first)
-      if (rc) return rc;
-      HIP_TRY(hipMemsetAsync(d_xw, 0, (size_t)npad * sizeof(double), stream));
-      if (perm.empty()) HIP_TRY(hipMemcpyAsync(d_xw, x_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-      else hipLaunchKernelGGL(k_perm_gather, dim3(grid_for(n, 256)), dim3(256), 0, stream, d_perm, n, x_dev, d_xw, 0, (double*)nullptr);
-      rc = tail_fwd(ctx(), d_xw);
-      if (rc) return rc;
-      rc = tail_bwd(ctx(), d_xw);
-      if (rc) return rc;
-      if (perm.empty()) HIP_TRY(hipMemcpyAsync(x_dev, d_xw, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-      else hipLaunchKernelGGL(k_perm_gather, dim3(grid_for(n, 256)), dim3(256), 0, stream, d_perm, n, (const double*)nullptr, d_xw, 1, x_dev);
-      return PIPS_OK;
-   }
-};
+#include "denseroot.hip.h"
 
 // add_regularization_local_kkt (DistributedLeafLinearSystem.C:108-143): K diag += primal on the leading n_primal rows,
 // -= dual on the rest
@@ -2470,16 +2011,6 @@ int pips_hip_device_count(void) {
    int n = 0;
    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
    return n;
-}
-
-static int resolve_device(int device, int* out) {
-   int cnt = 0;
-   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0)
-      PIPS_FAIL(PIPS_ERR_NO_DEVICE, "no HIP device visible: the MI355X backend has no CPU fallback");
-   if (device < 0) { HIP_TRY(hipGetDevice(&device)); }
-   if (device >= cnt) PIPS_FAIL(PIPS_ERR_ARG, "device %d out of range (%d visible)", device, cnt);
-   *out = device;
-   return PIPS_OK;
 }
 
 // ---- batch -------------------------------------------------------------------------------------------------------
@@ -2778,793 +2309,7 @@ int pips_hip_batch_get_timing(void* handle, double* ms, int64_t* cnt, int n) {
 
 void pips_hip_batch_destroy(void* handle) { delete (Engine*)handle; }
 
-// ---- single leaf solver handle -------------------------------------------------------------------------------------
-struct LdlGroup;
-// pips_hip_ldl_factor_schur of single handles: the leaf kernels address the Schur complement as a dense S x S array, but a leaf only touches
-// the nb x nb entries of its non-empty border columns - one S x S scratch array per DEVICE serves every handle (a call leaves it with a
-// stream synchronisation; 64 handles with an array each were 32 GB at S = 8000), and only the compact nb x nb block travels to the host.
-struct SchurScratch {
-   std::mutex mu;
-   std::map<int, DevBuf<double>> per_device;   // device -> array
-};
-static SchurScratch& g_schur_scratch = *new SchurScratch;   // (never destroyed: nothing is freed while the process exits)
-
-// C[i + j * nb] = SC[bm[i] + bm[j] * ld] (the block of a leaf's border columns, column-major; the lower triangle is what the caller reads) -
-// and SC is left zero on the whole block, whichever triangle a Schur mode wrote
-__global__ void k_schur_take_block(double* __restrict__ SC, int ld, const int* __restrict__ bm, int nb, double* __restrict__ C) {
-   const int j = blockIdx.y;
-   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nb; i += gridDim.x * blockDim.x) {
-      double* p = SC + bm[i] + (long long)bm[j] * ld;
-      C[i + (long long)j * nb] = *p;
-      *p = 0.0;
-   }
-}
-
-// Where a handle's (or a bound group's) Schur term goes: the caller's dense S x S matrix (pips_hip_ldl_factor_schur / _batch) or its
-// sparse one (pips_hip_ldl_factor_schur_sparse / _batch).  The first call with a Schur complement settles it for the handle's life: the
-// sparse entries move the kernels' targets into position tables (Engine::set_sc_tables), the dense ones address S x S.
-enum { SC_KIND_NONE = 0, SC_KIND_DENSE = 1, SC_KIND_SPARSE = 2 };
-// The sparse target (schurtarget.h): T doubles on the device, the T positions they belong to in the caller's value array, and what
-// identifies the pattern in later calls - nothing of size S x S or nnz
-struct SparseSchurBind {
-   bool bound = false;
-   SchurPatternId id;
-   std::vector<long long> pos;
-   DevBuf<double> d_val;
-   std::vector<double> h_val;
-};
-
-struct LdlHandle {
-   Engine eng;
-   bool have_perm = false;
-   int sc_kind = SC_KIND_NONE;
-   SparseSchurBind sparse_sc;
-   DevBuf<double> d_sc;           // compact nb x nb Schur term of this leaf (pips_hip_ldl_factor_schur)
-   std::vector<double> h_sc;
-   std::shared_ptr<LdlGroup> group;   // the leaves of a rank bound into one batch engine (pips_hip_ldl_factor_schur_batch)
-   int group_index = -1;
-   // which engine holds this leaf's NEWEST factors: the batch's (set for every member by pips_hip_ldl_factor_schur_batch) or the handle's
-   // own (pips_hip_ldl_factor / _factor_schur clear it) - a handle can go through both over its life (matrixChanged() alone, later the
-   // host's loop handed over), and solve / inertia must never answer from the older of the two
-   bool newest_in_group = false;
-   ~LdlHandle();
-};
-// Array-of-handles entries (INTEGRATION.md level 1.5b): the reference keeps one DoubleLinearSolver per leaf and loops over its children
-// (sLinsysRootAug::assembleLocalKKT :210-227, Lsolve / Ltsolve :323-365).  One leaf alone is a latency chain on the device (64 leaves of
-// configs[1] one after the other: 1.17 s per factorisation against 0.1 s as one batch), so the handles of a rank can be bound into ONE batch
-// engine: the patterns and borders the handles were given, analysed together; factor_schur_batch / solve_batch then run all leaves in every
-// launch, one S x S Schur buffer on the device and one transfer of it per factorisation instead of one per leaf.
-struct LdlGroup {
-   Engine eng;
-   std::vector<LdlHandle*> members;
-   DevBuf<double> d_sc, d_x;
-   std::vector<double> h_sc;
-   int sc_kind = SC_KIND_NONE;
-   SparseSchurBind sparse_sc;
-};
-// a handle that goes away leaves an empty slot in its group: the siblings keep the batch's factors (their own solves go through
-// group_solve_rows, which needs no sibling), the next array-of-handles call sees another array and binds anew
-LdlHandle::~LdlHandle() {
-   if (group && group_index >= 0 && group_index < (int)group->members.size() && group->members[group_index] == this) group->members[group_index] = nullptr;
-}
-// array-of-handles solves / queries answer from the batch's factors: refuse if a member has been factorised alone since
-static int ldl_group_is_current(const LdlGroup& g, const char* who) {
-   if (!g.eng.factored) PIPS_FAIL(PIPS_ERR_STATE, "%s: pips_hip_ldl_factor_schur_batch first", who);
-   for (size_t i = 0; i < g.members.size(); ++i)
-      if (g.members[i] && !g.members[i]->newest_in_group)
-         PIPS_FAIL(PIPS_ERR_STATE, "%s: handle %d was factorised on its own after the batch's factorisation - factorise the array again", who, (int)i);
-   return PIPS_OK;
-}
-static inline bool ldl_uses_group(const LdlHandle* h) { return h->group && h->newest_in_group && h->group->eng.factored; }
-// one member's right-hand sides through the batch engine (every block in every launch, the others with zeros - correct, and as long as
-// a batch solve: hosts that loop over their leaves should hand the loop over, pips_hip_ldl_solve_batch).  rhs: nrhs rows of length ld,
-// on the host or on the device
-static int group_solve_rows(LdlGroup& g, int index, int nrhs, double* rhs, long long ld, bool on_device, const char* who) {
-   Engine& e = g.eng;
-   HIP_TRY(hipSetDevice(e.device));
-   if (!g.d_x) PIPS_TRY(g.d_x.alloc((size_t)std::max<long long>(e.n_total, 1)));
-   const size_t cnt = (size_t)(e.x_off[index + 1] - e.x_off[index]) * sizeof(double);
-   for (int r = 0; r < nrhs; ++r) {
-      HIP_TRY(hipMemsetAsync(g.d_x, 0, (size_t)e.n_total * sizeof(double), e.stream));
-      HIP_TRY(hipMemcpyAsync(g.d_x + e.x_off[index], rhs + (size_t)r * ld, cnt, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e.stream));
-      int rc = e.solve(g.d_x);
-      if (rc) return rc;
-      HIP_TRY(hipMemcpyAsync(rhs + (size_t)r * ld, g.d_x + e.x_off[index], cnt, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e.stream));
-   }
-   if (!on_device) HIP_TRY(hipStreamSynchronize(e.stream));
-   return e.sweep.take_error(who);
-}
-
-int pips_hip_ldl_create(void** handle, int n, const int* krow, const int* jcol, int device, int flags) {
-   (void)flags;
-   if (!handle || n <= 0 || !krow || !jcol) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_create: bad arguments");
-   auto h = std::make_unique<LdlHandle>();
-   h->eng.nblk = 1;
-   h->eng.S = 0;
-   h->eng.device = device;
-   h->eng.in.assign(1, BlockInput());
-   BlockInput& in = h->eng.in[0];
-   in.n = n;
-   in.krow.assign(krow, krow + n + 1);
-   in.kcol.assign(jcol, jcol + krow[n]);
-   *handle = h.release();
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_set_inertia_hint(void* handle, int n_primal) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   h->eng.in[0].n_primal = n_primal;
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_set_pivot_rule(void* handle, double thr_rel, double repl_rel) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   h->eng.thr_rel = thr_rel;
-   h->eng.repl_rel = repl_rel;
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_set_refinement(void* handle, int max_steps, double tol) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   h->eng.refine_steps = max_steps;
-   h->eng.refine_tol = tol;
-   h->eng.refine_mode = 0;
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_set_deterministic(void* handle, int on) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   if (h->eng.analyzed) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_set_deterministic: before the first factorisation (the symbolic phase builds the slot lists)");
-   h->eng.deterministic = on != 0;
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_set_refinement_backward_error(void* handle, int max_steps, double tol) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || max_steps < 0 || tol < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_set_refinement_backward_error: bad arguments");
-   h->eng.refine_steps = max_steps;
-   h->eng.refine_tol = tol;
-   h->eng.refine_mode = 1;
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_analyze(void* handle) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   return pips_hip_batch_analyze(&h->eng, 1);
-}
-
-int pips_hip_ldl_factor(void* handle, const double* vals_host) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || !vals_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor: bad arguments");
-   if (!h->eng.analyzed) {
-      int rc = pips_hip_ldl_analyze(handle);
-      if (rc) return rc;
-   }
-   int rc = pips_hip_batch_set_values(&h->eng, 0, vals_host);
-   if (rc) return rc;
-   rc = h->eng.factor(nullptr, 0);
-   if (rc) return rc;
-   h->newest_in_group = false;      // (the batch's copy of this leaf is the older one now)
-   HIP_TRY(hipStreamSynchronize(h->eng.stream));
-   return PIPS_OK;
-}
-
-// The values alone: the twin of pips_hip_batch_set_values for a leaf handle.  The factors stay as they are - the solve sweeps read only
-// them - and the residual and the measure of the refinement read the new values: later solves refine against these values with the
-// factors they have.  (A handle whose newest factors are a group's has its values there, not here.)
-int pips_hip_ldl_set_values(void* handle, const double* K_val_host) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || !K_val_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_set_values: bad arguments");
-   if (ldl_uses_group(h)) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_set_values: the newest factors of this handle are a batch's (pips_hip_ldl_factor_schur_batch)");
-   if (!h->eng.factored) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_set_values: factor first");
-   return pips_hip_batch_set_values(&h->eng, 0, K_val_host);
-}
-
-// The leaf's Schur term without dense border columns over PCIe.  The border Br_i^T (S x n CSR, rows = Schur column ids: the
-// reference's border_left_transp, DistributedLeafLinearSystem.C:214-252) is declared before the analysis; factor_schur factorises
-// K_i and adds  -Br_i^T K_i^-1 Br_i  to the caller's Schur complement: what the K4-K6 chunk loop
-// (addBiTLeftKiBiRightToResBlockedParallelSolvers, DistributedLinearSystem.C:766-1047: densify <= 20 T border columns,
-// solve(nrhs, ...), sparse product back) computes, but with only the CSR values going up and the S x S term coming down.
-int pips_hip_ldl_set_border(void* handle, int S, const int* Bt_rowptr, const int* Bt_colidx) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || S <= 0 || !Bt_rowptr || !Bt_colidx) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_set_border: bad arguments");
-   if (h->eng.analyzed) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_set_border: declare the border before pips_hip_ldl_analyze / the first factor");
-   BlockInput& in = h->eng.in[0];
-   for (int p = 0; p < Bt_rowptr[S]; ++p)
-      if (Bt_colidx[p] < 0 || Bt_colidx[p] >= in.n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_set_border: column %d outside the leaf (n = %d)", Bt_colidx[p], in.n);
-   h->eng.S = S;
-   in.btrow.assign(Bt_rowptr, Bt_rowptr + S + 1);
-   in.btcol.assign(Bt_colidx, Bt_colidx + Bt_rowptr[S]);
-   in.btval.assign((size_t)Bt_rowptr[S], 0.0);
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_factor_schur(void* handle, const double* K_vals_host, const double* Bt_vals_host, double* SC_host, int ldSC) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || !K_vals_host || !Bt_vals_host || !SC_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur: bad arguments");
-   Engine& e = h->eng;
-   const int S = e.S;
-   if (S <= 0 || e.in[0].btrow.empty()) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur: no border declared (pips_hip_ldl_set_border)");
-   if (ldSC < S) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur: ldSC %d < S %d", ldSC, S);
-   if (h->sc_kind == SC_KIND_SPARSE) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur: the Schur target of this handle is sparse (pips_hip_ldl_factor_schur_sparse): one kind per handle");
-   h->sc_kind = SC_KIND_DENSE;
-   int rc;
-   if (!e.analyzed && (rc = pips_hip_ldl_analyze(handle))) return rc;
-   HIP_TRY(hipSetDevice(e.device));
-   if ((rc = pips_hip_batch_set_values(&e, 0, K_vals_host))) return rc;
-   if (e.nnzB_total > 0) HIP_TRY(hipMemcpyAsync(e.d_bval, Bt_vals_host, (size_t)e.nnzB_total * sizeof(double), hipMemcpyHostToDevice, e.stream));
-   const BlockSym& bs = e.sym[0];
-   const int nb = (int)bs.bmap.size();
-   // the device's shared S x S scratch array: zero on entry (allocated zeroed; every call takes its block out again and leaves zeros)
-   // (held to the end of the call: host threads that factorise their leaves side by side take turns on the scratch array)
-   std::lock_guard<std::mutex> scratch_lock(g_schur_scratch.mu);
-   DevBuf<double>& slot = g_schur_scratch.per_device[e.device];
-   if (slot.size() < (size_t)S * S) PIPS_TRY(slot.alloc_zero((size_t)S * S));
-   double* scratch = slot;
-   if ((rc = e.factor(scratch, S))) {   // (whatever reached the scratch array must not meet the next handle)
-      (void)hipStreamSynchronize(e.stream);
-      (void)hipMemset(scratch, 0, (size_t)S * S * sizeof(double));
-      return rc;
-   }
-   h->newest_in_group = false;
-   if (nb > 0) {
-      if (!h->d_sc) PIPS_TRY(h->d_sc.alloc((size_t)nb * nb));
-      hipLaunchKernelGGL(k_schur_take_block, dim3(std::max(1, std::min(16, (nb + 255) / 256)), nb), dim3(256), 0, e.stream, scratch, S, e.d_bmap, nb, h->d_sc);
-      h->h_sc.resize((size_t)nb * nb);
-      HIP_TRY(hipMemcpyAsync(h->h_sc.data(), h->d_sc, (size_t)nb * nb * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-   }
-   HIP_TRY(hipStreamSynchronize(e.stream));
-   // device: column-major with the lower triangle valid; caller: row-major DenseSymmetricMatrix, lower triangle meaningful
-   // (DenseStorage.C:64-83): entry [i][j], i >= j, takes the device's (i, j) - only the rows of this leaf's non-empty border columns differ from zero
-   for (int j = 0; j < nb; ++j)
-      for (int i = j; i < nb; ++i) SC_host[(size_t)bs.bmap[i] * ldSC + bs.bmap[j]] += h->h_sc[(size_t)i + (size_t)j * nb];
-   return e.sweep.take_error("pips_hip_ldl_factor_schur");
-}
-
-extern "C" int pips_hip_ldl_solve_batch(void* const* handles, int n, double* const* rhs_inout_host);
-// flags[q] = 1 where column q of X (ld apart, n entries) has an entry that is not zero (a NaN counts)
-__global__ __launch_bounds__(256) void k_columns_nonzero(const double* __restrict__ X, long long ld, int n, int* __restrict__ flags) {
-   const double* v = X + ld * blockIdx.x;
-   int any = 0;
-   for (int i = threadIdx.x; i < n; i += 256) any |= (v[i] != 0.0) ? 1 : 0;
-   any = __syncthreads_or(any);
-   if (threadIdx.x == 0) flags[blockIdx.x] = any ? 1 : 0;
-}
-
-int pips_hip_ldl_solve(void* handle, int nrhs, double* rhs, int ld) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || nrhs < 0 || !rhs || ld < h->eng.in[0].n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_solve: bad arguments");
-   if (ldl_uses_group(h))   // the newest factors of this leaf are the batch's
-      return group_solve_rows(*h->group, h->group_index, nrhs, rhs, ld, false, "pips_hip_ldl_solve");
-   Engine& e = h->eng;
-   if (!e.factored) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_solve: factor first");
-   if (nrhs == 0) return PIPS_OK;
-   HIP_TRY(hipSetDevice(e.device));
-   const size_t row = (size_t)e.n_total * sizeof(double);
-   if (nrhs == 1) {
-      HIP_TRY(hipMemcpyAsync(e.d_stage, rhs, row, hipMemcpyHostToDevice, e.stream));
-      int rc = e.solve(e.d_stage);
-      if (rc) return rc;
-      HIP_TRY(hipMemcpyAsync(rhs, e.d_stage, row, hipMemcpyDeviceToHost, e.stream));
-      HIP_TRY(hipStreamSynchronize(e.stream));
-      return PIPS_OK;
-   }
-   // all right-hand sides in one pass (one RHS per row of length ld).  Like PardisoSolver::solve (PardisoSolver.C:276-352) only the non-zero
-   // right-hand sides are solved.  Which ones those are is found on the device AFTER the upload: a scan on the host walks every column up
-   // to its first entry - the border columns of a chunk have theirs in the dual rows, behind 10 000 zeros each, 1.3 ms per call of 160 -
-   // while the whole chunk crosses the link in 0.35 ms and the flags come back with one small copy.
-   // (the device copy of the right-hand sides stays with the handle: the reference's loop calls this hundreds of times per factorisation
-   // with the same chunk size, an allocation and a release per call were a fifth of a millisecond each)
-   const size_t flag_bytes = ((size_t)nrhs * sizeof(int) + 15) & ~(size_t)15;
-   const size_t hostx_doubles = ((size_t)nrhs * row + flag_bytes) / sizeof(double);
-   if (e.d_hostx.size() < hostx_doubles) {
-      if (e.d_hostx) HIP_TRY(hipStreamSynchronize(e.stream));
-      PIPS_TRY(e.d_hostx.reserve(hostx_doubles));
-   }
-   double* d_X = e.d_hostx;
-   int* d_flags = (int*)(d_X + (size_t)nrhs * e.n_total);
-   std::vector<int> flags((size_t)nrhs), nz;
-   HIP_TRY(hipMemcpy2DAsync(d_X, row, rhs, (size_t)ld * sizeof(double), row, nrhs, hipMemcpyHostToDevice, e.stream));
-   hipLaunchKernelGGL(k_columns_nonzero, dim3(nrhs), dim3(256), 0, e.stream, d_X, (long long)e.n_total, (int)e.n_total, d_flags);
-   HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, (size_t)nrhs * sizeof(int), hipMemcpyDeviceToHost, e.stream));
-   HIP_TRY(hipStreamSynchronize(e.stream));
-   nz.reserve(nrhs);
-   for (int r = 0; r < nrhs; ++r) if (flags[r]) nz.push_back(r);
-   const int nnz_rhs = (int)nz.size();
-   if (nnz_rhs == 0) return PIPS_OK;
-   hipError_t err = hipSuccess;
-   if (nnz_rhs < nrhs)   // the non-zero columns move to the front (ascending: a column never lands on one that is still to move)
-      for (int q = 0; q < nnz_rhs && err == hipSuccess; ++q)
-         if (nz[q] != q) err = hipMemcpyAsync(d_X + (size_t)q * e.n_total, d_X + (size_t)nz[q] * e.n_total, row, hipMemcpyDeviceToDevice, e.stream);
-   int rc = err == hipSuccess ? (nnz_rhs == 1 ? e.solve(d_X) : e.solve_multi(d_X, nnz_rhs, e.n_total)) : PIPS_ERR_HIP;
-   if (!rc) {
-      if (nnz_rhs == nrhs)
-         err = hipMemcpy2DAsync(rhs, (size_t)ld * sizeof(double), d_X, row, row, nrhs, hipMemcpyDeviceToHost, e.stream);
-      else
-         for (int q = 0; q < nnz_rhs && err == hipSuccess; ++q)
-            err = hipMemcpyAsync(rhs + (size_t)nz[q] * ld, d_X + (size_t)q * e.n_total, row, hipMemcpyDeviceToHost, e.stream);
-   }
-   if (err == hipSuccess) err = hipStreamSynchronize(e.stream);
-   if (rc) return rc;
-   if (err != hipSuccess) PIPS_FAIL(PIPS_ERR_HIP, "pips_hip_ldl_solve: %s", hipGetErrorString(err));
-   return PIPS_OK;
-}
-
-// ---- device-pointer and sparse-row variants of the per-leaf solve
-int pips_hip_ldl_solve_dev(void* handle, int nrhs, double* rhs_inout_dev, long long ld) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || nrhs < 1 || !rhs_inout_dev || ld < h->eng.in[0].n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_solve_dev: bad arguments");
-   if (ldl_uses_group(h)) return group_solve_rows(*h->group, h->group_index, nrhs, rhs_inout_dev, ld, true, "pips_hip_ldl_solve_dev");
-   Engine& e = h->eng;
-   if (!e.factored) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_solve_dev: factor first");
-   HIP_TRY(hipSetDevice(e.device));
-   return nrhs == 1 ? e.solve(rhs_inout_dev) : e.solve_multi(rhs_inout_dev, nrhs, ld);
-}
-
-// rows[i] = rhs row (0 <= row < n) of packed entry i: X[q * ld + rows[i]] = packed[q * n_rows + i]
-__global__ void k_expand_rows(const int* __restrict__ rows, int n_rows, const double* __restrict__ packed, double* __restrict__ X, long long ld, int nrhs) {
-   const long long total = (long long)n_rows * nrhs;
-   for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-      const int q = (int)(idx / n_rows), i = (int)(idx - (long long)q * n_rows);
-      X[q * ld + rows[i]] = packed[idx];
-   }
-}
-
-// = DoubleLinearSolver::solve(int nrhss, double* rhss, int* colSparsity) with the third argument honoured: colSparsity[i] != 0 marks the rows
-// that can be non-zero in any of the right-hand sides (the caller's border_left_transp pattern, DistributedLinearSystem.C:903).  Only those
-// rows of the non-zero right-hand sides travel to the device (the solutions come back dense: K^-1 fills them).
-int pips_hip_ldl_solve_sparse(void* handle, int nrhs, double* rhs, int ld, const int* col_sparsity) {
-   if (!col_sparsity) return pips_hip_ldl_solve(handle, nrhs, rhs, ld);
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || nrhs < 0 || !rhs || ld < h->eng.in[0].n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_solve_sparse: bad arguments");
-   if (ldl_uses_group(h)) return pips_hip_ldl_solve(handle, nrhs, rhs, ld);   // (through the batch every row travels: colSparsity saves nothing there)
-   Engine& e = h->eng;
-   if (!e.factored) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_solve_sparse: factor first");
-   HIP_TRY(hipSetDevice(e.device));
-   const int n = (int)e.n_total;
-   std::vector<int> rows, nz;
-   for (int i = 0; i < n; ++i) if (col_sparsity[i]) rows.push_back(i);
-   // where most rows are marked the whole columns travel faster than a pack on the host (the union over a chunk of 160 border columns of
-   // configs[1] marks a fifth of the rows; 19 MB cross the link in 0.35 ms): the pack pays below an eighth
-   if ((long long)rows.size() * 8 >= n) return pips_hip_ldl_solve(handle, nrhs, rhs, ld);
-   for (int r = 0; r < nrhs; ++r) {
-      const double* v = rhs + (size_t)r * ld;
-      bool any = false;
-      for (int i : rows) if (v[i] != 0.0) { any = true; break; }
-      if (any) nz.push_back(r);
-   }
-   const int nq = (int)nz.size(), nr = (int)rows.size();
-   if (nq == 0) return PIPS_OK;
-   std::vector<double> packed((size_t)nq * nr);
-   for (int q = 0; q < nq; ++q) {
-      const double* v = rhs + (size_t)nz[q] * ld;
-      for (int i = 0; i < nr; ++i) packed[(size_t)q * nr + i] = v[rows[i]];
-   }
-   // (device copies kept with the handle, like pips_hip_ldl_solve's: no allocation and release per call)
-   const size_t row = (size_t)n * sizeof(double), pack_bytes = packed.size() * sizeof(double) + (size_t)nr * sizeof(int);
-   const size_t pack_doubles = (pack_bytes + sizeof(double) - 1) / sizeof(double);
-   if (e.d_hostx.size() < (size_t)nq * n) {
-      if (e.d_hostx) HIP_TRY(hipStreamSynchronize(e.stream));
-      PIPS_TRY(e.d_hostx.reserve((size_t)nq * n));
-   }
-   if (e.d_hostpack.size() < pack_doubles) {
-      if (e.d_hostpack) HIP_TRY(hipStreamSynchronize(e.stream));
-      PIPS_TRY(e.d_hostpack.reserve(pack_doubles));
-   }
-   double *d_X = e.d_hostx, *d_packed = e.d_hostpack;
-   int* d_rows = (int*)(e.d_hostpack + packed.size());
-   hipError_t err = hipMemcpyAsync(d_packed, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, e.stream);
-   if (err == hipSuccess) err = hipMemcpyAsync(d_rows, rows.data(), (size_t)nr * sizeof(int), hipMemcpyHostToDevice, e.stream);
-   if (err == hipSuccess) err = hipMemsetAsync(d_X, 0, (size_t)nq * row, e.stream);
-   int rc = PIPS_OK;
-   if (err == hipSuccess) {
-      hipLaunchKernelGGL(k_expand_rows, dim3(grid_for((long long)nq * nr, 256)), dim3(256), 0, e.stream, d_rows, nr, d_packed, d_X, (long long)n, nq);
-      rc = nq == 1 ? e.solve(d_X) : e.solve_multi(d_X, nq, n);
-      if (!rc && nq == nrhs)
-         err = hipMemcpy2DAsync(rhs, (size_t)ld * sizeof(double), d_X, row, row, nrhs, hipMemcpyDeviceToHost, e.stream);
-      else
-         for (int q = 0; q < nq && !rc && err == hipSuccess; ++q)
-            err = hipMemcpyAsync(rhs + (size_t)nz[q] * ld, d_X + (size_t)q * n, row, hipMemcpyDeviceToHost, e.stream);
-      if (err == hipSuccess) err = hipStreamSynchronize(e.stream);   // (the host vectors packed / rows live until here)
-   }
-   if (rc) return rc;
-   if (err != hipSuccess) PIPS_FAIL(PIPS_ERR_HIP, "pips_hip_ldl_solve_sparse: %s", hipGetErrorString(err));
-   return PIPS_OK;
-}
-
-// ---- array-of-handles entries
-// one kind of Schur target per handle and per bound group for their lives: refuse the other one, else take this one
-static int ldl_group_kind(LdlGroup& g, int kind, const char* who) {
-   bool other = g.sc_kind != SC_KIND_NONE && g.sc_kind != kind;
-   for (LdlHandle* m : g.members) other = other || (m && m->sc_kind != SC_KIND_NONE && m->sc_kind != kind);
-   if (other)
-      PIPS_FAIL(PIPS_ERR_STATE, "%s: the Schur target of these handles is %s: one kind per handle", who,
-                kind == SC_KIND_DENSE ? "sparse (pips_hip_ldl_factor_schur_sparse / _batch)" : "dense (pips_hip_ldl_factor_schur / _batch)");
-   g.sc_kind = kind;
-   for (LdlHandle* m : g.members) if (m) m->sc_kind = kind;
-   return PIPS_OK;
-}
-
-// want_det (the sparse entries): the batch engine in deterministic mode - a binding that is not is replaced
-static int ldl_group_of(void* const* handles, int n, std::shared_ptr<LdlGroup>& out, bool want_det = false) {
-   if (!handles || n <= 0) PIPS_FAIL(PIPS_ERR_ARG, "array of leaf handles: bad arguments");
-   LdlHandle* h0 = (LdlHandle*)handles[0];
-   if (!h0) PIPS_FAIL(PIPS_ERR_ARG, "array of leaf handles: null handle");
-   bool same = h0->group && (int)h0->group->members.size() == n && (!want_det || h0->group->eng.deterministic);
-   for (int i = 0; i < n && same; ++i) same = handles[i] && h0->group->members[i] == (LdlHandle*)handles[i];
-   if (same) { out = h0->group; return PIPS_OK; }
-   // bind: one batch engine over the patterns (and borders) the handles hold
-   auto g = std::make_shared<LdlGroup>();
-   Engine& e = g->eng;
-   e.nblk = n;
-   e.S = h0->eng.S;
-   e.device = h0->eng.device;
-   e.thr_rel = h0->eng.thr_rel; e.repl_rel = h0->eng.repl_rel;
-   e.refine_steps = h0->eng.refine_steps; e.refine_tol = h0->eng.refine_tol; e.refine_mode = h0->eng.refine_mode;
-   e.deterministic = want_det;
-   e.in.resize(n);
-   for (int i = 0; i < n; ++i) {
-      LdlHandle* h = (LdlHandle*)handles[i];
-      if (!h) PIPS_FAIL(PIPS_ERR_ARG, "array of leaf handles: null handle at %d", i);
-      if (h->eng.S != e.S) PIPS_FAIL(PIPS_ERR_ARG, "array of leaf handles: handle %d declares Schur dimension %d, handle 0 %d", i, h->eng.S, e.S);
-      if (h->eng.device != e.device) PIPS_FAIL(PIPS_ERR_ARG, "array of leaf handles: handles on different devices");
-      e.in[i] = h->eng.in[0];
-      g->members.push_back(h);
-   }
-   int rc = pips_hip_batch_analyze(&e, std::min(n, 16));
-   if (rc) return rc;
-   for (int i = 0; i < n; ++i) { ((LdlHandle*)handles[i])->group = g; ((LdlHandle*)handles[i])->group_index = i; }
-   out = g;
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_factor_schur_batch(void* const* handles, int n, const double* const* K_vals_host, const double* const* Bt_vals_host, double* SC_host,
-                                    int ldSC) {
-   std::shared_ptr<LdlGroup> g;
-   int rc = ldl_group_of(handles, n, g);
-   if (rc) return rc;
-   if (!K_vals_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_batch: no values");
-   Engine& e = g->eng;
-   const int S = e.S;
-   const bool schur = SC_host != nullptr;
-   if (schur && (S <= 0 || ldSC < S || !Bt_vals_host)) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_batch: Schur term asked for without border / ldSC %d < S %d", ldSC, S);
-   if (schur) {
-      if ((rc = ldl_group_kind(*g, SC_KIND_DENSE, "pips_hip_ldl_factor_schur_batch"))) return rc;
-   }
-   HIP_TRY(hipSetDevice(e.device));
-   for (int i = 0; i < n; ++i) {
-      if (!K_vals_host[i]) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_batch: no values for leaf %d", i);
-      HIP_TRY(hipMemcpyAsync(e.d_kval + e.kptr[i], K_vals_host[i], (size_t)(e.kptr[i + 1] - e.kptr[i]) * sizeof(double), hipMemcpyHostToDevice, e.stream));
-   }
-   if (schur && e.nnzB_total > 0) {
-      long long off = 0;
-      for (int i = 0; i < n; ++i) {
-         const size_t cnt = e.in[i].btcol.size();
-         if (cnt > 0) {
-            if (!Bt_vals_host[i]) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_batch: no border values for leaf %d", i);
-            HIP_TRY(hipMemcpyAsync(e.d_bval + off, Bt_vals_host[i], cnt * sizeof(double), hipMemcpyHostToDevice, e.stream));
-         }
-         off += (long long)cnt;
-      }
-   }
-   if (schur) {
-      if (!g->d_sc) PIPS_TRY(g->d_sc.alloc((size_t)S * S));
-      HIP_TRY(hipMemsetAsync(g->d_sc, 0, (size_t)S * S * sizeof(double), e.stream));
-   }
-   if ((rc = e.factor(schur ? g->d_sc : nullptr, S))) return rc;
-   for (LdlHandle* m : g->members) if (m) m->newest_in_group = true;
-   if (schur) {
-      g->h_sc.resize((size_t)S * S);
-      HIP_TRY(hipMemcpyAsync(g->h_sc.data(), g->d_sc, (size_t)S * S * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-      HIP_TRY(hipStreamSynchronize(e.stream));
-      // device: column-major, lower triangle valid; caller: row-major DenseSymmetricMatrix (DenseStorage.C:64-83), lower triangle meaningful
-      std::vector<char> used(S, 0);
-      for (const BlockSym& bs : e.sym) for (int c : bs.bmap) used[c] = 1;
-      std::vector<int> cols;
-      for (int c = 0; c < S; ++c) if (used[c]) cols.push_back(c);
-      for (int cb : cols)
-         for (int ra : cols)
-            if (ra >= cb) SC_host[(size_t)ra * ldSC + cb] += g->h_sc[(size_t)ra + (size_t)cb * S];
-   } else
-      HIP_TRY(hipStreamSynchronize(e.stream));
-   return e.sweep.take_error("pips_hip_ldl_factor_schur_batch");
-}
-
-// ---- the sparse Schur entries (INTEGRATION.md levels 1.5 / 1.5b for hosts with hasSparseKkt): the branch sparse_res = true of
-// addBiTLeftKiBiRightToResBlockedParallelSolvers (DistributedLinearSystem.C:766-770, 1050-1113, 1180-1190), which adds the term into a
-// SparseSymmetricMatrix.  The first call builds the position tables of the engine's blocks against the caller's pattern (schurtarget.cpp)
-// and hands them to set_sc_tables: from then on every kernel that writes the Schur complement - tile SYRK, head scatters,
-// k_border_schur_add, the packed blocked solves of Schur mode 2, deterministic mode's group buffers - addresses T doubles, the distinct
-// pattern positions the blocks' cliques touch.  Later calls compare S, nnz, the triangle and the hash of the consulted rows.
-static int sparse_schur_bind(Engine& e, SparseSchurBind& sb, int S, const int* sc_rowptr, const int* sc_colidx, int lower, const char* who) {
-   std::vector<const int*> bt((size_t)e.nblk, nullptr);
-   for (int b = 0; b < e.nblk; ++b) if (!e.in[b].btrow.empty()) bt[b] = e.in[b].btrow.data();
-   SchurPatternId id;
-   int rc;
-   if (sb.bound) {
-      if ((rc = build_schur_target(e.nblk, S, bt.data(), sc_rowptr, sc_colidx, lower, nullptr, id))) return rc;
-      if (!(id == sb.id))
-         PIPS_FAIL(PIPS_ERR_ARG, "%s: another pattern than the first call's (S %d / %d, %lld / %lld entries, %s / %s triangle, or other consulted rows)", who, S, sb.id.S,
-                   id.nnz, sb.id.nnz, id.lower ? "lower" : "upper", sb.id.lower ? "lower" : "upper");
-      return PIPS_OK;
-   }
-   SchurTarget t;
-   if ((rc = build_schur_target(e.nblk, S, bt.data(), sc_rowptr, sc_colidx, lower, &t, id))) return rc;
-   // (a target of at least one double: a length of 0 reads as "dense, S x S" in det_gstride)
-   if ((rc = e.set_sc_tables(t.tab, t.off, std::max<long long>((long long)t.pos.size(), 1)))) return rc;
-   if (e.deterministic && (rc = e.set_det_groups(0, 1))) return rc;   // group buffers as long as the compact array
-   PIPS_TRY(sb.d_val.alloc(t.pos.size()));
-   sb.pos = std::move(t.pos);
-   sb.id = id;
-   sb.bound = true;
-   return PIPS_OK;
-}
-// clear the compact array, factorise into it, one copy of its T doubles, sc_val_host[pos[t]] += values[t]
-static int sparse_schur_factor(Engine& e, SparseSchurBind& sb, double* sc_val_host, const char* who, LdlHandle* leaf, LdlGroup* group) {
-   const size_t T = sb.pos.size();
-   const bool schur = sc_val_host && T > 0;
-   int rc;
-   if (schur) HIP_TRY(hipMemsetAsync(sb.d_val, 0, T * sizeof(double), e.stream));
-   if ((rc = e.factor(schur ? sb.d_val.get() : nullptr, 0))) return rc;
-   // who holds the newest factors, as after the dense entries: the leaf itself, or the batch for every member
-   if (leaf) leaf->newest_in_group = false;
-   if (group)
-      for (LdlHandle* m : group->members) if (m) m->newest_in_group = true;
-   if (schur) {
-      sb.h_val.resize(T);
-      HIP_TRY(hipMemcpyAsync(sb.h_val.data(), sb.d_val, T * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-   }
-   HIP_TRY(hipStreamSynchronize(e.stream));
-   if ((rc = e.sweep.take_error(who))) return rc;
-   if (schur)
-      for (size_t t = 0; t < T; ++t) sc_val_host[sb.pos[t]] += sb.h_val[t];
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_factor_schur_sparse(void* handle, const double* K_vals_host, const double* Bt_vals_host, int S, const int* sc_rowptr, const int* sc_colidx,
-                                     double* sc_val_host, int lower) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || !K_vals_host || !Bt_vals_host || !sc_rowptr || !sc_colidx || !sc_val_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_sparse: bad arguments");
-   Engine& e = h->eng;
-   if (e.S <= 0 || e.in[0].btrow.empty()) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur_sparse: no border declared (pips_hip_ldl_set_border)");
-   if (S != e.S) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_factor_schur_sparse: S %d, the border was declared with %d", S, e.S);
-   if (h->sc_kind == SC_KIND_DENSE) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_factor_schur_sparse: the Schur target of this handle is dense (pips_hip_ldl_factor_schur): one kind per handle");
-   int rc;
-   if (!e.analyzed) {
-      if (env_deterministic()) e.deterministic = true;   // (the default, as for batches: pips_hip_batch_create)
-      if ((rc = pips_hip_ldl_analyze(handle))) return rc;
-   }
-   HIP_TRY(hipSetDevice(e.device));
-   if ((rc = sparse_schur_bind(e, h->sparse_sc, S, sc_rowptr, sc_colidx, lower, "pips_hip_ldl_factor_schur_sparse"))) return rc;
-   h->sc_kind = SC_KIND_SPARSE;
-   if ((rc = pips_hip_batch_set_values(&e, 0, K_vals_host))) return rc;
-   if (e.nnzB_total > 0) HIP_TRY(hipMemcpyAsync(e.d_bval, Bt_vals_host, (size_t)e.nnzB_total * sizeof(double), hipMemcpyHostToDevice, e.stream));
-   return sparse_schur_factor(e, h->sparse_sc, sc_val_host, "pips_hip_ldl_factor_schur_sparse", h, nullptr);
-}
-
-int pips_hip_ldl_factor_schur_sparse_batch(void* const* handles, int n, const double* const* K_vals_host, const double* const* Bt_vals_host, int S,
-                                           const int* sc_rowptr, const int* sc_colidx, double* sc_val_host, int lower) {
-   const char* who = "pips_hip_ldl_factor_schur_sparse_batch";
-   std::shared_ptr<LdlGroup> g;
-   const bool want_det = handles && n > 0 && handles[0] && (((LdlHandle*)handles[0])->eng.deterministic || env_deterministic());
-   int rc = ldl_group_of(handles, n, g, want_det);
-   if (rc) return rc;
-   if (!K_vals_host) PIPS_FAIL(PIPS_ERR_ARG, "%s: no values", who);
-   Engine& e = g->eng;
-   const bool schur = sc_val_host != nullptr;
-   HIP_TRY(hipSetDevice(e.device));
-   if (schur) {
-      if (e.S <= 0 || !Bt_vals_host || !sc_rowptr || !sc_colidx) PIPS_FAIL(PIPS_ERR_ARG, "%s: Schur term asked for without border or pattern", who);
-      if (S != e.S) PIPS_FAIL(PIPS_ERR_ARG, "%s: S %d, the borders were declared with %d", who, S, e.S);
-      bool other = g->sc_kind == SC_KIND_DENSE;
-      for (LdlHandle* m : g->members) other = other || (m && m->sc_kind == SC_KIND_DENSE);
-      if (other) PIPS_FAIL(PIPS_ERR_STATE, "%s: the Schur target of these handles is dense (pips_hip_ldl_factor_schur / _batch): one kind per handle", who);
-      if ((rc = sparse_schur_bind(e, g->sparse_sc, S, sc_rowptr, sc_colidx, lower, who))) return rc;
-      if ((rc = ldl_group_kind(*g, SC_KIND_SPARSE, who))) return rc;
-   }
-   for (int i = 0; i < n; ++i) {
-      if (!K_vals_host[i]) PIPS_FAIL(PIPS_ERR_ARG, "%s: no values for leaf %d", who, i);
-      if (schur && !e.in[i].btcol.empty() && !Bt_vals_host[i]) PIPS_FAIL(PIPS_ERR_ARG, "%s: no border values for leaf %d", who, i);
-   }
-   for (int i = 0; i < n; ++i)
-      HIP_TRY(hipMemcpyAsync(e.d_kval + e.kptr[i], K_vals_host[i], (size_t)(e.kptr[i + 1] - e.kptr[i]) * sizeof(double), hipMemcpyHostToDevice, e.stream));
-   if (schur && e.nnzB_total > 0) {
-      long long off = 0;
-      for (int i = 0; i < n; ++i) {
-         const size_t cnt = e.in[i].btcol.size();
-         if (cnt > 0) HIP_TRY(hipMemcpyAsync(e.d_bval + off, Bt_vals_host[i], cnt * sizeof(double), hipMemcpyHostToDevice, e.stream));
-         off += (long long)cnt;
-      }
-   }
-   return sparse_schur_factor(e, g->sparse_sc, schur ? sc_val_host : nullptr, who, nullptr, g.get());
-}
-
-int pips_hip_ldl_solve_batch_dev(void* const* handles, int n, double* x_dev) {
-   std::shared_ptr<LdlGroup> g;
-   int rc = ldl_group_of(handles, n, g);
-   if (rc) return rc;
-   if (!x_dev) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_solve_batch_dev: null vector");
-   if ((rc = ldl_group_is_current(*g, "pips_hip_ldl_solve_batch_dev"))) return rc;
-   HIP_TRY(hipSetDevice(g->eng.device));
-   return g->eng.solve(x_dev);
-}
-
-int pips_hip_ldl_solve_batch(void* const* handles, int n, double* const* rhs_inout_host) {
-   std::shared_ptr<LdlGroup> g;
-   int rc = ldl_group_of(handles, n, g);
-   if (rc) return rc;
-   if (!rhs_inout_host) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_ldl_solve_batch: null array");
-   Engine& e = g->eng;
-   if ((rc = ldl_group_is_current(*g, "pips_hip_ldl_solve_batch"))) return rc;
-   HIP_TRY(hipSetDevice(e.device));
-   if (!g->d_x) PIPS_TRY(g->d_x.alloc((size_t)std::max<long long>(e.n_total, 1)));
-   // a leaf without a right-hand side this time (NULL) is solved with zeros: the batch runs every block in every launch
-   HIP_TRY(hipMemsetAsync(g->d_x, 0, (size_t)e.n_total * sizeof(double), e.stream));
-   for (int i = 0; i < n; ++i)
-      if (rhs_inout_host[i])
-         HIP_TRY(hipMemcpyAsync(g->d_x + e.x_off[i], rhs_inout_host[i], (size_t)(e.x_off[i + 1] - e.x_off[i]) * sizeof(double), hipMemcpyHostToDevice, e.stream));
-   if ((rc = e.solve(g->d_x))) return rc;
-   for (int i = 0; i < n; ++i)
-      if (rhs_inout_host[i])
-         HIP_TRY(hipMemcpyAsync(rhs_inout_host[i], g->d_x + e.x_off[i], (size_t)(e.x_off[i + 1] - e.x_off[i]) * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-   HIP_TRY(hipStreamSynchronize(e.stream));
-   return e.sweep.take_error("pips_hip_ldl_solve_batch");
-}
-
-int pips_hip_ldl_inertia_batch(void* const* handles, int n, int* pos, int* neg, int* zero) {
-   std::shared_ptr<LdlGroup> g;
-   int rc = ldl_group_of(handles, n, g);
-   if (rc) return rc;
-   if ((rc = ldl_group_is_current(*g, "pips_hip_ldl_inertia_batch"))) return rc;
-   for (int i = 0; i < n; ++i) {
-      int p = 0, q = 0, z = 0;
-      if ((rc = pips_hip_batch_inertia(&g->eng, i, &p, &q, &z))) return rc;
-      if (pos) pos[i] = p;
-      if (neg) neg[i] = q;
-      if (zero) zero[i] = z;
-   }
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_inertia(void* handle, int* pos, int* neg, int* zero) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   if (ldl_uses_group(h))   // the newest factorisation of this leaf was the batch's (pips_hip_ldl_factor_schur_batch)
-      return pips_hip_batch_inertia(&h->group->eng, h->group_index, pos, neg, zero);
-   return pips_hip_batch_inertia(&h->eng, 0, pos, neg, zero);
-}
-
-int pips_hip_ldl_info(void* handle, int64_t* what, int n_what) {
-   LdlHandle* h = (LdlHandle*)handle;
-   const bool grp = h && ldl_uses_group(h);
-   if (!h || (h->eng.sym.empty() && !grp)) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_info: analyze first");
-   // (a handle that was only ever factorised through its batch has its analysis there)
-   const BlockSym& s = h->eng.sym.empty() ? h->group->eng.sym[h->group_index] : h->eng.sym[0];
-   // [8], [9]: of the engine that holds this leaf's newest factors - the Schur mode its analysis took and the doubles of its compact
-   // sparse Schur target (0: none, the target is dense)
-   const Engine& cur = grp ? h->group->eng : h->eng;
-   const SparseSchurBind& sb = grp ? h->group->sparse_sc : h->sparse_sc;
-   int64_t v[10] = {s.nnzL, s.n_head, s.m, (int64_t)s.sn.size(), s.n_levels, (int64_t)s.flops_factor, (int64_t)h->eng.last_refine_steps, (int64_t)h->eng.last_multi_path,
-                    (int64_t)cur.schur_mode_eff, sb.bound ? (int64_t)sb.pos.size() : 0};
-   for (int i = 0; i < n_what && i < 10; ++i) what[i] = v[i];
-   return PIPS_OK;
-}
-
-int pips_hip_ldl_get_perm(void* handle, int* perm) {
-   LdlHandle* h = (LdlHandle*)handle;
-   if (!h || h->eng.sym.empty() || !perm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_ldl_get_perm: analyze first");
-   std::copy(h->eng.sym[0].perm.begin(), h->eng.sym[0].perm.end(), perm);
-   return PIPS_OK;
-}
-
-void pips_hip_ldl_destroy(void* handle) { delete (LdlHandle*)handle; }
-
-// ---- dense root ----------------------------------------------------------------------------------------------------
-int pips_hip_dense_ldl_create(void** handle, int n, int n_primal, int device) {
-   if (!handle || n <= 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_create: bad arguments");
-   int dev;
-   int rc = resolve_device(device, &dev);
-   if (rc) return rc;
-   auto d = std::make_unique<DenseLdl>();
-   d->n = n;
-   d->n_primal = n_primal;
-   d->device = dev;
-   // no inertia hint = a plain DeSymIndefSolver replacement: pivot like dsytrf; with a hint the caller vouches for the quasi-definite order
-   d->pivoting = n_primal < 0 ? 1 : 0;
-   rc = d->init();
-   if (rc) return rc;
-   *handle = d.release();
-   return PIPS_OK;
-}
-
-int pips_hip_dense_ldl_set_distributed(void* handle, void* comm, int rank, int n_ranks) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d) PIPS_FAIL(PIPS_ERR_ARG, "null handle");
-   d->factored = false;
-   return d->set_distributed(comm, rank, n_ranks);
-}
-
-int pips_hip_dense_ldl_set_pivoting(void* handle, int mode) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d || mode < 0 || mode > 1) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_set_pivoting: mode 0 (static order) or 1 (Bunch-Kaufman inside the diagonal tiles)");
-   d->pivoting = mode;
-   d->factored = false;
-   return PIPS_OK;
-}
-
-int pips_hip_dense_ldl_factor(void* handle, const double* A_host, int lda) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d || !A_host || lda < d->n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_factor: bad arguments");
-   HIP_TRY(hipSetDevice(d->device));
-   // DenseStorage is row-major with the lower triangle authoritative (DeSymIndefSolver.h:41-42 hands exactly this to
-   // dsytrf_('U') as a column-major matrix); upload and let the copy kernel read it transposed.
-   if (int rc0 = d->ensure_input_buffer()) return rc0;
-   HIP_TRY(hipMemcpy2DAsync(d->d_in, (size_t)d->n * sizeof(double), A_host, (size_t)lda * sizeof(double),
-                            (size_t)d->n * sizeof(double), (size_t)d->n, hipMemcpyHostToDevice, d->stream));
-   int rc = d->factor_dev(d->d_in, d->n, 1);
-   if (rc) return rc;
-   if ((rc = d->check_pivots())) return rc;     // (the staged copy d_in stays valid: a new pivot order factorises from it again)
-   HIP_TRY(hipStreamSynchronize(d->stream));
-   return d->take_root_error("pips_hip_dense_ldl_factor");
-}
-
-int pips_hip_dense_ldl_factor_dev(void* handle, const double* A_dev, int lda) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d || !A_dev || lda < d->n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_factor_dev: bad arguments");
-   return d->factor_dev(A_dev, lda, 0);
-}
-
-int pips_hip_dense_ldl_solve_dev(void* handle, double* rhs_inout_dev) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d || !rhs_inout_dev) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_solve_dev: bad arguments");
-   return d->solve_dev(rhs_inout_dev);
-}
-
-int pips_hip_dense_ldl_solve(void* handle, int nrhs, double* rhs, int ld) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d || !rhs || nrhs < 0 || ld < d->n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_solve: bad arguments");
-   HIP_TRY(hipSetDevice(d->device));
-   if (int rc0 = d->ensure_input_buffer()) return rc0;
-   for (int k = 0; k < nrhs; ++k) {
-      double* x = rhs + (size_t)k * ld;
-      HIP_TRY(hipMemcpyAsync(d->d_in, x, (size_t)d->n * sizeof(double), hipMemcpyHostToDevice, d->stream));
-      int rc = d->solve_dev(d->d_in);
-      if (rc) return rc;
-      HIP_TRY(hipMemcpyAsync(x, d->d_in, (size_t)d->n * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-      HIP_TRY(hipStreamSynchronize(d->stream));
-   }
-   return d->sweep.take_error("pips_hip_dense_ldl_solve");
-}
-
-int pips_hip_dense_ldl_inertia(void* handle, int* pos, int* neg, int* zero) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d || !d->factored) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_dense_ldl_inertia: factor first");
-   HIP_TRY(hipSetDevice(d->device));
-   { const int rcp = d->check_pivots(); if (rcp) return rcp; }
-   HIP_TRY(hipMemcpyAsync(d->h_inertia, d->d_inertia, 3 * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-   HIP_TRY(hipStreamSynchronize(d->stream));
-   { const int rce = d->sweep.take_error("pips_hip_dense_ldl_inertia"); if (rce) return rce; }
-   { const int rce = d->take_root_error("pips_hip_dense_ldl_inertia"); if (rce) return rce; }
-   if (pos) *pos = d->h_inertia[0];
-   if (neg) *neg = d->h_inertia[1];
-   if (zero) *zero = d->h_inertia[2];
-   return PIPS_OK;
-}
-
-int pips_hip_dense_ldl_info(void* handle, int64_t* what, int n_what) {
-   DenseLdl* d = (DenseLdl*)handle;
-   if (!d || !what || n_what < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_info: bad arguments");
-   const int64_t v[5] = {d->factored && d->last_single ? 1 : 0, d->npad / TILE, d->dist_P, d->pivoting, d->bk_refactorizations};
-   for (int i = 0; i < n_what && i < 5; ++i) what[i] = v[i];
-   return PIPS_OK;
-}
-
-void pips_hip_dense_ldl_destroy(void* handle) { delete (DenseLdl*)handle; }
+#include "ldlhandle.hip.h"
 
 // ---- plain device buffers ------------------------------------------------------------------------------------------
 // (what the caller holds is owned here under its address, so that it is counted like every other allocation)

@@ -1,4 +1,4 @@
-"""The dense root's solves (DenseLdl in csrc/engine.hip, k_root_ldl in csrc/rootkernel.hip.h) judged against a long-double reference.
+"""The dense root's solves (DenseLdl in csrc/denseroot.hip.h, k_root_ldl in csrc/rootkernel.hip.h) judged against a long-double reference.
 
 The root factorises the Schur complement and solves with the factor WITHOUT refinement, so its solutions are measured as
 tests/test_unrefined_sweeps_gpu.py measures the leaf sweeps, per right-hand side:

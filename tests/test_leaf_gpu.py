@@ -306,7 +306,7 @@ def test_dense_root_matches_lapack(n, n_primal):
 
 def test_dense_root_large_right_looking_with_lookahead():
     """S = 6400 (50 tile columns): the single-block root runs right-looking with the one-column lookahead on a side stream
-    (DenseLdl, engine.hip); checked against LAPACK dsytrf/dsytrs like the small sizes, and for determinism across calls."""
+    (DenseLdl, denseroot.hip.h); checked against LAPACK dsytrf/dsytrs like the small sizes, and for determinism across calls."""
     import torch
     from oracle import oracle as orc
     n, n_primal = 6400, 3200
