@@ -545,6 +545,50 @@ int pips_ipm_get_schur_mode(void* handle, int* mode);
  * 3 max iterations, 4 breakdown, 5 diverged, 6 stagnation), iterations, ||r||_2, ||rhs||_2, preconditioner applications, host
  * synchronisations} */
 int pips_ipm_mult(void* handle, int transposed, const double* in_host, double* out_host);
+/* The harness kernels beside a handle, for parity tests as well (tests/harness_cases.py): host arrays in, the launch code the handle
+ * runs (the launch_* functions of csrc/harness.hip: kernel choice, grid sizes, the long-row pair), host arrays out.  Synchronous, on the
+ * current device.  PIPS_ERR_ARG with a message for arguments a kernel would read out of bounds with, then PIPS_ERR_NO_DEVICE without a
+ * GPU; every device buffer is freed before the call returns.
+ * pips_ipm_probe_spmv: out = epilogue(M in) for the CSR matrix M (nrows x ncols) and mode 0 rQ = e0 [+ e3] - s - e1 + e2, 1 [rA|rC] =
+ *   s - (r < split ? e0[r] : e1[r - split]), 2 e0 e1 [+ e3] + s, 3 s + e0 e1, 4 e2 - (e0 e1 [+ e3] + s), 5 e2 - (s + e0 e1), 6 s (s the row's
+ *   sum; e0..e2 nrows long - mode 1: e0 split, e1 nrows - split entries - and there where the mode reads them; e3 NULL or nrows long, modes
+ *   0, 2, 4).  lin, r0e, r1b, r1e: on the rows [0, r0e) and [r1b, r1e) a rank with lin != 0 produces +-s alone, and e3 +- s with lin = 2
+ *   (which needs e3).  pred: -1 none, else 0 / 1 stored on the device for the kernels to test.  out: in-out, out_len >= nrows entries,
+ *   all of them uploaded and read back - what no kernel writes keeps the caller's content.  *lanes: the lanes per row chosen (4 or 8; 0
+ *   without rows), *n_long and long_rows (nrows ints, or NULL): the rows handed to the long-row kernels, from the builder of the layout's lists.
+ * pips_ipm_probe_reduce: out[k] = term k, 1 <= n_terms <= 12, in ONE launch.  kind 0 sum [w] a b, 1 max |a| (|a w| with w, else |a / d|
+ *   with d), 2 min a over c != 0, 3 min -a / b over b < 0, 4 sum [w] (a + p c)(b + q d); operands n long, the unread ones NULL.  out in-out
+ *   (pred = 0 leaves it).
+ * pips_ipm_probe_step: ONE entry for the nine element-wise kernels (one argument convention instead of nine prototypes; the kernel's own
+ *   argument list, in its order, is `in` followed by `out`).  in[k] has in_len[k], out[k] (in-out) out_len[k] entries, at least what the
+ *   kernel touches with ncp = 2 mz + 2 nx, nyz = my + mz; longer arrays travel whole (guard entries).  scalars: 5 doubles.
+ *     kernel              in                                                        out                        flag      scalars
+ *     0 bound_residuals   x(nx) s(mz) z(mz) G L M Bd (ncp)                          rz(mz) rG(ncp)
+ *     1 diagonals         G L M (ncp)                                               dd(nx) ddp(nx) dyz(nyz)              free_reg
+ *     2 leaf_diag         ddp(nx) nOmegaInv(mz) qdiag(nx or NULL); idx: n codes     leaf_diag(n)                         primal_reg dual_reg reg
+ *     3 reg_operator      ddp(nx) dyz(nyz)                                          dop_r(nx) dyz_r(nyz)                 reg dual_reg
+ *     4 rhs_reduce        rQ(nx) rAC(nyz) rz(mz) rG rL G L M (ncp) dyz(nyz)         rhs(nx + nyz) rs(mz)       zero_lin
+ *     5 recover           sol(nx + nyz) rs(mz) rG rL G L M (ncp) dyz(nyz)           sP(nx + mz + ncp) sD(nyz + ncp)  zero_lin
+ *     6 compl_rhs         G L dG dL M (n)                                           r(n)                       mode      alpha ap ad rmin rmax
+ *     7 masked_const      M(n)                                                      y(n)                       add       a
+ *     8 gather            in; idx: n indices                                        out                        scatter
+ *   gather: out[i] = in[idx[i]] (flag 0) or out[idx[i]] = in[i] (flag 1); the indexed array's length bounds the indices. */
+typedef struct {
+   int kind;
+   long long n;
+   const double *a, *b, *c, *d, *w;
+   double p, q;
+} pips_ipm_red_term;
+enum {
+   PIPS_STEP_BOUND_RESIDUALS = 0, PIPS_STEP_DIAGONALS, PIPS_STEP_LEAF_DIAG, PIPS_STEP_REG_OPERATOR, PIPS_STEP_RHS_REDUCE,
+   PIPS_STEP_RECOVER, PIPS_STEP_COMPL_RHS, PIPS_STEP_MASKED_CONST, PIPS_STEP_GATHER
+};
+int pips_ipm_probe_spmv(int mode, int nrows, int ncols, const int* rowptr, const int* colidx, const double* val, const double* in,
+                        const double* e0, const double* e1, const double* e2, const double* e3, int split, int lin, int r0e, int r1b, int r1e,
+                        int pred, double* out, long long out_len, int* lanes, int* n_long, int* long_rows);
+int pips_ipm_probe_reduce(int n_terms, const pips_ipm_red_term* terms, int pred, double* out);
+int pips_ipm_probe_step(int kernel, int nx, int my, int mz, long long n, int flag, const double* scalars, int n_in, const double* const* in,
+                        const long long* in_len, const long long* idx, long long idx_len, int n_out, double* const* out, const long long* out_len);
 /* Problem scaling (the reference's Scaler stage, ScalerType in Core/Preprocessing/PreprocessType.h; same order).  Curtis-Reid is
  * reserved and not supported. */
 enum {

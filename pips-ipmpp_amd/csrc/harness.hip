@@ -757,6 +757,68 @@ __global__ void k_bicg_set_target(double* st, double tol) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// launch sequences shared by the handle (Ipm below) and the probe entries (pips_ipm_probe_*, end of the file): whoever launches
+// one of the kernels above does it through these, so a probe runs the grid sizes and the kernel choice the handle runs
+// ---------------------------------------------------------------------------------------------------------------------------
+// lanes per row of the product: four where the rows average fewer than six entries, else eight
+static inline int spmv_lanes(int nrows, long long nnz) { return nnz < 6LL * nrows ? 4 : 8; }
+// out = epilogue<MODE>(matrix * in): the short rows two per lane group, then the long rows (list of n_long rows, LONG_PARTS scratch
+// entries each) in parts and their finishing kernel
+template <int MODE>
+static void launch_spmv(const SpmvArgs& a, long long nnz, const int* long_rows, int n_long, double* long_scratch, hipStream_t stream) {
+   if (a.nrows > 0 && spmv_lanes(a.nrows, nnz) == 4) hipLaunchKernelGGL((k_spmv<MODE, 4>), dim3(egrid(2LL * a.nrows)), dim3(256), 0, stream, a);
+   else if (a.nrows > 0) hipLaunchKernelGGL((k_spmv<MODE, 8>), dim3(egrid(4LL * a.nrows)), dim3(256), 0, stream, a);
+   if (n_long > 0) {
+      hipLaunchKernelGGL(k_spmv_long_part, dim3(n_long, LONG_PARTS), dim3(256), 0, stream, a, long_rows, long_scratch);
+      hipLaunchKernelGGL(k_spmv_long_finish<MODE>, dim3((n_long + 255) / 256), dim3(256), 0, stream, a, long_rows, n_long, long_scratch);
+   }
+}
+// out[k] = term k of the pack; partial: RED_MAX * RED_GRID entries
+static void launch_reduce(const RedPack& pk, double* partial, double* out, const int* pred, hipStream_t stream) {
+   hipLaunchKernelGGL(k_multi_reduce, dim3(RED_GRID, pk.n_terms), dim3(256), 0, stream, pk, partial, pred);
+   hipLaunchKernelGGL(k_multi_reduce_final, dim3(pk.n_terms), dim3(256), 0, stream, pk, RED_GRID, partial, out, pred);
+}
+static void launch_bound_residuals(const Lay& d, const double* x, const double* s, const double* z, const double* G, const double* L,
+                                   const double* M, const double* Bd, double* rz, double* rG, hipStream_t stream) {
+   hipLaunchKernelGGL(k_bound_residuals, dim3(egrid(std::max(d.nx, d.mz))), dim3(256), 0, stream, d, x, s, z, G, L, M, Bd, rz, rG);
+}
+static void launch_diagonals(const Lay& d, const double* G, const double* L, const double* M, double free_reg, double* dd, double* ddp,
+                             double* dyz, hipStream_t stream) {
+   hipLaunchKernelGGL(k_diagonals, dim3(egrid(std::max(d.nx, d.mz))), dim3(256), 0, stream, d, G, L, M, free_reg, dd, ddp, dyz);
+}
+static void launch_leaf_diag(long long nleaf, const long long* code, const double* ddp, const double* nomega, const double* qdiag,
+                             double primal_reg, double dual_reg, double reg, double* leaf_diag, hipStream_t stream) {
+   if (nleaf > 0)
+      hipLaunchKernelGGL(k_leaf_diag, dim3(egrid(nleaf)), dim3(256), 0, stream, nleaf, code, ddp, nomega, qdiag, primal_reg, dual_reg, reg, leaf_diag);
+}
+static void launch_reg_operator(const Lay& d, const double* ddp, const double* dyz, double reg, double dual_reg, double* dop_r, double* dyz_r,
+                                hipStream_t stream) {
+   hipLaunchKernelGGL(k_reg_operator, dim3(egrid(std::max<long long>(d.nx, (long long)d.my + d.mz))), dim3(256), 0, stream, (long long)d.nx,
+                      (long long)d.my, (long long)d.mz, ddp, dyz, reg, dual_reg, dop_r, dyz_r);
+}
+static void launch_rhs_reduce(const Lay& d, int zero_lin, const double* rQ, const double* rAC, const double* rz, const double* rG,
+                              const double* rL, const double* G, const double* L, const double* M, const double* dyz, double* rhs, double* rs,
+                              hipStream_t stream) {
+   hipLaunchKernelGGL(k_rhs_reduce, dim3(egrid(std::max(std::max(d.nx, d.mz), d.my))), dim3(256), 0, stream, d, zero_lin, rQ, rAC, rz, rG, rL, G, L, M,
+                      dyz, rhs, rs);
+}
+static void launch_recover(const Lay& d, int zero_lin, const double* sol, const double* rs, const double* rG, const double* rL, const double* G,
+                           const double* L, const double* M, const double* dyz, double* sP, double* sD, hipStream_t stream) {
+   hipLaunchKernelGGL(k_recover, dim3(egrid(std::max(std::max(d.nx, d.mz), d.my))), dim3(256), 0, stream, d, zero_lin, sol, rs, rG, rL, G, L, M, dyz,
+                      sP, sD);
+}
+static void launch_compl_rhs(long long n, int mode, const double* G, const double* L, const double* dG, const double* dL, const double* M,
+                             double alpha, double ap, double ad, double rmin, double rmax, double* r, hipStream_t stream) {
+   hipLaunchKernelGGL(k_compl_rhs, dim3(egrid(n)), dim3(256), 0, stream, n, mode, G, L, dG, dL, M, alpha, ap, ad, rmin, rmax, r);
+}
+static void launch_masked_const(long long n, int add, double a, const double* M, double* y, hipStream_t stream) {
+   hipLaunchKernelGGL(k_masked_const, dim3(egrid(n)), dim3(256), 0, stream, n, add, a, M, y);
+}
+static void launch_gather(long long n, const long long* src, const double* in, double* out, int scatter, hipStream_t stream) {
+   hipLaunchKernelGGL(k_gather, dim3(egrid(n)), dim3(256), 0, stream, n, src, in, out, scatter);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 struct Vars {   // pointers into one iterate-shaped array
    double *base = nullptr, *P = nullptr, *D = nullptr;
    double *x = nullptr, *s = nullptr, *G = nullptr, *yz = nullptr, *y = nullptr, *z = nullptr, *L = nullptr;
@@ -865,8 +927,7 @@ struct Ipm {
 
    // one fused reduction -> host.  out[k] for every term; over the ranks: sums added, extrema combined
    int reduce(RedPack& pk, double* out) {
-      hipLaunchKernelGGL(k_multi_reduce, dim3(RED_GRID, pk.n_terms), dim3(256), 0, stream, pk, d_partial, (const int*)nullptr);
-      hipLaunchKernelGGL(k_multi_reduce_final, dim3(pk.n_terms), dim3(256), 0, stream, pk, RED_GRID, d_partial, d_out, (const int*)nullptr);
+      launch_reduce(pk, d_partial, d_out, nullptr, stream);
       HIP_TRYH(hipMemcpyAsync(h_out, d_out, pk.n_terms * sizeof(double), hipMemcpyDeviceToHost, stream));
       HIP_TRYH(hipStreamSynchronize(stream));
       ++n_host_syncs;
@@ -915,14 +976,7 @@ struct Ipm {
       const bool staged = n_ranks > 1 && pred != nullptr;
       if (staged) a.out = transposed ? w_tmp : w_tmp + nx;
       // eight lanes per row (four where the rows are short), two rows per lane group
-      const long long nnz_m = transposed ? Jt_nnz : J_nnz;
-      if (a.nrows > 0 && nnz_m < 6LL * a.nrows) hipLaunchKernelGGL((k_spmv<MODE, 4>), dim3(egrid(2LL * a.nrows)), dim3(256), 0, stream, a);
-      else if (a.nrows > 0) hipLaunchKernelGGL((k_spmv<MODE, 8>), dim3(egrid(4LL * a.nrows)), dim3(256), 0, stream, a);
-      const int nl = transposed ? nJt_long : nJ_long;
-      if (nl > 0) {
-         hipLaunchKernelGGL(k_spmv_long_part, dim3(nl, LONG_PARTS), dim3(256), 0, stream, a, transposed ? Jt_long : J_long, long_scratch);
-         hipLaunchKernelGGL(k_spmv_long_finish<MODE>, dim3((nl + 255) / 256), dim3(256), 0, stream, a, transposed ? Jt_long : J_long, nl, long_scratch);
-      }
+      launch_spmv<MODE>(a, transposed ? Jt_nnz : J_nnz, transposed ? Jt_long : J_long, transposed ? nJt_long : nJ_long, long_scratch, stream);
       HIP_TRYH(hipGetLastError());
       if (n_ranks > 1) {   // replicated rows: sum of the ranks' contributions
          if (transposed) TRY(root_sum(a.out, n0));
@@ -942,12 +996,7 @@ struct Ipm {
       a.in = in; a.out = out; a.e0 = a.e1 = a.e2 = a.e3 = nullptr; a.split = 0;
       a.lin = 0; a.r0e = a.r1b = a.r1e = 0;
       a.pred = pred;
-      if (nx > 0 && Q_nnz < 6LL * nx) hipLaunchKernelGGL((k_spmv<SP_QX, 4>), dim3(egrid(2LL * nx)), dim3(256), 0, stream, a);
-      else if (nx > 0) hipLaunchKernelGGL((k_spmv<SP_QX, 8>), dim3(egrid(4LL * nx)), dim3(256), 0, stream, a);
-      if (nQ_long > 0) {
-         hipLaunchKernelGGL(k_spmv_long_part, dim3(nQ_long, LONG_PARTS), dim3(256), 0, stream, a, Q_long, long_scratch);
-         hipLaunchKernelGGL(k_spmv_long_finish<SP_QX>, dim3((nQ_long + 255) / 256), dim3(256), 0, stream, a, Q_long, nQ_long, long_scratch);
-      }
+      launch_spmv<SP_QX>(a, Q_nnz, Q_long, nQ_long, long_scratch, stream);
       HIP_TRYH(hipGetLastError());
       return PIPS_OK;
    }
@@ -957,7 +1006,7 @@ struct Ipm {
       if (has_q) TRY(hess(it.x, qx));
       TRY((spmv<SP_RQ>(true, it.yz, rQ, c, it.L + 2 * mz, it.L + 2 * mz + nx, qx)));
       TRY((spmv<SP_RAC>(false, it.x, rAC, bA, it.s, nullptr, nullptr)));
-      hipLaunchKernelGGL(k_bound_residuals, dim3(egrid(std::max(nx, mz))), dim3(256), 0, stream, lay, it.x, it.s, it.z, it.G, it.L, M, Bd, rz, rG);
+      launch_bound_residuals(lay, it.x, it.s, it.z, it.G, it.L, M, Bd, rz, rG, stream);
       RedPack pk;
       pk.n_terms = 8;
       pk.t[0] = term(R_ABSMAX, nx, rQ);
@@ -1024,7 +1073,7 @@ struct Ipm {
       // infinitely far, and the basic variables' own diagonal gamma/v is O(mu) - so the term follows mu downwards (a fixed 1e-6
       // dominates those diagonals by three orders of magnitude at mu = 1e-9 and the outer solve stops converging)
       const double freg = free_reg_follows_mu ? std::min(free_reg, std::max(cur_mu, free_reg_min)) : free_reg;
-      hipLaunchKernelGGL(k_diagonals, dim3(egrid(std::max(nx, mz))), dim3(256), 0, stream, lay, it.G, it.L, M, freg, dd, ddp, dyz);
+      launch_diagonals(lay, it.G, it.L, M, freg, dd, ddp, dyz, stream);
       double reg = reg_start;
       // Escalation that does not lower the number of perturbed pivots only ruins the preconditioner (a pivot can be perturbed for
       // reasons regularisation does not touch): remember the smallest regularisation with the lowest count, stop after two
@@ -1032,8 +1081,7 @@ struct Ipm {
       int best_pert = INT_MAX, stalled = 0;
       double best_reg = reg;
       auto factor_with = [&](double r, int* pert) -> int {
-         if (nleaf > 0)
-            hipLaunchKernelGGL(k_leaf_diag, dim3(egrid(nleaf)), dim3(256), 0, stream, nleaf, d_code, ddp, dyz + my, (const double*)qdiag, r, dual_reg + r, r, leaf_diag);
+         launch_leaf_diag(nleaf, d_code, ddp, dyz + my, qdiag, r, dual_reg + r, r, leaf_diag, stream);
          TRY(pips_hip_kkt_set_root_regularization(kkt, r, dual_reg + r));
          if (e_mz0 > 0) hipLaunchKernelGGL(k_shift_diag, dim3(egrid(e_mz0)), dim3(256), 0, stream, dyz + my, dual_reg + r, zd0, e_mz0);
          TRY(pips_hip_kkt_factorize(kkt, leaf_diag, ddp, e_mzl > 0 ? dyz + my + e_mz0 : nullptr));
@@ -1057,8 +1105,7 @@ struct Ipm {
       }
       last_pert = pert;
       last_reg = reg;
-      hipLaunchKernelGGL(k_reg_operator, dim3(egrid(std::max<long long>(nx, (long long)my + mz))), dim3(256), 0, stream, (long long)nx, (long long)my,
-                         (long long)mz, free_in_operator ? ddp : dd, dyz, reg, dual_reg, dop_r, dyz_r);
+      launch_reg_operator(lay, free_in_operator ? ddp : dd, dyz, reg, dual_reg, dop_r, dyz_r, stream);
       return PIPS_OK;
    }
 
@@ -1069,9 +1116,9 @@ struct Ipm {
    // divergence counter runs up and the best iterate is restored, :741-760).  0 in every production path.
    int test_precond = 0;
    int precond(double* z_) {   // z := solveCompressed(z)
-      hipLaunchKernelGGL(k_gather, dim3(egrid(npack)), dim3(256), 0, stream, npack, d_pack, z_, b0, 0);   // b0 and bl are one array
+      launch_gather(npack, d_pack, z_, b0, 0, stream);   // b0 and bl are one array
       TRY(pips_hip_kkt_solve_compressed(kkt, b0, bl));
-      hipLaunchKernelGGL(k_gather, dim3(egrid(npack)), dim3(256), 0, stream, npack, d_pack, b0, z_, 1);
+      launch_gather(npack, d_pack, b0, z_, 1, stream);
       if (test_precond) hipLaunchKernelGGL(k_test_distort, dim3(egrid(nxyz)), dim3(256), 0, stream, nxyz, test_precond, z_);
       ++n_precond;
       return PIPS_OK;
@@ -1114,8 +1161,7 @@ struct Ipm {
    }
    // device-side reduction for BiCGStab: results to st[B_RED0 ..], summed over the ranks
    int bred(RedPack& pk, const int* pred) {
-      hipLaunchKernelGGL(k_multi_reduce, dim3(RED_GRID, pk.n_terms), dim3(256), 0, stream, pk, d_partial, pred);
-      hipLaunchKernelGGL(k_multi_reduce_final, dim3(pk.n_terms), dim3(256), 0, stream, pk, RED_GRID, d_partial, d_bst + B_RED0, pred);
+      launch_reduce(pk, d_partial, d_bst + B_RED0, pred, stream);
       if (n_ranks > 1) TRY(pips_hip_allreduce_sum(comm, d_bst + B_RED0, (size_t)pk.n_terms, stream));
       return PIPS_OK;
    }
@@ -1267,8 +1313,7 @@ struct Ipm {
 
    // LinearSystem::solve + step.negate() for the current residual set (zero_lin: linear residuals cleared)
    int solve(bool zero_lin, Vars& out) {
-      hipLaunchKernelGGL(k_rhs_reduce, dim3(egrid(std::max(std::max(nx, mz), my))), dim3(256), 0, stream, lay, zero_lin ? 1 : 0, rQ, rAC, rz, rG, rL,
-                         it.G, it.L, M, dyz, rhs, rs);
+      launch_rhs_reduce(lay, zero_lin ? 1 : 0, rQ, rAC, rz, rG, rL, it.G, it.L, M, dyz, rhs, rs, stream);
       // A pivot whose value is rounding noise can keep the right sign and pass the inertia test; the factors are then useless as
       // a preconditioner and the outer solve does not reach its tolerance.  The reference treats a failed outer solve as
       // numerical trouble of the factorisation; here the system is factorised again with (more) regularisation - which also
@@ -1290,8 +1335,7 @@ struct Ipm {
          ++n_refactor_outer;
          TRY(factorize(last_reg > 0.0 ? std::min(last_reg * 100.0, reg_max) : 1e-8));
       }
-      hipLaunchKernelGGL(k_recover, dim3(egrid(std::max(std::max(nx, mz), my))), dim3(256), 0, stream, lay, zero_lin ? 1 : 0, sol, rs, rG, rL, it.G, it.L,
-                         M, dyz, out.P, out.D);
+      launch_recover(lay, zero_lin ? 1 : 0, sol, rs, rG, rL, it.G, it.L, M, dyz, out.P, out.D, stream);
       HIP_TRYH(hipGetLastError());
       return PIPS_OK;
    }
@@ -1385,7 +1429,7 @@ struct Ipm {
       return PIPS_OK;
    }
    void compl_rhs(int mode, double alpha, double ap, double ad, double rmin, double rmax) {
-      hipLaunchKernelGGL(k_compl_rhs, dim3(egrid(ncp)), dim3(256), 0, stream, ncp, mode, it.G, it.L, st.G, st.L, M, alpha, ap, ad, rmin, rmax, rL);
+      launch_compl_rhs(ncp, mode, it.G, it.L, st.G, st.L, M, alpha, ap, ad, rmin, rmax, rL, stream);
    }
    // Gondzio's multiple centrality correctors (gondzio_correction_loop, InteriorPointMethod.cpp:236-358, primal-dual variant)
    int gondzio_loop(double sigma, double mu_now, double* ap, double* ad) {
@@ -1629,8 +1673,8 @@ struct Ipm {
       // ---- start point: push_to_interior(sqrt(dnorm)), one affine solve, full step, shift (PIPSIPMppSolver.cpp:36-42, Solver.cpp:19-31)
       const double s0 = std::sqrt(dnorm);
       TRY(pips_hip_vec_set(NP + ND, 0.0, it.base, stream));
-      hipLaunchKernelGGL(k_masked_const, dim3(egrid(ncp)), dim3(256), 0, stream, ncp, 0, s0, M, it.G);
-      hipLaunchKernelGGL(k_masked_const, dim3(egrid(ncp)), dim3(256), 0, stream, ncp, 0, s0, M, it.L);
+      launch_masked_const(ncp, 0, s0, M, it.G, stream);
+      launch_masked_const(ncp, 0, s0, M, it.L, stream);
       double rnorm, pobj, dobj, m;
       TRY(residuals(&rnorm, &pobj, &dobj, &m));
       compl_rhs(0, 0, 0, 0, 0, 0);
@@ -1648,8 +1692,8 @@ struct Ipm {
          TRY(reduce(pk, o));
          const double viol = std::max(0.0, std::max(-o[0], -o[1]));
          const double shift = 1e3 + 2.0 * viol;
-         hipLaunchKernelGGL(k_masked_const, dim3(egrid(ncp)), dim3(256), 0, stream, ncp, 1, shift, M, it.G);
-         hipLaunchKernelGGL(k_masked_const, dim3(egrid(ncp)), dim3(256), 0, stream, ncp, 1, shift, M, it.L);
+         launch_masked_const(ncp, 1, shift, M, it.G, stream);
+         launch_masked_const(ncp, 1, shift, M, it.L, stream);
       }
       int iter = 0, status = 1;  // 1 = max iterations
       trace.clear();
@@ -2277,5 +2321,198 @@ int pips_ipm_outer_solve(void* handle, const double* G_host, const double* L_hos
 }
 
 void pips_ipm_destroy(void* handle) { delete (Ipm*)handle; }
+
+}  // extern "C"
+
+/* ---- the harness kernels beside the handle, for parity tests: host arrays in, the handle's launch code (launch_* above), host arrays out.
+ * Synchronous, on the current device's null stream; every device buffer is a local DevBuf, so nothing outlives a call. ---- */
+namespace {
+
+int probe_device(const char* who) {
+   int cnt = 0;
+   if ((hipGetDeviceCount)(&cnt) != hipSuccess || cnt == 0) PIPS_FAIL(PIPS_ERR_NO_DEVICE, "%s: no HIP device visible: the MI355X backend has no CPU fallback", who);
+   return PIPS_OK;
+}
+template <class T>
+int probe_up(DevBuf<T>& b, const T* h, long long n) {   // a null h: an empty (one-element) buffer nobody reads
+   TRY(b.alloc((size_t)std::max<long long>(h ? n : 0, 0)));
+   if (h && n > 0) HIP_TRYH(hipMemcpy(b.get(), h, (size_t)n * sizeof(T), hipMemcpyHostToDevice));
+   return PIPS_OK;
+}
+// pred: -1 none, else the value the kernels find behind their predicate pointer
+int probe_pred(DevBuf<int>& b, int pred, const int** p) {
+   *p = nullptr;
+   if (pred < 0) return PIPS_OK;
+   const int v = pred != 0;
+   TRY(probe_up(b, &v, 1));
+   *p = b.get();
+   return PIPS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pips_ipm_probe_spmv(int mode, int nrows, int ncols, const int* rowptr, const int* colidx, const double* val, const double* in,
+                        const double* e0, const double* e1, const double* e2, const double* e3, int split, int lin, int r0e, int r1b, int r1e,
+                        int pred, double* out, long long out_len, int* lanes, int* n_long, int* long_rows) {
+   const char* who = "pips_ipm_probe_spmv";
+   if (mode < SP_RQ || mode > SP_QX || nrows < 0 || ncols < 0 || !rowptr || !out || out_len < nrows || lin < 0 || lin > 2 || split < 0 || split > nrows)
+      PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments (mode 0..6, lin 0..2, 0 <= split <= nrows <= out_len)", who);
+   if (rowptr[0] != 0) PIPS_FAIL(PIPS_ERR_ARG, "%s: rowptr[0] is %d", who, rowptr[0]);
+   for (int r = 0; r < nrows; ++r)
+      if (rowptr[r + 1] < rowptr[r]) PIPS_FAIL(PIPS_ERR_ARG, "%s: rowptr decreases at row %d", who, r);
+   const long long nnz = rowptr[nrows];
+   if (nnz > 0 && (!colidx || !val || !in)) PIPS_FAIL(PIPS_ERR_ARG, "%s: entries without colidx / val / in", who);
+   for (long long p = 0; p < nnz; ++p)
+      if (colidx[p] < 0 || colidx[p] >= ncols) PIPS_FAIL(PIPS_ERR_ARG, "%s: column index %d at entry %lld outside [0, %d)", who, colidx[p], p, ncols);
+   // the operands an epilogue reads on some row must be there (e3 is optional: a QP handle's Q x); SP_RAC: e0 has split entries, e1 the rest
+   const bool need[7][3] = {{1, 1, 1}, {1, 1, 0}, {1, 1, 0}, {1, 1, 0}, {1, 1, 1}, {1, 1, 1}, {0, 0, 0}};
+   const double* e[4] = {e0, e1, e2, e3};
+   long long elen[4] = {nrows, nrows, nrows, nrows};
+   if (mode == SP_RAC) { elen[0] = split; elen[1] = nrows - split; }
+   for (int k = 0; k < 3; ++k)
+      if (need[mode][k] && !e[k] && elen[k] > 0) PIPS_FAIL(PIPS_ERR_ARG, "%s: mode %d reads e%d", who, mode, k);
+   if (lin == 2 && !e3 && (mode == SP_RQ || mode == SP_KX || mode == SP_RES_X) && nrows > 0)
+      PIPS_FAIL(PIPS_ERR_ARG, "%s: lin = 2 is a handle with a cross Hessian: mode %d reads e3", who, mode);
+   TRY(probe_device(who));
+   std::vector<int> rp(rowptr, rowptr + nrows + 1), list;
+   const int nl = csr_long_rows(rp, list);   // the builder of the layout's lists
+   DevBuf<int> d_rp, d_ci, d_long, d_pred;
+   DevBuf<double> d_v, d_in, d_out, d_e[4], d_scratch;
+   TRY(d_rp.upload(rp)); TRY(probe_up(d_ci, colidx, nnz)); TRY(probe_up(d_v, val, nnz)); TRY(probe_up(d_in, in, ncols));
+   TRY(d_long.upload(list));
+   TRY(d_scratch.alloc_zero((size_t)std::max(nl, 1) * LONG_PARTS));
+   TRY(probe_up(d_out, (const double*)out, out_len));
+   SpmvArgs a;
+   for (int k = 0; k < 4; ++k) TRY(probe_up(d_e[k], e[k], elen[k]));
+   a.nrows = nrows; a.rp = d_rp; a.ci = d_ci; a.v = d_v; a.in = d_in; a.out = d_out;
+   a.e0 = e0 ? d_e[0].get() : nullptr; a.e1 = e1 ? d_e[1].get() : nullptr; a.e2 = e2 ? d_e[2].get() : nullptr; a.e3 = e3 ? d_e[3].get() : nullptr;
+   a.split = split; a.lin = lin; a.r0e = r0e; a.r1b = r1b; a.r1e = r1e;
+   TRY(probe_pred(d_pred, pred, &a.pred));
+   hipStream_t stream = nullptr;
+   switch (mode) {
+      case SP_RQ:     launch_spmv<SP_RQ>(a, nnz, d_long, nl, d_scratch, stream); break;
+      case SP_RAC:    launch_spmv<SP_RAC>(a, nnz, d_long, nl, d_scratch, stream); break;
+      case SP_KX:     launch_spmv<SP_KX>(a, nnz, d_long, nl, d_scratch, stream); break;
+      case SP_KYZ:    launch_spmv<SP_KYZ>(a, nnz, d_long, nl, d_scratch, stream); break;
+      case SP_RES_X:  launch_spmv<SP_RES_X>(a, nnz, d_long, nl, d_scratch, stream); break;
+      case SP_RES_YZ: launch_spmv<SP_RES_YZ>(a, nnz, d_long, nl, d_scratch, stream); break;
+      default:        launch_spmv<SP_QX>(a, nnz, d_long, nl, d_scratch, stream); break;
+   }
+   HIP_TRYH(hipGetLastError());
+   HIP_TRYH(hipStreamSynchronize(stream));
+   if (out_len > 0) HIP_TRYH(hipMemcpy(out, d_out.get(), (size_t)out_len * sizeof(double), hipMemcpyDeviceToHost));
+   if (lanes) *lanes = nrows > 0 ? spmv_lanes(nrows, nnz) : 0;
+   if (n_long) *n_long = nl;
+   if (long_rows) std::copy(list.begin(), list.begin() + nl, long_rows);
+   return PIPS_OK;
+}
+
+int pips_ipm_probe_reduce(int n_terms, const pips_ipm_red_term* terms, int pred, double* out) {
+   const char* who = "pips_ipm_probe_reduce";
+   if (n_terms < 1 || n_terms > RED_MAX || !terms || !out) PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments (1 <= n_terms <= %d)", who, RED_MAX);
+   // the operands a kind reads: a b c d (w is optional, and R_ABSMAX takes d as an optional divisor)
+   const bool need[5][4] = {{1, 1, 0, 0}, {1, 0, 0, 0}, {1, 0, 1, 0}, {1, 1, 0, 0}, {1, 1, 1, 1}};
+   for (int k = 0; k < n_terms; ++k) {
+      const pips_ipm_red_term& t = terms[k];
+      if (t.kind < R_DOT || t.kind > R_DOT_SHIFTED || t.n < 0) PIPS_FAIL(PIPS_ERR_ARG, "%s: term %d: kind %d, n %lld", who, k, t.kind, t.n);
+      const double* o[4] = {t.a, t.b, t.c, t.d};
+      for (int j = 0; j < 4; ++j)
+         if (t.n > 0 && need[t.kind][j] && !o[j]) PIPS_FAIL(PIPS_ERR_ARG, "%s: term %d of kind %d reads operand %c", who, k, t.kind, "abcd"[j]);
+   }
+   TRY(probe_device(who));
+   std::vector<DevBuf<double>> opd((size_t)5 * n_terms);
+   DevBuf<double> d_partial, d_out;
+   DevBuf<int> d_pred;
+   RedPack pk;
+   pk.n_terms = n_terms;
+   for (int k = 0; k < n_terms; ++k) {
+      const pips_ipm_red_term& t = terms[k];
+      const double* o[5] = {t.a, t.b, t.c, t.d, t.w};
+      const double* dv[5];
+      for (int j = 0; j < 5; ++j) {
+         TRY(probe_up(opd[(size_t)5 * k + j], o[j], t.n));
+         dv[j] = o[j] ? opd[(size_t)5 * k + j].get() : nullptr;
+      }
+      pk.t[k] = Ipm::term(t.kind, t.n, dv[0], dv[1], dv[2], dv[3], dv[4], t.p, t.q);
+   }
+   TRY(d_partial.alloc_zero((size_t)RED_MAX * RED_GRID));
+   TRY(probe_up(d_out, (const double*)out, n_terms));
+   const int* p = nullptr;
+   TRY(probe_pred(d_pred, pred, &p));
+   hipStream_t stream = nullptr;
+   launch_reduce(pk, d_partial, d_out, p, stream);
+   HIP_TRYH(hipGetLastError());
+   HIP_TRYH(hipStreamSynchronize(stream));
+   HIP_TRYH(hipMemcpy(out, d_out.get(), (size_t)n_terms * sizeof(double), hipMemcpyDeviceToHost));
+   return PIPS_OK;
+}
+
+int pips_ipm_probe_step(int kernel, int nx, int my, int mz, long long n, int flag, const double* scalars, int n_in, const double* const* in,
+                        const long long* in_len, const long long* idx, long long idx_len, int n_out, double* const* out, const long long* out_len) {
+   const char* who = "pips_ipm_probe_step";
+   if (kernel < PIPS_STEP_BOUND_RESIDUALS || kernel > PIPS_STEP_GATHER || nx < 0 || my < 0 || mz < 0 || n < 0 || n_in < 0 || n_out < 0 ||
+       (n_in > 0 && (!in || !in_len)) || (n_out > 0 && (!out || !out_len)) || !scalars)
+      PIPS_FAIL(PIPS_ERR_ARG, "%s: bad arguments", who);
+   const long long ncp = 2LL * mz + 2LL * nx, nyz = (long long)my + mz, nxyz = nx + nyz;
+   // what each kernel reads and writes, in the order of its argument list: the least lengths (a longer array is taken whole: guards)
+   std::vector<long long> ni, no;
+   int opt = -1;        // an input that may be NULL
+   long long nidx = 0;
+   switch (kernel) {
+      case PIPS_STEP_BOUND_RESIDUALS: ni = {nx, mz, mz, ncp, ncp, ncp, ncp}; no = {mz, ncp}; break;
+      case PIPS_STEP_DIAGONALS:       ni = {ncp, ncp, ncp}; no = {nx, nx, nyz}; break;
+      case PIPS_STEP_LEAF_DIAG:       ni = {nx, mz, nx}; no = {n}; opt = 2; nidx = n; break;
+      case PIPS_STEP_REG_OPERATOR:    ni = {nx, nyz}; no = {nx, nyz}; break;
+      case PIPS_STEP_RHS_REDUCE:      ni = {nx, nyz, mz, ncp, ncp, ncp, ncp, ncp, nyz}; no = {nxyz, mz}; break;
+      case PIPS_STEP_RECOVER:         ni = {nxyz, mz, ncp, ncp, ncp, ncp, ncp, nyz}; no = {nx + mz + ncp, nyz + ncp}; break;
+      case PIPS_STEP_COMPL_RHS:       ni = {n, n, n, n, n}; no = {n}; break;
+      case PIPS_STEP_MASKED_CONST:    ni = {n}; no = {n}; break;
+      default:                            ni = {0}; no = {0}; nidx = n; break;   // gather: the lengths bound the indices, below
+   }
+   if (n_in != (int)ni.size() || n_out != (int)no.size()) PIPS_FAIL(PIPS_ERR_ARG, "%s: kernel %d takes %zu inputs and %zu outputs", who, kernel, ni.size(), no.size());
+   for (int k = 0; k < n_in; ++k)
+      if (!in[k] ? (k != opt && ni[k] > 0) : in_len[k] < ni[k]) PIPS_FAIL(PIPS_ERR_ARG, "%s: kernel %d: input %d is NULL or shorter than %lld", who, kernel, k, ni[k]);
+   for (int k = 0; k < n_out; ++k)
+      if (out_len[k] < no[k] || (!out[k] && out_len[k] > 0)) PIPS_FAIL(PIPS_ERR_ARG, "%s: kernel %d: output %d is NULL or shorter than %lld", who, kernel, k, no[k]);
+   if (idx_len < nidx || (nidx > 0 && !idx)) PIPS_FAIL(PIPS_ERR_ARG, "%s: kernel %d reads %lld indices", who, kernel, nidx);
+   if (kernel == PIPS_STEP_LEAF_DIAG)
+      for (long long p = 0; p < n; ++p)
+         if (idx[p] >= nx || -2 - idx[p] >= mz) PIPS_FAIL(PIPS_ERR_ARG, "%s: leaf code %lld at %lld outside x (%d) or the inequality rows (%d)", who, idx[p], p, nx, mz);
+   if (kernel == PIPS_STEP_GATHER) {
+      const long long lim = flag ? out_len[0] : in_len[0];
+      if ((flag ? in_len[0] : out_len[0]) < n) PIPS_FAIL(PIPS_ERR_ARG, "%s: gather: the array walked in order is shorter than n", who);
+      for (long long p = 0; p < n; ++p)
+         if (idx[p] < 0 || idx[p] >= lim) PIPS_FAIL(PIPS_ERR_ARG, "%s: gather: index %lld at %lld outside [0, %lld)", who, idx[p], p, lim);
+   }
+   TRY(probe_device(who));
+   std::vector<DevBuf<double>> di((size_t)n_in), dout((size_t)n_out);
+   DevBuf<long long> d_idx;
+   std::vector<const double*> I((size_t)n_in);
+   std::vector<double*> O((size_t)n_out);
+   for (int k = 0; k < n_in; ++k) { TRY(probe_up(di[k], in[k], in_len[k])); I[k] = in[k] ? di[k].get() : nullptr; }
+   for (int k = 0; k < n_out; ++k) { TRY(probe_up(dout[k], (const double*)out[k], out_len[k])); O[k] = dout[k].get(); }
+   TRY(probe_up(d_idx, idx, nidx));
+   const Lay lay{nx, my, mz, ncp};
+   const double* sc = scalars;
+   hipStream_t stream = nullptr;
+   switch (kernel) {
+      case PIPS_STEP_BOUND_RESIDUALS: launch_bound_residuals(lay, I[0], I[1], I[2], I[3], I[4], I[5], I[6], O[0], O[1], stream); break;
+      case PIPS_STEP_DIAGONALS:       launch_diagonals(lay, I[0], I[1], I[2], sc[0], O[0], O[1], O[2], stream); break;
+      case PIPS_STEP_LEAF_DIAG:       launch_leaf_diag(n, d_idx, I[0], I[1], I[2], sc[0], sc[1], sc[2], O[0], stream); break;
+      case PIPS_STEP_REG_OPERATOR:    launch_reg_operator(lay, I[0], I[1], sc[0], sc[1], O[0], O[1], stream); break;
+      case PIPS_STEP_RHS_REDUCE:      launch_rhs_reduce(lay, flag, I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], O[0], O[1], stream); break;
+      case PIPS_STEP_RECOVER:         launch_recover(lay, flag, I[0], I[1], I[2], I[3], I[4], I[5], I[6], I[7], O[0], O[1], stream); break;
+      case PIPS_STEP_COMPL_RHS:       launch_compl_rhs(n, flag, I[0], I[1], I[2], I[3], I[4], sc[0], sc[1], sc[2], sc[3], sc[4], O[0], stream); break;
+      case PIPS_STEP_MASKED_CONST:    launch_masked_const(n, flag, sc[0], I[0], O[0], stream); break;
+      default:                            launch_gather(n, d_idx, I[0], O[0], flag, stream); break;
+   }
+   HIP_TRYH(hipGetLastError());
+   HIP_TRYH(hipStreamSynchronize(stream));
+   for (int k = 0; k < n_out; ++k)
+      if (out_len[k] > 0) HIP_TRYH(hipMemcpy(out[k], dout[k].get(), (size_t)out_len[k] * sizeof(double), hipMemcpyDeviceToHost));
+   return PIPS_OK;
+}
 
 }  // extern "C"

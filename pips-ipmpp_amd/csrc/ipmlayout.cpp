@@ -154,7 +154,7 @@ static void rows_to_csr(std::vector<std::vector<std::pair<int, double>>>& rows, 
       }
    }
 }
-static int long_rows(const std::vector<int>& rp, std::vector<int>& list) {
+int csr_long_rows(const std::vector<int>& rp, std::vector<int>& list) {
    list.clear();
    for (size_t r = 0; r + 1 < rp.size(); ++r)
       if (rp[r + 1] - rp[r] > CSR_LONG_ROW) list.push_back((int)r);
@@ -178,8 +178,8 @@ void ipm_rows_J(const IpmInput& in, int rank, IpmLayout& L) {
       add(b.BL, L.my0, L.xoff[i]); add(b.DL, L.my + L.mz0, L.xoff[i]);
    }
    rows_to_csr(rows, L.nx, L.J);
-   L.J.n_long = long_rows(L.J.rp, L.J.long_rows);
-   L.J.n_tlong = long_rows(L.J.trp, L.J.long_trows);
+   L.J.n_long = csr_long_rows(L.J.rp, L.J.long_rows);
+   L.J.n_tlong = csr_long_rows(L.J.trp, L.J.long_trows);
 }
 
 // ---- leaf systems: K_i pattern / values and border for the engine ------------------------------------------------------------------
@@ -374,7 +374,7 @@ void ipm_flat_hessian(const IpmInput& in, IpmLayout& L) {
       L.Q_rp[(size_t)r + 1] = (int)L.Q_ci.size();
    }
    L.Q_nnz = (long long)L.Q_ci.size();
-   L.nQ_long = long_rows(L.Q_rp, L.Q_long);
+   L.nQ_long = csr_long_rows(L.Q_rp, L.Q_long);
    L.Q_ci.push_back(0); L.Q_v.push_back(0.0);   // never empty arrays
 }
 

@@ -37,6 +37,9 @@ struct HostCsr {
    std::vector<double> v, tv;
    int n_long = 0, n_tlong = 0;
 };
+// the rows of a CSR row pointer longer than CSR_LONG_ROW, ascending, padded by one entry; returns their count.  The one builder of
+// every long-row list: J, J^T and Q of a layout, and the matrix handed to pips_ipm_probe_spmv
+int csr_long_rows(const std::vector<int>& rp, std::vector<int>& list);
 // One block's Hessian as the caller gave it, checked and with sorted rows (duplicates added up): lower-triangular CSR like the
 // reference's SparseSymmetricMatrix.
 struct LowerQ { bool have = false; std::vector<int> rp, ci; std::vector<double> v; };

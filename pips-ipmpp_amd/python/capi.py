@@ -71,7 +71,7 @@ SYMBOLS = [
     "pips_hip_vec_add_const", "pips_hip_vec_mul", "pips_hip_vec_div", "pips_hip_vec_add_product", "pips_hip_vec_add_quotient",
     "pips_hip_vec_divide_some", "pips_hip_vec_select_nonzeros", "pips_hip_vec_safe_invert", "pips_hip_vec_gondzio_projection", "pips_hip_vec_dot",
     "pips_hip_vec_one_norm", "pips_hip_vec_inf_norm", "pips_hip_vec_min", "pips_hip_vec_sumsq_scaled", "pips_hip_vec_stepbound",
-    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_create_qp_scaled", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
+    "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_create_qp_scaled", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_probe_spmv", "pips_ipm_probe_reduce", "pips_ipm_probe_step", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
     "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe", "pips_det_plan_probe", "pips_schur_target_probe",
@@ -1123,6 +1123,68 @@ class vec:
     def dot_shifted(x, a, dx, y, b, dy, skip_root=0):
         return vec._red(lib.pips_hip_vec_dot_shifted, vec._n(x), C.c_longlong(skip_root), _ptr(x), C.c_double(a), _ptr(dx),
                         _ptr(y), C.c_double(b), _ptr(dy))
+
+
+class _RedTerm(C.Structure):   # pips_ipm_red_term
+    _fields_ = [("kind", C.c_int), ("n", C.c_longlong), ("a", _vp), ("b", _vp), ("c", _vp), ("d", _vp), ("w", _vp), ("p", C.c_double), ("q", C.c_double)]
+
+
+class harness:
+    """The kernels of csrc/harness.hip beside a handle (pips_ipm_probe_*): numpy arrays in, the handle's launch code, numpy arrays out."""
+    SP_RQ, SP_RAC, SP_KX, SP_KYZ, SP_RES_X, SP_RES_YZ, SP_QX = range(7)
+    R_DOT, R_ABSMAX, R_MIN_MASKED, R_STEPBOUND, R_DOT_SHIFTED = range(5)
+    STEP = {"bound_residuals": 0, "diagonals": 1, "leaf_diag": 2, "reg_operator": 3, "rhs_reduce": 4, "recover": 5, "compl_rhs": 6,
+            "masked_const": 7, "gather": 8}
+
+    @staticmethod
+    def _d(a):
+        return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+    @staticmethod
+    def spmv(mode, nrows, ncols, rowptr, colidx, val, x, out, e0=None, e1=None, e2=None, e3=None, split=0, lin=0, r0e=0, r1b=0, r1e=0, pred=-1):
+        """out (float64, at least nrows long, written in place) = epilogue(M x); returns (lanes per row, the long rows)"""
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable
+        rp, ci, v, x = _i32(rowptr), _i32(colidx), _f64(val), _f64(x)
+        e = [harness._d(a) for a in (e0, e1, e2, e3)]
+        lanes, nl = C.c_int(), C.c_int()
+        rows = np.zeros(max(nrows, 1), np.int32)
+        _check(lib.pips_ipm_probe_spmv(C.c_int(mode), C.c_int(nrows), C.c_int(ncols), _ptr(rp), _ptr(ci), _ptr(v), _ptr(x), *[_ptr(a) for a in e],
+                                       C.c_int(split), C.c_int(lin), C.c_int(r0e), C.c_int(r1b), C.c_int(r1e), C.c_int(pred), _ptr(out),
+                                       C.c_longlong(out.size), C.byref(lanes), C.byref(nl), _ptr(rows)), "pips_ipm_probe_spmv")
+        return lanes.value, rows[:nl.value].copy()
+
+    @staticmethod
+    def reduce(terms, out, pred=-1):
+        """terms: dicts with kind, n and any of a b c d w (arrays) p q; out (float64, one entry per term) is written in place"""
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.size >= len(terms)
+        arr = (_RedTerm * max(len(terms), 1))()
+        keep = []
+        for k, t in enumerate(terms):
+            arr[k].kind, arr[k].n, arr[k].p, arr[k].q = int(t["kind"]), int(t["n"]), float(t.get("p", 0.0)), float(t.get("q", 0.0))
+            for f in "abcdw":
+                a = harness._d(t.get(f))
+                keep.append(a)
+                assert a is None or a.size >= arr[k].n
+                setattr(arr[k], f, None if a is None else a.ctypes.data)
+        _check(lib.pips_ipm_probe_reduce(C.c_int(len(terms)), arr, C.c_int(pred), _ptr(out)), "pips_ipm_probe_reduce")
+        return out
+
+    @staticmethod
+    def step(kernel, nx, my, mz, ins, outs, n=0, flag=0, scalars=(), idx=None):
+        """kernel: a name of STEP; ins / outs: the kernel's arrays in the order of include/pips_hip.h (outs float64, written in place)"""
+        ins = [harness._d(a) for a in ins]
+        for o in outs:
+            assert o.dtype == np.float64 and o.flags.c_contiguous and o.flags.writeable
+        sc = np.zeros(5)
+        sc[:len(scalars)] = scalars
+        ip = (_vp * max(len(ins), 1))(*[None if a is None else a.ctypes.data for a in ins])
+        op = (_vp * max(len(outs), 1))(*[o.ctypes.data for o in outs])
+        il = np.array([0 if a is None else a.size for a in ins] + [0], np.int64)
+        ol = np.array([o.size for o in outs] + [0], np.int64)
+        ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        _check(lib.pips_ipm_probe_step(C.c_int(harness.STEP[kernel]), C.c_int(nx), C.c_int(my), C.c_int(mz), C.c_longlong(n), C.c_int(flag), _ptr(sc),
+                                       C.c_int(len(ins)), ip, _ptr(il), _ptr(ix), C.c_longlong(0 if ix is None else ix.size), C.c_int(len(outs)), op,
+                                       _ptr(ol)), "pips_ipm_probe_step")
 
 
 class IpmSolver:
