@@ -39,6 +39,9 @@ public:
       const auto [nrows, ncols] = rhs.n_rows_columns();
       check(pips_hip_dense_ldl_solve(h, static_cast<int>(nrows), &rhs[0][0], static_cast<int>(ncols)), "solve(matrix)");
    }
+   // nrhss contiguous right-hand sides of length n, what sLinsysRootAug.C:529 calls on the root solver (DeSymIndefSolver leaves it at the
+   // base class's assert); the column sparsity has no meaning for a dense solve and is ignored
+   void solve(int nrhss, double* rhss, int*) override { check(pips_hip_dense_ldl_solve(h, nrhss, rhss, n), "solve(nrhss)"); }
    [[nodiscard]] bool reports_inertia() const override { return true; }
    [[nodiscard]] std::tuple<unsigned, unsigned, unsigned> get_inertia() const override {
       int p, ng, z; check(pips_hip_dense_ldl_inertia(h, &p, &ng, &z), "inertia"); return {unsigned(p), unsigned(ng), unsigned(z)};

@@ -168,12 +168,21 @@ int pips_hip_dense_ldl_set_distributed(void* handle, void* comm, int rank, int n
 int pips_hip_dense_ldl_factor(void* handle, const double* A_host, int lda);
 /* factorise a matrix that already lives on the device in column-major-lower form (fused path, see section 3) */
 int pips_hip_dense_ldl_factor_dev(void* handle, const double* A_dev, int lda);
+/* = DeSymIndefSolver::solve: nrhs vectors of length n at distance ld >= n in host memory, overwritten with the solutions.  Fewer than 8
+ * right-hand sides (PIPS_HIP_MULTI as for the leaf solver: set non-zero 2, set to 0 never) are solved one at a time; from there on in
+ * chunks of at most 256 through interleaved panels of 32 on the matrix pipe, the factor read once per panel (= the one dsytrs call of
+ * DeSymIndefSolver::solve(GeneralMatrix&), DeSymIndefSolver.C:120-129), with one host stop per chunk. */
 int pips_hip_dense_ldl_solve(void* handle, int nrhs, double* rhs_inout_host, int ld);
 int pips_hip_dense_ldl_solve_dev(void* handle, double* rhs_inout_dev);
+/* ... the same for nrhs vectors at distance ld >= n in device memory, overwritten; asynchronous on the handle's stream.  nrhs == 0 is a
+ * no-op.  PIPS_ERR_ARG for a null pointer, nrhs < 0, ld < n; PIPS_ERR_STATE before a factorisation. */
+int pips_hip_dense_ldl_solve_multi_dev(void* handle, int nrhs, double* rhs_inout_dev, long long ld);
 int pips_hip_dense_ldl_inertia(void* handle, int* pos, int* neg, int* zero);
 /* diagnostics (read-only; tests assert which path ran): what[0]=1 if the last factorisation was the single launch, what[1]=tile columns
  * of 128, what[2]=ranks the factorisation is distributed over, what[3]=pivoting mode, what[4]=how often Bunch-Kaufman pivoting had to
- * factorise again under a new order since the handle was created */
+ * factorise again under a new order since the handle was created, what[5]=how the last solve call went (0 one sweep pair per
+ * right-hand side, 1 interleaved panels), what[6]=slices per panel of the last interleaved solve (1, 2, 4; 0: none yet), what[7]=1 if
+ * its tail sweeps were the single launches, 0 the launches per tile column */
 int pips_hip_dense_ldl_info(void* handle, int64_t* what, int n_what);
 void pips_hip_dense_ldl_destroy(void* handle);
 

@@ -11,6 +11,32 @@ __global__ void k_inertia_to_double(const int* __restrict__ in, double* __restri
    if (threadIdx.x < 3) { if (!back) out[threadIdx.x] = (double)in[threadIdx.x]; else in_out[threadIdx.x] = (int)(out[threadIdx.x] + 0.5); }
 }
 
+// Several right-hand sides (DenseLdl::solve_multi_dev): the transposing copy between the caller's nr vectors at distance ld and the interleaved
+// panels of MQ (kernels.hip.h "multi-vector solves": entry k of right-hand side q of panel p at xm[p * panel_stride + k * MQ + q]).  k_mpermute
+// is the leaf's version; its consecutive threads walk q, ld doubles apart on the caller's side - which for a dense root is the whole of the
+// data.  Here a workgroup moves 32 rows x 32 right-hand sides through an LDS tile padded to 33 columns, so that both sides are read and
+// written along their contiguous direction (with a Bunch-Kaufman order, perm != nullptr, the caller's side is a gather / scatter: position k
+// is x[perm[k]]).  grid (npad / 32, panels), 256 threads.  In (out = 0): all npad rows and MQ columns of every panel are written, zeros for
+// k >= n and q >= nr; out = 1: only k < n, q < nr go back.  Nothing of x outside the nr x n entries is touched.
+__global__ __launch_bounds__(256) void k_root_interleave(double* __restrict__ x, long long ld, int nr, int n, const int* __restrict__ perm,
+                                                         double* __restrict__ xm, long long panel_stride, int out) {
+   __shared__ double t[MQ][MQ + 1];   // t[q][k]
+   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5, k0 = 32 * blockIdx.x, q0 = MQ * blockIdx.y;
+   double* w = xm + panel_stride * blockIdx.y + (long long)k0 * MQ;
+   const int k = k0 + tx;
+   const long long col = k < n ? (perm ? perm[k] : k) : 0;
+   if (!out) {
+      for (int q = ty; q < MQ; q += 8) t[q][tx] = (k < n && q0 + q < nr) ? x[(long long)(q0 + q) * ld + col] : 0.0;
+      __syncthreads();
+      for (int r = ty; r < 32; r += 8) w[r * MQ + tx] = t[tx][r];
+   } else {
+      for (int r = ty; r < 32; r += 8) t[tx][r] = w[r * MQ + tx];
+      __syncthreads();
+      for (int q = ty; q < MQ; q += 8)
+         if (k < n && q0 + q < nr) x[(long long)(q0 + q) * ld + col] = t[q][tx];
+   }
+}
+
 struct DenseLdl {
    int device = 0, n = 0, npad = 0, n_primal = -1;
    // 0: static pivot order with the expected signs of the inertia hint (right for the quasi-definite Schur complement the fused
@@ -457,6 +483,7 @@ struct DenseLdl {
       HIP_TRY(hipSetDevice(device));
       int rc = check_pivots();     // (a factorisation whose pivots were not looked at yet: host-pointer callers come here first)
       if (rc) return rc;
+      last_solve_path = 0;
       HIP_TRY(hipMemsetAsync(d_xw, 0, (size_t)npad * sizeof(double), stream));
       if (perm.empty()) HIP_TRY(hipMemcpyAsync(d_xw, x_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
       else hipLaunchKernelGGL(k_perm_gather, dim3(grid_for(n, 256)), dim3(256), 0, stream, d_perm, n, x_dev, d_xw, 0, (double*)nullptr);
@@ -466,6 +493,59 @@ struct DenseLdl {
       if (rc) return rc;
       if (perm.empty()) HIP_TRY(hipMemcpyAsync(x_dev, d_xw, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
       else hipLaunchKernelGGL(k_perm_gather, dim3(grid_for(n, 256)), dim3(256), 0, stream, d_perm, n, (const double*)nullptr, d_xw, 1, x_dev);
+      return PIPS_OK;
+   }
+
+   // ---- several right-hand sides (= DeSymIndefSolver::solve(GeneralMatrix&), one dsytrs call for all of them: DeSymIndefSolver.C:120-129).
+   // From Engine::multi_knob().from right-hand sides on (8; PIPS_HIP_MULTI as for the leaves) they go through the leaf solver's interleaved
+   // tail sweeps - panels of MQ = 32 on the matrix pipe, L read once per panel instead of once per right-hand side (mtail_sweep: the root is
+   // one block without a head).  Chunks of at most Engine::MULTI_CHUNK_MAX right-hand sides; k_root_interleave copies in and out of d_xm.
+   DevBuf<double> d_xm;             // np * MQ * npad doubles: panel p at d_xm + p * MQ * npad, entry k of right-hand side q at [k * MQ + q]
+   int xm_cap = 0;                  // right-hand sides it holds
+   DevBuf<double> d_stage;          // the host-pointer entry's copy of a chunk (nr x n; d_in is n x n and nrhs may exceed n)
+   int stage_cap = 0;
+   int last_solve_path = 0, last_solve_slices = 0, last_solve_rows = 0;   // pips_hip_dense_ldl_info what[5 .. 7]
+   static int grow(DevBuf<double>& buf, int& cap, int want, size_t per_rhs, hipStream_t st) {
+      if (cap >= want) return PIPS_OK;
+      if (buf) HIP_TRY(hipStreamSynchronize(st));   // (work queued on the smaller one)
+      buf.reset();
+      cap = 0;
+      PIPS_TRY(buf.alloc((size_t)want * std::max<size_t>(per_rhs, 1)));
+      cap = want;
+      return PIPS_OK;
+   }
+   static bool use_multi(int nrhs) {
+      const int from = Engine::multi_knob().from;
+      return from > 0 && nrhs >= from;
+   }
+   // X_dev: nrhs vectors of length n at distance ld >= n on the device, overwritten; asynchronous on the handle's stream.
+   // part_of_more: a chunk of a larger set that took the interleaved path (the host-pointer entry): however few, it takes it too
+   int solve_multi_dev(double* X_dev, int nrhs, long long ld, bool part_of_more = false) {
+      if (!factored) PIPS_FAIL(PIPS_ERR_STATE, "dense solve called before factor");
+      HIP_TRY(hipSetDevice(device));
+      PIPS_TRY(check_pivots());
+      if (!part_of_more && !use_multi(nrhs)) {
+         last_solve_path = 0;
+         for (int r = 0; r < nrhs; ++r) PIPS_TRY(solve_dev(X_dev + (long long)r * ld));
+         return PIPS_OK;
+      }
+      const int chunk_max = Engine::MULTI_CHUNK_MAX;
+      PIPS_TRY(grow(d_xm, xm_cap, (std::min(nrhs, chunk_max) + MQ - 1) / MQ * MQ, (size_t)npad, stream));
+      const TailCtx c = ctx();
+      const long long ps = (long long)MQ * npad;
+      const int* pm = perm.empty() ? (const int*)nullptr : (const int*)d_perm;
+      for (int r0 = 0; r0 < nrhs; r0 += chunk_max) {
+         const int nr = std::min(chunk_max, nrhs - r0), np = (nr + MQ - 1) / MQ;
+         double* X = X_dev + (long long)r0 * ld;
+         const dim3 grid(npad / 32, np);
+         const int sl = mtail_slices(c, np, Engine::multi_knob().slices);
+         hipLaunchKernelGGL(k_root_interleave, grid, dim3(256), 0, stream, X, ld, nr, n, pm, (double*)d_xm, ps, 0);
+         mtail_sweep(c, d_xm, ps, np, sl, 0);
+         mtail_sweep(c, d_xm, ps, np, sl, 1);
+         hipLaunchKernelGGL(k_root_interleave, grid, dim3(256), 0, stream, X, ld, nr, n, pm, (double*)d_xm, ps, 1);
+         last_solve_path = 1; last_solve_slices = std::max(sl, 1); last_solve_rows = sl > 0 ? 1 : 0;
+      }
+      HIP_TRY(hipGetLastError());
       return PIPS_OK;
    }
 };
@@ -533,10 +613,33 @@ int pips_hip_dense_ldl_solve_dev(void* handle, double* rhs_inout_dev) {
    return d->solve_dev(rhs_inout_dev);
 }
 
+int pips_hip_dense_ldl_solve_multi_dev(void* handle, int nrhs, double* rhs_inout_dev, long long ld) {
+   DenseLdl* d = (DenseLdl*)handle;
+   if (nrhs < 0 || !d || !rhs_inout_dev || ld < d->n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_solve_multi_dev: bad arguments");
+   if (nrhs == 0) return PIPS_OK;
+   return d->solve_multi_dev(rhs_inout_dev, nrhs, ld);
+}
+
 int pips_hip_dense_ldl_solve(void* handle, int nrhs, double* rhs, int ld) {
    DenseLdl* d = (DenseLdl*)handle;
    if (!d || !rhs || nrhs < 0 || ld < d->n) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_solve: bad arguments");
    HIP_TRY(hipSetDevice(d->device));
+   if (DenseLdl::use_multi(nrhs)) {
+      // interleaved panels: per chunk one strided copy into a staging buffer of its own, one solve_multi_dev, one copy back, one host stop
+      const int chunk_max = Engine::MULTI_CHUNK_MAX;
+      const size_t row = (size_t)d->n * sizeof(double);
+      PIPS_TRY(DenseLdl::grow(d->d_stage, d->stage_cap, std::min(nrhs, chunk_max), (size_t)d->n, d->stream));
+      for (int r0 = 0; r0 < nrhs; r0 += chunk_max) {
+         const int nr = std::min(chunk_max, nrhs - r0);
+         double* x = rhs + (size_t)r0 * ld;
+         HIP_TRY(hipMemcpy2DAsync(d->d_stage, row, x, (size_t)ld * sizeof(double), row, (size_t)nr, hipMemcpyHostToDevice, d->stream));
+         PIPS_TRY(d->solve_multi_dev(d->d_stage, nr, d->n, true));
+         HIP_TRY(hipMemcpy2DAsync(x, (size_t)ld * sizeof(double), d->d_stage, row, row, (size_t)nr, hipMemcpyDeviceToHost, d->stream));
+         HIP_TRY(hipStreamSynchronize(d->stream));
+      }
+      return d->sweep.take_error("pips_hip_dense_ldl_solve");
+   }
+   d->last_solve_path = 0;
    if (int rc0 = d->ensure_input_buffer()) return rc0;
    for (int k = 0; k < nrhs; ++k) {
       double* x = rhs + (size_t)k * ld;
@@ -567,8 +670,9 @@ int pips_hip_dense_ldl_inertia(void* handle, int* pos, int* neg, int* zero) {
 int pips_hip_dense_ldl_info(void* handle, int64_t* what, int n_what) {
    DenseLdl* d = (DenseLdl*)handle;
    if (!d || !what || n_what < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_dense_ldl_info: bad arguments");
-   const int64_t v[5] = {d->factored && d->last_single ? 1 : 0, d->npad / TILE, d->dist_P, d->pivoting, d->bk_refactorizations};
-   for (int i = 0; i < n_what && i < 5; ++i) what[i] = v[i];
+   const int64_t v[8] = {d->factored && d->last_single ? 1 : 0, d->npad / TILE, d->dist_P, d->pivoting, d->bk_refactorizations,
+                         d->last_solve_path, d->last_solve_slices, d->last_solve_rows};
+   for (int i = 0; i < n_what && i < 8; ++i) what[i] = v[i];
    return PIPS_OK;
 }
 

@@ -574,6 +574,43 @@ static int tail_bwd(const TailCtx& c, double* xw, int nrhs = 1, long long xw_str
    return PIPS_OK;
 }
 
+// The tail sweeps of np interleaved panels of MQ right-hand sides (kernels.hip.h "multi-vector solves"; panel p at xm + p * panel_stride), the
+// one launch site of k_mtail_rows_fwd / _bwd<NC> and k_mtail_fwd / _bwd for both owners (Engine::solve_once_multi, DenseLdl::solve_multi_dev).
+// mtail_slices chooses once per pass: 0 = the launch per tile column, else the slices per panel of the single launch per direction.
+// Few tile rows per step (a single leaf, a small root): a workgroup takes a quarter or a half of a panel's right-hand sides, so that the chain
+// of a pass - one workgroup's tile products per step - is shorter; many: whole panels, L read once per 32 right-hand sides.  Every workgroup
+// of the launch must be resident for the slices to advance side by side (two per compute unit: the whole tile sits in registers), so the
+// finest slicing that keeps the launch within 512 workgroups is taken.  forced: PIPS_HIP_MULTI = 2 / 4 (Engine::multi_knob().slices; tests);
+// pin: a fixed slicing - the blocked Schur solves of deterministic mode, whose bits must not follow sweep->n_tasks, i.e. the blocks per rank
+static int mtail_slices(const TailCtx& c, int np, int forced, int pin = 0) {
+   if (!(c.sweep && c.sweep->enabled && np * 4 <= SWEEP_NRHS_MAX && c.plan->ntc_max > 0)) return 0;   // (tickets and flag rows are per blockIdx.y)
+   const long long wg = (long long)c.sweep->n_tasks * np;
+   return pin ? pin : forced ? forced : wg * 4 <= 512 ? 4 : wg * 2 <= 512 ? 2 : 1;
+}
+static void mtail_sweep(const TailCtx& c, double* xm, long long panel_stride, int np, int sl, int backward) {
+   const TailPlan& p = *c.plan;
+   if (sl > 0) {
+      const SweepArgs sa = c.sweep->args(0, c.stream);
+      const dim3 grid(c.sweep->n_tasks, np * sl), wg(256);
+      if (sl == 4 && !backward) hipLaunchKernelGGL(k_mtail_rows_fwd<2>, grid, wg, 0, c.stream, sa, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, xm, panel_stride);
+      else if (sl == 4) hipLaunchKernelGGL(k_mtail_rows_bwd<2>, grid, wg, 0, c.stream, sa, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, xm, panel_stride);
+      else if (sl == 2 && !backward) hipLaunchKernelGGL(k_mtail_rows_fwd<4>, grid, wg, 0, c.stream, sa, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, xm, panel_stride);
+      else if (sl == 2) hipLaunchKernelGGL(k_mtail_rows_bwd<4>, grid, wg, 0, c.stream, sa, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, xm, panel_stride);
+      else if (!backward) hipLaunchKernelGGL(k_mtail_rows_fwd<8>, grid, wg, 0, c.stream, sa, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, xm, panel_stride);
+      else hipLaunchKernelGGL(k_mtail_rows_bwd<8>, grid, wg, 0, c.stream, sa, c.d_blks, c.d_arena, c.d_dtail, c.d_winv, xm, panel_stride);
+   } else if (!backward) {
+      for (int j = 0; j < p.ntc_max; ++j)
+         if (p.fwd[j].cnt > 0)
+            hipLaunchKernelGGL(k_mtail_fwd, dim3(p.fwd[j].cnt, np), dim3(256), 0, c.stream, p.d_tasks + p.fwd[j].off, c.d_blks, c.d_arena, c.d_dtail,
+                               c.d_winv, xm, j, panel_stride);
+   } else {
+      for (int i = p.ntc_max - 1; i >= 0; --i)
+         if (p.bwd[i].cnt > 0)
+            hipLaunchKernelGGL(k_mtail_bwd, dim3(p.bwd[i].cnt, np), dim3(256), 0, c.stream, p.d_tasks + p.bwd[i].off, c.d_blks, c.d_arena, c.d_dtail,
+                               c.d_winv, xm, i, panel_stride);
+   }
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // batched leaf engine (BlockInput, LevelRange, MfLaunch and the host pass of the analysis: layout.h)
@@ -1577,40 +1614,14 @@ struct Engine : EngineAnalysis, BatchLayout {
       for (const LevelRange& L : levels) head(L, 0);
       for (const LevelRange& L : levels_top) head(L, 0);
       }
-      const TailPlan& p = plan;
-      const bool rows = sweep.enabled && np * 4 <= SWEEP_NRHS_MAX && p.ntc_max > 0;   // the tail sweeps as one launch per direction (tickets, flags)
-      // few tile rows per step (a single leaf): a workgroup takes a quarter or a half of a panel's right-hand sides, so that the chain of a pass -
-      // one workgroup's tile products per step - is shorter; many blocks: whole panels, L read once per 32 right-hand sides.  Every workgroup
-      // of the launch must be resident for the slices to advance side by side (two per compute unit: the whole tile sits in registers), so the
-      // finest slicing that keeps the launch within 512 workgroups is taken
-      const long long wg = (long long)sweep.n_tasks * np;
-      const int forced = multi_knob().slices;   // (tests)
-      // (pin_slices: a fixed slicing - the blocked Schur solves of deterministic mode, whose bits must not follow sweep.n_tasks, i.e. the blocks per rank)
-      const int sl = pin_slices ? pin_slices : forced ? forced : wg * 4 <= 512 ? 4 : wg * 2 <= 512 ? 2 : 1;
-      auto tail_rows = [&](int backward) {
-         const SweepArgs sa = sweep.args(0, stream);
-         if (sl == 4 && !backward) hipLaunchKernelGGL(k_mtail_rows_fwd<2>, dim3(sweep.n_tasks, np * 4), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);
-         else if (sl == 4) hipLaunchKernelGGL(k_mtail_rows_bwd<2>, dim3(sweep.n_tasks, np * 4), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);
-         else if (sl == 2 && !backward) hipLaunchKernelGGL(k_mtail_rows_fwd<4>, dim3(sweep.n_tasks, np * 2), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);
-         else if (sl == 2) hipLaunchKernelGGL(k_mtail_rows_bwd<4>, dim3(sweep.n_tasks, np * 2), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);
-         else if (!backward) hipLaunchKernelGGL(k_mtail_rows_fwd<8>, dim3(sweep.n_tasks, np), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);
-         else hipLaunchKernelGGL(k_mtail_rows_bwd<8>, dim3(sweep.n_tasks, np), dim3(256), 0, stream, sa, d_blks, d_arena, d_dtail, d_winv, xm, ps);
-      };
-      if (rows) tail_rows(0);
-      else
-      for (int j = 0; j < p.ntc_max; ++j)
-         if (p.fwd[j].cnt > 0)
-            hipLaunchKernelGGL(k_mtail_fwd, dim3(p.fwd[j].cnt, np), dim3(256), 0, stream, p.d_tasks + p.fwd[j].off, d_blks, d_arena, d_dtail,
-                               d_winv, xm, j, ps);
+      // the tail sweeps: slicing and launches are mtail_slices / mtail_sweep's (shared with the dense root)
+      const TailCtx c = ctx();
+      const int sl = mtail_slices(c, np, multi_knob().slices, pin_slices);
+      mtail_sweep(c, xm, ps, np, sl, 0);
       if (nsn_total > 0)
          hipLaunchKernelGGL(k_mhead_dscale, dim3(grid_for((long long)nsn_total * MQ, 256), np), dim3(256), 0, stream, d_sns, nsn_total, d_blks,
                             d_arena, xm, ps);
-      if (rows) tail_rows(1);
-      else
-      for (int i = p.ntc_max - 1; i >= 0; --i)
-         if (p.bwd[i].cnt > 0)
-            hipLaunchKernelGGL(k_mtail_bwd, dim3(p.bwd[i].cnt, np), dim3(256), 0, stream, p.d_tasks + p.bwd[i].off, d_blks, d_arena, d_dtail,
-                               d_winv, xm, i, ps);
+      mtail_sweep(c, xm, ps, np, sl, 1);
       for (int l = (int)levels_top.size() - 1; l >= 0; --l) head(levels_top[l], 1);
       for (int l = (int)levels.size() - 1; l >= 0; --l) head(levels[l], 1);
       hipLaunchKernelGGL(k_mpermute, pg, dim3(256), 0, stream, d_blks, d_perm, d_perm_off, X, x_stride, nr, xm, 1, ps);

@@ -54,7 +54,7 @@ SYMBOLS = [
     "pips_hip_ldl_solve_dev", "pips_hip_ldl_solve_sparse", "pips_hip_ldl_factor_schur_batch", "pips_hip_ldl_solve_batch", "pips_hip_ldl_solve_batch_dev",
     "pips_hip_ldl_inertia_batch", "pips_hip_ldl_factor_schur_sparse", "pips_hip_ldl_factor_schur_sparse_batch",
     "pips_hip_dense_ldl_create", "pips_hip_dense_ldl_factor", "pips_hip_dense_ldl_factor_dev", "pips_hip_dense_ldl_solve",
-    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_first_touch_probe", "pips_ipm_layout_probe", "pips_ipm_layout_probe_cross", "pips_ipm_create_qp_cross", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_knobs", "pips_hip_knob_value", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
+    "pips_hip_dense_ldl_solve_dev", "pips_hip_dense_ldl_solve_multi_dev", "pips_hip_dense_ldl_inertia", "pips_hip_dense_ldl_info", "pips_hip_dense_ldl_set_pivoting", "pips_hip_dense_ldl_set_distributed", "pips_hip_dense_ldl_destroy", "pips_root_plan_build", "pips_layout_probe", "pips_tail_plan_probe", "pips_first_touch_probe", "pips_ipm_layout_probe", "pips_ipm_layout_probe_cross", "pips_ipm_create_qp_cross", "pips_hip_host_wait_count", "pips_hip_host_wait_sites", "pips_hip_knobs", "pips_hip_knob_value", "pips_hip_device_allocs_live", "pips_hip_device_bytes_live",
     "pips_hip_batch_create", "pips_hip_batch_set_block", "pips_hip_batch_set_options", "pips_hip_batch_set_schur_mode", "pips_hip_batch_set_deterministic", "pips_hip_batch_get_schur_mode", "pips_hip_batch_add_regularization", "pips_hip_batch_set_refinement",
     "pips_hip_batch_last_refinement_steps", "pips_hip_batch_set_refinement_backward_error",
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
@@ -587,16 +587,20 @@ class HipDenseLdlSolver:
     def solve_dev(self, x_dev):
         _check(lib.pips_hip_dense_ldl_solve_dev(self._h, _ptr(x_dev)), "pips_hip_dense_ldl_solve_dev")
 
+    def solve_multi_dev(self, x_dev, nrhs, ld):
+        """nrhs right-hand sides of length n at distance ld >= n in device memory, overwritten; asynchronous"""
+        _check(lib.pips_hip_dense_ldl_solve_multi_dev(self._h, C.c_int(nrhs), _ptr(x_dev), C.c_longlong(ld)), "pips_hip_dense_ldl_solve_multi_dev")
+
     def get_inertia(self):
         p, n, z = C.c_int(), C.c_int(), C.c_int()
         _check(lib.pips_hip_dense_ldl_inertia(self._h, C.byref(p), C.byref(n), C.byref(z)), "dense inertia")
         return p.value, n.value, z.value
 
     def info(self):
-        what = np.zeros(5, np.int64)
-        _check(lib.pips_hip_dense_ldl_info(self._h, _ptr(what), C.c_int(5)), "pips_hip_dense_ldl_info")
+        what = np.zeros(8, np.int64)
+        _check(lib.pips_hip_dense_ldl_info(self._h, _ptr(what), C.c_int(8)), "pips_hip_dense_ldl_info")
         return dict(single_launch=int(what[0]), tile_columns=int(what[1]), ranks=int(what[2]), pivoting=int(what[3]),
-                    bk_refactorizations=int(what[4]))
+                    bk_refactorizations=int(what[4]), last_solve_path=int(what[5]), last_solve_slices=int(what[6]), last_solve_rows=int(what[7]))
 
     def close(self):
         if self._h:
