@@ -33,6 +33,9 @@ The cases with the generator's diagonals have them narrowed to 1e-2 .. 1e2 (util
   5. PIPS_HIP_SWEEP_LAUNCHES=1 on dense_tail: layout.cpp's aug_paths needs the single-launch tail sweeps or no tail, so augmented_sweeps == 0
      and the solves go the refined way 0 (border_backward_ok needs those sweeps too), which is judged.
   6. the refined ways as the baseline: PIPS_HIP_AUG_SWEEPS=0 with PIPS_HIP_BORDER_BACKWARD 0 (way 0) and 1 on dense_tail and time-coupled.
+     6d. the same with set_deterministic(True): lsolve_det without the sweeps (k_border_rowdot into g_btm_grp, k_reduce_groups) and the Ltsolve through
+     k_border_entry_products + k_gather_slots; way 0 with either value of PIPS_HIP_BORDER_BACKWARD (border_backward_ok needs !deterministic); a
+     repeated solve, on the same handle and on a second one, gives the same bits.
   7. the general structure with sweeps: GeneralProblem(21, 3,400,160,80,20,6,mz0,9,5) with mz0 = 0 and mz0 = 4 (k_z0_elim, the reduced vector).
   8. sparse root: TwoLinkProblem(77, 6,120,60,4,3) and (77, 30,60,30,5,20), PIPS_HIP_SPARSE_ROOT_BAND in {1, 0}.
   9. one handle, new factors: factorize, three solves, factorize with 1.3 x the leaf diagonals (the reference rebuilt for it), three solves.
@@ -47,6 +50,7 @@ the group: the smallest power of two that is at least 4 x the largest of the fou
     4. deterministic   3.96 (small)                   0.83 (small)                   3.17 (time_coupled, e_last)            2.98 (small)                       16
     5. sweep_launches  0.74 (way 0)                   0.81                           1.20                                   1.17                                8
     6. refined         1.03 (dense_tail, way 1)       1.03 (dense_tail, way 1)       2.25 (time_coupled, way 0, e_last)     1.53 (time_coupled, way 0)         16
+    6d. refined, det.  0.88 (dense_tail, b_leaf = 0)  0.88 (dense_tail, b_leaf = 0)  3.17 (time_coupled, e_last)            1.62 (time_coupled, e_last)        16
     7. general         0.55 (general)                 1.95 (general_mz0)             3.39 (general_mz0, b_leaf = 0)         2.83 (general_mz0)                 16
     8. sparse_root     0.62 (two_link_30/amd)         0.62 (two_link_30/amd)         1.79 (two_link_30/band)                0.99 (two_link_30/amd)              8
     9. new_factors     1.10 (small/first)             0.88 (small/second)            3.50 (time_coupled/first, e_last)      2.48 (small/second)                16
@@ -74,8 +78,8 @@ from tests import util as u
 pytestmark = pytest.mark.gpu
 
 # per group: the smallest power of two >= 4 x the largest measured ratio (see above); never above 64
-M = {"measured": 16, "on_trust": 16, "widths": 32, "deterministic": 16, "sweep_launches": 8, "refined": 16, "general": 16, "sparse_root": 8,
-     "new_factors": 16}
+M = {"measured": 16, "on_trust": 16, "widths": 32, "deterministic": 16, "sweep_launches": 8, "refined": 16, "refined_deterministic": 16, "general": 16,
+     "sparse_root": 8, "new_factors": 16}
 _KNOBS = ("PIPS_HIP_AUG_SWEEPS", "PIPS_HIP_MF_KONLY", "PIPS_HIP_SWEEP_LAUNCHES", "PIPS_HIP_BORDER_BACKWARD", "PIPS_HIP_SPARSE_ROOT_BAND", "PIPS_HIP_AUG_WITNESS")
 _ALL = tuple(range(len(u.ARROWHEAD_RHS)))
 # beyond every admissible margin for a reason that lies in the measure, not in a kernel (see above): (path, right-hand side) -> the measured forward_root
@@ -298,6 +302,34 @@ def test_refined_ways(case, border_backward, monkeypatch):
     print(f"solve-compressed-ways {case}/border_backward{border_backward} {ways}")
     # (way 1 needs a refined Lsolve that took no refinement step in the same call: on these cases every one is)
     assert ways == [int(border_backward)] * len(_ALL) and counts == (0, 0), (ways, counts)
+
+
+@pytest.mark.parametrize("border_backward", ["0", "1"])
+@pytest.mark.parametrize("case", ["dense_tail", "time_coupled"])
+def test_refined_ways_deterministic(case, border_backward, monkeypatch):
+    """the deterministic Lsolve without the sweeps (lsolve_det in csrc/kkt.hip.h): refined leaf solve, k_border_rowdot into the group buffers
+    (g_btm_grp), k_reduce_groups; the Ltsolve goes through k_border_entry_products + k_gather_slots.  layout.cpp's border_backward_ok needs
+    !deterministic, so PIPS_HIP_BORDER_BACKWARD=1 changes nothing here: way 0 on every solve."""
+    _env(monkeypatch, aug_sweeps="0", border_backward=border_backward)
+    ref = u.arrowhead_reference(case)
+    path = f"{case}/border_backward{border_backward}/deterministic"
+    h = _Handles(ref, deterministic=True)
+    info = h.bt.info()
+    assert info["augmented_sweeps"] == 0 and info["ltsolve_from_augmented_factor"] == 0, info
+    h.factorize(ref)
+    first = h.solve(ref, 0)
+    ways = _solve_and_judge(h, ref, "refined_deterministic", path)
+    repeated = h.solve(ref, 0)
+    counts = h.kkt.solve_check_counts()
+    h.close()
+    assert first[2] == repeated[2] == 0 and ways == [0] * len(_ALL) and counts == (0, 0), (first[2], repeated[2], ways, counts)
+    # (the one comparison with the device's own earlier output: the same right-hand side, solved again on this handle and on a second one)
+    assert np.array_equal(first[0], repeated[0]) and np.array_equal(first[1], repeated[1])
+    h2 = _Handles(ref, deterministic=True)
+    h2.factorize(ref)
+    again = h2.solve(ref, 0)
+    h2.close()
+    assert again[2] == 0 and np.array_equal(first[0], again[0]) and np.array_equal(first[1], again[1])
 
 
 # ---- 7. the general structure with sweeps ------------------------------------------------------------------------------------------------------
