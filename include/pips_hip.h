@@ -249,6 +249,15 @@ int pips_hip_batch_solve(void* handle, double* x_host);
 int pips_hip_batch_border_tmult_dev(void* handle, const double* z_dev, double* b0_dev, double alpha);
 /* t_b += alpha * Br_b x0 for every block   (LniTransMult) */
 int pips_hip_batch_border_mult_dev(void* handle, const double* x0_dev, double* t_dev, double alpha);
+/* The same two products on nrhs vectors, the border read once for all of them (the kernels pips_hip_kkt_solve_compressed_multi runs
+ * between its panel solves; not in deterministic mode, whose form of the first product is reached through that call alone - PIPS_ERR_STATE):
+ *   tmult_panel:  T(s, q) += alpha * sum_b (Br_b^T z_b(q))_s;  vector q of Z at Z_dev + q * ldz (ldz >= sum of n), T(s, q) at
+ *                 T_dev[s * ldt + q] (S rows of ldt >= nrhs doubles: the layout the kernel's atomic adds are contiguous in);
+ *   mult_panel:   W(:, q) = alpha * Br X0(:, q) for every block - a store, rows without border entries get zeros;  vector q of X0 at
+ *                 X0_dev + q * ldx (ldx >= S), of W at W_dev + q * ldw (ldw >= sum of n).
+ * Asynchronous on the batch's stream; nrhs == 0 does nothing. */
+int pips_hip_batch_border_tmult_panel_dev(void* handle, int nrhs, const double* Z_dev, long long ldz, double* T_dev, long long ldt, double alpha);
+int pips_hip_batch_border_mult_panel_dev(void* handle, int nrhs, const double* X0_dev, long long ldx, double* W_dev, long long ldw, double alpha);
 int pips_hip_batch_inertia(void* handle, int b, int* pos, int* neg, int* zero);
 /* the factorised dense tail of block b as it lies in device memory (tests compare two kernels' factors entry for entry): which = 0 the tail
  * panel, column-major ldT x m_pad (m_pad tail rows - D on the diagonal, L below it - then the border rows), 1 its scaled copy U = L D,
@@ -329,6 +338,30 @@ int pips_hip_kkt_set_root_hessian(void* handle, const int* Q0_rowptr, const int*
 /* in place: b0 (replicated on every rank; [x0 | y0 | ylink | zlink], or [x0 | y0 | z0 | ylink | zlink] when mz0 > 0) and
  * the flat leaf vector of this rank's blocks */
 int pips_hip_kkt_solve_compressed(void* handle, double* b0_dev, double* b_leaf_dev);
+/* solveCompressed for nrhs right-hand sides on one factorisation (the reference: addBlTKiInvBrToResBlockwise's LsolveHierarchyBorder /
+ * DsolveHierarchyBorder / LtsolveHierarchyBorder on a buffer of SC_BLOCKSIZE_HIERARCHICAL columns, sLinsysRootAug.C:1815-1940).
+ * Column q of B0_dev starts at B0_dev + q * ld0 and has the layout pips_hip_kkt_solve_compressed takes (S + mz0 entries); column q of
+ * Bleaf_dev is the flat leaf vector of this rank's blocks at Bleaf_dev + q * ldl.  Both are overwritten in place, asynchronously on the
+ * batch's stream except where adaptive refinement makes the host wait; entries between the columns (ld0 > S + mz0, ldl > n_total) are
+ * neither read nor written.  nrhs == 0 does nothing.
+ *   nrhs below the threshold of the multi-vector sweeps (8; PIPS_HIP_MULTI as for pips_hip_ldl_solve and the dense root): exactly the
+ *     sequence of pips_hip_kkt_solve_compressed calls, column by column - way, checks, counters, graph replay.
+ *   From the threshold on: the refined way 0 on panels - the leaves' interleaved sweeps (panels of 32 on the matrix pipe, adaptive
+ *     refinement per column), the two border products with the border read once per chunk, the root's panel solve - in chunks of at
+ *     most 256 columns, fewer where the leaf panel n_total x chunk would exceed 2 GiB, never fewer than 32.  Several ranks: one
+ *     all-reduce of S x chunk doubles per chunk; every rank must pass the same nrhs.  This path takes no augmented sweep, captures no
+ *     graph, and leaves what pips_hip_kkt_last_solve_path, _last_ltsolve_from_factor and _solve_check_counts report - and which way the
+ *     next pips_hip_kkt_solve_compressed goes - as they were.  Only those: the leaf batch's own reports of its last solve
+ *     (pips_hip_batch_last_refinement_steps / _measure, the multi-vector path in pips_hip_batch_info) are the panel call's afterwards.
+ *     In deterministic mode the leaves solve in panels only where the slots of a panel fit (a leaf handle, a small batch), else one
+ *     right-hand side at a time as pips_hip_ldl_solve does there; the border products and the root run on panels either way.
+ * PIPS_ERR_ARG: nrhs < 0 and, with nrhs > 0, a NULL pointer, ld0 < S + mz0, ldl < n_total.  PIPS_ERR_STATE: before the first pips_hip_kkt_factorize. */
+int pips_hip_kkt_solve_compressed_multi(void* handle, int nrhs, double* B0_dev, long long ld0, double* Bleaf_dev, long long ldl);
+/* How the last pips_hip_kkt_solve_compressed_multi went: what[0] 0 = column by column through the single path, 1 = panels; what[1] its
+ * chunks (column by column: one per column); what[2] the right-hand sides of a full chunk (of the first one); what[3] / what[4] the
+ * refinement steps of the last chunk's Lsolve / Ltsolve leaf solves (panels); what[5] panel chunks solved since the handle was created.
+ * Entries beyond these are 0. */
+int pips_hip_kkt_solve_multi_info(void* handle, int64_t* what, int n_what);
 int pips_hip_kkt_get_schur(void* handle, double** SC_dev, int* ld);
 int pips_hip_kkt_root_inertia(void* handle, int* pos, int* neg, int* zero);
 /* dense root: 0 static pivot order (default: the Schur complement the leaves build is quasi-definite in the order x0, duals),
@@ -826,6 +859,14 @@ int pips_schur_pack_probe(int nblk, int S, const int* const* bt_rowptr, int* nb,
  * bm[la]) of an upper pattern, (bm[la], bm[lb]) of a lower one, bm the block's non-empty columns ascending; the other half is 0. */
 int pips_schur_target_probe(int nblk, int S, const int* const* bt_rowptr, const int* sc_rowptr, const int* sc_colidx, int lower, int* nb,
                             long long* n_touched, long long* pos, long long cap, int* const* tab);
+
+/* The chunks pips_hip_kkt_solve_compressed_multi cuts nrhs right-hand sides into, without a device; the function the call itself uses.
+ * from: the fewest right-hand sides that go by panels (0 = never); chunk_max: the most a chunk may hold (256); n_total: the length of
+ * the leaf vector (several ranks: the longest of any rank); budget_bytes: the bound on n_total x chunk doubles (2 GiB).  *n_chunks: how
+ * many; out (when cap >= *n_chunks; 3 ints each): first column, count, path (0 = the single solveCompressed, one column per chunk;
+ * 1 = panels).  A panel chunk holds whole panels of 32 within the budget, at most max(chunk_max, 32), never fewer than 32 - the last
+ * chunk takes what is left. */
+int pips_kkt_multi_plan_probe(int nrhs, int from, int chunk_max, long long n_total, long long budget_bytes, int* out, int cap, int* n_chunks);
 
 /* ---- 6. input files ---------------------------------------------------------------------------------------------------
  * One block of a block-structured LP from a "jacobian" GDX file, the format gmspips_reader opens per block

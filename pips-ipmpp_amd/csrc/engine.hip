@@ -21,6 +21,7 @@
 #include "layout.h"
 #include "detplan.h"
 #include "tileplan.h"
+#include "multiplan.h"
 #include "knobs.h"
 #include "schurtarget.h"
 #include "kernels.hip.h"
@@ -1989,6 +1990,27 @@ __global__ void k_add_regularization(const BlkDesc* __restrict__ blks, const int
       kval[kdiag[bd.x_off + i]] += (np < 0 || i < np) ? primal : -dual;
 }
 
+#include "borderpanel.hip.h"
+
+// the one launch site of the two border-panel products outside deterministic mode (KktSystem::solve_panel, pips_hip_batch_border_*_panel_dev)
+static void launch_border_tmult_panel(Engine* e, const double* Z, long long ldz, int nr, double* T, long long ldt, double alpha) {
+   if (e->bt_rows_total > 0)
+      hipLaunchKernelGGL(k_border_tmult_panel<false>, dim3(grid_for(e->bt_rows_total * BT_LANES, 256, 65536)), dim3(256), 0, e->stream, e->d_bt_rowptr, e->d_bt_colidx,
+                         e->d_bval, e->d_bt_rowsc, e->d_bt_xoff, Z, ldz, nr, T, ldt, e->bt_rows_total, alpha);
+}
+// W = alpha Br X0: every row of W is written.  layout_border_csr builds the border by leaf row whenever the border has entries (fewer than
+// 2^31: the int row pointers of the concatenated Bt CSR hold no more), so the lists are never missing where there is something to multiply -
+// building them on first use, which the single path's k_border_mult stands in for, has no case; a batch that had none would be told so
+static int launch_border_mult_panel(Engine* e, const double* X0, long long ldx, int nr, double* W, long long ldw, double alpha) {
+   if (e->bt_rows_total > 0 && e->d_br_rowptr)
+      hipLaunchKernelGGL(k_border_mult_panel, dim3(grid_for(e->n_total, 256, 1 << 20)), dim3(256), 0, e->stream, e->d_br_rowptr, e->d_br_sc, e->d_br_src, e->d_bval,
+                         X0, ldx, nr, W, ldw, e->n_total, alpha);
+   else if (e->bt_rows_total == 0 || e->nnzB_total == 0)
+      HIP_TRY(hipMemset2DAsync(W, (size_t)ldw * sizeof(double), 0, (size_t)e->n_total * sizeof(double), (size_t)nr, e->stream));
+   else
+      PIPS_FAIL(PIPS_ERR_STATE, "the border by leaf row was not built (2^31 or more border entries): no panel product of Br");
+   return PIPS_OK;
+}
 #include "kkt.hip.h"
 
 }  // namespace pips
@@ -2229,6 +2251,30 @@ int pips_hip_batch_border_mult_dev(void* handle, const double* x0_dev, double* t
    return PIPS_OK;
 }
 
+// the two border products on nrhs vectors (borderpanel.hip.h): the launches KktSystem::solve_panel makes outside deterministic mode
+int pips_hip_batch_border_tmult_panel_dev(void* handle, int nrhs, const double* Z_dev, long long ldz, double* T_dev, long long ldt, double alpha) {
+   Engine* e = (Engine*)handle;
+   if (!e || !e->analyzed) PIPS_FAIL(PIPS_ERR_STATE, "border_tmult_panel: analyze first");
+   if (nrhs < 0 || !Z_dev || !T_dev || ldz < e->n_total || ldt < nrhs) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_batch_border_tmult_panel_dev: bad arguments");
+   if (e->deterministic) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_batch_border_tmult_panel_dev: deterministic mode sums the panel through pips_hip_kkt_solve_compressed_multi");
+   if (nrhs == 0 || e->bt_rows_total == 0) return PIPS_OK;
+   HIP_TRY(hipSetDevice(e->device));
+   launch_border_tmult_panel(e, Z_dev, ldz, nrhs, T_dev, ldt, alpha);
+   HIP_TRY(hipGetLastError());
+   return PIPS_OK;
+}
+
+int pips_hip_batch_border_mult_panel_dev(void* handle, int nrhs, const double* X0_dev, long long ldx, double* W_dev, long long ldw, double alpha) {
+   Engine* e = (Engine*)handle;
+   if (!e || !e->analyzed) PIPS_FAIL(PIPS_ERR_STATE, "border_mult_panel: analyze first");
+   if (nrhs < 0 || !X0_dev || !W_dev || ldx < e->S || ldw < e->n_total) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_batch_border_mult_panel_dev: bad arguments");
+   if (nrhs == 0) return PIPS_OK;
+   HIP_TRY(hipSetDevice(e->device));
+   if (int rc = launch_border_mult_panel(e, X0_dev, ldx, nrhs, W_dev, ldw, alpha)) return rc;
+   HIP_TRY(hipGetLastError());
+   return PIPS_OK;
+}
+
 int pips_hip_batch_inertia(void* handle, int b, int* pos, int* neg, int* zero) {
    Engine* e = (Engine*)handle;
    if (!e || !e->factored || b < 0 || b >= e->nblk) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_batch_inertia: factor first");
@@ -2400,6 +2446,26 @@ int pips_hip_kkt_solve_compressed(void* handle, double* b0_dev, double* b_leaf_d
    if (!k || !b0_dev || !b_leaf_dev) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_compressed: bad arguments");
    HIP_TRY(hipSetDevice(k->leaves->device));
    return k->solve_compressed(b0_dev, b_leaf_dev);
+}
+
+int pips_hip_kkt_solve_compressed_multi(void* handle, int nrhs, double* B0_dev, long long ld0, double* Bleaf_dev, long long ldl) {
+   KktSystem* k = (KktSystem*)handle;
+   if (!k) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_compressed_multi: null handle");
+   if (nrhs < 0) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_compressed_multi: nrhs = %d is negative", nrhs);
+   if (k->factor_gen == 0) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_solve_compressed_multi: pips_hip_kkt_factorize first");
+   if (nrhs == 0) return PIPS_OK;   // (no column is touched: the pointers of an empty set may be anything)
+   if (!B0_dev || !Bleaf_dev) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_compressed_multi: %s is NULL", !B0_dev ? "B0_dev" : "Bleaf_dev");
+   if (ld0 < k->S + k->mz0) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_compressed_multi: ld0 = %lld is below S + mz0 = %d", ld0, k->S + k->mz0);
+   if (ldl < k->leaves->n_total) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_compressed_multi: ldl = %lld is below n_total = %lld", ldl, (long long)k->leaves->n_total);
+   HIP_TRY(hipSetDevice(k->leaves->device));
+   return k->solve_compressed_multi(nrhs, B0_dev, ld0, Bleaf_dev, ldl);
+}
+
+int pips_hip_kkt_solve_multi_info(void* handle, int64_t* what, int n_what) {
+   KktSystem* k = (KktSystem*)handle;
+   if (!k || !what || n_what < 1) PIPS_FAIL(PIPS_ERR_ARG, "pips_hip_kkt_solve_multi_info: bad arguments");
+   for (int i = 0; i < n_what; ++i) what[i] = i < 6 ? k->multi_info[i] : 0;
+   return PIPS_OK;
 }
 
 int pips_hip_kkt_set_root_stream(void* handle, int own_stream) {

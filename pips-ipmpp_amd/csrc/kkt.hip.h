@@ -834,4 +834,141 @@ struct KktSystem {
       ++graph_replays;
       return PIPS_OK;
    }
+
+   // ---- solveCompressed for several right-hand sides (pips_hip_kkt_solve_compressed_multi) ---------------------------------------------
+   // = sLinsysRootAug::addBlTKiInvBrToResBlockwise's LsolveHierarchyBorder / DsolveHierarchyBorder / LtsolveHierarchyBorder on a buffer of
+   // columns (sLinsysRootAug.C:1815-1940).  Below Engine::multi_knob().from columns the call IS the sequence of solve_compressed calls,
+   // state and all.  From there on: the refined way 0 on panels, chunk by chunk (multiplan.h) - leaves->solve_multi, the border products
+   // of borderpanel.hip.h, the root's solve_multi_dev / solve_multi.  The panel path takes no augmented sweep, captures no graph and leaves
+   // what the single path decides by alone: solves_since_factor, aug_validated_gen, aug_failed_gen, last_solve_path,
+   // last_ltsolve_from_factor, the check counters, the phase timer.
+   DevBuf<double> d_pw;       // W = Br X0, n_total x nr (the budget of the chunks)
+   DevBuf<double> d_pt;       // T = -sum_i Br_i^T Z_i, S x nr: [s][q] under the atomics, [q][s] in deterministic mode
+   DevBuf<double> d_pred;     // mz0 > 0: the reduced panel [x0 | y0 | ylink | zlink], S x nr
+   DevBuf<double> d_pdot;     // deterministic mode: the row dots, bt_rows_total x nr
+   DevBuf<double> d_pg, d_pg_all;   // ... and the group panels (this rank's / all eight), 8 x nr x S
+   DevBuf<double> d_pn;
+   long long multi_info[6] = {0, 0, 0, 0, 0, 0};   // pips_hip_kkt_solve_multi_info
+   long long panel_nt_max = 0, panel_nt_gen = -1;
+   // the longest leaf vector of any rank: every rank cuts the same chunks (each ends in collectives of S x chunk doubles).  Once per analysis
+   int panel_n_total(long long* out) {
+      Engine* e = leaves;
+      *out = e->n_total;
+      if (n_ranks <= 1) return PIPS_OK;
+      if (!comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_solve_compressed_multi: n_ranks > 1 needs a communicator");
+      if (panel_nt_gen != e->analysis_gen) {
+         std::vector<double> h((size_t)n_ranks, 0.0);
+         h[(size_t)rank] = (double)e->n_total;
+         PIPS_TRY(d_pn.reserve((size_t)n_ranks));
+         HIP_TRY(hipMemcpyAsync(d_pn, h.data(), (size_t)n_ranks * sizeof(double), hipMemcpyHostToDevice, e->stream));
+         HIP_TRY(hipStreamSynchronize(e->stream));
+         if (int rc = pips_hip_allreduce_sum(comm, d_pn, (size_t)n_ranks, e->stream)) return rc;
+         HIP_TRY(hipMemcpyAsync(h.data(), d_pn, (size_t)n_ranks * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+         HIP_TRY(hipStreamSynchronize(e->stream));
+         panel_nt_max = (long long)*std::max_element(h.begin(), h.end());
+         panel_nt_gen = e->analysis_gen;
+      }
+      *out = panel_nt_max;
+      return PIPS_OK;
+   }
+   // one chunk of nr columns: B0 + q ld0 and BL + q ldl, q < nr
+   int solve_panel(int nr, double* B0, long long ld0, double* BL, long long ldl) {
+      Engine* e = leaves;
+      int rc;
+      const int head = n0 + my0, tailn = myl + mzl;
+      const bool reduce = n_ranks > 1 || force_reduce;
+      const bool det = e->deterministic && e->d_gvec;
+      const size_t col = sizeof(double);
+      const long long sn = (long long)S * nr;
+      if (reduce && !comm) PIPS_FAIL(PIPS_ERR_STATE, "pips_hip_kkt_solve_compressed_multi: n_ranks > 1 needs a communicator");
+      // 1. root inequalities: the reduced panel, as solve_enqueue copies one vector
+      double* red = B0;
+      long long ldr = ld0;
+      if (mz0 > 0) {
+         PIPS_TRY(d_pred.reserve((size_t)sn));
+         red = d_pred; ldr = S;
+         if (head > 0) HIP_TRY(hipMemcpy2DAsync(red, (size_t)ldr * col, B0, (size_t)ld0 * col, (size_t)head * col, nr, hipMemcpyDeviceToDevice, e->stream));
+         if (tailn > 0)
+            HIP_TRY(hipMemcpy2DAsync(red + head, (size_t)ldr * col, B0 + head + mz0, (size_t)ld0 * col, (size_t)tailn * col, nr, hipMemcpyDeviceToDevice, e->stream));
+      }
+      // 2. Lsolve: Z = K^-1 B_leaf; T = -sum_i Br_i^T Z_i formed on its own, summed over the ranks, added to the reduced panel on every rank
+      if ((rc = e->solve_multi(BL, nr, ldl))) return rc;
+      multi_info[3] = e->last_refine_steps;
+      PIPS_TRY(d_pt.reserve((size_t)sn));
+      HIP_TRY(hipMemsetAsync(d_pt, 0, (size_t)sn * col, e->stream));
+      const dim3 bt_grid(grid_for(e->bt_rows_total * BT_LANES, 256, 65536));
+      const dim3 vec_grid((unsigned)std::max(1LL, std::min(1024LL, (sn + 255) / 256)), 1);
+      if (det) {
+         const long long gstride = sn;
+         PIPS_TRY(d_pg.reserve((size_t)8 * sn));
+         HIP_TRY(hipMemsetAsync(d_pg, 0, (size_t)8 * sn * col, e->stream));
+         if (e->bt_rows_total > 0) {
+            PIPS_TRY(d_pdot.reserve((size_t)e->bt_rows_total * nr));
+            HIP_TRY(hipMemsetAsync(d_pdot, 0, (size_t)e->bt_rows_total * nr * col, e->stream));
+            hipLaunchKernelGGL(k_border_tmult_panel<true>, bt_grid, dim3(256), 0, e->stream, e->d_bt_rowptr, e->d_bt_colidx, e->d_bval, e->d_bt_rowsc,
+                               e->d_bt_xoff, BL, ldl, nr, d_pdot, (long long)nr, e->bt_rows_total, -1.0);
+            const Engine::GatherList& g = e->g_btm_grp;
+            if (g.n_targets > 0)
+               hipLaunchKernelGGL(k_gather_rows_panel, dim3(grid_for(g.n_targets * nr, 256, 65536)), dim3(256), 0, e->stream, g.n_targets, g.d_tgt, g.d_off,
+                                  g.d_slots, d_pdot, (long long)nr, nr, S, d_pg, gstride);
+         }
+         // the group panels in the fixed tree of k_reduce_groups (a panel as one vector of S nr entries), as lsolve_det adds the group vectors
+         if (e->det.global && n_ranks > 1) {
+            PIPS_TRY(d_pg_all.reserve((size_t)8 * sn));
+            HIP_TRY(hipMemsetAsync(d_pg_all, 0, (size_t)8 * sn * col, e->stream));
+            HIP_TRY(hipMemcpyAsync(d_pg_all + (size_t)e->det.first_slot * sn, d_pg, (size_t)e->det.n_groups * sn * col, hipMemcpyDeviceToDevice, e->stream));
+            if ((rc = pips_hip_all_gather(comm, d_pg_all, (size_t)e->det.slots * sn, 8 / e->det.slots, e->stream))) return rc;
+            hipLaunchKernelGGL(k_reduce_groups, vec_grid, dim3(256), 0, e->stream, d_pt, 0, (int)sn, d_pg_all, gstride, 8, 0);
+         } else {
+            hipLaunchKernelGGL(k_reduce_groups, vec_grid, dim3(256), 0, e->stream, d_pt, 0, (int)sn, d_pg, gstride, e->det.n_groups, e->det.first_slot);
+            if (reduce && (rc = pips_hip_allreduce_sum(comm, d_pt, (size_t)sn, e->stream))) return rc;
+         }
+         hipLaunchKernelGGL(k_panel_add, vec_grid, dim3(256), 0, e->stream, red, ldr, d_pt, 1LL, (long long)S, S, nr);
+      } else {
+         launch_border_tmult_panel(e, BL, ldl, nr, d_pt, (long long)nr, -1.0);
+         if (reduce && (rc = pips_hip_allreduce_sum(comm, d_pt, (size_t)sn, e->stream))) return rc;
+         hipLaunchKernelGGL(k_panel_add, vec_grid, dim3(256), 0, e->stream, red, ldr, d_pt, (long long)nr, 1LL, S, nr);
+      }
+      // 3. Dsolve: z0 elimination on the panel, the root's panel solve, z0 recovered, the caller's columns put together again
+      if ((rc = root_wait())) return rc;
+      if (mz0 > 0)
+         hipLaunchKernelGGL(k_z0_elim_panel, e->deterministic ? dim3(1, nr) : dim3(grid_for(mz0, 128), nr), e->deterministic ? dim3(1) : dim3(128), 0, e->stream, 0,
+                            mz0, d_c0_rp, d_c0_ci, d_c0_val, d_zdiag0, B0 + head, ld0, red, ldr);
+      if ((rc = sparse ? root_sp->solve_multi(red, nr, ldr) : root->solve_multi_dev(red, nr, ldr))) return rc;
+      if (mz0 > 0) {
+         hipLaunchKernelGGL(k_z0_elim_panel, dim3(grid_for(mz0, 128), nr), dim3(128), 0, e->stream, 1, mz0, d_c0_rp, d_c0_ci, d_c0_val, d_zdiag0, B0 + head, ld0, red,
+                            ldr);
+         if (head > 0) HIP_TRY(hipMemcpy2DAsync(B0, (size_t)ld0 * col, red, (size_t)ldr * col, (size_t)head * col, nr, hipMemcpyDeviceToDevice, e->stream));
+         if (tailn > 0)
+            HIP_TRY(hipMemcpy2DAsync(B0 + head + mz0, (size_t)ld0 * col, red + head, (size_t)ldr * col, (size_t)tailn * col, nr, hipMemcpyDeviceToDevice, e->stream));
+      }
+      // 4. Ltsolve: W = Br X0 (every row of W is written), W = K^-1 W, B_leaf -= W
+      PIPS_TRY(d_pw.reserve((size_t)std::max<long long>(e->n_total, 1) * nr));
+      if ((rc = launch_border_mult_panel(e, red, ldr, nr, d_pw, e->n_total, 1.0))) return rc;
+      if ((rc = e->solve_multi(d_pw, nr, e->n_total))) return rc;
+      multi_info[4] = e->last_refine_steps;
+      hipLaunchKernelGGL(k_maxpy, dim3(grid_for(e->n_total, 256, 1024), nr), dim3(256), 0, e->stream, BL, ldl, d_pw, e->n_total, -1.0, e->n_total);
+      ++multi_info[5];
+      HIP_TRY(hipGetLastError());
+      return PIPS_OK;
+   }
+   int solve_compressed_multi(int nrhs, double* B0, long long ld0, double* BL, long long ldl) {
+      Engine* e = leaves;
+      int rc;
+      const int from = Engine::multi_knob().from;
+      const bool panels = from > 0 && nrhs >= from;
+      long long nt = e->n_total;
+      if (panels && (rc = panel_n_total(&nt))) return rc;
+      const std::vector<KktMultiChunk> plan = kkt_multi_plan(nrhs, from, Engine::MULTI_CHUNK_MAX, nt, KKT_MULTI_BUDGET_BYTES);
+      multi_info[0] = panels ? 1 : 0;
+      multi_info[1] = (long long)plan.size();
+      multi_info[2] = plan.empty() ? 0 : plan[0].count;
+      multi_info[3] = multi_info[4] = 0;
+      for (const KktMultiChunk& c : plan) {
+         double* b0 = B0 + (long long)c.first * ld0;
+         double* bl = BL + (long long)c.first * ldl;
+         if ((rc = c.path == 0 ? solve_compressed(b0, bl) : solve_panel(c.count, b0, ld0, bl, ldl))) return rc;
+      }
+      return PIPS_OK;
+   }
 };

@@ -8,6 +8,7 @@
 #include "layout.h"
 #include "detplan.h"
 #include "tileplan.h"
+#include "multiplan.h"
 #include "knobs.h"
 #include "pips_hip.h"
 
@@ -392,4 +393,15 @@ int pips_det_plan_probe(int nblk, const int* n, const int* n_primal, const int* 
    std::copy(head, head + 16, counts);
    return PIPS_OK;
 }
+// ---- the chunks of pips_hip_kkt_solve_compressed_multi (multiplan.h), as the call cuts them -------------------------------------------
+int pips_kkt_multi_plan_probe(int nrhs, int from, int chunk_max, long long n_total, long long budget_bytes, int* out, int cap, int* n_chunks) {
+   if (nrhs < 0 || from < 0 || chunk_max < 1 || n_total < 0 || budget_bytes < 0 || !n_chunks || cap < 0 || (cap > 0 && !out))
+      PIPS_FAIL(PIPS_ERR_ARG, "pips_kkt_multi_plan_probe: bad arguments");
+   const std::vector<KktMultiChunk> plan = kkt_multi_plan(nrhs, from, chunk_max, n_total, budget_bytes);
+   *n_chunks = (int)plan.size();
+   if ((size_t)cap >= plan.size())
+      for (size_t i = 0; i < plan.size(); ++i) { out[3 * i] = plan[i].first; out[3 * i + 1] = plan[i].count; out[3 * i + 2] = plan[i].path; }
+   return PIPS_OK;
+}
+
 }  // extern "C"

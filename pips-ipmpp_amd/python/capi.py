@@ -59,10 +59,10 @@ SYMBOLS = [
     "pips_hip_batch_last_refinement_steps", "pips_hip_batch_set_refinement_backward_error",
     "pips_hip_batch_last_refinement_measure", "pips_hip_batch_analyze",
     "pips_hip_batch_set_values", "pips_hip_batch_set_diagonals_dev", "pips_hip_batch_set_diagonals", "pips_hip_batch_factor",
-    "pips_hip_batch_solve_dev", "pips_hip_batch_solve", "pips_hip_batch_border_tmult_dev", "pips_hip_batch_border_mult_dev",
+    "pips_hip_batch_solve_dev", "pips_hip_batch_solve", "pips_hip_batch_border_tmult_dev", "pips_hip_batch_border_mult_dev", "pips_hip_batch_border_tmult_panel_dev", "pips_hip_batch_border_mult_panel_dev",
     "pips_hip_batch_inertia", "pips_hip_batch_tail_to_host", "pips_hip_batch_info", "pips_hip_batch_sync", "pips_hip_batch_set_timing",
     "pips_hip_batch_get_timing", "pips_hip_batch_destroy",
-    "pips_hip_kkt_create", "pips_hip_kkt_create_sparse", "pips_hip_kkt_get_schur_sparse", "pips_hip_kkt_sparse_root_info", "pips_hip_kkt_factorize", "pips_hip_kkt_set_root_regularization", "pips_hip_kkt_solve_compressed", "pips_hip_kkt_get_schur",
+    "pips_hip_kkt_create", "pips_hip_kkt_create_sparse", "pips_hip_kkt_get_schur_sparse", "pips_hip_kkt_sparse_root_info", "pips_hip_kkt_factorize", "pips_hip_kkt_set_root_regularization", "pips_hip_kkt_solve_compressed", "pips_hip_kkt_solve_compressed_multi", "pips_hip_kkt_solve_multi_info", "pips_hip_kkt_get_schur",
     "pips_hip_kkt_set_root_inequalities", "pips_hip_kkt_set_zdiag0_dev", "pips_hip_kkt_set_root_hessian",
     "pips_hip_kkt_root_inertia", "pips_hip_kkt_get_timing", "pips_hip_kkt_last_ltsolve_from_factor", "pips_hip_kkt_last_solve_path", "pips_hip_kkt_set_solve_check", "pips_hip_kkt_solve_check_counts", "pips_hip_kkt_set_solve_graph", "pips_hip_kkt_set_root_stream", "pips_hip_kkt_solve_graph_stats", "pips_hip_kkt_set_root_pivoting", "pips_hip_kkt_destroy",
     "pips_hip_malloc", "pips_hip_free", "pips_hip_memcpy_h2d", "pips_hip_memcpy_d2h", "pips_hip_memset",
@@ -74,7 +74,7 @@ SYMBOLS = [
     "pips_hip_vec_find_blocking", "pips_hip_vec_weighted_stepbounds", "pips_hip_vec_dot_shifted", "pips_ipm_create", "pips_ipm_create_rank", "pips_ipm_create_general", "pips_ipm_create_general_scaled", "pips_ipm_create_qp", "pips_ipm_create_qp_scaled", "pips_ipm_hessian_mult", "pips_ipm_get_scaling", "pips_ipm_get_dims", "pips_ipm_get_iterate", "pips_ipm_get_stats2", "pips_ipm_get_schur_mode", "pips_ipm_mult", "pips_ipm_probe_spmv", "pips_ipm_probe_reduce", "pips_ipm_probe_step", "pips_ipm_outer_solve", "pips_ipm_solve", "pips_ipm_set_gondzio", "pips_ipm_set_option", "pips_ipm_set_free_variables", "pips_ipm_get_solution", "pips_ipm_get_trace", "pips_ipm_get_stats", "pips_ipm_destroy",
     "pips_gdx_read_block", "pips_gdx_block_counts", "pips_gdx_block_vector", "pips_gdx_block_matrix", "pips_gdx_block_destroy",
     "pips_gen_row_nnz", "pips_gen_block", "pips_gen_root", "pips_gen_diagonal", "pips_kkt_leaf_assemble",
-    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe", "pips_det_plan_probe", "pips_schur_target_probe",
+    "pips_border_assemble", "pips_symbolic_probe", "pips_symbolic_probe_hubs", "pips_map_children_to_ranks", "pips_schur_pack_probe", "pips_det_plan_probe", "pips_schur_target_probe", "pips_kkt_multi_plan_probe",
 ]
 
 # problem scalers (pips_ipm_create_general_scaled; the order of the reference's ScalerType)
@@ -337,6 +337,17 @@ def schur_target_probe(Bts, sc_rowptr, sc_colidx, S, lower=False):
     tp = (ip * nblk)(*[(t.ctypes.data_as(ip) if t.size else ip()) for t in tabs])
     _check(lib.pips_schur_target_probe(*head, _ptr(pos), C.c_longlong(len(pos)), tp), "pips_schur_target_probe")
     return nb, pos[:int(T.value)], tabs
+
+
+def kkt_multi_plan_probe(nrhs, from_=8, chunk_max=256, n_total=1, budget_bytes=2 << 30):
+    """the chunks KktSystem.solve_compressed_multi cuts nrhs right-hand sides into, without a device (pips_kkt_multi_plan_probe):
+    [(first column, count, path)], path 0 = solve_compressed column by column, 1 = panels"""
+    n = C.c_int()
+    head = (C.c_int(nrhs), C.c_int(from_), C.c_int(chunk_max), C.c_longlong(n_total), C.c_longlong(budget_bytes))
+    _check(lib.pips_kkt_multi_plan_probe(*head, None, C.c_int(0), C.byref(n)), "pips_kkt_multi_plan_probe")
+    out = np.zeros(3 * max(n.value, 1), np.int32)
+    _check(lib.pips_kkt_multi_plan_probe(*head, _ptr(out), C.c_int(n.value), C.byref(n)), "pips_kkt_multi_plan_probe")
+    return [tuple(int(v) for v in out[3 * i:3 * i + 3]) for i in range(n.value)]
 
 
 def det_plan_probe(blocks, S, rank=0, n_ranks=1, n_panels=1):
@@ -698,6 +709,18 @@ class LeafBatch:
     def border_mult(self, x0_dev, t_dev, alpha):
         _check(lib.pips_hip_batch_border_mult_dev(self._h, _ptr(x0_dev), _ptr(t_dev), C.c_double(alpha)), "border_mult")
 
+    def border_tmult_panel(self, Z_dev, T_dev, alpha):
+        """T(s, q) += alpha (Br^T z_q)_s for the rows z_q of the 2-D device tensor Z_dev (nrhs x >= n_total); T_dev is S x >= nrhs ([s][q])"""
+        nrhs = int(Z_dev.shape[0])
+        _check(lib.pips_hip_batch_border_tmult_panel_dev(self._h, C.c_int(nrhs), _ptr(Z_dev), C.c_longlong(max(int(Z_dev.stride(0)), int(Z_dev.shape[1]))), _ptr(T_dev),
+                                                         C.c_longlong(int(T_dev.stride(0))), C.c_double(alpha)), "pips_hip_batch_border_tmult_panel_dev")
+
+    def border_mult_panel(self, X0_dev, W_dev, alpha):
+        """row q of W_dev (nrhs x >= n_total) = alpha Br x0_q for the rows x0_q of X0_dev (nrhs x >= S)"""
+        nrhs = int(X0_dev.shape[0])
+        _check(lib.pips_hip_batch_border_mult_panel_dev(self._h, C.c_int(nrhs), _ptr(X0_dev), C.c_longlong(max(int(X0_dev.stride(0)), int(X0_dev.shape[1]))), _ptr(W_dev),
+                                                        C.c_longlong(max(int(W_dev.stride(0)), int(W_dev.shape[1]))), C.c_double(alpha)), "pips_hip_batch_border_mult_panel_dev")
+
     def inertia(self, b):
         p, n, z = C.c_int(), C.c_int(), C.c_int()
         _check(lib.pips_hip_batch_inertia(self._h, C.c_int(b), C.byref(p), C.byref(n), C.byref(z)), "batch inertia")
@@ -905,6 +928,31 @@ class KktSystem:
 
     def solve_compressed(self, b0_dev, b_leaf_dev):
         _check(lib.pips_hip_kkt_solve_compressed(self._h, _ptr(b0_dev), _ptr(b_leaf_dev)), "pips_hip_kkt_solve_compressed")
+
+    def solve_compressed_multi(self, B0_dev, Bleaf_dev):
+        """solveCompressed for several right-hand sides, one per ROW of the 2-D device tensors B0_dev (nrhs x >= S + mz0) and Bleaf_dev
+        (nrhs x >= n_total), in place: nrhs = shape[0], the distances between right-hand sides are stride(0), stride(1) must be 1.  Fewer than
+        the multi-vector threshold (8): exactly solve_compressed row by row; else the refined way on panels (solve_multi_info())."""
+        if B0_dev.dim() != 2 or Bleaf_dev.dim() != 2 or B0_dev.shape[0] != Bleaf_dev.shape[0]:
+            raise ValueError("solve_compressed_multi: two 2-D tensors with one right-hand side per row")
+        if B0_dev.dtype != torch.float64 or Bleaf_dev.dtype != torch.float64:
+            raise ValueError("solve_compressed_multi: float64 tensors")
+        nrhs = int(B0_dev.shape[0])
+        for t in (B0_dev, Bleaf_dev):
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("solve_compressed_multi: the entries of a right-hand side must be contiguous")
+        ld0 = int(B0_dev.stride(0)) if nrhs > 1 else max(int(B0_dev.stride(0)), int(B0_dev.shape[1]))
+        ldl = int(Bleaf_dev.stride(0)) if nrhs > 1 else max(int(Bleaf_dev.stride(0)), int(Bleaf_dev.shape[1]))
+        _check(lib.pips_hip_kkt_solve_compressed_multi(self._h, C.c_int(nrhs), _ptr(B0_dev), C.c_longlong(ld0), _ptr(Bleaf_dev), C.c_longlong(ldl)),
+               "pips_hip_kkt_solve_compressed_multi")
+
+    def solve_multi_info(self):
+        """how the last solve_compressed_multi went: path (0 column by column through solve_compressed, 1 panels), chunks, per_chunk, the
+        refinement steps of the last chunk's two leaf solves, and the panel chunks solved since the handle was created"""
+        what = np.zeros(8, np.int64)
+        _check(lib.pips_hip_kkt_solve_multi_info(self._h, _ptr(what), C.c_int(8)), "pips_hip_kkt_solve_multi_info")
+        return dict(path=int(what[0]), chunks=int(what[1]), per_chunk=int(what[2]), lsolve_refinement_steps=int(what[3]),
+                    ltsolve_refinement_steps=int(what[4]), panel_calls=int(what[5]))
 
     def schur_sparse_nnz(self):
         """Sparse-root systems: stored entries of the Schur complement (= doubles every rank reduces per factorisation)."""
